@@ -18,10 +18,18 @@ Ranks: under torchrun (WORLD_SIZE set) this process is one rank. Started as plai
 parent touches the GPU) and exits with the first non-zero child code.
 
 value = rays of all ranks / max-over-ranks wall time of K steps (median over --reps repetitions of the
-K-step timed region, each bracketed by barrier + synchronize); a ray is one trace_ray invocation,
-shadow rays included (gRayCount[0], src/Shaders/common/intersection.hlsli:66).
+K-step timed region, each bracketed by barrier + synchronize; one repetition unless --reps or --full says
+otherwise, so that --steps is the number of timed steps); a ray is one trace_ray invocation, shadow rays
+included (gRayCount[0], src/Shaders/common/intersection.hlsli:66). ms_per_step = that wall time / K.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, counts their rays and prints the JSON line.
+--dump-outputs DIR also writes what the last timed step delivered to its caller (rank 0's frame: radiance and
+the G-buffer AOVs) as DIR/<name>.npy in float64, finite (an infinite depth is written as the largest float64), on a
+fixed seeded sample of pixels when the whole frame would not fit in 64 MB (DIR/pixel_index.npy: which ones).
+
+--full adds everything else the line reports (null in a plain run): the timed region five times (--reps 5),
+then, in passes of their own, `sustained` (--sustained-seconds 3), the exchange alone (N > 1), `last_ray_filter`,
+`host_output_value`, `other_workloads`, and
   roofline      for the dominant kernel (k_trace): algorithmic bytes per launch (48 B ray+hit, + node
                 bytes x nodes visited, + 48 B x triangles tested) over the kernel's mean
                 launch duration measured here with HIP events on the launch stream, against the HBM
@@ -86,12 +94,39 @@ def committed_profile():
     return out
 
 
+DUMP_PIXELS = 1 << 18  # at most this many pixels of each output: 136 B per pixel over all of them (index included), 36 MB
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: `outputs` = name -> numpy array of one frame (H x W x channels), written as directory/<name>.npy with
+    one row per pixel in float64, which holds every float32 and 32-bit integer value exactly. An infinite value (the depth of
+    a pixel whose ray missed the scene is +inf) is written as the largest finite float64 of its sign, beyond any float32:
+    the files hold finite numbers only and keep every value distinguishable. Frames larger than DUMP_PIXELS pixels are
+    sampled at the same pixels for every output (a fixed seed: the same pixels run after run for the same frame size),
+    listed in directory/pixel_index.npy (row-major index y * W + x)."""
+    os.makedirs(directory, exist_ok=True)
+    first = next(iter(outputs.values()))
+    pixels = first.shape[0] * first.shape[1]
+    if pixels > DUMP_PIXELS:
+        index = np.sort(np.random.default_rng(0).choice(pixels, DUMP_PIXELS, replace=False))
+    else:
+        index = np.arange(pixels)
+    np.save(os.path.join(directory, "pixel_index.npy"), index.astype(np.float64))
+    big = np.finfo(np.float64).max
+    for name, a in outputs.items():
+        rows = a.reshape(pixels, -1)[index].astype(np.float64)
+        rows[rows == np.inf], rows[rows == -np.inf] = big, -big
+        np.save(os.path.join(directory, name + ".npy"), rows)
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the K-step timed region; value = their median")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (module docstring); off: the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the K-step timed region; value = their median (default 1, 5 with --full)")
     ap.add_argument("--scene", default="atrium")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -109,10 +144,12 @@ def parse_args():
     ap.add_argument("--shard", choices=("tiles", "seeds"), default="tiles",
                     help="N > 1: tiles (default): every rank renders its 64x32 tiles of every seed, one gather of the packed tiles; seeds: every rank renders the WHOLE frame for its "
                     "part of the step's seeds and one sum-reduce of the accumulation buffer adds them (SURVEY 8e 'replicas + sum-reduce': what the whole-frame estimators need)")
-    ap.add_argument("--sustained-seconds", type=float, default=3.0, help="after the timed repetitions: one pass of back-to-back steps (the same seeds cycling) at least this long, reported as `sustained` beside `value` (0: skip)")
+    ap.add_argument("--sustained-seconds", type=float, default=3.0, help="--full: after the timed repetitions, one pass of back-to-back steps (the same seeds cycling) at least this long, reported as `sustained` beside `value` (0: skip)")
     ap.add_argument("--dump-frame", default=None, help="rank 0 saves the outputs of one more step (seed block 0) as <path>.npz after the measurements: what tests compare between N = 1 and N > 1")
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the config-5 forest sub-record (other_workloads.forest; N = 1 only)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
     os.environ.setdefault("STHIP_STRICT_FLAGS", "1")
     from stratum_amd.bdpt import known_flag
 
@@ -343,7 +380,7 @@ def main():
 
     # The CPU-baseline library is compiled for THIS box's cores (-march=native) and before the GPU is initialised:
     # make / g++ are children of a process that has not touched the GPU yet.
-    want_cpu = world == 1 and not args.no_cpu_baseline
+    want_cpu = world == 1 and args.full and not args.no_cpu_baseline
     if want_cpu:
         from oracle import oracle_py
 
@@ -554,6 +591,12 @@ def main():
         drain()
         barrier()
         rep_dt.append(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:  # what the last timed step delivered (drained: on rank 0 the assembled frame)
+        frame_outputs = {"radiance": radiance.cpu().numpy()}
+        frame_outputs.update({k: v.cpu().numpy() for k, v in aov.items()})
+        if "visibility" in frame_outputs:  # VisibilityInfo: two uint32 fields
+            frame_outputs["visibility"] = frame_outputs["visibility"].view(np.uint32)
+        dump_outputs(args.dump_outputs, frame_outputs)
     # rays of the timed region: the same steps again with the counters read back (untimed; every repetition traces
     # the same seeds, hence the same rays)
     rays_local = answered_local = 0
@@ -570,8 +613,8 @@ def main():
         answered_local += st["rays_answered"]  # of them: last rays of paths answered from the emitters' bounds, no traversal (sthip.h)
     # the exchange alone (untimed region): the gather of one step's packed tiles and their assembly, between syncs, so that
     # a scaling record can be split into render time and exchange time
-    exchange_ms = 0.0
-    if dist is not None:
+    exchange_ms = None
+    if dist is not None and args.full:
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
@@ -611,7 +654,7 @@ def main():
     # of a cycle are the counted ones), between the same barriers. Reported beside `value`, never instead of it: `value` is the
     # median of short bursts; this shows what survives the clocks and power the chip settles at.
     sustained = None
-    if args.sustained_seconds > 0:
+    if args.full and args.sustained_seconds > 0:
         cycles = 0
         barrier()
         t0 = time.perf_counter()
@@ -639,7 +682,8 @@ def main():
         }
 
     result = None
-    if rank == 0:
+    roofline = last_ray_filter = host_rate = cpu = other_workloads = None  # (--full)
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel (k_trace: BVH traversal of closest-hit and shadow rays), this rank ----
         r.set_option("time_kernels", 1)
         ms_trace, ms_primary, ms_shade, ms_total, launches, launches_primary = 0.0, 0.0, 0.0, 0.0, 0, 0
@@ -782,7 +826,6 @@ def main():
 
         # ---- the library's default: last rays answered from the emitters' bounds (identical frames and ray counts). Timed the same
         # way as the headline, reported beside it: rays = the reference's trace_ray calls (gRayCount), of which `answered` walk no tree.
-        last_ray_filter = None
         if world == 1 and not args.no_last_ray_filter:
             r.set_option("answer_last_rays", 1)
             for i in range(2):
@@ -816,7 +859,6 @@ def main():
 
         # ---- the same steps through HOST output pointers (what a caller without device buffers pays): the frame comes
         # back over PCIe inside the call. Reported next to `value`, never as `value`.
-        host_rate = None
         if world == 1:
             r.render(frame, seed_begin=0, seed_count=1, aovs=False)
             th = time.perf_counter()
@@ -826,7 +868,6 @@ def main():
             host_rate = round(hrays / (time.perf_counter() - th) / 1e6, 2)
 
         # ---- CPU baseline: the oracle on a bounded sample of the same workload (rank 0, N = 1 only) ----
-        cpu = None
         if want_cpu:
             from oracle import oracle_py
 
@@ -878,7 +919,6 @@ def main():
             }
         # ---- BASELINE.json configs[4] on this one GPU, as a clearly labelled second record (never `value`): the 10M-triangle
         # instanced forest, 3840x2160, 16 seeds in one call, 8 diffuse / 10 path vertices, ~coherentrr, every output written
-        other_workloads = None
         if world == 1 and not args.no_other_workloads and args.scene == "atrium":
             box, box_cam = scenes.cornell_box()
             other_workloads = {
@@ -888,6 +928,7 @@ def main():
                 "scene_build": scene_build_record(sc, local_rank),
                 "host_outputs": host_outputs_record(local_rank, sc, cam, W, H),
             }
+    if rank == 0:
         flags_text = "default BDPT flags" if not (args.bdpt_flag or args.max_diffuse_vertices) else "flags %s maxDiffuseVertices %s" % (args.bdpt_flag, args.max_diffuse_vertices)
         result = {
             "metric": "Mray/s at 1920x1080x1spp (1M-tri scene)",
@@ -911,7 +952,7 @@ def main():
                 "parallelism": ("seed-split replicas x%d" % world if seed_split else "tile-shard x%d" % world) if world > 1 else "single GPU",
                 "exchange": exchange,
                 "exchange_bytes_per_step": exchange_bytes_per_step,  # what reaches rank 0 per step: every rank's tiles of every output
-                "exchange_alone_ms_per_step": round(exchange_ms, 4) if world > 1 else None,  # gather + assembly of one step's tiles, not overlapped (in the timed region it runs behind the next step's render)
+                "exchange_alone_ms_per_step": round(exchange_ms, 4) if exchange_ms is not None else None,  # (--full, N > 1) gather + assembly of one step's tiles, not overlapped (in the timed region it runs behind the next step's render)
                 "seeds_per_step": seeds_per_step,
                 "options": options or None,  # sthip_set_option overrides of this run (none: the library's defaults, answer_last_rays aside)
                 "world_size": world_seen,

@@ -1,4 +1,5 @@
-"""Generates tests/golden/hdr_writer.npz: input images and the bytes the REFERENCE's HDR writer produces for them.
+"""Generates tests/golden/hdr_writer.npz: input images and the bytes the REFERENCE's HDR writer produces for them
+(the hand-made cases below, and random_<W>x<H>: seeded log-normal images with plenty of runs).
 
 The reference exports HDR frames with the stb_image_write v1.16 it vendors (src/Node/BDPT.cpp:335 ->
 src/extern/stb_image_write.h). `make -C oracle ref` compiles that header as it lies under /root/reference into
@@ -41,6 +42,16 @@ def cases():
     return out
 
 
+def random_cases():
+    rng = np.random.default_rng(3)
+    out = {}
+    for w, h in [(1, 1), (7, 2), (8, 1), (129, 3), (640, 8)]:
+        img = np.exp(rng.normal(0, 3, (h, w, 4))).astype(np.float32)
+        img[rng.random((h, w)) < 0.4] = 0.125  # plenty of runs
+        out["random_%dx%d" % (w, h)] = img
+    return out
+
+
 def main():
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "ref"])
     ref = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libstbiw_ref.so"))
@@ -48,7 +59,7 @@ def main():
     ref.stbi_write_hdr.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     blob = {}
     with tempfile.TemporaryDirectory() as d:
-        for name, img in cases().items():
+        for name, img in dict(cases(), **random_cases()).items():
             path = os.path.join(d, name + ".hdr")
             assert ref.stbi_write_hdr(path.encode(), img.shape[1], img.shape[0], 4, img.ctypes.data) == 1
             blob[name + "_in"] = img

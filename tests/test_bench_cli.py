@@ -55,3 +55,39 @@ def test_unknown_flag_names_are_refused_by_the_tools_and_ignored_by_the_mirror()
             seen += 1
             assert known_flag(name), (path, name)
     assert seen > 10
+
+
+def test_dump_outputs_sample_a_large_frame_at_fixed_pixels(tmp_path):
+    """--dump-outputs of a 1080p frame with every AOV: at most 64 MB in all, float64 and finite only (every float32 and uint32
+    value exact; the +inf depth of a miss as the largest float64), the same pixels of every output, and the same pixels from one
+    run to the next."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+
+    H, W = 1080, 1920
+    rng = np.random.default_rng(5)
+    frame = {
+        "radiance": rng.random((H, W, 4), dtype=np.float32),
+        "albedo": rng.random((H, W, 4), dtype=np.float32),
+        "visibility": rng.integers(0, 2**32, (H, W, 2), dtype=np.uint64).astype(np.uint32),
+        "depth": rng.random((H, W, 4), dtype=np.float32),
+        "prev_uv": rng.random((H, W, 2), dtype=np.float32),
+    }
+    frame["depth"][rng.random((H, W)) < 0.3, :2] = np.inf  # misses: z and prev_z infinite
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frame)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted([k + ".npy" for k in frame] + ["pixel_index.npy"])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    index = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert index.dtype == np.float64 and len(index) == bench.DUMP_PIXELS and np.all(np.diff(index) > 0) and index[-1] < H * W
+    rows = index.astype(np.int64)
+    for k, a in frame.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.isfinite(got).all(), k
+        want = a.reshape(H * W, -1)[rows].astype(np.float64)
+        assert np.array_equal(np.where(np.isinf(want), np.finfo(np.float64).max, want), got), k
+        assert np.array_equal(got, np.load(tmp_path / "b" / (k + ".npy"))), k
+    assert (np.load(tmp_path / "a" / "depth.npy") == np.finfo(np.float64).max).any()

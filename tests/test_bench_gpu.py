@@ -1,6 +1,7 @@
 """bench.py on the GPU box: a two-rank rehearsal (both ranks on device 0, gloo in place of RCCL) must deliver the frame the one-rank
 run delivers — radiance AND the G-buffer, which travels with it (sthip_pack_tiles -> gather -> sthip_assemble_tiles_bytes) — and
-the JSON line must carry what the driver and the judge read (sustained, exchange bytes)."""
+the JSON line must carry what the driver and the judge read (sustained, exchange bytes: --full); a plain run's --dump-outputs must hold
+what its last timed step delivered."""
 import json
 import os
 import subprocess
@@ -10,15 +11,15 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--scene", "cornell_box", "--width", "256", "--height", "128", "--steps", "2", "--warmup", "1", "--reps", "1", "--no-cpu-baseline", "--no-ceilings", "--no-last-ray-filter",
+SMALL = ["--full", "--scene", "cornell_box", "--width", "256", "--height", "128", "--steps", "2", "--warmup", "1", "--reps", "1", "--no-cpu-baseline", "--no-ceilings", "--no-last-ray-filter",
          "--no-other-workloads", "--scaling", "strong", "--strong-seeds", "2"]
 
 
-def _run(tmp_path, gpus, extra_env=None, extra=()):
+def _run(tmp_path, gpus, extra_env=None, extra=(), base=SMALL):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(extra_env or {})
     dump = str(tmp_path / ("frame%d" % gpus))
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dump-frame", dump] + SMALL + list(extra), env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dump-frame", dump] + base + list(extra), env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
     return json.loads(line), np.load(dump + ".npz")
@@ -53,3 +54,22 @@ def test_two_rank_seed_split_rehearsal(tmp_path):
         assert np.array_equal(f1[k].view(np.uint32), f2[k].view(np.uint32)), k
     assert one["config"]["rays_per_step"] == two["config"]["rays_per_step"]
     assert two["config"]["exchange_bytes_per_step"] == 2 * 256 * 128 * 16 and "seed-split" in two["config"]["parallelism"] and one["sustained"] is None
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_timed_step(tmp_path):
+    """Without --full the line carries the headline alone, over exactly --steps timed steps. --dump-outputs holds what the last
+    of them delivered: with one timed step and no warm-up that is seed block 0, the frame --dump-frame renders again after it."""
+    out = tmp_path / "outputs"
+    line, f = _run(tmp_path, 1, extra=["--steps", "1", "--warmup", "0", "--dump-outputs", str(out)], base=SMALL[1:])
+    assert line["steps"] == 1 and line["repetitions"]["n"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    for key in ("sustained", "roofline", "last_ray_filter", "host_output_value", "other_workloads", "cpu_baseline"):
+        assert line[key] is None, key
+    pixels = 256 * 128
+    assert np.array_equal(np.load(out / "pixel_index.npy"), np.arange(pixels, dtype=np.float64))
+    for k in ("radiance", "albedo", "depth", "prev_uv", "visibility"):
+        got = np.load(out / (k + ".npy"))
+        want = (f[k].view(np.uint32) if k == "visibility" else f[k]).reshape(pixels, -1).astype(np.float64)
+        assert got.dtype == np.float64 and got.shape == want.shape and np.isfinite(got).all(), k
+        assert np.array_equal(got.view(np.uint64), np.where(np.isinf(want), np.finfo(np.float64).max, want).view(np.uint64)), k
+    assert f["radiance"].any()
