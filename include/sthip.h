@@ -110,14 +110,24 @@ typedef struct sthip_frame_desc {
 /* Output images/buffers of the two passes (bdpt.hlsl:44-49, BDPT.cpp:553-558).
  * gRadiance is required, the others may be NULL. With device_ptrs = 1 every non-NULL
  * pointer is a device pointer on the context's GPU (no copy; results are complete when
- * the call's stream work is complete, see sthip_set_stream). */
+ * the call's stream work is complete, see sthip_set_stream).
+ * Half colour precision (sthip_set_option "half_color_precision" = 1, the reference's mHalfColorPrecision,
+ * BDPT.cpp:231,553-558): the three colour images gRadiance (both layouts), gAlbedo and gDebugImage (in and out) are
+ * RGBA16F instead of RGBA32F — 8 bytes per pixel, four IEEE binary16 values in rgba order; the float* points at halves.
+ * gVisibility, gDepth, gPrevUVs (RG32F upstream too) and gRayCount do not change. The arithmetic is the binary32 one;
+ * a value is rounded to nearest even (det_f32tof16) only where it leaves the call: the radiance mean once, at its store;
+ * the albedo once; the debug image at every seed (the seeds of a call are successive frames), so a call of N seeds
+ * equals N chained calls of one. Hence radiance / albedo = RTNE(the binary32 call's arrays), bit for bit, and a 1-seed
+ * call's debug image = RTNE(the binary32 call given the upcast half image). Upstream also rounds at each
+ * read-modify-write of gRadiance / gDebugImage within a frame (trace_shadows, add_light_trace, debug `+=`); here the
+ * running value stays binary32 between those statements. */
 #define STHIP_LAYOUT_IMAGE 0u       /* gRadiance is the W x H image; pixels the shard does not own are zero */
 #define STHIP_LAYOUT_SHARD_TILES 1u /* gRadiance holds only the shard's tiles, in slot order: sthip_shard_slot_count() float4 */
 typedef struct sthip_outputs {
   uint32_t device_ptrs;
   uint32_t radiance_layout; /* STHIP_LAYOUT_*: the packed form is what ranks exchange (sthip_assemble_tiles) */
-  float* gRadiance;                  /* RGBA32F, W*H*4: rgb = mean over the seeds of this call, a = sample count */
-  float* gAlbedo;                    /* RGBA32F */
+  float* gRadiance;                  /* RGBA32F (RGBA16F: half colour precision), W*H*4: rgb = mean over the seeds of this call, a = sample count */
+  float* gAlbedo;                    /* RGBA32F (RGBA16F: half colour precision) */
   sthip_VisibilityInfo* gVisibility; /* W*H */
   sthip_DepthInfo* gDepth;           /* W*H */
   float* gPrevUVs;                   /* RG32F, W*H*2 */
@@ -209,7 +219,8 @@ int sthip_render(sthip_ctx* ctx, const sthip_BDPTPushConstants* push_constants, 
 int sthip_set_shard(sthip_ctx* ctx, uint32_t shard_rank, uint32_t shard_count, uint32_t tile_w, uint32_t tile_h);
 
 /* The exchange step of a sharded frame without the zero padding: each rank renders with
- * outputs.radiance_layout = STHIP_LAYOUT_SHARD_TILES (sthip_shard_slot_count() float4 entries, 1/shard_count of the
+ * outputs.radiance_layout = STHIP_LAYOUT_SHARD_TILES (sthip_shard_slot_count() float4 entries — 8-byte half4 entries
+ * and a RGBA16F frame with "half_color_precision", bit-identical to the unsharded half frame — 1/shard_count of the
  * frame), the ranks' buffers are gathered on one GPU (RCCL gather / all_gather, rank r at packed + r * rank_stride
  * float4 entries; rank_stride >= rank 0's slot count, which is the largest), and sthip_assemble_tiles scatters them into
  * the W x H image on that GPU's context (device pointers, enqueued on the context's stream). */
@@ -217,7 +228,7 @@ uint32_t sthip_shard_slot_count(uint32_t width, uint32_t height, uint32_t shard_
                                 uint32_t tile_h);
 int sthip_assemble_tiles(sthip_ctx* ctx, const float* packed, uint64_t rank_stride, uint32_t shard_count, uint32_t tile_w,
                          uint32_t tile_h, uint32_t width, uint32_t height, float* frame);
-/* The same for the other outputs of a sharded frame (the G-buffer: albedo 16 B, VisibilityInfo 8 B, DepthInfo 16 B, prev-uv
+/* The same for the other outputs of a sharded frame (the G-buffer: albedo 16 B (8 B with half colour precision), VisibilityInfo 8 B, DepthInfo 16 B, prev-uv
  * 8 B per pixel), which sthip_render writes as W x H images that are zero outside the shard's tiles:
  * sthip_pack_tiles gathers the context's own tiles (its sthip_set_shard) out of such an image into slot order —
  * sthip_shard_slot_count() entries of entry_bytes each, the padding slots of edge tiles zero — and
@@ -233,7 +244,8 @@ int sthip_assemble_tiles_bytes(sthip_ctx* ctx, const void* packed, uint64_t rank
  * a tile shard cannot; the mean of N seeds then depends on the order of a floating-point sum (~1e-7 relative against the
  * one-GPU frame, where a tile shard is bit-identical). A call's radiance output is (mean over its seeds, their number):
  * sthip_radiance_to_sums turns `entries` RGBA32F entries in place into (sum over the seeds, their number), which a
- * sum-reduce can add; with back != 0 it turns such sums back into (mean, number). Device pointer; enqueued on the stream. */
+ * sum-reduce can add; with back != 0 it turns such sums back into (mean, number). Device pointer; enqueued on the stream.
+ * Returns STHIP_ERR_UNSUPPORTED while "half_color_precision" is on: a sum of rounded means is not a rounded mean. */
 int sthip_radiance_to_sums(sthip_ctx* ctx, float* image, uint64_t entries, uint32_t back);
 
 /* ---- the traversal contract on its own (T1/T2 of SURVEY.md §8a; intersection.hlsli:65-239) ---- */
@@ -349,7 +361,14 @@ int sthip_measure_ceiling(sthip_ctx* ctx, uint32_t kind, double* gbytes_per_s);
  * the hit contract itself needs),
  * "keep_scene" (default 1: a host copy of the uploaded arrays, see sthip_scene_update_transforms), "treetop" (default 0), "embed_leaves" (default 0), "lds_materials" (default 1), "lds_stack_levels" (4..150: LDS levels of the traversal stack; a higher
  * tree runs the bounded kernels, default: bounded at 32 levels beyond a height of 40): layout / scheduling options that
- * never change results, read at the next sthip_scene_upload / sthip_scene_update_transforms */
+ * never change results, read at the next sthip_scene_upload / sthip_scene_update_transforms.
+ *
+ * An option that DOES change results: "half_color_precision" (0 = default, 1; other values are refused). While it is 1
+ * the colour images of sthip_render (gRadiance, gAlbedo, gDebugImage; see sthip_outputs), sthip_tonemap (gInput,
+ * gAlbedo, gOutput), sthip_accumulate (gRadiance, gAlbedo, gPrevAccumColor, gAccumColor), sthip_image_compare (both
+ * images) and sthip_assemble_tiles (8-byte entries) are RGBA16F; every other buffer keeps its type. It takes effect at
+ * the next call. A library without the feature answers STHIP_ERR_INVALID_ARGUMENT (unknown option): a host may probe
+ * with it. */
 int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value);
 
 /* ---- after the path: display transform, image metric, HDR export ---- */
@@ -361,7 +380,9 @@ int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value);
  * is blended in with alpha = n_new / n, n clamped by history_limit (gHistoryLimit, 0 = unlimited). The binding names
  * are the shader's (denoiser.h). gViews is always a host pointer; the images are host pointers unless device_ptrs
  * (then, with up to 4 views, the call only enqueues its kernel on the context's stream: nothing is allocated or waited for).
- * (sthip_render's own N-seed mean is the same-pixel branch of this kernel applied seed by seed.) */
+ * (sthip_render's own N-seed mean is the same-pixel branch of this kernel applied seed by seed.)
+ * With "half_color_precision" the four colour images are RGBA16F: read exactly, blended in binary32, gAccumColor rounded
+ * to nearest even at its store; gAccumMoments stays RG32F and comes out as the binary32 call's on the upcast inputs. */
 typedef struct sthip_accumulate_desc {
   uint32_t width, height;
   uint32_t view_count;        /* gViewCount */
@@ -371,17 +392,17 @@ typedef struct sthip_accumulate_desc {
   uint32_t device_ptrs;
   uint32_t instance_count;    /* entries of gInstanceIndexMap */
   const sthip_ViewData* gViews;
-  const float* gRadiance;                      /* RGBA32F: rgb = sample, a = its sample count */
-  const float* gAlbedo;                        /* RGBA32F; may be NULL unless demodulate_albedo */
+  const float* gRadiance;                      /* RGBA32F (RGBA16F: half colour precision): rgb = sample, a = its sample count */
+  const float* gAlbedo;                        /* RGBA32F (RGBA16F); may be NULL unless demodulate_albedo */
   const sthip_VisibilityInfo* gVisibility;     /* these five only with reprojection */
   const sthip_DepthInfo* gDepth;
   const float* gPrevUVs;                       /* RG32F */
   const sthip_VisibilityInfo* gPrevVisibility;
   const sthip_DepthInfo* gPrevDepth;
-  const float* gPrevAccumColor;                /* RGBA32F: rgb = mean so far, a = sample count */
+  const float* gPrevAccumColor;                /* RGBA32F (RGBA16F): rgb = mean so far, a = sample count */
   const float* gPrevAccumMoments;              /* RG32F: mean luminance, mean squared luminance */
   const uint32_t* gInstanceIndexMap;           /* SceneData::mInstanceIndexMap (Scene.cpp:383-385,414-418); NULL = identity */
-  float* gAccumColor;                          /* out, RGBA32F */
+  float* gAccumColor;                          /* out, RGBA32F (RGBA16F) */
   float* gAccumMoments;                        /* out, RG32F */
 } sthip_accumulate_desc;
 int sthip_accumulate(sthip_ctx* ctx, const sthip_accumulate_desc* desc);
@@ -407,7 +428,9 @@ enum {
  * gAlbedo, gOutput (RGBA32F, width*height). The two dispatches of the reference (clear gMax + reduce_max, then main)
  * happen inside one call. gExposureAlpha (smoothing of the maxima over frames, default 0 = off) is not taken: every
  * call uses the maxima of its own input. out_max (optional, host memory, 4 floats) receives the rgb and luminance
- * maxima main() sees. */
+ * maxima main() sees. With "half_color_precision" gInput, gAlbedo and gOutput are RGBA16F: the inputs are read exactly,
+ * gOutput is rounded to nearest even at its store; out_max and exposure_state are those of the binary32 call on the
+ * upcast inputs. */
 typedef struct sthip_tonemap_desc {
   uint32_t width, height;
   uint32_t mode;
@@ -434,11 +457,12 @@ enum { STHIP_COMPARE_SMAPE = 0, STHIP_COMPARE_MSE = 1, STHIP_COMPARE_AVERAGE = 2
  * per-pixel error over rgb, divided by 3*width*height, summed per group of 64 consecutive pixels, scaled by
  * `quantization` (gQuantization; the node's default is 1024, ImageComparer.hpp:18), truncated to uint and added atomically.
  * sum_out = the raw uint accumulator, overflow_out = the overflow flag; the displayed number is sum/quantization
- * (its square root for MSE, ImageComparer.cpp:88). image1/image2: RGBA32F, host unless device_ptrs. */
+ * (its square root for MSE, ImageComparer.cpp:88). image1/image2: RGBA32F (RGBA16F with "half_color_precision", read
+ * exactly: the sums of the binary32 call on the upcast images), host unless device_ptrs. */
 int sthip_image_compare(sthip_ctx* ctx, const float* image1, const float* image2, uint32_t width, uint32_t height, uint32_t metric, uint32_t quantization,
                         uint32_t device_ptrs, uint32_t* sum_out, uint32_t* overflow_out);
 
-/* Radiance .hdr export of an RGBA32F host image, what BDPT's "Export HDR" does through stbi_write_hdr(path, w, h, 4,
+/* Radiance .hdr export of an RGBA32F host image (always RGBA32F: a half image is upcast by the caller), what BDPT's "Export HDR" does through stbi_write_hdr(path, w, h, 4,
  * pixels) (src/Node/BDPT.cpp:313-337): header "#?RADIANCE", FORMAT=32-bit_rle_rgbe, rows top to bottom, RGBE with
  * the shared exponent of the largest channel; rows of 8..32767 pixels are run-length coded per channel, others flat.
  * Host-only, needs no context. Returns STHIP_OK or STHIP_ERR_INVALID_ARGUMENT (bad arguments / cannot write). */

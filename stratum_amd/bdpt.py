@@ -72,6 +72,7 @@ class BDPT:
         self.mPushConstants.gLightPathCount = 64  # BDPT.cpp:70: the size of the light vertex cache unless --lightPathCount says otherwise (without eLVC: one path per pixel, :469-470)
         self._scene = None
         self._prev_result = None
+        self.half_color_precision = False  # BDPT.hpp mHalfColorPrecision: colour images RGBA16F (set_half_color_precision)
         args = args or {}
         for key, field in (
             ("minPathVertices", "gMinPathVertices"),
@@ -147,6 +148,18 @@ class BDPT:
     def set_option(self, name, value):
         self._check(self._lib.sthip_set_option(self._h, name.encode(), int(value)), "sthip_set_option")
 
+    def set_half_color_precision(self, on):
+        """The reference's "Half precision" switch (BDPT.cpp:231,553-558): while on, radiance, albedo and the debug image are
+        RGBA16F (np.float16 host arrays, float16 device buffers), as are the colour images of the post calls that follow this
+        renderer (post.py). Results are the binary32 ones rounded to nearest even (include/sthip.h: "half_color_precision")."""
+        self.set_option("half_color_precision", 1 if on else 0)
+        self.half_color_precision = bool(on)
+
+    @property
+    def color_dtype(self):
+        """numpy dtype of the colour images (radiance, albedo, debug) under the current precision."""
+        return np.float16 if self.half_color_precision else np.float32
+
     CEILINGS = {"triad": 0, "node_gather_table": 1, "node_gather_l2": 2, "node_gather_l1": 3}
 
     def measure_ceiling(self, kind):
@@ -183,7 +196,8 @@ class BDPT:
         written in place instead of fresh ones — a caller's own buffers). `device_outputs` = dict of raw device pointers
         {"radiance": ptr, ["albedo", "visibility", "depth", "prev_uv", "ray_count"]} renders in place on the
         GPU without synchronising. packed_tiles: "radiance" holds only this shard's tiles in slot order
-        (shard_slot_count() float4 entries) — the form ranks exchange, see assemble_tiles."""
+        (shard_slot_count() float4 entries) — the form ranks exchange, see assemble_tiles. With half_color_precision the
+        colour arrays (radiance, albedo, debug) are np.float16 (device buffers: 8 bytes per pixel)."""
         if self._scene is None:
             raise StratumHipError("BDPT.render before BDPT.update(scene)")
         pc = self.push_constants(frame)
@@ -206,27 +220,29 @@ class BDPT:
                 o.gDebugImage = device_outputs["debug"]
         else:
             W, H = frame.width, frame.height
+            cd = self.color_dtype
+            cb = 4 * np.dtype(cd).itemsize  # bytes of one colour pixel
             if host_outputs is None:
-                out = {"radiance": np.zeros((self.shard_slot_count(frame), 4) if packed_tiles else (H, W, 4), np.float32), "ray_count": np.zeros(2, np.uint64)}
+                out = {"radiance": np.zeros((self.shard_slot_count(frame), 4) if packed_tiles else (H, W, 4), cd), "ray_count": np.zeros(2, np.uint64)}
             else:
                 out = {k: host_outputs[k] for k in ("radiance", "ray_count")}
-                if out["radiance"].nbytes != (self.shard_slot_count(frame) if packed_tiles else H * W) * 16 or out["radiance"].dtype != np.float32 or not out["radiance"].flags["C_CONTIGUOUS"]:
+                if out["radiance"].nbytes != (self.shard_slot_count(frame) if packed_tiles else H * W) * cb or out["radiance"].dtype != cd or not out["radiance"].flags["C_CONTIGUOUS"]:
                     raise ValueError("host_outputs['radiance'] does not fit the frame")
             o.device_ptrs = 0
             o.gRadiance = wire.ptr(out["radiance"])
             o.gRayCount = wire.ptr(out["ray_count"])
             if debug_mode:  # BDPTDebugMode -> gDebugImage (in / out: a copy of what the caller passes, or zeros)
-                out["debug"] = np.ascontiguousarray(debug_image, np.float32).copy() if debug_image is not None else np.zeros((H, W, 4), np.float32)
+                out["debug"] = np.ascontiguousarray(debug_image).astype(cd) if debug_image is not None else np.zeros((H, W, 4), cd)
                 o.debug_mode = debug_mode
                 o.gDebugImage = wire.ptr(out["debug"])
             if aovs and host_outputs is not None:
-                for k, dtype, per_pixel in (("albedo", np.float32, 16), ("visibility", wire.VisibilityInfo, None), ("depth", wire.DepthInfo, None), ("prev_uv", np.float32, 8)):
+                for k, dtype, per_pixel in (("albedo", cd, cb), ("visibility", wire.VisibilityInfo, None), ("depth", wire.DepthInfo, None), ("prev_uv", np.float32, 8)):
                     a = host_outputs[k]
                     if a.dtype != dtype or a.nbytes != H * W * (per_pixel or a.dtype.itemsize) or not a.flags["C_CONTIGUOUS"]:
                         raise ValueError("host_outputs[%r] does not fit the frame" % k)
                     out[k] = a
             elif aovs:
-                out["albedo"] = np.zeros((H, W, 4), np.float32)
+                out["albedo"] = np.zeros((H, W, 4), cd)
                 out["visibility"] = np.zeros((H, W), wire.VisibilityInfo)
                 out["depth"] = np.zeros((H, W), wire.DepthInfo)
                 out["prev_uv"] = np.zeros((H, W, 2), np.float32)
@@ -251,13 +267,14 @@ class BDPT:
         return int(self._lib.sthip_shard_slot_count(frame.width, frame.height, r if rank is None else rank, n, tw, th))
 
     def assemble_tiles(self, frame, packed_ptr, rank_stride, frame_ptr):
-        """packed_ptr: device buffer with rank r's tiles at r * rank_stride float4 entries; frame_ptr: W x H RGBA32F."""
+        """packed_ptr: device buffer with rank r's tiles at r * rank_stride float4 entries; frame_ptr: W x H RGBA32F (with
+        half_color_precision: 8-byte RGBA16F entries and image)."""
         _, n, tw, th = getattr(self, "_shard", (0, 1, 64, 32))
         self._check(self._lib.sthip_assemble_tiles(self._h, packed_ptr, rank_stride, n, tw, th, frame.width, frame.height, frame_ptr), "sthip_assemble_tiles")
 
     def radiance_to_sums(self, image_ptr, entries, back=False):
         """(mean over the seeds, their number) -> (sum, number) in place, or back: what the seed-split replica mode reduces
-        (device pointer; include/sthip.h: sthip_radiance_to_sums)."""
+        (device pointer; include/sthip.h: sthip_radiance_to_sums). Refused (StratumHipError) with half_color_precision."""
         self._check(self._lib.sthip_radiance_to_sums(self._h, image_ptr, entries, 1 if back else 0), "sthip_radiance_to_sums")
 
     def pack_tiles(self, frame, image_ptr, entry_bytes, packed_ptr):

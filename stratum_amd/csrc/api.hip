@@ -273,7 +273,11 @@ struct sthip_ctx {
   DevBuf<uint32_t> post_scratch;  // maxima / metric accumulator of post.h
   DevBuf<sthip_ray> ray_staging;  // sthip_trace_rays with host pointers
   DevBuf<sthip_hit> hit_staging;
-  DevBuf<float4> out_radiance, out_albedo;
+  DevBuf<float4> out_radiance, out_albedo;  // staging of the colour images (out_debug too): color_bytes() per entry, so 16 B entries hold 1 or 2
+  DevBuf<float4> albedo_stage;  // half colour precision: k_shade's binary32 albedo, which k_resolve rounds into the RGBA16F image
+  // "half_color_precision": the colour images of sthip_render and of the post calls are RGBA16F (8 B per pixel) instead of RGBA32F
+  bool half_color = false;
+  size_t color_bytes() const { return half_color ? 8 : 16; }
   DevBuf<sthip_VisibilityInfo> out_visibility;
   DevBuf<sthip_DepthInfo> out_depth;
   DevBuf<float2> out_prev_uv;
@@ -500,6 +504,7 @@ void sthip_destroy(sthip_ctx* ctx) {
   ctx->post_scratch.release();
   ctx->out_radiance.release();
   ctx->out_albedo.release();
+  ctx->albedo_stage.release();
   ctx->out_visibility.release();
   ctx->out_depth.release();
   ctx->out_prev_uv.release();
@@ -583,7 +588,10 @@ int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value) {
     ctx->reuse_persist = value != 0;
     ctx->reuse_grids_valid = false;
   }
-  else if (!strcmp(name, "inner_min_lanes"))
+  else if (!strcmp(name, "half_color_precision")) {  // takes effect at the next call; refused outside 0 / 1
+    if (value != 0 && value != 1) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "half_color_precision: 0 or 1");
+    ctx->half_color = value != 0;
+  } else if (!strcmp(name, "inner_min_lanes"))
     ctx->inner_min_lanes = (uint32_t)std::min<int64_t>(64, std::max<int64_t>(1, value));
   else
     return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, std::string("unknown option ") + name);
@@ -1830,16 +1838,19 @@ static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32
 
   // outputs: device pointers are written in place, host pointers go through staging buffers
   const bool dev = out->device_ptrs != 0;
+  const size_t cb = ctx->color_bytes();  // bytes of one colour-image entry (radiance, albedo, debug)
+  const auto color_entries = [](size_t n, size_t bytes) { return (n * bytes + 15) / 16; };  // float4 entries of a staging buffer
+  p.out_half = ctx->half_color ? 1u : 0u;
   p.debug_mode = debug_mode;
   p.debug = debug_mode ? ctx->debug.p : nullptr;
   p.out_debug = nullptr;
   p.shadow_debug = nullptr;
   if (debug_mode) {
     if (dev) {
-      p.out_debug = reinterpret_cast<float4*>(out->gDebugImage);
+      p.out_debug = out->gDebugImage;
     } else {  // in / out: what the caller's image holds goes up first
-      HIP_TRY(ctx, ctx->out_debug.ensure(pixels));
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->out_debug.p, out->gDebugImage, pixels * 16, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, ctx->out_debug.ensure(color_entries(pixels, cb)));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->out_debug.p, out->gDebugImage, pixels * cb, hipMemcpyHostToDevice, st));
       p.out_debug = ctx->out_debug.p;
     }
     // inline shadow rays add to the debug image only where they are unoccluded: they are traced once more, with what they add
@@ -1858,16 +1869,16 @@ static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32
   if (out->radiance_layout > STHIP_LAYOUT_SHARD_TILES) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: unknown radiance_layout");
   const size_t radiance_entries = p.out_packed ? std::max<size_t>(1, p.paths_per_seed) : pixels;
   if (dev) {
-    p.out_radiance = reinterpret_cast<float4*>(out->gRadiance);
+    p.out_radiance = out->gRadiance;
     p.out_albedo = reinterpret_cast<float4*>(out->gAlbedo);
     p.out_visibility = out->gVisibility;
     p.out_depth = out->gDepth;
     p.out_prev_uv = reinterpret_cast<float2*>(out->gPrevUVs);
   } else {
-    HIP_TRY(ctx, ctx->out_radiance.ensure(radiance_entries));
+    HIP_TRY(ctx, ctx->out_radiance.ensure(color_entries(radiance_entries, cb)));
     p.out_radiance = ctx->out_radiance.p;
     if (out->gAlbedo) {
-      HIP_TRY(ctx, ctx->out_albedo.ensure(pixels));
+      HIP_TRY(ctx, ctx->out_albedo.ensure(color_entries(pixels, cb)));
       p.out_albedo = ctx->out_albedo.p;
     }
     if (out->gVisibility) {
@@ -1907,13 +1918,21 @@ static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32
       }
     }
   }
+  // half colour precision: k_shade writes the albedo in binary32 to a stage, k_resolve rounds it into the caller's image (or its staging)
+  p.out_albedo16 = nullptr;
+  if (ctx->half_color && p.out_albedo) {
+    p.out_albedo16 = reinterpret_cast<Half4*>(p.out_albedo);
+    HIP_TRY(ctx, ctx->albedo_stage.ensure(pixels));
+    p.out_albedo = ctx->albedo_stage.p;
+  }
   // Pixels this shard does not own and pixels outside every view are zero (a sum-reduce over shards assembles the frame).
   // When the shard is the whole frame and every pixel lies in a view, every output entry is written by the pass itself —
   // the first vertex's G-buffer stores (hit or miss) and k_resolve — so the five fills (131 MB at 1080p) are left out.
   const bool every_entry_written = p.shard_count == 1 && !p.out_packed && !media && pc->gMaxPathVertices >= 2 && (size_t)primary_rays == pixels;
   if (!every_entry_written) {
-    HIP_TRY(ctx, hipMemsetAsync(p.out_radiance, 0, radiance_entries * 16, st));
+    HIP_TRY(ctx, hipMemsetAsync(p.out_radiance, 0, radiance_entries * cb, st));
     if (p.out_albedo) HIP_TRY(ctx, hipMemsetAsync(p.out_albedo, 0, pixels * 16, st));
+    if (p.out_albedo16) HIP_TRY(ctx, hipMemsetAsync(p.out_albedo16, 0, pixels * 8, st));
     if (p.out_visibility) HIP_TRY(ctx, hipMemsetAsync(p.out_visibility, 0, pixels * 8, st));
     if (p.out_depth) HIP_TRY(ctx, hipMemsetAsync(p.out_depth, 0, pixels * 16, st));
     if (p.out_prev_uv) HIP_TRY(ctx, hipMemsetAsync(p.out_prev_uv, 0, pixels * 8, st));
@@ -2137,7 +2156,7 @@ static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32
       // bdpt.hlsl:190-205: sample_visibility returns before it traces anything; the frame stays (0, 0, 0, 1), no ray is counted
       // (the G-buffer outputs are not written upstream either: they are left zero here)
       if (s == 0) {
-        if (p.out_albedo) HIP_TRY(ctx, hipMemsetAsync(p.out_albedo, 0, pixels * 16, st));
+        if (p.out_albedo) HIP_TRY(ctx, hipMemsetAsync(p.out_albedo, 0, pixels * 16, st));  // (the binary32 stage with half colour precision)
         if (p.out_visibility) HIP_TRY(ctx, hipMemsetAsync(p.out_visibility, 0, pixels * 8, st));
         if (p.out_depth) HIP_TRY(ctx, hipMemsetAsync(p.out_depth, 0, pixels * 16, st));
         if (p.out_prev_uv) HIP_TRY(ctx, hipMemsetAsync(p.out_prev_uv, 0, pixels * 8, st));
@@ -2297,12 +2316,12 @@ static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32
   }
 
   if (!dev) {
-    HIP_TRY(ctx, hipMemcpyAsync(out->gRadiance, p.out_radiance, radiance_entries * 16, hipMemcpyDeviceToHost, st));
-    if (out->gAlbedo) HIP_TRY(ctx, hipMemcpyAsync(out->gAlbedo, p.out_albedo, pixels * 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(out->gRadiance, p.out_radiance, radiance_entries * cb, hipMemcpyDeviceToHost, st));
+    if (out->gAlbedo) HIP_TRY(ctx, hipMemcpyAsync(out->gAlbedo, p.out_albedo16 ? (const void*)p.out_albedo16 : (const void*)p.out_albedo, pixels * cb, hipMemcpyDeviceToHost, st));
     if (out->gVisibility) HIP_TRY(ctx, hipMemcpyAsync(out->gVisibility, p.out_visibility, pixels * 8, hipMemcpyDeviceToHost, st));
     if (out->gDepth) HIP_TRY(ctx, hipMemcpyAsync(out->gDepth, p.out_depth, pixels * 16, hipMemcpyDeviceToHost, st));
     if (out->gPrevUVs) HIP_TRY(ctx, hipMemcpyAsync(out->gPrevUVs, p.out_prev_uv, pixels * 8, hipMemcpyDeviceToHost, st));
-    if (debug_mode) HIP_TRY(ctx, hipMemcpyAsync(out->gDebugImage, p.out_debug, pixels * 16, hipMemcpyDeviceToHost, st));
+    if (debug_mode) HIP_TRY(ctx, hipMemcpyAsync(out->gDebugImage, p.out_debug, pixels * cb, hipMemcpyDeviceToHost, st));
     unsigned long long c[CNT_TOTAL];
     HIP_TRY(ctx, hipMemcpyAsync(c, ctx->counters.p, sizeof(c), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -2354,11 +2373,13 @@ int sthip_assemble_tiles_bytes(sthip_ctx* ctx, const void* packed, uint64_t rank
 }
 int sthip_assemble_tiles(sthip_ctx* ctx, const float* packed, uint64_t rank_stride, uint32_t shard_count, uint32_t tile_w, uint32_t tile_h, uint32_t width, uint32_t height,
                          float* frame) {
-  return sthip_assemble_tiles_bytes(ctx, packed, rank_stride, shard_count, tile_w, tile_h, width, height, 16, frame);
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  return sthip_assemble_tiles_bytes(ctx, packed, rank_stride, shard_count, tile_w, tile_h, width, height, (uint32_t)ctx->color_bytes(), frame);
 }
 int sthip_radiance_to_sums(sthip_ctx* ctx, float* image, uint64_t entries, uint32_t back) {
   if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
   if (!image) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_radiance_to_sums: image is NULL");
+  if (ctx->half_color) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_radiance_to_sums: not with half_color_precision (a sum of rounded means is not a rounded mean)");
   if (entries == 0) return STHIP_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_radiance_sums, dim3(grid_for(ctx, (size_t)entries)), dim3(STHIP_BLOCK), 0, ctx->stream, reinterpret_cast<float4*>(image), (size_t)entries, back ? 0u : 1u);
@@ -2427,27 +2448,28 @@ int sthip_accumulate(sthip_ctx* ctx, const sthip_accumulate_desc* d) {
       staged.push_back(q);
     p.views = (const sthip_ViewData*)q;
   }
-  p.radiance = (const float4*)in(d->gRadiance, n * 16);
-  p.albedo = (const float4*)in(d->gAlbedo, n * 16);
+  const size_t cb = ctx->color_bytes();  // gRadiance, gAlbedo, gPrevAccumColor, gAccumColor
+  p.radiance = in(d->gRadiance, n * cb);
+  p.albedo = in(d->gAlbedo, n * cb);
   p.visibility = (const sthip_VisibilityInfo*)in(d->gVisibility, n * 8);
   p.depth = (const sthip_DepthInfo*)in(d->gDepth, n * 16);
   p.prev_uvs = (const float2*)in(d->gPrevUVs, n * 8);
   p.prev_visibility = (const sthip_VisibilityInfo*)in(d->gPrevVisibility, n * 8);
   p.prev_depth = (const sthip_DepthInfo*)in(d->gPrevDepth, n * 16);
-  p.prev_accum_color = (const float4*)in(d->gPrevAccumColor, n * 16);
+  p.prev_accum_color = in(d->gPrevAccumColor, n * cb);
   p.prev_accum_moments = (const float2*)in(d->gPrevAccumMoments, n * 8);
   p.instance_index_map = (const uint32_t*)in(d->gInstanceIndexMap, (size_t)d->instance_count * 4);
-  float4* out_c = reinterpret_cast<float4*>(d->gAccumColor);
+  void* out_c = d->gAccumColor;
   float2* out_m = reinterpret_cast<float2*>(d->gAccumMoments);
   if (!d->device_ptrs) {
     void *qc = nullptr, *qm = nullptr;
-    if (hipMalloc(&qc, n * 16) != hipSuccess || hipMalloc(&qm, n * 8) != hipSuccess) bad = true;
+    if (hipMalloc(&qc, n * cb) != hipSuccess || hipMalloc(&qm, n * 8) != hipSuccess) bad = true;
     if (qc) staged.push_back(qc);
     if (qm) staged.push_back(qm);
-    out_c = (float4*)qc;
+    out_c = qc;
     out_m = (float2*)qm;
     // pixels outside every view keep what the caller's buffers hold
-    if (!bad && (hipMemcpyAsync(qc, d->gAccumColor, n * 16, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(qm, d->gAccumMoments, n * 8, hipMemcpyHostToDevice, st) != hipSuccess)) bad = true;
+    if (!bad && (hipMemcpyAsync(qc, d->gAccumColor, n * cb, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(qm, d->gAccumMoments, n * 8, hipMemcpyHostToDevice, st) != hipSuccess)) bad = true;
   }
   if (bad) {
     (void)hipStreamSynchronize(st);
@@ -2456,10 +2478,13 @@ int sthip_accumulate(sthip_ctx* ctx, const sthip_accumulate_desc* d) {
   }
   p.accum_color = out_c;
   p.accum_moments = out_m;
-  hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
+  if (ctx->half_color)
+    hipLaunchKernelGGL(k_accumulate<Half4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL(k_accumulate<float4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && !d->device_ptrs) {
-    e = hipMemcpyAsync(d->gAccumColor, out_c, n * 16, hipMemcpyDeviceToHost, st);
+    e = hipMemcpyAsync(d->gAccumColor, out_c, n * cb, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d->gAccumMoments, out_m, n * 8, hipMemcpyDeviceToHost, st);
   }
   // staged copies must outlive the kernel; with device pointers and inline views nothing is staged: the call is only enqueued
@@ -2469,27 +2494,40 @@ int sthip_accumulate(sthip_ctx* ctx, const sthip_accumulate_desc* d) {
   return STHIP_OK;
 }
 
+// C: the colour images' element, float4 (RGBA32F) or Half4 ("half_color_precision")
+extern "C++" {
+template <typename C>
+static int tonemap_images(sthip_ctx* ctx, const sthip_tonemap_desc* d);
+template <typename C>
+static int compare_images(sthip_ctx* ctx, const float* image1, const float* image2, uint32_t width, uint32_t height, uint32_t metric, uint32_t quantization, uint32_t device_ptrs,
+                          uint32_t* sum_out, uint32_t* overflow_out);
+}
 int sthip_tonemap(sthip_ctx* ctx, const sthip_tonemap_desc* d) {
   if (!ctx || !d) return STHIP_ERR_INVALID_ARGUMENT;
   if (!d->gInput || !d->gOutput || d->width == 0 || d->height == 0) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_tonemap: gInput, gOutput and a non-empty extent are required");
   if (d->mode >= eTonemapModeCount) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_tonemap: unknown mode " + std::to_string(d->mode));
   if (d->modulate_albedo && !d->gAlbedo) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_tonemap: gModulateAlbedo needs gAlbedo");
   if ((uint64_t)d->width * d->height > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_tonemap: extent too large");
+  return ctx->half_color ? tonemap_images<Half4>(ctx, d) : tonemap_images<float4>(ctx, d);
+}
+extern "C++" {
+template <typename C>
+static int tonemap_images(sthip_ctx* ctx, const sthip_tonemap_desc* d) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const uint32_t n = d->width * d->height;
-  const float4 *in = reinterpret_cast<const float4*>(d->gInput), *alb = reinterpret_cast<const float4*>(d->gAlbedo);
-  float4* out = reinterpret_cast<float4*>(d->gOutput);
-  DevBuf<float4> bin, balb, bout;
+  const C *in = reinterpret_cast<const C*>(d->gInput), *alb = reinterpret_cast<const C*>(d->gAlbedo);
+  C* out = reinterpret_cast<C*>(d->gOutput);
+  DevBuf<C> bin, balb, bout;
   if (!d->device_ptrs) {
     HIP_TRY(ctx, bin.ensure(n));
     HIP_TRY(ctx, bout.ensure(n));
-    HIP_TRY(ctx, hipMemcpyAsync(bin.p, d->gInput, (size_t)n * 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(bin.p, d->gInput, (size_t)n * sizeof(C), hipMemcpyHostToDevice, st));
     in = bin.p;
     out = bout.p;
     if (d->modulate_albedo) {
       HIP_TRY(ctx, balb.ensure(n));
-      HIP_TRY(ctx, hipMemcpyAsync(balb.p, d->gAlbedo, (size_t)n * 16, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, hipMemcpyAsync(balb.p, d->gAlbedo, (size_t)n * sizeof(C), hipMemcpyHostToDevice, st));
       alb = balb.p;
     }
   }
@@ -2499,11 +2537,11 @@ int sthip_tonemap(sthip_ctx* ctx, const sthip_tonemap_desc* d) {
   for (int k = 0; k < 6; k++) prev.v[k] = d->exposure_state ? d->exposure_state[k] : 0.0f;
   float* state_out = d->exposure_state ? reinterpret_cast<float*>(ctx->post_scratch.p + 4) : nullptr;
   const uint32_t grid = (uint32_t)std::min<size_t>(((size_t)n + 255) / 256, (size_t)ctx->cu_count * 16);
-  hipLaunchKernelGGL(k_tonemap_reduce_max, dim3(grid), dim3(256), 0, st, in, alb, n, d->modulate_albedo, ctx->post_scratch.p);
-  hipLaunchKernelGGL(k_tonemap, dim3(grid), dim3(256), 0, st, in, alb, out, n, d->mode, d->modulate_albedo, d->gamma_correction, d->exposure, ctx->post_scratch.p,
+  hipLaunchKernelGGL(k_tonemap_reduce_max<C>, dim3(grid), dim3(256), 0, st, in, alb, n, d->modulate_albedo, ctx->post_scratch.p);
+  hipLaunchKernelGGL(k_tonemap<C>, dim3(grid), dim3(256), 0, st, in, alb, out, n, d->mode, d->modulate_albedo, d->gamma_correction, d->exposure, ctx->post_scratch.p,
                      d->exposure_state ? d->exposure_alpha : 0.0f, prev, state_out);
   HIP_TRY(ctx, hipGetLastError());
-  if (!d->device_ptrs) HIP_TRY(ctx, hipMemcpyAsync(d->gOutput, bout.p, (size_t)n * 16, hipMemcpyDeviceToHost, st));
+  if (!d->device_ptrs) HIP_TRY(ctx, hipMemcpyAsync(d->gOutput, bout.p, (size_t)n * sizeof(C), hipMemcpyDeviceToHost, st));
   if (d->out_max) {
     uint32_t m[4];
     HIP_TRY(ctx, hipMemcpyAsync(m, ctx->post_scratch.p, 16, hipMemcpyDeviceToHost, st));
@@ -2518,6 +2556,7 @@ int sthip_tonemap(sthip_ctx* ctx, const sthip_tonemap_desc* d) {
   }
   return STHIP_OK;
 }
+}  // extern "C++"
 
 int sthip_image_compare(sthip_ctx* ctx, const float* image1, const float* image2, uint32_t width, uint32_t height, uint32_t metric, uint32_t quantization, uint32_t device_ptrs,
                         uint32_t* sum_out, uint32_t* overflow_out) {
@@ -2525,22 +2564,29 @@ int sthip_image_compare(sthip_ctx* ctx, const float* image1, const float* image2
   if (!image1 || !image2 || !sum_out || width == 0 || height == 0) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_image_compare: two images, sum_out and a non-empty extent are required");
   if (metric > 2) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_image_compare: unknown metric " + std::to_string(metric));
   if ((uint64_t)width * height * 3 > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_image_compare: extent too large");
+  return ctx->half_color ? compare_images<Half4>(ctx, image1, image2, width, height, metric, quantization, device_ptrs, sum_out, overflow_out)
+                         : compare_images<float4>(ctx, image1, image2, width, height, metric, quantization, device_ptrs, sum_out, overflow_out);
+}
+extern "C++" {
+template <typename C>
+static int compare_images(sthip_ctx* ctx, const float* image1, const float* image2, uint32_t width, uint32_t height, uint32_t metric, uint32_t quantization, uint32_t device_ptrs,
+                          uint32_t* sum_out, uint32_t* overflow_out) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const uint32_t n = width * height;
-  const float4 *a = reinterpret_cast<const float4*>(image1), *b = reinterpret_cast<const float4*>(image2);
-  DevBuf<float4> ba, bb;
+  const C *a = reinterpret_cast<const C*>(image1), *b = reinterpret_cast<const C*>(image2);
+  DevBuf<C> ba, bb;
   if (!device_ptrs) {
     HIP_TRY(ctx, ba.ensure(n));
     HIP_TRY(ctx, bb.ensure(n));
-    HIP_TRY(ctx, hipMemcpyAsync(ba.p, image1, (size_t)n * 16, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(bb.p, image2, (size_t)n * 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ba.p, image1, (size_t)n * sizeof(C), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(bb.p, image2, (size_t)n * sizeof(C), hipMemcpyHostToDevice, st));
     a = ba.p;
     b = bb.p;
   }
   HIP_TRY(ctx, ctx->post_scratch.ensure(4));
   HIP_TRY(ctx, hipMemsetAsync(ctx->post_scratch.p, 0, 16, st));
-  hipLaunchKernelGGL(k_image_compare, dim3((n + 63) / 64), dim3(64), 0, st, a, b, n, metric, quantization, ctx->post_scratch.p);
+  hipLaunchKernelGGL(k_image_compare<C>, dim3((n + 63) / 64), dim3(64), 0, st, a, b, n, metric, quantization, ctx->post_scratch.p);
   HIP_TRY(ctx, hipGetLastError());
   uint32_t r[2];
   HIP_TRY(ctx, hipMemcpyAsync(r, ctx->post_scratch.p, 8, hipMemcpyDeviceToHost, st));
@@ -2549,6 +2595,7 @@ int sthip_image_compare(sthip_ctx* ctx, const float* image1, const float* image2
   if (overflow_out) *overflow_out = r[1];
   return STHIP_OK;
 }
+}  // extern "C++"
 
 // ---- measured ceilings for the roofline (ceilings.h) ----
 int sthip_measure_ceiling(sthip_ctx* ctx, uint32_t kind, double* gbytes_per_s) {

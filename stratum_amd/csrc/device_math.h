@@ -115,3 +115,19 @@ DEV float ray_plane(f3 origin, f3 dir, f3 normal) {
   if (fabsf(denom) > 0) return -dot3(origin, normal) / denom;
   return __builtin_inff();
 }
+
+// Colour images in RGBA16F ("half_color_precision", sthip.h): one pixel is four IEEE binary16 words, x in the low half of the
+// first 32-bit word, so the pixel moves as one 8-byte load / store. Conversion is det_f32tof16 / det_f16tof32 (round to nearest
+// even, the arithmetic contract); everything between a load and a store stays binary32.
+struct alignas(8) Half4 {
+  uint32_t xy, zw;
+};
+DEV float4 load_px(const float4* img, size_t i) { return img[i]; }
+DEV float4 load_px(const Half4* img, size_t i) {
+  const uint2 u = reinterpret_cast<const uint2*>(img)[i];
+  return make_float4(det_f16tof32(u.x & 0xFFFFu), det_f16tof32(u.x >> 16), det_f16tof32(u.y & 0xFFFFu), det_f16tof32(u.y >> 16));
+}
+DEV void store_px(float4* img, size_t i, float4 v) { img[i] = v; }
+DEV void store_px(Half4* img, size_t i, float4 v) {
+  reinterpret_cast<uint2*>(img)[i] = make_uint2(det_f32tof16(v.x) | (det_f32tof16(v.y) << 16), det_f32tof16(v.z) | (det_f32tof16(v.w) << 16));
+}

@@ -65,7 +65,7 @@ struct FrameParams {
   // writes it back), and — inline shadow rays only — what an unoccluded shadow ray adds to it, beside the ray's record
   uint32_t debug_mode;
   float4* debug;
-  float4* out_debug;
+  void* out_debug;     // a colour image: RGBA32F, or RGBA16F with out_half (load_color / store_color)
   float4* shadow_debug;
   uint32_t* hit_leaf;  // the hit triangle's index in the leaf-triangle array (RayHit::leaf): where k_shade reads its vertices
   float4* beta;        // xyz beta, w = bits(rng counter)
@@ -152,13 +152,16 @@ struct FrameParams {
   uint32_t seg_stride;           // entries between the segments of queue[]
   uint32_t rounds;               // bounce rounds of this render (<= 63)
   // outputs (device pointers; may be null)
-  float4* out_radiance;
-  float4* out_albedo;
+  void* out_radiance;  // a colour image (as out_debug): RGBA32F, or RGBA16F with out_half
+  float4* out_albedo;  // binary32 always: with out_half a stage that k_resolve rounds into out_albedo16
   sthip_VisibilityInfo* out_visibility;
   sthip_DepthInfo* out_depth;
   float2* out_prev_uv;
   uint32_t write_aov;
   uint32_t out_packed;       // out_radiance holds this shard's tiles in slot order instead of the W x H image
+  uint32_t out_half;         // "half_color_precision": the colour images are RGBA16F (a runtime field: no extra k_shade instantiations)
+  Half4* out_albedo16;       // with out_half: the caller's albedo image. k_shade's first-hit stores stay binary32 (into out_albedo), so
+                             // its registers are those of the binary32 build; k_resolve's last pass rounds every owned pixel once
   uint32_t count_traversal;
   uint32_t refill_idle;      // persistent trace kernels: refill when this many lanes of a wave are idle
   uint32_t inner_min_lanes;  // leave the inner-node loop when fewer lanes than this are still walking
@@ -168,6 +171,17 @@ struct FrameParams {
   uint32_t emitter_count;                // 0: the last-ray filter of k_shade is off
   uint32_t no_specular;                  // no material of the scene is specular: the diffuse budget ends every path that reaches it
 };
+// every access to a colour image of FrameParams (out_radiance, out_debug; out_albedo16 is written in k_resolve): RGBA32F, or with half = out_half RGBA16F,
+// one 8-byte word pair of det_f32tof16 halves per pixel (device_math.h: Half4); rounded where the value leaves, read back exactly
+DEV float4 load_color(const void* img, size_t i, uint32_t half) {
+  return half ? load_px(reinterpret_cast<const Half4*>(img), i) : load_px(reinterpret_cast<const float4*>(img), i);
+}
+DEV void store_color(void* img, size_t i, float4 v, uint32_t half) {
+  if (half)
+    store_px(reinterpret_cast<Half4*>(img), i, v);
+  else
+    store_px(reinterpret_cast<float4*>(img), i, v);
+}
 // One emissive triangle instance: the box of its vertices in the space the traversal tests its triangles in (world space for an
 // instance with identity transforms, the instance's object space otherwise) and a sphere around it that sizes the per-ray
 // padding of the slab test exactly as the traversal's own boxes are padded (setup_space).
@@ -284,7 +298,7 @@ inline __global__ void __launch_bounds__(STHIP_BLOCK) k_generate(FrameParams p) 
       if (view_index >= 0) p.meta[slot] = 0xFFFFFFFEu;  // inside a view but gMaxPathVertices < 2: radiance stays 0
       if (p.debug_mode && view_index >= 0) {
         const bool clears = p.debug_mode == STHIP_DEBUG_PATH_LENGTH_CONTRIBUTION || p.debug_mode == STHIP_DEBUG_VIEW_TRACE_CONTRIBUTION;
-        p.debug[slot] = clears ? make_float4(0, 0, 0, 1) : p.out_debug[(size_t)py * p.pc.gOutputExtent[0] + px];
+        p.debug[slot] = clears ? make_float4(0, 0, 0, 1) : load_color(p.out_debug, (size_t)py * p.pc.gOutputExtent[0] + px, p.out_half);
       }
       continue;
     }
@@ -309,7 +323,7 @@ inline __global__ void __launch_bounds__(STHIP_BLOCK) k_generate(FrameParams p) 
     p.meta[slot] = 1u;  // path_length = 1, diffuse_vertices = 0
     if (p.debug_mode) {  // bdpt.hlsl:161-162: two modes start from (0,0,0,1), the others from what the image holds
       const bool clears = p.debug_mode == STHIP_DEBUG_PATH_LENGTH_CONTRIBUTION || p.debug_mode == STHIP_DEBUG_VIEW_TRACE_CONTRIBUTION;
-      p.debug[slot] = clears ? make_float4(0, 0, 0, 1) : p.out_debug[(size_t)py * p.pc.gOutputExtent[0] + px];
+      p.debug[slot] = clears ? make_float4(0, 0, 0, 1) : load_color(p.out_debug, (size_t)py * p.pc.gOutputExtent[0] + px, p.out_half);
     }
     if (p.media) {  // bdpt.hlsl:208: the medium the camera sits in
       p.media_state[2 * (size_t)slot] = make_float4(t.r0.w, t.r1.w, t.r2.w, 1.0f);
@@ -3233,6 +3247,10 @@ inline __global__ void __launch_bounds__(STHIP_BLOCK) k_resolve(FrameParams p, u
     uint32_t px, py;
     const bool inside = slot_to_pixel(p, q, px, py);
     if (!inside) continue;
+    if (last_seed && p.out_albedo16) {  // half colour precision: the first hit's albedo, rounded once (zero where nothing wrote it)
+      const size_t i = (size_t)py * p.pc.gOutputExtent[0] + px;
+      store_px(p.out_albedo16, i, p.out_albedo[i]);
+    }
     if (p.meta[q] == 0xFFFFFFFFu) {
       // no view covers the pixel: sample_visibility returned at once, but add_light_trace runs for every pixel of the image
       // (bdpt.hlsl:328-338) and, in two debug modes, writes what it loaded — nothing, no splat lands outside the views — there
@@ -3244,7 +3262,7 @@ inline __global__ void __launch_bounds__(STHIP_BLOCK) k_resolve(FrameParams p, u
           lc = F3((float)((v.w & 1u) ? 0xFFFFFFFFu : v.x), (float)((v.w & 2u) ? 0xFFFFFFFFu : v.y), (float)((v.w & 4u) ? 0xFFFFFFFFu : v.z)) / qq;
           if (lc.x < 0 || lc.y < 0 || lc.z < 0 || any_nan(lc)) lc = F3s(0.0f);
         }
-        p.out_debug[(size_t)py * p.pc.gOutputExtent[0] + px] = make_float4(lc.x, lc.y, lc.z, 1);
+        store_color(p.out_debug, (size_t)py * p.pc.gOutputExtent[0] + px, make_float4(lc.x, lc.y, lc.z, 1), p.out_half);
       }
       continue;
     }
@@ -3288,7 +3306,7 @@ inline __global__ void __launch_bounds__(STHIP_BLOCK) k_resolve(FrameParams p, u
       if (p.light_trace_empty && p.debug_mode != STHIP_DEBUG_VIEW_TRACE_CONTRIBUTION &&
           (p.debug_mode == STHIP_DEBUG_LIGHT_TRACE_CONTRIBUTION || (p.debug_mode == STHIP_DEBUG_PATH_LENGTH_CONTRIBUTION && p.pc.gDebugViewPathLength == 1)))
         p.debug[slot] = make_float4(0, 0, 0, 1);
-      if (p.debug_mode) p.out_debug[(size_t)py * p.pc.gOutputExtent[0] + px] = p.debug[slot];  // (one seed in flight: the seeds of a call are upstream's successive frames)
+      if (p.debug_mode) store_color(p.out_debug, (size_t)py * p.pc.gOutputExtent[0] + px, p.debug[slot], p.out_half);  // (one seed in flight: the seeds of a call are upstream's successive frames)
       if (isinf(cur.x) || isinf(cur.y) || isinf(cur.z) || cur.x != cur.x || cur.y != cur.y || cur.z != cur.z) cur = make_float4(0, 0, 0, 0);
       if (acc.w > 0) {
         const float nn = acc.w + cur.w;
@@ -3302,7 +3320,7 @@ inline __global__ void __launch_bounds__(STHIP_BLOCK) k_resolve(FrameParams p, u
       }
     }
     p.accum[q] = acc;
-    if (last_seed && p.out_radiance) p.out_radiance[p.out_packed ? (size_t)q : (size_t)py * p.pc.gOutputExtent[0] + px] = acc;
+    if (last_seed && p.out_radiance) store_color(p.out_radiance, p.out_packed ? (size_t)q : (size_t)py * p.pc.gOutputExtent[0] + px, acc, p.out_half);
   }
 }
 #endif

@@ -87,12 +87,17 @@ DEV float aces_approx1(float v) {
   return saturate1((v * (2.51f * v + 0.03f)) / (v * (2.43f * v + 0.59f) + 0.14f));
 }
 
+// The colour images of these kernels are C = float4 (RGBA32F) or Half4 (RGBA16F, "half_color_precision"): both forms are
+// instantiated. A Half4 image is read exactly and rounded only where the kernel stores (load_px / store_px, device_math.h);
+// everything in between, the maxima and the moments included, is the binary32 arithmetic of the float4 form.
+
 // reduce_max, tonemap.hlsl:106-153: per-channel and luminance maxima, quantised so that InterlockedMax works on uints
-__global__ void k_tonemap_reduce_max(const float4* input, const float4* albedo, uint32_t n, uint32_t modulate, uint32_t* gmax) {
+template <typename C>
+__global__ void k_tonemap_reduce_max(const C* input, const C* albedo, uint32_t n, uint32_t modulate, uint32_t* gmax) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    float4 v = input[i];
+    float4 v = load_px(input, i);
     if (modulate) {
-      const float4 a = albedo[i];
+      const float4 a = load_px(albedo, i);
       v.x *= a.x;
       v.y *= a.y;
       v.z *= a.z;
@@ -112,7 +117,8 @@ __global__ void k_tonemap_reduce_max(const float4* input, const float4* albedo, 
 struct TonemapState {
   float v[6];
 };
-__global__ void k_tonemap(const float4* input, const float4* albedo, float4* output, uint32_t n, uint32_t mode, uint32_t modulate, uint32_t gamma, float exposure, const uint32_t* gmax,
+template <typename C>
+__global__ void k_tonemap(const C* input, const C* albedo, C* output, uint32_t n, uint32_t mode, uint32_t modulate, uint32_t gamma, float exposure, const uint32_t* gmax,
                           float exposure_alpha, TonemapState prev, float* state_out) {
   f3 cur_max = F3((float)gmax[0] / TONEMAP_MAX_QUANTIZATION, (float)gmax[1] / TONEMAP_MAX_QUANTIZATION, (float)gmax[2] / TONEMAP_MAX_QUANTIZATION);
   float cur_max_l = (float)gmax[3] / TONEMAP_MAX_QUANTIZATION;
@@ -138,8 +144,8 @@ __global__ void k_tonemap(const float4* input, const float4* albedo, float4* out
   }
   const float scale = det_expf(exposure * 0.693147180559945f);  // pow(2, gExposure)
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    f3 radiance = xyz(input[i]);
-    if (modulate) radiance = radiance * (F3s(1e-2f) + xyz(albedo[i]));
+    f3 radiance = xyz(load_px(input, i));
+    if (modulate) radiance = radiance * (F3s(1e-2f) + xyz(load_px(albedo, i)));
     radiance = radiance * scale;
     switch (mode) {
       case eReinhard: radiance = tonemap_reinhard(radiance); break;
@@ -155,19 +161,20 @@ __global__ void k_tonemap(const float4* input, const float4* albedo, float4* out
       default: break;
     }
     if (gamma) radiance = F3(rgb_to_srgb1(radiance.x), rgb_to_srgb1(radiance.y), rgb_to_srgb1(radiance.z));
-    output[i] = make_float4(radiance.x, radiance.y, radiance.z, 1.0f);
+    store_px(output, i, make_float4(radiance.x, radiance.y, radiance.z, 1.0f));
   }
 }
 
 // image_compare.hlsl:13-46. The reference sums a wave with WaveActiveSum (order and wave shape are the
 // hardware's); pinned here as: 64 consecutive pixels (row-major) per group, summed in pixel order, truncated to
 // uint after scaling by the quantisation, groups added with an integer atomic (order independent).
-__global__ void __launch_bounds__(64) k_image_compare(const float4* image1, const float4* image2, uint32_t n, uint32_t metric, uint32_t quantization, uint32_t* out) {
+template <typename C>
+__global__ void __launch_bounds__(64) k_image_compare(const C* image1, const C* image2, uint32_t n, uint32_t metric, uint32_t quantization, uint32_t* out) {
   __shared__ float err[64];
   const uint32_t i = blockIdx.x * 64 + threadIdx.x;
   float error = 0;
   if (i < n) {
-    const f3 c1 = xyz(image1[i]), c2 = xyz(image2[i]);
+    const f3 c1 = xyz(load_px(image1, i)), c2 = xyz(load_px(image2, i));
     const f3 d = c1 - c2;
     if (metric == 0) {  // eSMAPE
       const f3 q = F3(fabsf(d.x) / (fabsf(c1.x) + fabsf(c2.x)), fabsf(d.y) / (fabsf(c1.y) + fabsf(c2.y)), fabsf(d.z) / (fabsf(c1.z) + fabsf(c2.z)));
@@ -204,20 +211,21 @@ struct AccumulateParams {
   uint32_t instance_count;
   const sthip_ViewData* views;  // device array, or null: the views travel in `inline_views` (up to ACCUMULATE_INLINE_VIEWS: no staging, no wait)
   sthip_ViewData inline_views[4];
-  const float4* radiance;
-  const float4* albedo;
+  const void* radiance;  // colour images (albedo, prev_accum_color, accum_color too): k_accumulate<C>'s C
+  const void* albedo;
   const sthip_VisibilityInfo* visibility;
   const sthip_DepthInfo* depth;
   const float2* prev_uvs;
   const sthip_VisibilityInfo* prev_visibility;
   const sthip_DepthInfo* prev_depth;
-  const float4* prev_accum_color;
+  const void* prev_accum_color;
   const float2* prev_accum_moments;
   const uint32_t* instance_index_map;  // may be null: identity
-  float4* accum_color;
+  void* accum_color;
   float2* accum_moments;
 };
 DEV bool bad4(float4 c) { return c.x != c.x || c.y != c.y || c.z != c.z || c.w != c.w || isinf(c.x) || isinf(c.y) || isinf(c.z) || isinf(c.w); }
+template <typename C>
 __global__ void __launch_bounds__(256) k_accumulate(AccumulateParams p) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.width * p.height) return;
@@ -262,7 +270,7 @@ __global__ void __launch_bounds__(256) k_accumulate(AccumulateParams p) {
           if (mapped != (pv.instance_primitive_index & 0xFFFFu)) continue;
           if (dot3(n, unpack_normal_octahedron(pv.packed_normal)) < cd) continue;
           if (fabsf(depth.prev_z - p.prev_depth[q].z) >= 1.5f * dz) continue;
-          const float4 c = p.prev_accum_color[q];
+          const float4 c = load_px(static_cast<const C*>(p.prev_accum_color), q);
           if (c.w <= 0 || bad4(c)) continue;
           const float wc = (xx == 0 ? (1 - wx) : wx) * (yy == 0 ? (1 - wy) : wy);
           color_prev.x += c.x * wc;
@@ -276,16 +284,16 @@ __global__ void __launch_bounds__(256) k_accumulate(AccumulateParams p) {
         }
     }
   } else {
-    color_prev = p.prev_accum_color[i];
+    color_prev = load_px(static_cast<const C*>(p.prev_accum_color), i);
     if (color_prev.x != color_prev.x || color_prev.y != color_prev.y || color_prev.z != color_prev.z || isinf(color_prev.x) || isinf(color_prev.y) || isinf(color_prev.z))
       color_prev = make_float4(0, 0, 0, 0);
     else
       moments_prev = p.prev_accum_moments[i];
     sum_w = 1;
   }
-  float4 color_curr = p.radiance[i];
+  float4 color_curr = load_px(static_cast<const C*>(p.radiance), i);
   if (p.demodulate_albedo) {
-    const float4 a = p.albedo[i];
+    const float4 a = load_px(static_cast<const C*>(p.albedo), i);
     color_curr.x /= (1e-2f + a.x);
     color_curr.y /= (1e-2f + a.y);
     color_curr.z /= (1e-2f + a.z);
@@ -305,10 +313,10 @@ __global__ void __launch_bounds__(256) k_accumulate(AccumulateParams p) {
     float n = color_prev.w + color_curr.w;
     if (p.history_limit > 0 && n > p.history_limit) n = p.history_limit;
     const float alpha = saturate1(color_curr.w / n);
-    p.accum_color[i] = make_float4(lerp1(color_prev.x, color_curr.x, alpha), lerp1(color_prev.y, color_curr.y, alpha), lerp1(color_prev.z, color_curr.z, alpha), n);
+    store_px(static_cast<C*>(p.accum_color), i, make_float4(lerp1(color_prev.x, color_curr.x, alpha), lerp1(color_prev.y, color_curr.y, alpha), lerp1(color_prev.z, color_curr.z, alpha), n));
     p.accum_moments[i] = make_float2(lerp1(moments_prev.x, l, alpha), lerp1(moments_prev.y, l * l, alpha));
   } else {
-    p.accum_color[i] = color_curr;
+    store_px(static_cast<C*>(p.accum_color), i, color_curr);
     p.accum_moments[i] = make_float2(l, l * l);
   }
 }

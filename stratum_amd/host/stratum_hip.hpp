@@ -35,6 +35,7 @@
 #include <dlfcn.h>
 
 #include "../../include/sthip.h"
+#include "../../include/sthip_detmath.h"  // det_f16tof32: export_hdr of a half frame
 
 namespace stm {
 
@@ -822,6 +823,9 @@ class BDPT {
     std::vector<DepthInfo> mDepth;
     uint64_t mRayCount[2] = {0, 0};
     std::vector<float> mDebugImage;  // gDebugImage (BDPT.cpp:560): RGBA32F, only with a debug mode
+    // with set_half_color_precision(true) (mHalfColorPrecision, BDPT.cpp:231,553-558) these RGBA16F images (IEEE binary16 bits)
+    // are filled instead of mRadiance / mAlbedo / mTonemapResult / mDebugImage, which then stay empty
+    std::vector<uint16_t> mRadiance16, mAlbedo16, mTonemapResult16, mDebugImage16;
   };
 
   explicit BDPT(Node& node, int device = 0) : mNode(node) {
@@ -910,11 +914,28 @@ class BDPT {
   float& exposure_alpha() { return mExposureAlpha; }
   bool& gamma_correction() { return mGammaCorrection; }
   // "Export" -> "Save" (BDPT.cpp:313-337): the last frame's radiance as a Radiance .hdr file
+  // (a half frame is upcast exactly, det_f16tof32: the writer takes RGBA32F)
   void export_hdr(const std::string& path) const {
-    if (mPrevFrame.mRadiance.empty()) throw std::runtime_error("BDPT::export_hdr: no frame rendered yet");
-    if (sthip_write_hdr(path.c_str(), mPrevFrame.width, mPrevFrame.height, mPrevFrame.mRadiance.data()) != STHIP_OK)
+    if (mPrevFrame.mRadiance.empty() && mPrevFrame.mRadiance16.empty()) throw std::runtime_error("BDPT::export_hdr: no frame rendered yet");
+    std::vector<float> up;
+    if (mPrevFrame.mRadiance.empty()) {
+      up.resize(mPrevFrame.mRadiance16.size());
+      for (size_t i = 0; i < up.size(); i++) up[i] = det_f16tof32(mPrevFrame.mRadiance16[i]);
+    }
+    if (sthip_write_hdr(path.c_str(), mPrevFrame.width, mPrevFrame.height, up.empty() ? mPrevFrame.mRadiance.data() : up.data()) != STHIP_OK)
       throw std::runtime_error("BDPT::export_hdr: cannot write " + path);
   }
+  // the inspector's "Half precision" (BDPT.cpp:231, mHalfColorPrecision): radiance, albedo, debug and tone-map images in RGBA16F
+  // (include/sthip.h "half_color_precision"); a change drops the persisted debug image, as a change of the debug mode does
+  virtual void set_half_color_precision(bool on) {
+    if (sthip_set_option(mCtx, "half_color_precision", on ? 1 : 0) != STHIP_OK) throw std::runtime_error(std::string("half_color_precision: ") + sthip_last_error(mCtx));
+    if (on != mHalfColorPrecision) {
+      mDebugImage.clear();
+      mDebugImage16.clear();
+    }
+    mHalfColorPrecision = on;
+  }
+  bool half_color_precision() const { return mHalfColorPrecision; }
 
   // BDPT::update (BDPT.cpp:341-421): (re)bind the scene when Scene::update produced new SceneData
   virtual void update(CommandBuffer& cb, float) {
@@ -1016,22 +1037,34 @@ class BDPT {
     fr.width = width;
     fr.height = height;
     const size_t n = (size_t)width * height;
-    fr.mRadiance.assign(4 * n, 0.f);
-    fr.mAlbedo.assign(4 * n, 0.f);
     fr.mPrevUVs.assign(2 * n, 0.f);
     fr.mVisibility.assign(n, VisibilityInfo{});
     fr.mDepth.assign(n, DepthInfo{});
     sthip_outputs o{};
-    o.gRadiance = fr.mRadiance.data();
-    o.gAlbedo = fr.mAlbedo.data();
+    if (mHalfColorPrecision) {  // the float* of the ABI points at halves
+      fr.mRadiance16.assign(4 * n, 0);
+      fr.mAlbedo16.assign(4 * n, 0);
+      o.gRadiance = reinterpret_cast<float*>(fr.mRadiance16.data());
+      o.gAlbedo = reinterpret_cast<float*>(fr.mAlbedo16.data());
+    } else {
+      fr.mRadiance.assign(4 * n, 0.f);
+      fr.mAlbedo.assign(4 * n, 0.f);
+      o.gRadiance = fr.mRadiance.data();
+      o.gAlbedo = fr.mAlbedo.data();
+    }
     o.gVisibility = fr.mVisibility.data();
     o.gDepth = fr.mDepth.data();
     o.gPrevUVs = fr.mPrevUVs.data();
     o.gRayCount = fr.mRayCount;
     if (mDebugMode != STHIP_DEBUG_NONE) {  // BDPT.cpp:526-541 (gDebugMode), :560: the image persists from frame to frame
-      if (mDebugImage.size() != 4 * n) mDebugImage.assign(4 * n, 0.f);
       o.debug_mode = mDebugMode;
-      o.gDebugImage = mDebugImage.data();
+      if (mHalfColorPrecision) {
+        if (mDebugImage16.size() != 4 * n) mDebugImage16.assign(4 * n, 0);
+        o.gDebugImage = reinterpret_cast<float*>(mDebugImage16.data());
+      } else {
+        if (mDebugImage.size() != 4 * n) mDebugImage.assign(4 * n, 0.f);
+        o.gDebugImage = mDebugImage.data();
+      }
     }
     (void)sthip_set_stream(mCtx, cb.hip_stream);
     // BDPT.cpp:474,482-483: a frame whose first camera moved since the last one reuses nothing (gReservoirSpatialM = 0) unless the
@@ -1040,13 +1073,21 @@ class BDPT {
     if (changed && !mReprojection) (void)sthip_set_option(mCtx, "reuse_grids_persist", 1);
     if (sthip_render(mCtx, &pc, mSamplingFlags, scene_flags, &f, mFrameNumber, seed_count, &o) != STHIP_OK)
       throw std::runtime_error(std::string("sthip_render: ") + sthip_last_error(mCtx));
-    if (mDebugMode != STHIP_DEBUG_NONE) fr.mDebugImage = mDebugImage;
+    if (mDebugMode != STHIP_DEBUG_NONE) {
+      if (mHalfColorPrecision)
+        fr.mDebugImage16 = mDebugImage16;
+      else
+        fr.mDebugImage = mDebugImage;
+    }
     finish_frame(std::move(fr), fs, seed_count);
   }
   // BDPTDebugMode (bdpt.h:177-193; the inspector's "Debug mode", BDPT.cpp:253-262) with mPushConstants.gDebugViewPathLength /
   // gDebugLightPathLength; the image starts from zero when the mode or the frame size changes
   void set_debug_mode(uint32_t mode) {
-    if (mode != mDebugMode) mDebugImage.clear();
+    if (mode != mDebugMode) {
+      mDebugImage.clear();
+      mDebugImage16.clear();
+    }
     mDebugMode = mode < STHIP_DEBUG_MODE_COUNT ? mode : (uint32_t)STHIP_DEBUG_NONE;
   }
   uint32_t debug_mode() const { return mDebugMode; }
@@ -1067,10 +1108,21 @@ class BDPT {
   void finish_frame(Frame fr, const FrameSetup& fs, uint32_t seed_count, bool noted_at_submit = false) {
     const uint32_t width = fr.width, height = fr.height;
     const size_t n = (size_t)width * height;
-    if (fr.mAlbedo.size() != 4 * n) fr.mAlbedo.assign(4 * n, 0.f);
     // tone map (BDPT.cpp:783-815); without a denoiser gModulateAlbedo stays off (:779-780 only run when one exists)
-    fr.mTonemapResult.assign(4 * n, 0.f);
     sthip_tonemap_desc tm{};
+    if (mHalfColorPrecision) {  // (the context's option makes all three images RGBA16F)
+      if (fr.mAlbedo16.size() != 4 * n) fr.mAlbedo16.assign(4 * n, 0);
+      fr.mTonemapResult16.assign(4 * n, 0);
+      tm.gInput = reinterpret_cast<const float*>(fr.mDebugImage16.size() == 4 * n ? fr.mDebugImage16.data() : fr.mRadiance16.data());
+      tm.gAlbedo = reinterpret_cast<const float*>(fr.mAlbedo16.data());
+      tm.gOutput = reinterpret_cast<float*>(fr.mTonemapResult16.data());
+    } else {
+      if (fr.mAlbedo.size() != 4 * n) fr.mAlbedo.assign(4 * n, 0.f);
+      fr.mTonemapResult.assign(4 * n, 0.f);
+      tm.gInput = fr.mDebugImage.size() == 4 * n ? fr.mDebugImage.data() : fr.mRadiance.data();  // BDPT.cpp:764: with a debug mode the debug image is what is shown
+      tm.gAlbedo = fr.mAlbedo.data();
+      tm.gOutput = fr.mTonemapResult.data();
+    }
     tm.width = width;
     tm.height = height;
     tm.mode = mTonemapMode;
@@ -1079,9 +1131,6 @@ class BDPT {
     tm.exposure = mExposure;
     tm.exposure_alpha = mExposureAlpha;       // gExposureAlpha, BDPT.cpp:51,192,307
     tm.exposure_state = mTonemapState;        // mPrevFrame->mTonemapMax bytes 16..39 -> gPrevMax, BDPT.cpp:810-811
-    tm.gInput = fr.mDebugImage.size() == 4 * n ? fr.mDebugImage.data() : fr.mRadiance.data();  // BDPT.cpp:764: with a debug mode the debug image is what is shown
-    tm.gAlbedo = fr.mAlbedo.data();
-    tm.gOutput = fr.mTonemapResult.data();
     tm.out_max = fr.mTonemapMax;
     if (sthip_tonemap(mCtx, &tm) != STHIP_OK) throw std::runtime_error(std::string("sthip_tonemap: ") + sthip_last_error(mCtx));
     if (!noted_at_submit) note_submitted(fs, seed_count);
@@ -1114,6 +1163,8 @@ class BDPT {
   uint32_t mDebugMode = STHIP_DEBUG_NONE;
   bool mReprojection = false;
   std::vector<float> mDebugImage;
+  bool mHalfColorPrecision = false;  // BDPT.cpp:231
+  std::vector<uint16_t> mDebugImage16;  // mDebugImage while mHalfColorPrecision is on
   uint32_t mTonemapMode = STHIP_TONEMAP_RAW;  // BDPT.cpp:48
   float mExposure = 0;
   float mExposureAlpha = 0;

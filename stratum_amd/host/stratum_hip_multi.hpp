@@ -192,8 +192,18 @@ class MultiDeviceBDPT : public BDPT {
   size_t world() const { return mRanks.size(); }
   void gather_aovs(bool on) { mGatherAOVs = on; }  // also exchange albedo / visibility / depth / prev-uv (default on)
   void split_seeds(bool on) {                       // replicas of the whole frame over disjoint seed ranges + one sum-reduce, instead of tiles + a gather
+    if (on && mHalfColorPrecision) throw std::runtime_error(kHalfSeedSplit);
     flush();
     mSplitSeeds = on;
+  }
+  // half colour precision on every rank's context: tiles travel as 8-byte radiance / albedo entries and the frame stays
+  // bit-identical to the one-GPU half frame; the seed split cannot have it (sthip_radiance_to_sums refuses it)
+  void set_half_color_precision(bool on) override {
+    if (on && mSplitSeeds) throw std::runtime_error(kHalfSeedSplit);
+    flush();
+    for (size_t r = 1; r < mRanks.size(); r++)
+      if (sthip_set_option(mRanks[r].ctx, "half_color_precision", on ? 1 : 0) != STHIP_OK) throw std::runtime_error(std::string("half_color_precision: ") + sthip_last_error(mRanks[r].ctx));
+    BDPT::set_half_color_precision(on);  // (rank 0's context)
   }
   void read_back(bool on) { mReadBack = on; }       // false: prev_result() carries the ray counts only, the images stay on devices[0]
   void pipelined(bool on) {
@@ -288,7 +298,7 @@ class MultiDeviceBDPT : public BDPT {
           const void* img[4] = {b.img_albedo, b.img_visibility, b.img_depth, b.img_prev_uv};
           void* pk[4] = {b.albedo, b.visibility, b.depth, b.prev_uv};
           for (int a = 0; a < 4; a++)
-            if (sthip_pack_tiles(rk.ctx, img[a], width, height, kEntryBytes[a + 1], pk[a]) != STHIP_OK) throw std::runtime_error(std::string("sthip_pack_tiles: ") + sthip_last_error(rk.ctx));
+            if (sthip_pack_tiles(rk.ctx, img[a], width, height, (uint32_t)entry_bytes(a + 1), pk[a]) != STHIP_OK) throw std::runtime_error(std::string("sthip_pack_tiles: ") + sthip_last_error(rk.ctx));
         }
       }
       check_hip(hipMemcpyAsync(rk.ray_count[k], b.counters, 16, hipMemcpyDeviceToHost, rk.stream), "hipMemcpyAsync");
@@ -314,7 +324,7 @@ class MultiDeviceBDPT : public BDPT {
             const int parts = mGatherAOVs ? 5 : 1;
             check_nccl(ncclGroupStart(), "ncclGroupStart");
             for (int a = 0; a < parts; a++) {
-              const size_t bytes = stride * kEntryBytes[a];
+              const size_t bytes = stride * entry_bytes(a);
               check_nccl(ncclSend(src[a], bytes, ncclChar, 0, use.comm, rk.comm_stream), "ncclSend");
               if (r == 0)
                 for (size_t q = 0; q < mRanks.size(); q++) check_nccl(ncclRecv((char*)dst[a] + q * bytes, bytes, ncclChar, (int)q, use.comm, rk.comm_stream), "ncclRecv");
@@ -362,6 +372,10 @@ class MultiDeviceBDPT : public BDPT {
 
  private:
   static constexpr size_t kEntryBytes[5] = {16, 16, 8, 16, 8};  // radiance, albedo, VisibilityInfo, DepthInfo, prev-uv
+  // what an entry of part a weighs now: radiance and albedo are 8-byte RGBA16F with half colour precision (the buffers below are
+  // sized for kEntryBytes, enough for either precision, so that switching needs no reallocation)
+  size_t entry_bytes(int a) const { return a < 2 && mHalfColorPrecision ? 8 : kEntryBytes[a]; }
+  static constexpr const char* kHalfSeedSplit = "split_seeds: not with half colour precision (a sum of rounded means is not a rounded mean; tile sharding is exact)";
   struct Buffers {  // one set per frame in flight, per rank: packed tiles (what travels) and the G-buffer images sthip_render writes
     void *radiance = nullptr, *albedo = nullptr, *visibility = nullptr, *depth = nullptr, *prev_uv = nullptr;
     void *img_albedo = nullptr, *img_visibility = nullptr, *img_depth = nullptr, *img_prev_uv = nullptr;
@@ -473,21 +487,35 @@ class MultiDeviceBDPT : public BDPT {
       void* dst[5] = {mFrameDev.radiance, mFrameDev.albedo, mFrameDev.visibility, mFrameDev.depth, mFrameDev.prev_uv};
       const int parts = aovs ? 5 : 1;
       for (int a = 0; a < parts; a++)
-        if (sthip_assemble_tiles_bytes(r0.ctx, src[a], stride, (uint32_t)mRanks.size(), mTileW, mTileH, width, height, (uint32_t)kEntryBytes[a], dst[a]) != STHIP_OK)
+        if (sthip_assemble_tiles_bytes(r0.ctx, src[a], stride, (uint32_t)mRanks.size(), mTileW, mTileH, width, height, (uint32_t)entry_bytes(a), dst[a]) != STHIP_OK)
           throw std::runtime_error(sthip_last_error(r0.ctx));
     }
     Frame fr;
     fr.width = width;
     fr.height = height;
     if (mReadBack) {
-      fr.mRadiance.assign(4 * pixels, 0.f);
-      check_hip(hipMemcpyAsync(fr.mRadiance.data(), mFrameDev.radiance, pixels * 16, hipMemcpyDeviceToHost, r0.comm_stream), "hipMemcpyAsync");
+      void* rad_host = nullptr;
+      void* alb_host = nullptr;
+      if (mHalfColorPrecision) {
+        fr.mRadiance16.assign(4 * pixels, 0);
+        rad_host = fr.mRadiance16.data();
+      } else {
+        fr.mRadiance.assign(4 * pixels, 0.f);
+        rad_host = fr.mRadiance.data();
+      }
+      check_hip(hipMemcpyAsync(rad_host, mFrameDev.radiance, pixels * entry_bytes(0), hipMemcpyDeviceToHost, r0.comm_stream), "hipMemcpyAsync");
       if (aovs) {
-        fr.mAlbedo.assign(4 * pixels, 0.f);
+        if (mHalfColorPrecision) {
+          fr.mAlbedo16.assign(4 * pixels, 0);
+          alb_host = fr.mAlbedo16.data();
+        } else {
+          fr.mAlbedo.assign(4 * pixels, 0.f);
+          alb_host = fr.mAlbedo.data();
+        }
         fr.mVisibility.assign(pixels, VisibilityInfo{});
         fr.mDepth.assign(pixels, DepthInfo{});
         fr.mPrevUVs.assign(2 * pixels, 0.f);
-        check_hip(hipMemcpyAsync(fr.mAlbedo.data(), mFrameDev.albedo, pixels * 16, hipMemcpyDeviceToHost, r0.comm_stream), "hipMemcpyAsync");
+        check_hip(hipMemcpyAsync(alb_host, mFrameDev.albedo, pixels * entry_bytes(1), hipMemcpyDeviceToHost, r0.comm_stream), "hipMemcpyAsync");
         check_hip(hipMemcpyAsync(fr.mVisibility.data(), mFrameDev.visibility, pixels * 8, hipMemcpyDeviceToHost, r0.comm_stream), "hipMemcpyAsync");
         check_hip(hipMemcpyAsync(fr.mDepth.data(), mFrameDev.depth, pixels * 16, hipMemcpyDeviceToHost, r0.comm_stream), "hipMemcpyAsync");
         check_hip(hipMemcpyAsync(fr.mPrevUVs.data(), mFrameDev.prev_uv, pixels * 8, hipMemcpyDeviceToHost, r0.comm_stream), "hipMemcpyAsync");

@@ -1,7 +1,10 @@
 """What the reference does with the renderer's output, on the GPU: the tone-map block of BDPT::render
 (src/Node/BDPT.cpp:783-815 -> kernels/tonemap.hlsl), the ImageComparer node (src/Node/ImageComparer.cpp:61-90 ->
 kernels/image_compare.hlsl) and the "Export HDR" button (BDPT.cpp:313-337). Thin host code over the C ABI
-(sthip_tonemap / sthip_image_compare / sthip_write_hdr); there is no CPU implementation behind it."""
+(sthip_tonemap / sthip_image_compare / sthip_write_hdr); there is no CPU implementation behind it.
+The colour images follow the renderer's precision (BDPT.set_half_color_precision): np.float16 in and out while it is on,
+np.float32 otherwise; luminance moments, maxima and sums are float32 either way. write_hdr always takes float32 (a
+float16 image is upcast exactly)."""
 import ctypes as C
 
 import numpy as np
@@ -17,18 +20,19 @@ def _mode(table, m):
     return int(m)
 
 
-def _rgba(a, name):
-    a = np.ascontiguousarray(a, dtype=np.float32)
+def _rgba(a, name, dtype=np.float32):
+    a = np.ascontiguousarray(a, dtype=dtype)
     if a.ndim != 3 or a.shape[2] != 4:
-        raise ValueError("%s must be an (H, W, 4) float32 image" % name)
+        raise ValueError("%s must be an (H, W, 4) %s image" % (name, np.dtype(dtype).name))
     return a
 
 
-def accumulate_desc(frame_out, history, views, reprojection, demodulate_albedo, history_limit, instance_index_map, keep):
+def accumulate_desc(frame_out, history, views, reprojection, demodulate_albedo, history_limit, instance_index_map, keep, color_dtype=np.float32):
     """Fills a wire.AccumulateDesc from a render's output dict (`frame_out`: radiance, albedo, visibility, depth,
     prev_uv) and the previous state (`history`: accum_color, accum_moments, visibility, depth). `keep` receives the
-    arrays the descriptor points at. Returns (desc, accum_color, accum_moments)."""
-    rad = _rgba(frame_out["radiance"], "radiance")
+    arrays the descriptor points at. Returns (desc, accum_color, accum_moments). color_dtype: np.float16 for a context
+    with half_color_precision on (radiance, albedo and both accumulated colours are RGBA16F there)."""
+    rad = _rgba(frame_out["radiance"], "radiance", color_dtype)
     H, W = rad.shape[0], rad.shape[1]
     d = wire.AccumulateDesc()
     d.width, d.height = W, H
@@ -38,18 +42,18 @@ def accumulate_desc(frame_out, history, views, reprojection, demodulate_albedo, 
     d.demodulate_albedo = int(bool(demodulate_albedo))
     d.history_limit = float(history_limit)
     d.device_ptrs = 0
-    out_c = np.zeros((H, W, 4), np.float32)
+    out_c = np.zeros((H, W, 4), color_dtype)
     out_m = np.zeros((H, W, 2), np.float32)
     arrays = {
         "gViews": v,
         "gRadiance": rad,
-        "gAlbedo": np.ascontiguousarray(frame_out["albedo"], np.float32) if "albedo" in frame_out else None,
+        "gAlbedo": np.ascontiguousarray(frame_out["albedo"], color_dtype) if "albedo" in frame_out else None,
         "gVisibility": np.ascontiguousarray(frame_out["visibility"], wire.VisibilityInfo) if "visibility" in frame_out else None,
         "gDepth": np.ascontiguousarray(frame_out["depth"], wire.DepthInfo) if "depth" in frame_out else None,
         "gPrevUVs": np.ascontiguousarray(frame_out["prev_uv"], np.float32) if "prev_uv" in frame_out else None,
         "gPrevVisibility": np.ascontiguousarray(history["visibility"], wire.VisibilityInfo) if history.get("visibility") is not None else None,
         "gPrevDepth": np.ascontiguousarray(history["depth"], wire.DepthInfo) if history.get("depth") is not None else None,
-        "gPrevAccumColor": np.ascontiguousarray(history["accum_color"], np.float32),
+        "gPrevAccumColor": np.ascontiguousarray(history["accum_color"], color_dtype),
         "gPrevAccumMoments": np.ascontiguousarray(history["accum_moments"], np.float32),
         "gInstanceIndexMap": np.ascontiguousarray(instance_index_map, np.uint32) if instance_index_map is not None else None,
         "gAccumColor": out_c,
@@ -77,15 +81,16 @@ class TemporalAccumulation:
         self.history = None
 
     def __call__(self, frame_out, views, instance_index_map=None):
-        rad = _rgba(frame_out["radiance"], "radiance")
+        cd = self._bdpt.color_dtype
+        rad = _rgba(frame_out["radiance"], "radiance", cd)
         H, W = rad.shape[0], rad.shape[1]
         history = self.history
         if history is None:  # first frame: nothing accumulated yet (sample count 0 everywhere)
             vis = np.zeros((H, W), wire.VisibilityInfo)
             vis["instance_primitive_index"] = wire.MISS
-            history = {"accum_color": np.zeros((H, W, 4), np.float32), "accum_moments": np.zeros((H, W, 2), np.float32), "visibility": vis, "depth": np.zeros((H, W), wire.DepthInfo)}
+            history = {"accum_color": np.zeros((H, W, 4), cd), "accum_moments": np.zeros((H, W, 2), np.float32), "visibility": vis, "depth": np.zeros((H, W), wire.DepthInfo)}
         keep = []
-        d, out_c, out_m = accumulate_desc(frame_out, history, views, self.reprojection, self.demodulate_albedo, self.history_limit, instance_index_map, keep)
+        d, out_c, out_m = accumulate_desc(frame_out, history, views, self.reprojection, self.demodulate_albedo, self.history_limit, instance_index_map, keep, cd)
         self._bdpt._check(_lib.lib().sthip_accumulate(self._bdpt._h, C.byref(d)), "sthip_accumulate")
         self.history = {"accum_color": out_c, "accum_moments": out_m, "visibility": frame_out.get("visibility"), "depth": frame_out.get("depth")}
         return out_c, out_m
@@ -103,8 +108,9 @@ class Tonemapper:
         self.state = np.zeros(6, np.float32)  # what the reference keeps in mTonemapMax from frame to frame
 
     def __call__(self, radiance, albedo=None, modulate_albedo=False, return_max=False):
-        img = _rgba(radiance, "radiance")
-        alb = _rgba(albedo, "albedo") if albedo is not None else None
+        cd = self._bdpt.color_dtype
+        img = _rgba(radiance, "radiance", cd)
+        alb = _rgba(albedo, "albedo", cd) if albedo is not None else None
         if alb is not None and alb.shape != img.shape:
             raise ValueError("albedo and radiance extents differ")
         out = np.empty_like(img)
@@ -128,7 +134,7 @@ class Tonemapper:
         return (out, mx) if return_max else out
 
     def device(self, width, height, input_ptr, albedo_ptr, output_ptr, modulate_albedo=False):
-        """Device-pointer form (RGBA32F buffers in HBM); enqueues on the context's stream and returns."""
+        """Device-pointer form (RGBA32F buffers in HBM, RGBA16F with half_color_precision); enqueues on the context's stream and returns."""
         d = wire.TonemapDesc(
             width, height, _mode(wire.TONEMAP, self.mode), int(bool(modulate_albedo)), int(self.gamma_correction), self.exposure, 1, 0.0, input_ptr, albedo_ptr, output_ptr, None, None
         )
@@ -144,7 +150,8 @@ class ImageComparer:
         self.quantization = int(quantization)
 
     def raw(self, image1, image2):
-        a, b = _rgba(image1, "image1"), _rgba(image2, "image2")
+        cd = self._bdpt.color_dtype
+        a, b = _rgba(image1, "image1", cd), _rgba(image2, "image2", cd)
         if a.shape != b.shape:
             raise ValueError("image extents differ")
         s, o = C.c_uint32(0), C.c_uint32(0)

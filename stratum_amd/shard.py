@@ -61,9 +61,10 @@ def slot_pixels(width, height, rank, world, tile_w=64, tile_h=32):
 
 
 def assemble_tiles(packed_per_rank, width, height, tile_w=64, tile_h=32):
-    """numpy mirror of sthip_assemble_tiles: list of (slots_r, 4) arrays -> (H, W, 4) frame."""
+    """numpy mirror of sthip_assemble_tiles: list of (slots_r, 4) arrays -> (H, W, 4) frame of their dtype (float32, or
+    float16 for the 8-byte entries of half colour precision)."""
     world = len(packed_per_rank)
-    frame = np.zeros((height, width, 4), np.float32)
+    frame = np.zeros((height, width, 4), np.asarray(packed_per_rank[0]).dtype if world else np.float32)
     for rank, packed in enumerate(packed_per_rank):
         xy = slot_pixels(width, height, rank, world, tile_w, tile_h)
         ok = xy[:, 0] >= 0
@@ -80,6 +81,16 @@ def gather_tiles(packed, gathered, dist, dst=0, async_op=False):
 
 
 # ---- the other split (SURVEY.md 8e "replicas + sum-reduce"): whole frames over disjoint seed ranges ----
+# Not with half colour precision (BDPT.set_half_color_precision): a sum of rounded means is not a rounded mean, so the
+# library refuses sthip_radiance_to_sums there and the helpers below refuse float16 images. Tile sharding stays exact.
+HALF_SEED_SPLIT = "the seed split does not support half colour precision: a sum of rounded means is not a rounded mean (use tile sharding)"
+
+
+def _no_half(image):
+    if str(getattr(image, "dtype", "")).endswith("float16"):
+        raise ValueError(HALF_SEED_SPLIT)
+
+
 def seed_range(rank, world, seed_count):
     """(first, count) of the seeds of a call that rank `rank` renders: the first seed_count % world ranks take one more
     (the rule of MultiDeviceBDPT::split_seeds, stratum_hip_multi.hpp); count may be 0 when there are more ranks than seeds."""
@@ -90,13 +101,15 @@ def seed_range(rank, world, seed_count):
 
 def to_sums(image):
     """(mean over the seeds, their number) -> (sum, number) per pixel: what a sum-reduce can add (sthip_radiance_to_sums).
-    Works on numpy arrays and torch tensors of shape (..., 4), in place."""
+    Works on numpy arrays and torch tensors of shape (..., 4), in place. float16 images raise ValueError (see above)."""
+    _no_half(image)
     image[..., :3] *= image[..., 3:4]
     return image
 
 
 def from_sums(image):
     """(sum, number) -> (mean, number), pixels without samples stay zero."""
+    _no_half(image)
     n = image[..., 3:4]
     image[..., :3] /= n.clip(1) if hasattr(n, "clip") and not hasattr(n, "clamp") else n.clamp(min=1)
     return image
@@ -104,4 +117,5 @@ def from_sums(image):
 
 def reduce_seed_sums(tensor, dist, dst=0, async_op=False):
     """One sum-reduce of the accumulation buffer (the rank's whole-frame sums) to `dst`: north_star's collective."""
+    _no_half(tensor)
     return dist.reduce(tensor, dst=dst, op=dist.ReduceOp.SUM, async_op=async_op)

@@ -16,6 +16,9 @@ FOG = np.load(os.path.join(ROOT, "tests", "golden", "fog_sphere.npz"))["grid"]
 # one the full run has at that number); STHIP_FUZZ_TRACE=1 prints every case before it runs (to find the one a fault belongs to)
 ONLY = os.environ.get("STHIP_FUZZ_ONLY")
 TRACE = os.environ.get("STHIP_FUZZ_TRACE") == "1"
+# STHIP_FUZZ_HALF=1: every case is rendered once more with half colour precision and compared with RTNE of its binary32 frame
+# (draws no random numbers: the cases of a seed stay the same)
+HALF = os.environ.get("STHIP_FUZZ_HALF") == "1"
 
 
 class _Dry:
@@ -205,6 +208,21 @@ def run(cases=60, seed=1):
             for f in ("z", "prev_z", "dz_dxy"):
                 ok &= np.array_equal(got["depth"][f].view(np.uint32), ref["depth"][f].view(np.uint32))
             ok &= np.array_equal(got["ray_count"], ref["ray_count"])
+            if HALF:  # the case again with half colour precision: radiance / albedo = RTNE of this binary32 frame, the rest identical
+                r.set_half_color_precision(True)
+                try:
+                    gh = r.render(fr, seed0, seeds, debug_mode=debug_mode, debug_image=debug_start)
+                finally:
+                    r.set_half_color_precision(False)
+                for k in ("radiance", "albedo"):
+                    with np.errstate(over="ignore"):
+                        want = got[k].astype(np.float16)
+                    nan = np.isnan(want)
+                    ok_h = gh[k].dtype == np.float16 and np.array_equal(np.isnan(gh[k]), nan) and np.array_equal(gh[k].view(np.uint16)[~nan], want.view(np.uint16)[~nan])
+                    if not ok_h: print("MISMATCH (half %s) %s %s %s" % (k, kind, flags, args))
+                    ok &= ok_h
+                for k in ("prev_uv", "visibility", "depth", "ray_count"):
+                    ok &= np.array_equal(gh[k].view(np.uint8), got[k].view(np.uint8))
             done += 1
             if not ok:
                 bad += 1
