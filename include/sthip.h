@@ -211,6 +211,62 @@ int sthip_render(sthip_ctx* ctx, const sthip_BDPTPushConstants* push_constants, 
                  uint32_t scene_flags, const sthip_frame_desc* frame, uint32_t seed_begin, uint32_t seed_count,
                  const sthip_outputs* outputs);
 
+/* ---- pipelined host outputs: frame i + 1 renders while frame i copies back ----
+ * sthip_render with host pointers renders, copies and synchronises inside the call, one after the other. The calls below
+ * split that: sthip_render_async enqueues the frame and returns a ticket; the library renders it on the context's stream
+ * into one of "output_ring" device staging sets and copies the set to the caller's host memory on a copy stream of its
+ * own, ordered by events only (no kernel of this library moves the bytes: the runtime's device-to-host copy does, on a
+ * copy engine or with its own copy kernel on a second hardware queue, beside the next frame's kernels); the caller
+ * collects the frame later with sthip_wait_outputs. sthip_render itself is unchanged.
+ *
+ * sthip_host_alloc / sthip_host_free: pinned (page-locked) host memory of the context's device — the only kind a
+ * device-to-host copy overlaps with anything. sthip_host_free first completes the frames in flight (one may still copy
+ * into the block); blocks not freed are freed by sthip_destroy.
+ *
+ * sthip_render_async takes sthip_render's arguments and computes sthip_render's results: after sthip_wait_outputs(ticket)
+ * the five images and gRayCount hold, byte for byte, what sthip_render with the same arguments writes (both
+ * radiance_layouts, on a shard, with "half_color_precision"), and sthip_get_stats describes that frame. *ticket counts up
+ * from 1.
+ *   Argument lifetimes: push_constants, frame and everything frame points at are borrowed for the call only (the library
+ *   keeps its own copy of the view arrays in pinned memory of the staging set). The host pointers inside `outputs` are
+ *   borrowed until sthip_wait_outputs has returned for the ticket, or until the context is destroyed. gRayCount is
+ *   written by the host when the ticket completes (sthip_wait_outputs, a sthip_outputs_ready that returns 1, or one of
+ *   the draining calls below), from the frame's pinned counter record. outputs->device_ptrs must be 0 (the
+ *   device-pointer form of sthip_render only enqueues already): otherwise STHIP_ERR_INVALID_ARGUMENT.
+ *   Any host memory is correct; pinned memory overlaps: pointers from sthip_host_alloc, or memory the caller registered
+ *   itself with hipHostRegister, get a true asynchronous copy. Pageable pointers still hold the right bytes at
+ *   sthip_wait_outputs, but the runtime stages such a copy and the submit call may block until the frame is rendered.
+ *   Ordering: tickets complete in submission order; sthip_wait_outputs(t) implies every earlier ticket is complete, and
+ *   sthip_outputs_ready is monotone in the same way. A ticket that was never issued is STHIP_ERR_INVALID_ARGUMENT;
+ *   waiting twice on the same ticket is STHIP_OK. The render work of all frames stays in one stream order, so the
+ *   reservoir-reuse flags with "reuse_grids_persist" keep "N calls of one seed = one call of N seeds".
+ *   What the submit call may wait for: in the steady state nothing on the GPU. Two exceptions: when "output_ring" frames
+ *   are already in flight it waits for the COPY of the oldest one (its ticket stays valid and waitable); and on the
+ *   out-of-memory retry (see sthip_render: the batch is halved) every frame in flight is completed before the path
+ *   state is released.
+ *   Rejected, never ignored, with STHIP_ERR_UNSUPPORTED and a sthip_last_error that says to use sthip_render:
+ *   outputs->debug_mode != 0 (gDebugImage is in / out and chains from frame to frame through the caller's memory: a
+ *   diagnostic mode, not a throughput mode) and "time_kernels" = 1 (its events synchronise the host).
+ *   Other calls while frames are in flight: sthip_destroy, a sthip_set_stream that changes the stream, sthip_scene_upload,
+ *   sthip_scene_update_transforms, sthip_host_free and a change of "output_ring" first complete every frame in flight
+ *   (render and copy). After any of them except sthip_destroy the tickets stay waitable and waiting returns at once;
+ *   after sthip_destroy the caller's buffers are complete and the tickets are gone with the context. A sthip_render or
+ *   any other call between two async frames is legal and ordered after them on the stream. "half_color_precision" takes
+ *   effect at the next submit; frames in flight keep the type they were submitted with.
+ * sthip_outputs_ready: 1 = the frame's outputs are in host memory, 0 = not yet, < 0 = a sthip_status; never blocks.
+ * sthip_wait_outputs: blocks until they are.
+ * Option "output_ring" (1..8, default 2; other values are refused): frames in flight = device staging sets (the five
+ * images: 64 B per pixel, 48 B with half colour precision — 132.7 MB at 1080p), allocated at first use, released when the
+ * ring size or the frame size changes. A library without the feature answers STHIP_ERR_INVALID_ARGUMENT (unknown option):
+ * a host may probe with it. */
+int sthip_host_alloc(sthip_ctx* ctx, uint64_t bytes, void** out);
+int sthip_host_free(sthip_ctx* ctx, void* p);
+int sthip_render_async(sthip_ctx* ctx, const sthip_BDPTPushConstants* push_constants, uint32_t sampling_flags,
+                       uint32_t scene_flags, const sthip_frame_desc* frame, uint32_t seed_begin, uint32_t seed_count,
+                       const sthip_outputs* outputs, uint64_t* ticket);
+int sthip_outputs_ready(sthip_ctx* ctx, uint64_t ticket);
+int sthip_wait_outputs(sthip_ctx* ctx, uint64_t ticket);
+
 /* Pixel-tile sharding for multi-GPU (one context per GPU): the frame is cut into
  * tile_w x tile_h tiles (multiples of the reference's 8x4 workgroup, bdpt.hlsl:11-12),
  * tile t is rendered iff t % shard_count == shard_rank; other pixels are written as zero
@@ -368,7 +424,8 @@ int sthip_measure_ceiling(sthip_ctx* ctx, uint32_t kind, double* gbytes_per_s);
  * gAlbedo, gOutput), sthip_accumulate (gRadiance, gAlbedo, gPrevAccumColor, gAccumColor), sthip_image_compare (both
  * images) and sthip_assemble_tiles (8-byte entries) are RGBA16F; every other buffer keeps its type. It takes effect at
  * the next call. A library without the feature answers STHIP_ERR_INVALID_ARGUMENT (unknown option): a host may probe
- * with it. */
+ * with it.
+ * "output_ring" (1..8, default 2): see sthip_render_async. */
 int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value);
 
 /* ---- after the path: display transform, image metric, HDR export ---- */

@@ -24,6 +24,11 @@ EXPORTS = [
     "sthip_scene_upload",
     "sthip_scene_update_transforms",
     "sthip_render",
+    "sthip_host_alloc",
+    "sthip_host_free",
+    "sthip_render_async",
+    "sthip_outputs_ready",
+    "sthip_wait_outputs",
     "sthip_set_shard",
     "sthip_trace_rays",
     "sthip_get_stats",
@@ -103,6 +108,16 @@ def lib():
         C.c_uint32,
         C.POINTER(wire.Outputs),
     ]
+    L.sthip_host_alloc.restype = C.c_int
+    L.sthip_host_alloc.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.sthip_host_free.restype = C.c_int
+    L.sthip_host_free.argtypes = [C.c_void_p, C.c_void_p]
+    L.sthip_render_async.restype = C.c_int
+    L.sthip_render_async.argtypes = L.sthip_render.argtypes + [C.POINTER(C.c_uint64)]
+    L.sthip_outputs_ready.restype = C.c_int
+    L.sthip_outputs_ready.argtypes = [C.c_void_p, C.c_uint64]
+    L.sthip_wait_outputs.restype = C.c_int
+    L.sthip_wait_outputs.argtypes = [C.c_void_p, C.c_uint64]
     L.sthip_set_shard.restype = C.c_int
     L.sthip_set_shard.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sthip_trace_rays.restype = C.c_int

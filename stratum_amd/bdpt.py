@@ -117,6 +117,10 @@ class BDPT:
 
     def close(self):
         if getattr(self, "_h", None):
+            for ptr in getattr(self, "_host_blocks", []):  # alloc_host_outputs (completes the frames in flight first)
+                self._lib.sthip_host_free(self._h, C.c_void_p(ptr))
+            self._host_blocks = []
+            self._tickets = {}
             self._lib.sthip_destroy(self._h)
             self._h = None
 
@@ -256,6 +260,85 @@ class BDPT:
         if out is not None:
             self._prev_result = out["radiance"]
         return out
+
+    # ---- pipelined host outputs (include/sthip.h: sthip_render_async) ----
+    def _host_output_spec(self, frame, aovs, packed_tiles):
+        """(key, shape, dtype) of the host arrays render() would make for this frame."""
+        W, H = frame.width, frame.height
+        cd = self.color_dtype
+        spec = [("radiance", (self.shard_slot_count(frame), 4) if packed_tiles else (H, W, 4), cd)]
+        if aovs:
+            spec += [("albedo", (H, W, 4), cd), ("visibility", (H, W), wire.VisibilityInfo), ("depth", (H, W), wire.DepthInfo), ("prev_uv", (H, W, 2), np.float32)]
+        return spec + [("ray_count", (2,), np.uint64)]
+
+    def alloc_host_outputs(self, frame, aovs=True, packed_tiles=False):
+        """The dict of arrays render() returns for this frame, over pinned memory of sthip_host_alloc (the kind a device-to-host
+        copy overlaps the next frame with), zero-filled; colour images in color_dtype. The memory is freed in close(): the
+        arrays must not be used after it."""
+        if not getattr(self, "_h", None):
+            raise StratumHipError("BDPT.alloc_host_outputs on a closed renderer")
+        out = {}
+        for key, shape, dtype in self._host_output_spec(frame, aovs, packed_tiles):
+            nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+            ptr = C.c_void_p()
+            self._check(self._lib.sthip_host_alloc(self._h, max(1, nbytes), C.byref(ptr)), "sthip_host_alloc")
+            self.__dict__.setdefault("_host_blocks", []).append(ptr.value)
+            buf = (C.c_uint8 * nbytes).from_address(ptr.value)
+            out[key] = np.frombuffer(buf, dtype=dtype).reshape(shape)
+            out[key][...] = np.zeros((), dtype)
+        return out
+
+    def render_async(self, frame, seed_begin=0, seed_count=1, host_outputs=None, aovs=True, packed_tiles=False):
+        """render() with host outputs, but only enqueued: returns a ticket for wait() / ready(). `host_outputs`: a dict from
+        alloc_host_outputs (pinned: the copy overlaps the next frame) or of any C-contiguous numpy arrays of the right shapes
+        (pageable: correct, but the submit may block); None = fresh pinned arrays. The arrays and the descriptors of a ticket
+        are kept alive here until it has been waited for."""
+        if self._scene is None:
+            raise StratumHipError("BDPT.render_async before BDPT.update(scene)")
+        if host_outputs is None:
+            host_outputs = self.alloc_host_outputs(frame, aovs=aovs, packed_tiles=packed_tiles)
+        out = {}
+        for key, shape, dtype in self._host_output_spec(frame, aovs, packed_tiles):
+            a = host_outputs[key]
+            if a.dtype != dtype or a.nbytes != int(np.prod(shape)) * np.dtype(dtype).itemsize or not a.flags["C_CONTIGUOUS"]:
+                raise ValueError("host_outputs[%r] does not fit the frame" % key)
+            out[key] = a
+        pc = self.push_constants(frame)
+        if self._scene.volumes:  # gViewMediumInstances, BDPT.cpp:456-466
+            frame.view_medium_instances = self._scene.view_medium_instances(frame.view_transforms)
+        fd = frame.desc()
+        o = wire.Outputs()
+        o.device_ptrs = 0
+        o.radiance_layout = wire.LAYOUT_SHARD_TILES if packed_tiles else wire.LAYOUT_IMAGE
+        o.gRadiance = wire.ptr(out["radiance"])
+        o.gRayCount = wire.ptr(out["ray_count"])
+        if aovs:
+            o.gAlbedo = wire.ptr(out["albedo"])
+            o.gVisibility = wire.ptr(out["visibility"])
+            o.gDepth = wire.ptr(out["depth"])
+            o.gPrevUVs = wire.ptr(out["prev_uv"])
+        ticket = C.c_uint64(0)
+        rc = self._lib.sthip_render_async(self._h, C.byref(pc), self.mSamplingFlags, self._scene.scene_flags, C.byref(fd), seed_begin, seed_count, C.byref(o), C.byref(ticket))
+        self._check(rc, "sthip_render_async")
+        self.__dict__.setdefault("_tickets", {})[ticket.value] = (out, o, fd, pc)
+        return ticket.value
+
+    def ready(self, ticket):
+        """Whether the outputs of `ticket` are in host memory; never blocks."""
+        rc = self._lib.sthip_outputs_ready(self._h, int(ticket))
+        if rc < 0:
+            self._check(rc, "sthip_outputs_ready")
+        return rc == 1
+
+    def wait(self, ticket):
+        """Blocks until the outputs of `ticket` (and of every earlier one) are in host memory; returns its dict of arrays
+        (None for a ticket already collected)."""
+        self._check(self._lib.sthip_wait_outputs(self._h, int(ticket)), "sthip_wait_outputs")
+        kept = getattr(self, "_tickets", {}).pop(int(ticket), None)
+        if kept is None:
+            return None
+        self._prev_result = kept[0]["radiance"]
+        return kept[0]
 
     # ---- multi-GPU assembly (include/sthip.h: sthip_shard_slot_count / sthip_assemble_tiles) ----
     def set_shard(self, rank, count, tile_w=64, tile_h=32):

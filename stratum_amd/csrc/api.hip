@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -158,6 +159,41 @@ struct KeptScene {
     d.gVolumes = volumes.empty() ? nullptr : volumes.data();
     d.volume_count = (uint32_t)volumes.size();
     return d;
+  }
+};
+
+// One frame in flight of sthip_render_async: a device staging set of the five images, the copy of the call's view arrays in
+// pinned memory (the arguments are borrowed for the call only), the frame's counters on the device and in a pinned record,
+// and the two events that order it: `rendered` on the render stream, `copied` on the copy stream.
+struct AsyncSlot {
+  DevBuf<float4> radiance, albedo;
+  DevBuf<sthip_VisibilityInfo> visibility;
+  DevBuf<sthip_DepthInfo> depth;
+  DevBuf<float2> prev_uv;
+  DevBuf<unsigned long long> counters;
+  size_t key[3] = {0, 0, 0};  // (pixels, radiance entries, bytes per colour entry) the set was allocated for
+  uint8_t* params = nullptr;  // pinned: gViews | gViewTransforms | gPrevViews | gPrevInverseViewTransforms | gInverseViewTransforms | gViewMediumInstances
+  size_t params_cap = 0;
+  unsigned long long* record = nullptr;  // pinned: CNT_TOTAL counters of the frame
+  hipEvent_t rendered = nullptr, copied = nullptr;
+  uint64_t ticket = 0;            // the ticket in flight in this slot, 0 = free
+  uint64_t* ray_count = nullptr;  // the caller's gRayCount: written from `record` when the ticket is retired
+  AsyncSlot() = default;
+  AsyncSlot(const AsyncSlot&) = delete;
+  AsyncSlot& operator=(const AsyncSlot&) = delete;
+  ~AsyncSlot() {
+    if (params) (void)hipHostFree(params);
+    if (record) (void)hipHostFree(record);
+    if (rendered) (void)hipEventDestroy(rendered);
+    if (copied) (void)hipEventDestroy(copied);
+  }
+  void release_images() {
+    radiance.release();
+    albedo.release();
+    visibility.release();
+    depth.release();
+    prev_uv.release();
+    key[0] = key[1] = key[2] = 0;
   }
 };
 
@@ -310,6 +346,18 @@ struct sthip_ctx {
   bool render_launched = false;            // the render call in progress has enqueued work (no second attempt from here on)
   bool stats_pending = false;  // ray / traversal counters of the last render still live on the device
   hipEvent_t ev[2] = {nullptr, nullptr};
+  // sthip_render_async: "output_ring" staging sets (made at the first submit), the copy stream, tickets issued / retired
+  uint32_t output_ring = 2;
+  std::vector<AsyncSlot*> ring;
+  hipStream_t copy_stream = nullptr;
+  uint64_t next_ticket = 1, retired = 0;
+  // a finished frame whose slot a later submit took over before its ticket was waited for: its counters and the caller's gRayCount
+  struct FinishedFrame {
+    std::vector<unsigned long long> counters;
+    uint64_t* ray_count = nullptr;
+  };
+  std::map<uint64_t, FinishedFrame> finished;
+  std::vector<void*> host_allocs;  // sthip_host_alloc
 };
 
 // The traversal stack is stack_depth x 1 KB of dynamic LDS per 256-thread block. Up to 64 KB needs nothing; beyond it
@@ -384,6 +432,63 @@ static int fail(sthip_ctx* ctx, int code, const std::string& msg) {
   return code;
 }
 
+// ---- frames in flight of sthip_render_async ----
+static AsyncSlot* slot_of(sthip_ctx* ctx, uint64_t ticket) { return ctx->ring[ticket % ctx->ring.size()]; }
+
+// Tickets retired + 1 .. t, in order; their "copied" events have been reached (the copy stream runs them in submission order,
+// so the caller has waited for t's). What the host owes a finished frame: gRayCount and the stats, from the pinned record.
+static void retire_through(sthip_ctx* ctx, uint64_t t) {
+  while (ctx->retired < t) {
+    const uint64_t k = ++ctx->retired;
+    AsyncSlot* s = slot_of(ctx, k);
+    const unsigned long long* c = nullptr;
+    uint64_t* ray_count = nullptr;
+    const auto it = ctx->finished.find(k);
+    if (s->ticket == k) {
+      c = s->record;
+      ray_count = s->ray_count;
+    } else if (it != ctx->finished.end()) {
+      c = it->second.counters.data();
+      ray_count = it->second.ray_count;
+    } else {
+      continue;
+    }
+    if (ray_count) {
+      ray_count[0] = c[CNT_RAYS_CLOSEST] + c[CNT_RAYS_SHADOW];
+      ray_count[1] = c[CNT_RAYS_CLOSEST] - c[CNT_CROSSINGS];
+    }
+    fill_counter_stats(ctx, c);
+    ctx->stats_pending = false;
+    if (s->ticket == k) {
+      s->ticket = 0;
+      s->ray_count = nullptr;
+    } else {
+      ctx->finished.erase(it);
+    }
+  }
+}
+
+// Blocks until ticket t's outputs are in host memory (and with them every earlier ticket's: the copy stream runs the frames in
+// submission order). A ticket that is no longer in its slot was completed when a later submit took the slot over.
+static hipError_t complete_ticket(sthip_ctx* ctx, uint64_t t) {
+  AsyncSlot* s = slot_of(ctx, t);
+  return s->ticket == t ? hipEventSynchronize(s->copied) : hipSuccess;
+}
+
+// Completes every frame in flight (render and copy) and retires its ticket; the tickets stay waitable.
+static hipError_t drain_in_flight(sthip_ctx* ctx) {
+  if (ctx->retired + 1 == ctx->next_ticket) return hipSuccess;
+  const hipError_t e = complete_ticket(ctx, ctx->next_ticket - 1);
+  if (e != hipSuccess) return e;
+  retire_through(ctx, ctx->next_ticket - 1);
+  return hipSuccess;
+}
+
+static void release_ring(sthip_ctx* ctx) {
+  for (AsyncSlot* s : ctx->ring) delete s;
+  ctx->ring.clear();
+}
+
 extern "C" {
 
 int sthip_abi_version(void) { return STHIP_ABI_VERSION; }
@@ -447,6 +552,10 @@ void sthip_destroy(sthip_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   (void)hipDeviceSynchronize();
+  if (ctx->retired + 1 != ctx->next_ticket) retire_through(ctx, ctx->next_ticket - 1);  // (the device is idle: every copy has landed)
+  release_ring(ctx);
+  if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
+  for (void* q : ctx->host_allocs) (void)hipHostFree(q);
   sthip::device_wide_scratch_destroy(ctx->wide_scratch);
   ctx->wide_scratch = nullptr;
   ctx->vertices.release();
@@ -517,6 +626,10 @@ const char* sthip_last_error(const sthip_ctx* ctx) { return ctx ? ctx->error.c_s
 
 int sthip_set_stream(sthip_ctx* ctx, void* hip_stream) {
   if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if ((hipStream_t)hip_stream != ctx->stream && ctx->retired + 1 != ctx->next_ticket) {  // frames of sthip_render_async in flight are ordered by the stream they were enqueued on: a CHANGE of stream completes them
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, drain_in_flight(ctx));
+  }
   ctx->stream = (hipStream_t)hip_stream;
   return STHIP_OK;
 }
@@ -591,6 +704,14 @@ int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value) {
   else if (!strcmp(name, "half_color_precision")) {  // takes effect at the next call; refused outside 0 / 1
     if (value != 0 && value != 1) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "half_color_precision: 0 or 1");
     ctx->half_color = value != 0;
+  } else if (!strcmp(name, "output_ring")) {  // frames in flight of sthip_render_async = device staging sets; a change first completes the frames in flight
+    if (value < 1 || value > 8) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "output_ring: 1 .. 8");
+    if ((uint32_t)value != ctx->output_ring) {
+      HIP_TRY(ctx, hipSetDevice(ctx->device));
+      HIP_TRY(ctx, drain_in_flight(ctx));
+      release_ring(ctx);
+      ctx->output_ring = (uint32_t)value;
+    }
   } else if (!strcmp(name, "inner_min_lanes"))
     ctx->inner_min_lanes = (uint32_t)std::min<int64_t>(64, std::max<int64_t>(1, value));
   else
@@ -673,6 +794,7 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
   // frames of the previous scene may still be in flight on the caller's stream (device output pointers: sthip_render only
   // enqueues), and the copies below go through the null stream, which a non-blocking stream does not wait for
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, drain_in_flight(ctx));  // ... and the copy stream of sthip_render_async still reads the staging sets of its frames
   ctx->has_scene = false;
   for (uint32_t i = 0; i < s->light_count; i++)
     if (s->gLightInstances[i] >= s->instance_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: gLightInstances entry out of range");
@@ -1314,6 +1436,7 @@ int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf,
   if (stack_depth > STHIP_MAX_STACK_DEPTH) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the new top level is too deep for the traversal stack");
   if ((size_t)next.blas_nodes + tlas.size() > ctx->nodes.n) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the new top level does not fit: upload the scene again");
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old top level
+  HIP_TRY(ctx, drain_in_flight(ctx));               // (sthip_render_async: their copies too, so that their tickets are complete)
   const uint32_t n = instance_count;
   HIP_TRY(ctx, hipMemcpy(ctx->xf.p, xf, (size_t)n * 48, hipMemcpyHostToDevice));
   HIP_TRY(ctx, hipMemcpy(ctx->inv_xf.p, inv, (size_t)n * 48, hipMemcpyHostToDevice));
@@ -1438,7 +1561,7 @@ static void release_path_state(sthip_ctx* ctx) {
 }
 
 static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32_t sampling_flags, uint32_t scene_flags, const sthip_frame_desc* frame, uint32_t seed_begin, uint32_t seed_count,
-                       const sthip_outputs* out);
+                       const sthip_outputs* out, AsyncSlot* slot);
 
 // A render allocates its path state (~330 B per path in flight at the default flags) before it enqueues anything. Should the
 // device not have that much left — a host application that holds memory of its own, several contexts on one device — the
@@ -1450,12 +1573,13 @@ int sthip_render(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32_t sam
   for (;;) {
     ctx->last_hip_error = hipSuccess;
     ctx->render_launched = false;
-    const int rc = render_once(ctx, pc, sampling_flags, scene_flags, frame, seed_begin, seed_count, out);
+    const int rc = render_once(ctx, pc, sampling_flags, scene_flags, frame, seed_begin, seed_count, out, nullptr);
     ctx->stats.max_paths_in_flight = ctx->max_paths_in_flight;
     if (rc != STHIP_ERR_HIP || ctx->last_hip_error != hipErrorOutOfMemory || ctx->render_launched) return rc;
     (void)hipGetLastError();  // (the allocation's error is not sticky, but it is the "last error" until read)
     const uint64_t per_seed = std::max<uint64_t>(1, ctx->stats.paths_per_seed);
     if (ctx->max_paths_in_flight <= per_seed || ctx->max_paths_in_flight <= 1) return rc;  // one seed in flight already: it does not fit
+    (void)drain_in_flight(ctx);  // (frames of sthip_render_async: complete before the state they were traced with goes)
     release_path_state(ctx);
     ctx->max_paths_in_flight = std::max<uint64_t>(per_seed, ctx->max_paths_in_flight / 2);
     ctx->stats.batch_halvings++;
@@ -1463,8 +1587,110 @@ int sthip_render(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32_t sam
   }
 }
 
+// ---- pipelined host outputs (sthip.h: sthip_render_async) ----
+
+int sthip_host_alloc(sthip_ctx* ctx, uint64_t bytes, void** out) {
+  if (!ctx || !out) return STHIP_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  if (bytes == 0) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_host_alloc: 0 bytes");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  void* q = nullptr;
+  HIP_TRY(ctx, hipHostMalloc(&q, (size_t)bytes, hipHostMallocDefault));
+  ctx->host_allocs.push_back(q);
+  *out = q;
+  return STHIP_OK;
+}
+
+int sthip_host_free(sthip_ctx* ctx, void* p) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if (!p) return STHIP_OK;
+  const auto it = std::find(ctx->host_allocs.begin(), ctx->host_allocs.end(), p);
+  if (it == ctx->host_allocs.end()) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_host_free: not a pointer of sthip_host_alloc");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, drain_in_flight(ctx));  // a frame in flight may still copy into it
+  ctx->host_allocs.erase(it);
+  HIP_TRY(ctx, hipHostFree(p));
+  return STHIP_OK;
+}
+
+int sthip_render_async(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32_t sampling_flags, uint32_t scene_flags, const sthip_frame_desc* frame, uint32_t seed_begin,
+                       uint32_t seed_count, const sthip_outputs* out, uint64_t* ticket) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if (!ticket || !out) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render_async: outputs or ticket is NULL");
+  *ticket = 0;
+  if (out->device_ptrs) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render_async: device_ptrs must be 0 (sthip_render with device pointers only enqueues already)");
+  if (out->debug_mode != 0) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render_async: debug_mode != 0 (gDebugImage chains from frame to frame through host memory): use sthip_render");
+  if (ctx->time_kernels) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render_async: \"time_kernels\" = 1 (its events synchronise the host): use sthip_render");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+  while (ctx->ring.size() < ctx->output_ring) {
+    AsyncSlot* s = new AsyncSlot();
+    hipError_t e = hipEventCreateWithFlags(&s->rendered, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->copied, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&s->record, CNT_TOTAL * sizeof(unsigned long long), hipHostMallocDefault);
+    if (e != hipSuccess) delete s;  // (a slot is whole or absent)
+    HIP_TRY(ctx, e);
+    ctx->ring.push_back(s);
+  }
+  const uint64_t t = ctx->next_ticket;
+  AsyncSlot* slot = slot_of(ctx, t);
+  // The ring is full: the oldest frame in flight owns this slot. Its COPY is waited for (the slot's pinned blocks and staging
+  // set are about to be rewritten). Its ticket is NOT retired: what the host still owes it — gRayCount, the stats — moves to
+  // ctx->finished until the caller waits for it.
+  if (slot->ticket) {
+    HIP_TRY(ctx, hipEventSynchronize(slot->copied));
+    sthip_ctx::FinishedFrame& f = ctx->finished[slot->ticket];
+    f.counters.assign(slot->record, slot->record + CNT_TOTAL);
+    f.ray_count = slot->ray_count;
+    slot->ticket = 0;
+    slot->ray_count = nullptr;
+  }
+  for (;;) {
+    ctx->last_hip_error = hipSuccess;
+    ctx->render_launched = false;
+    const int rc = render_once(ctx, pc, sampling_flags, scene_flags, frame, seed_begin, seed_count, out, slot);
+    ctx->stats.max_paths_in_flight = ctx->max_paths_in_flight;
+    if (rc == STHIP_OK) break;
+    if (rc != STHIP_ERR_HIP || ctx->last_hip_error != hipErrorOutOfMemory || ctx->render_launched) return rc;
+    (void)hipGetLastError();
+    const uint64_t per_seed = std::max<uint64_t>(1, ctx->stats.paths_per_seed);
+    if (ctx->max_paths_in_flight <= per_seed || ctx->max_paths_in_flight <= 1) return rc;
+    (void)drain_in_flight(ctx);  // the out-of-memory retry of sthip_render: every frame in flight completes before its path state goes
+    release_path_state(ctx);
+    ctx->max_paths_in_flight = std::max<uint64_t>(per_seed, ctx->max_paths_in_flight / 2);
+    ctx->stats.batch_halvings++;
+  }
+  slot->ticket = t;
+  ctx->next_ticket = t + 1;
+  *ticket = t;
+  return STHIP_OK;
+}
+
+int sthip_outputs_ready(sthip_ctx* ctx, uint64_t ticket) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if (ticket == 0 || ticket >= ctx->next_ticket) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "outputs_ready: no such ticket");
+  if (ticket <= ctx->retired) return 1;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  AsyncSlot* s = slot_of(ctx, ticket);
+  const hipError_t e = s->ticket == ticket ? hipEventQuery(s->copied) : hipSuccess;  // (not in its slot any more: completed when the slot was taken over)
+  if (e == hipErrorNotReady) return 0;
+  HIP_TRY(ctx, e);
+  retire_through(ctx, ticket);  // (the copy stream runs the frames in submission order: the earlier ones are complete too)
+  return 1;
+}
+
+int sthip_wait_outputs(sthip_ctx* ctx, uint64_t ticket) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if (ticket == 0 || ticket >= ctx->next_ticket) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "wait_outputs: no such ticket");
+  if (ticket <= ctx->retired) return STHIP_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, complete_ticket(ctx, ticket));
+  retire_through(ctx, ticket);
+  return STHIP_OK;
+}
+
 static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32_t sampling_flags, uint32_t scene_flags, const sthip_frame_desc* frame, uint32_t seed_begin, uint32_t seed_count,
-                       const sthip_outputs* out) {
+                       const sthip_outputs* out, AsyncSlot* slot) {
   if (!pc || !frame || !out || !out->gRadiance || !frame->gViews || !frame->gViewTransforms || frame->view_count == 0 || seed_count == 0)
     return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: a required argument is NULL/zero");
   if (!ctx->has_scene) return fail(ctx, STHIP_ERR_NO_SCENE, "no scene uploaded");
@@ -1698,22 +1924,30 @@ static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32
   const uint32_t nv = frame->view_count;
   const size_t vbytes = (size_t)nv * 48;
   HIP_TRY(ctx, ctx->views.ensure(5 * vbytes));
+  if (slot && slot->params_cap < 5 * vbytes + (size_t)nv * 4) {  // the pipelined form keeps the call's arrays in the slot's pinned block
+    if (slot->params) (void)hipHostFree(slot->params);
+    slot->params = nullptr;
+    slot->params_cap = 0;
+    HIP_TRY(ctx, hipHostMalloc((void**)&slot->params, 5 * vbytes + (size_t)nv * 4, hipHostMallocDefault));
+    slot->params_cap = 5 * vbytes + (size_t)nv * 4;
+  }
   {
-    std::vector<uint8_t> host(5 * vbytes);
+    std::vector<uint8_t> stack_copy(slot ? 0 : 5 * vbytes);
+    uint8_t* const host = slot ? slot->params : stack_copy.data();
     if (frame->gInverseViewTransforms)
-      memcpy(host.data() + 4 * vbytes, frame->gInverseViewTransforms, vbytes);
+      memcpy(host + 4 * vbytes, frame->gInverseViewTransforms, vbytes);
     else
-      memset(host.data() + 4 * vbytes, 0, vbytes);
-    memcpy(host.data(), frame->gViews, vbytes);
-    memcpy(host.data() + vbytes, frame->gViewTransforms, vbytes);
-    memcpy(host.data() + 2 * vbytes, frame->gPrevViews ? frame->gPrevViews : frame->gViews, vbytes);
+      memset(host + 4 * vbytes, 0, vbytes);
+    memcpy(host, frame->gViews, vbytes);
+    memcpy(host + vbytes, frame->gViewTransforms, vbytes);
+    memcpy(host + 2 * vbytes, frame->gPrevViews ? frame->gPrevViews : frame->gViews, vbytes);
     const sthip_TransformData* piv = frame->gPrevInverseViewTransforms ? frame->gPrevInverseViewTransforms : frame->gInverseViewTransforms;
     if (piv)
-      memcpy(host.data() + 3 * vbytes, piv, vbytes);
+      memcpy(host + 3 * vbytes, piv, vbytes);
     else
-      memset(host.data() + 3 * vbytes, 0, vbytes);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->views.p, host.data(), 5 * vbytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));  // `host` goes out of scope
+      memset(host + 3 * vbytes, 0, vbytes);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->views.p, host, 5 * vbytes, hipMemcpyHostToDevice, st));
+    if (!slot) HIP_TRY(ctx, hipStreamSynchronize(st));  // `stack_copy` goes out of scope (the slot's block lives until the slot's next frame, which waits for this one)
   }
   p.views = reinterpret_cast<const sthip_ViewData*>(ctx->views.p);
   p.view_xf = reinterpret_cast<const sthip_TransformData*>(ctx->views.p + vbytes);
@@ -1822,8 +2056,13 @@ static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32
         if (mi != 0xFFFFu && (mi >= ctx->instance_count || !ctx->instance_is_volume[mi]))
           return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: gViewMediumInstances entry is not a volume instance");
       }
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->view_medium.p, frame->gViewMediumInstances, (size_t)frame->view_count * 4, hipMemcpyHostToDevice, st));
-      HIP_TRY(ctx, hipStreamSynchronize(st));
+      if (slot) {  // (the caller's array is borrowed for the call only: the upload reads the slot's pinned copy)
+        memcpy(slot->params + 5 * vbytes, frame->gViewMediumInstances, (size_t)frame->view_count * 4);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->view_medium.p, slot->params + 5 * vbytes, (size_t)frame->view_count * 4, hipMemcpyHostToDevice, st));
+      } else {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->view_medium.p, frame->gViewMediumInstances, (size_t)frame->view_count * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+      }
       p.view_medium = ctx->view_medium.p;
     }
   }
@@ -1875,24 +2114,38 @@ static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32
     p.out_depth = out->gDepth;
     p.out_prev_uv = reinterpret_cast<float2*>(out->gPrevUVs);
   } else {
-    HIP_TRY(ctx, ctx->out_radiance.ensure(color_entries(radiance_entries, cb)));
-    p.out_radiance = ctx->out_radiance.p;
+    // the synchronous form has one staging set per context; a frame of sthip_render_async has its slot's, which the copy
+    // stream reads while the next frame renders into another (allocated at first use, released when the frame's size changes)
+    if (slot && (slot->key[0] != pixels || slot->key[1] != radiance_entries || slot->key[2] != cb)) {
+      slot->release_images();
+      slot->key[0] = pixels;
+      slot->key[1] = radiance_entries;
+      slot->key[2] = cb;
+    }
+    DevBuf<float4>& s_radiance = slot ? slot->radiance : ctx->out_radiance;
+    DevBuf<float4>& s_albedo = slot ? slot->albedo : ctx->out_albedo;
+    DevBuf<sthip_VisibilityInfo>& s_visibility = slot ? slot->visibility : ctx->out_visibility;
+    DevBuf<sthip_DepthInfo>& s_depth = slot ? slot->depth : ctx->out_depth;
+    DevBuf<float2>& s_prev_uv = slot ? slot->prev_uv : ctx->out_prev_uv;
+    HIP_TRY(ctx, s_radiance.ensure(color_entries(radiance_entries, cb)));
+    p.out_radiance = s_radiance.p;
     if (out->gAlbedo) {
-      HIP_TRY(ctx, ctx->out_albedo.ensure(color_entries(pixels, cb)));
-      p.out_albedo = ctx->out_albedo.p;
+      HIP_TRY(ctx, s_albedo.ensure(color_entries(pixels, cb)));
+      p.out_albedo = s_albedo.p;
     }
     if (out->gVisibility) {
-      HIP_TRY(ctx, ctx->out_visibility.ensure(pixels));
-      p.out_visibility = ctx->out_visibility.p;
+      HIP_TRY(ctx, s_visibility.ensure(pixels));
+      p.out_visibility = s_visibility.p;
     }
     if (out->gDepth) {
-      HIP_TRY(ctx, ctx->out_depth.ensure(pixels));
-      p.out_depth = ctx->out_depth.p;
+      HIP_TRY(ctx, s_depth.ensure(pixels));
+      p.out_depth = s_depth.p;
     }
     if (out->gPrevUVs) {
-      HIP_TRY(ctx, ctx->out_prev_uv.ensure(pixels));
-      p.out_prev_uv = ctx->out_prev_uv.p;
+      HIP_TRY(ctx, s_prev_uv.ensure(pixels));
+      p.out_prev_uv = s_prev_uv.p;
     }
+    if (slot) HIP_TRY(ctx, slot->counters.ensure(CNT_TOTAL));
   }
   // primary rays = owned pixels that lie inside the image and inside a view (known without asking the GPU)
   uint32_t primary_rays = 0;
@@ -1929,6 +2182,10 @@ static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32
   // When the shard is the whole frame and every pixel lies in a view, every output entry is written by the pass itself —
   // the first vertex's G-buffer stores (hit or miss) and k_resolve — so the five fills (131 MB at 1080p) are left out.
   const bool every_entry_written = p.shard_count == 1 && !p.out_packed && !media && pc->gMaxPathVertices >= 2 && (size_t)primary_rays == pixels;
+  // The next writer of a staging set — the fills below or the first G-buffer store — runs after the copy of the frame that used
+  // the set before (a no-op for an event that was never recorded). The binary32 albedo stage of half colour precision is one
+  // per context: only k_shade and k_resolve touch it, in stream order; the copy reads the slot's RGBA16F image.
+  if (slot) HIP_TRY(ctx, hipStreamWaitEvent(st, slot->copied, 0));
   if (!every_entry_written) {
     HIP_TRY(ctx, hipMemsetAsync(p.out_radiance, 0, radiance_entries * cb, st));
     if (p.out_albedo) HIP_TRY(ctx, hipMemsetAsync(p.out_albedo, 0, pixels * 16, st));
@@ -2315,7 +2572,25 @@ static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32
     ctx->reuse_grids_valid = true;
   }
 
-  if (!dev) {
+  if (slot) {
+    // The read-back of the pipelined form: on the copy stream, behind the "rendered" event, so that the runtime moves this frame
+    // (a copy engine, or its copy kernel on a hardware queue of its own: ~0.6 ms per 33 MB image) while the next one is traced. ctx->counters is rewritten by the next frame's k_clear: its read-out into
+    // the slot is a device-to-device copy ON THE RENDER STREAM, ordered before that rewrite; the copy stream then takes the
+    // slot's counters to the pinned record. Nothing waits on the host, nothing spins on the device: events only.
+    hipStream_t cs = ctx->copy_stream;
+    HIP_TRY(ctx, hipMemcpyAsync(slot->counters.p, ctx->counters.p, CNT_TOTAL * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, hipEventRecord(slot->rendered, st));
+    HIP_TRY(ctx, hipStreamWaitEvent(cs, slot->rendered, 0));
+    HIP_TRY(ctx, hipMemcpyAsync(out->gRadiance, p.out_radiance, radiance_entries * cb, hipMemcpyDeviceToHost, cs));
+    if (out->gAlbedo) HIP_TRY(ctx, hipMemcpyAsync(out->gAlbedo, p.out_albedo16 ? (const void*)p.out_albedo16 : (const void*)p.out_albedo, pixels * cb, hipMemcpyDeviceToHost, cs));
+    if (out->gVisibility) HIP_TRY(ctx, hipMemcpyAsync(out->gVisibility, p.out_visibility, pixels * 8, hipMemcpyDeviceToHost, cs));
+    if (out->gDepth) HIP_TRY(ctx, hipMemcpyAsync(out->gDepth, p.out_depth, pixels * 16, hipMemcpyDeviceToHost, cs));
+    if (out->gPrevUVs) HIP_TRY(ctx, hipMemcpyAsync(out->gPrevUVs, p.out_prev_uv, pixels * 8, hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipMemcpyAsync(slot->record, slot->counters.p, CNT_TOTAL * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipEventRecord(slot->copied, cs));
+    slot->ray_count = out->gRayCount;
+    ctx->stats_pending = true;  // (until the ticket is retired, sthip_get_stats reads the counters of the last frame enqueued)
+  } else if (!dev) {
     HIP_TRY(ctx, hipMemcpyAsync(out->gRadiance, p.out_radiance, radiance_entries * cb, hipMemcpyDeviceToHost, st));
     if (out->gAlbedo) HIP_TRY(ctx, hipMemcpyAsync(out->gAlbedo, p.out_albedo16 ? (const void*)p.out_albedo16 : (const void*)p.out_albedo, pixels * cb, hipMemcpyDeviceToHost, st));
     if (out->gVisibility) HIP_TRY(ctx, hipMemcpyAsync(out->gVisibility, p.out_visibility, pixels * 8, hipMemcpyDeviceToHost, st));

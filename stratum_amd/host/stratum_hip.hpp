@@ -853,7 +853,10 @@ class BDPT {
     if (auto app = node.find_in_ancestor<Application>())
       app->OnUpdate.add_listener(node, [this](CommandBuffer& cb, float dt) { update(cb, dt); }, Node::EventPriority::eAlmostLast);  // BDPT.cpp:38
   }
-  virtual ~BDPT() { sthip_destroy(mCtx); }
+  virtual ~BDPT() {
+    mAsync.reset();  // (the pinned ring of submit(), through the deleter submit() installed: before the context goes)
+    sthip_destroy(mCtx);
+  }
   BDPT(const BDPT&) = delete;
 
   // the instance arguments BDPT's constructor reads (BDPT.cpp:78-127): `minPathVertices`, `maxPathVertices`,
@@ -1081,6 +1084,89 @@ class BDPT {
     }
     finish_frame(std::move(fr), fs, seed_count);
   }
+  // render() in two halves, for a host that keeps frames in flight (include/sthip.h: sthip_render_async): submit() enqueues the
+  // frame — the path on `cb`'s stream, the read-back on the library's copy stream into a set of PINNED buffers this object owns
+  // — and returns a ticket; finish(ticket) waits for that frame's outputs, runs the tone map block and makes the frame
+  // prev_result(), as render() does. Frames are finished in the order they were submitted. Frame i + 1 renders while frame i
+  // copies back as long as no more than "output_ring" (2) frames are submitted and not yet in host memory. The frame number and
+  // the "previous views" advance at submit (note_submitted). Not with a debug mode (the debug image chains through host memory).
+  // finish() copies the pinned images into the Frame's vectors (prev_result() keeps its type); a host that wants the pinned
+  // bytes themselves reads them through the ABI. Non-virtual, and the only code that refers to the pipelined entry points.
+  uint64_t submit(CommandBuffer& cb, uint32_t width, uint32_t height, const std::vector<std::pair<ViewData, TransformData>>& views, uint32_t seed_count = 1) {
+    if (mDebugMode != STHIP_DEBUG_NONE) throw std::runtime_error("BDPT::submit: not with a debug mode: use render()");
+    FrameSetup fs;
+    prepare_frame(width, height, views, fs);
+    if (!mAsync) {
+      mAsync = std::shared_ptr<AsyncRing>(new AsyncRing{mCtx, {}}, [](AsyncRing* r) {
+        for (AsyncSet& a : r->sets) (void)sthip_host_free(r->ctx, a.block);
+        delete r;
+      });
+    }
+    const size_t n = (size_t)width * height, cb_bytes = mHalfColorPrecision ? 8 : 16;
+    const size_t bytes = n * (2 * cb_bytes + 8 + 16 + 8) + 16;
+    AsyncSet* set = nullptr;
+    for (AsyncSet& a : mAsync->sets)
+      if (a.ticket == 0) set = &a;
+    if (!set) {
+      mAsync->sets.push_back(AsyncSet{});
+      set = &mAsync->sets.back();
+    }
+    if (set->bytes != bytes) {
+      if (set->block && sthip_host_free(mCtx, set->block) != STHIP_OK) throw std::runtime_error(std::string("sthip_host_free: ") + sthip_last_error(mCtx));
+      set->block = nullptr;
+      set->bytes = 0;
+      if (sthip_host_alloc(mCtx, bytes, &set->block) != STHIP_OK) throw std::runtime_error(std::string("sthip_host_alloc: ") + sthip_last_error(mCtx));
+      set->bytes = bytes;
+    }
+    set->width = width;
+    set->height = height;
+    set->half = mHalfColorPrecision;
+    uint8_t* q = static_cast<uint8_t*>(set->block);
+    sthip_outputs o{};
+    o.gRadiance = reinterpret_cast<float*>(q);
+    o.gAlbedo = reinterpret_cast<float*>(q + n * cb_bytes);
+    o.gVisibility = reinterpret_cast<VisibilityInfo*>(q + 2 * n * cb_bytes);
+    o.gDepth = reinterpret_cast<DepthInfo*>(q + 2 * n * cb_bytes + 8 * n);
+    o.gPrevUVs = reinterpret_cast<float*>(q + 2 * n * cb_bytes + 24 * n);
+    o.gRayCount = reinterpret_cast<uint64_t*>(q + 2 * n * cb_bytes + 32 * n);
+    (void)sthip_set_stream(mCtx, cb.hip_stream);
+    const bool changed = !mPrevInverseViewTransforms.empty() && !fs.ti.empty() && std::memcmp(&mPrevInverseViewTransforms[0], &fs.ti[0], sizeof(TransformData)) != 0;
+    if (changed && !mReprojection) (void)sthip_set_option(mCtx, "reuse_grids_persist", 1);  // (as render())
+    uint64_t ticket = 0;
+    if (sthip_render_async(mCtx, &fs.pc, mSamplingFlags, fs.scene_flags, &fs.f, mFrameNumber, seed_count, &o, &ticket) != STHIP_OK)
+      throw std::runtime_error(std::string("sthip_render_async: ") + sthip_last_error(mCtx));
+    set->ticket = ticket;
+    note_submitted(fs, seed_count);
+    return ticket;
+  }
+  void finish(uint64_t ticket) {
+    AsyncSet* set = nullptr;
+    if (mAsync)
+      for (AsyncSet& a : mAsync->sets)
+        if (a.ticket == ticket && ticket != 0) set = &a;
+    if (!set) throw std::runtime_error("BDPT::finish: no such frame in flight");
+    if (sthip_wait_outputs(mCtx, ticket) != STHIP_OK) throw std::runtime_error(std::string("sthip_wait_outputs: ") + sthip_last_error(mCtx));
+    Frame fr;
+    fr.width = set->width;
+    fr.height = set->height;
+    const size_t n = (size_t)set->width * set->height, cb_bytes = set->half ? 8 : 16;
+    const uint8_t* q = static_cast<const uint8_t*>(set->block);
+    if (set->half) {
+      fr.mRadiance16.assign(reinterpret_cast<const uint16_t*>(q), reinterpret_cast<const uint16_t*>(q) + 4 * n);
+      fr.mAlbedo16.assign(reinterpret_cast<const uint16_t*>(q + n * cb_bytes), reinterpret_cast<const uint16_t*>(q + n * cb_bytes) + 4 * n);
+    } else {
+      fr.mRadiance.assign(reinterpret_cast<const float*>(q), reinterpret_cast<const float*>(q) + 4 * n);
+      fr.mAlbedo.assign(reinterpret_cast<const float*>(q + n * cb_bytes), reinterpret_cast<const float*>(q + n * cb_bytes) + 4 * n);
+    }
+    const uint8_t* g = q + 2 * n * cb_bytes;
+    fr.mVisibility.assign(reinterpret_cast<const VisibilityInfo*>(g), reinterpret_cast<const VisibilityInfo*>(g) + n);
+    fr.mDepth.assign(reinterpret_cast<const DepthInfo*>(g + 8 * n), reinterpret_cast<const DepthInfo*>(g + 8 * n) + n);
+    fr.mPrevUVs.assign(reinterpret_cast<const float*>(g + 24 * n), reinterpret_cast<const float*>(g + 24 * n) + 2 * n);
+    std::memcpy(fr.mRayCount, g + 32 * n, 16);
+    set->ticket = 0;
+    finish_frame(std::move(fr), FrameSetup{}, 0, true);
+  }
+
   // BDPTDebugMode (bdpt.h:177-193; the inspector's "Debug mode", BDPT.cpp:253-262) with mPushConstants.gDebugViewPathLength /
   // gDebugLightPathLength; the image starts from zero when the mode or the frame size changes
   void set_debug_mode(uint32_t mode) {
@@ -1172,6 +1258,20 @@ class BDPT {
   bool mGammaCorrection = true;
   std::vector<ViewData> mPrevViews;
   std::vector<TransformData> mPrevInverseViewTransforms;
+  // submit() / finish(): a set of pinned images per frame in flight (sthip_host_alloc), owned through a handle whose deleter
+  // submit() installs — nothing else here refers to the pipelined entry points
+  struct AsyncSet {
+    void* block = nullptr;  // radiance | albedo | visibility | depth | prev-uv | gRayCount
+    size_t bytes = 0;
+    uint64_t ticket = 0;  // 0: free
+    uint32_t width = 0, height = 0;
+    bool half = false;
+  };
+  struct AsyncRing {
+    sthip_ctx* ctx;
+    std::vector<AsyncSet> sets;
+  };
+  std::shared_ptr<AsyncRing> mAsync;
   Frame mPrevFrame;
 };
 
