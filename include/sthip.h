@@ -188,6 +188,40 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* scene);
 int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* gInstanceTransforms, const sthip_TransformData* gInstanceInverseTransforms,
                                   const sthip_TransformData* gInstanceMotionTransforms, uint32_t instance_count);
 
+/* A mesh deformed, nothing else changed (the reference rebuilds the BLAS of a dirty mesh, Scene.cpp:345,435-459): new
+ * contents for the records [first_vertex, first_vertex + vertex_count) of gVertices — position, normal and both texture
+ * coordinates; the index buffer, instances, materials and transforms are those of the last sthip_scene_upload. The range
+ * is copied into the resident gVertices (and into the copy "keep_scene" keeps, so a later rebuild sees the deformed mesh);
+ * then, on the device, every leaf triangle is gathered again through the index triple it came from, the shading records
+ * beside the triangles are made again, and the boxes of the bottom levels are refitted bottom-up in place, one launch per
+ * height of the tree; the top level, the entries' bounding spheres, the scene bounds, the emitter bounds of
+ * "answer_last_rays" and the 4-wide form follow. The trees keep their shape: closest hit is the minimum over all triangles
+ * (ties by id), so the frame is the one a fresh upload of the deformed scene gives, bit for bit, whatever the deformation
+ * did to the quality of the tree. sah_cost / sah_cost_at_build says what it did: that ratio is the host's signal to upload
+ * again (the walk slows down as it grows). Measured on the 1M-triangle atrium (profiles/r06/refit.json): 1.69 ms for the
+ * call with all 408 970 vertices replaced (0.72 ms of it on the stream), 0.134 of the 12.57 ms the re-upload with the device
+ * builder takes in the same run; the first call on a tree also makes the schedule, 8.2 ms; a sine displacement of 0.15 m
+ * raises the cost ratio to 1.11 and the frame time to 1.03 of a freshly built tree's, one of 1 m to 1.77 and 1.15. Waits for the stream and completes the frames in flight first, as
+ * sthip_scene_update_transforms does; kept reservoir grids ("reuse_grids_persist") are dropped, as at an upload.
+ * Layouts the refit does not serve — "embed_leaves", "treetop", the 8-wide form of "wide_bvh" = 3 — are built again from
+ * the kept scene instead (rebuilt = 1, counted in sthip_stats::full_rebuilds); with "keep_scene" = 0 the call then returns
+ * STHIP_ERR_UNSUPPORTED and changes nothing. STHIP_ERR_INVALID_ARGUMENT: no scene, a NULL pointer, a range past the
+ * uploaded vertex_count. Everything that can be refused or can run out of memory is checked or allocated before the
+ * resident scene is touched, and a call that fails there leaves it as it was. Should a step fail after the vertices have
+ * gone up (a HIP error, or a top level over the new boxes that is too deep or too large for what is resident), the scene is
+ * never left with new triangles under an old top level: with a kept scene it is built again from it (rebuilt = 1); with
+ * "keep_scene" = 0 the call returns the error and NO scene is resident afterwards, as after a failed sthip_scene_upload:
+ * upload again. A library without the feature lacks the symbol. */
+typedef struct sthip_refit_info { /* optional out-parameter, may be NULL */
+  float device_ms;                /* stream time of gather + refit + derived forms (HIP events) */
+  float total_ms;                 /* wall time of the call */
+  float sah_cost;                 /* SAH cost of the bottom levels after the refit, same formula as sah_cost_at_build */
+  float sah_cost_at_build;        /* the same cost of the tree as it was built, before any refit */
+  uint32_t rebuilt;               /* 1: the call fell back to a full rebuild from the kept scene */
+  uint32_t pad;
+} sthip_refit_info;
+int sthip_scene_update_vertices(sthip_ctx* ctx, const sthip_PackedVertexData* vertices, uint32_t first_vertex, uint32_t vertex_count, sthip_refit_info* info);
+
 /* ---- frame: replaces the dispatch sequence of BDPT::render (BDPT.cpp:607-720) ----
  * Renders seeds seed_begin .. seed_begin+seed_count-1 (gRandomSeed = seed, BDPT.cpp:480), one
  * sample per pixel centre per seed (bdpt.hlsl:167), and averages them with the running mean of

@@ -23,6 +23,7 @@ EXPORTS = [
     "sthip_set_stream",
     "sthip_scene_upload",
     "sthip_scene_update_transforms",
+    "sthip_scene_update_vertices",
     "sthip_render",
     "sthip_host_alloc",
     "sthip_host_free",
@@ -97,6 +98,8 @@ def lib():
     L.sthip_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.sthip_scene_upload.restype = C.c_int
     L.sthip_scene_upload.argtypes = [C.c_void_p, C.POINTER(wire.SceneDesc)]
+    L.sthip_scene_update_vertices.restype = C.c_int
+    L.sthip_scene_update_vertices.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(wire.RefitInfo)]
     L.sthip_render.restype = C.c_int
     L.sthip_render.argtypes = [
         C.c_void_p,

@@ -134,6 +134,7 @@ class BDPT:
     def update(self, scene):
         d = scene.desc()
         self._check(self._lib.sthip_scene_upload(self._h, C.byref(d)), "sthip_scene_upload")
+        scene.dirty_vertices = None  # (the whole vertex array went up)
         self._scene = scene
 
     def update_transforms(self, scene):
@@ -145,6 +146,20 @@ class BDPT:
         )
         self._check(rc, "sthip_scene_update_transforms")
         self._scene = scene
+
+    def update_vertices(self, scene):
+        """Only vertex records changed since update(scene) (SceneData.set_vertices): the dirty range goes to the device, the
+        leaf triangles are gathered again and the bottom levels refitted in place (sthip_scene_update_vertices). Returns
+        sthip_refit_info as a dict; `rebuilt` = 1 when the resident layout had to be built again from the kept scene.
+        Raises StratumHipError (unsupported) for such a layout with keep_scene = 0: call update()."""
+        lo, hi = scene.dirty_vertices or (0, 0)
+        info = wire.RefitInfo()
+        part = scene.vertices[lo:hi] if hi > lo else scene.vertices[:0]
+        rc = self._lib.sthip_scene_update_vertices(self._h, wire.ptr(part) if hi > lo else wire.ptr(scene.vertices), lo, hi - lo, C.byref(info))
+        self._check(rc, "sthip_scene_update_vertices")
+        scene.dirty_vertices = None
+        self._scene = scene
+        return {f: getattr(info, f) for f, _ in wire.RefitInfo._fields_ if f != "pad"}
 
     def set_stream(self, stream_handle):
         self._check(self._lib.sthip_set_stream(self._h, C.c_void_p(stream_handle)), "sthip_set_stream")

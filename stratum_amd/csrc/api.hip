@@ -13,6 +13,7 @@
 #include <chrono>
 #include <map>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/sthip.h"
@@ -261,6 +262,16 @@ struct sthip_ctx {
   int use_wide = 1;
   size_t wide_node_count = 0;
   sthip::DeviceWideScratch* wide_scratch = nullptr;  // buffers of the device-side collapse (wide.hip), kept between calls
+  // sthip_scene_update_vertices (refit.hip): the schedule of the resident bottom levels and the refit's scratch; what the
+  // call needs to know of the uploaded arrays; whether the resident layout is one the refit serves
+  sthip::DeviceRefit* refit = nullptr;
+  // the distinct bottom-level roots of the resident entries and each entry's place among them (BVH_INVALID_REF: an entry
+  // without a bottom level): they belong to the resident tree, as the schedule does, and are made with it
+  std::vector<uint32_t> refit_roots, refit_root_of_entry;
+  bool refit_roots_valid = false;
+  uint32_t vertex_count = 0;
+  uint64_t indices_bytes = 0;
+  bool embedded_resident = false;  // the leaf triangles lie in the node array (BuiltBvh::embedded)
   bool want_wide = false;                            // the current scene is walked in its 4-wide form (decided at upload)
   bool lds_materials = true;  // k_shade stages gMaterialData in LDS when it fits 32 KB
   // frame
@@ -304,6 +315,7 @@ struct sthip_ctx {
   // (kernels.h: aims_at_emitter); 0 = every ray is queued and traced. Same frames and ray counts either way.
   int answer_last_rays = 1;
   DevBuf<EmitterBounds> emitters;
+  std::vector<EmitterBounds> emitters_host;  // the table as uploaded (sthip_scene_update_vertices makes its boxes again)
   uint32_t emitter_count = 0;  // 0: not applicable to this scene (no or too many emissive triangle instances)
   DevBuf<unsigned long long> qctl;  // queue control lines (queue_ctl)
   DevBuf<uint32_t> post_scratch;  // maxima / metric accumulator of post.h
@@ -558,6 +570,8 @@ void sthip_destroy(sthip_ctx* ctx) {
   for (void* q : ctx->host_allocs) (void)hipHostFree(q);
   sthip::device_wide_scratch_destroy(ctx->wide_scratch);
   ctx->wide_scratch = nullptr;
+  sthip::device_refit_destroy(ctx->refit);
+  ctx->refit = nullptr;
   ctx->vertices.release();
   ctx->volume_words.release();
   ctx->volumes.release();
@@ -752,6 +766,21 @@ static hipError_t upload_nodes(sthip_ctx* ctx, size_t first, const BvhNode* node
   return hipMemcpy(ctx->nodes.p + first, slots.data(), count * sizeof(BvhNodeSlot), hipMemcpyHostToDevice);
 }
 
+// EmitterBounds from the exact box of an emitter's vertices: widened by 2^-15 of its coordinates' magnitude, as the packed nodes
+// of the tree are, and the sphere that sizes the per-ray padding. false: not finite (the table cannot be used).
+static bool pad_emitter_bounds(EmitterBounds& b) {
+  double diag = 0;
+  for (int a = 0; a < 3; a++) {
+    const float mag = std::max(fabsf(b.lo[a]), fabsf(b.hi[a])) * (1.0f / 32768.0f) + 1e-30f;
+    b.lo[a] -= mag;
+    b.hi[a] += mag;
+    b.sphere[a] = 0.5f * b.lo[a] + 0.5f * b.hi[a];
+    diag += ((double)b.hi[a] - b.lo[a]) * ((double)b.hi[a] - b.lo[a]);
+  }
+  b.sphere[3] = (float)sqrt(diag);  // (twice the box's own radius: the padding only has to be large enough)
+  return std::isfinite(b.sphere[3]);
+}
+
 // The 4-wide form of the tree that is resident now (ctx->nodes / ctx->entries / ctx->bvh.root_ref), made on the device
 // (wide.hip): after a GPU build and after a transforms-only update. On failure the binary walk stays (STHIP_OK): a tree whose
 // boxes do not fit the wide nodes' grid is still a tree.
@@ -796,6 +825,8 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, drain_in_flight(ctx));  // ... and the copy stream of sthip_render_async still reads the staging sets of its frames
   ctx->has_scene = false;
+  sthip::device_refit_invalidate(ctx->refit);  // (the schedule of a refit belongs to the tree that goes away now)
+  ctx->refit_roots_valid = false;
   for (uint32_t i = 0; i < s->light_count; i++)
     if (s->gLightInstances[i] >= s->instance_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: gLightInstances entry out of range");
   bool any_specular = false, any_image = false, any_alpha = false;
@@ -980,22 +1011,14 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
         }
       }
       if (!prims || !(b.lo[0] <= b.hi[0])) continue;  // (no triangle: nothing to hit)
-      double diag = 0;
-      for (int a = 0; a < 3; a++) {
-        const float mag = std::max(fabsf(b.lo[a]), fabsf(b.hi[a])) * (1.0f / 32768.0f) + 1e-30f;
-        b.lo[a] -= mag;
-        b.hi[a] += mag;
-        b.sphere[a] = 0.5f * b.lo[a] + 0.5f * b.hi[a];
-        diag += ((double)b.hi[a] - b.lo[a]) * ((double)b.hi[a] - b.lo[a]);
-      }
-      b.sphere[3] = (float)sqrt(diag);  // (twice the box's own radius: the padding only has to be large enough)
-      if (!std::isfinite(b.sphere[3])) usable = false;
+      if (!pad_emitter_bounds(b)) usable = false;
       b.instance = i;
       static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
       b.identity = (!memcmp(&s->gInstanceTransforms[i], ident, 48) && !memcmp(&s->gInstanceInverseTransforms[i], ident, 48)) ? 1u : 0u;
       bounds.push_back(b);
     }
     ctx->emitter_count = usable ? (uint32_t)bounds.size() : 0u;
+    ctx->emitters_host = usable ? bounds : std::vector<EmitterBounds>();
     if (ctx->emitter_count) {
       HIP_TRY(ctx, ctx->emitters.ensure(bounds.size()));
       HIP_TRY(ctx, hipMemcpy(ctx->emitters.p, bounds.data(), bounds.size() * sizeof(EmitterBounds), hipMemcpyHostToDevice));
@@ -1211,6 +1234,9 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
   ctx->bvh.scene_radius = built.scene_radius;
   ctx->bvh_nodes = nodes_total;
   ctx->bvh_tris = tris_total;
+  ctx->vertex_count = s->vertex_count;
+  ctx->indices_bytes = s->indices_bytes;
+  ctx->embedded_resident = built.embedded;
   ctx->top = std::move(built.top);
   if (ctx->want_wide && built.dev_nodes != 0) {  // the GPU builder's tree: its wide form is made where the nodes are
     const int rc = collapse_resident_tree(ctx);
@@ -1405,49 +1431,10 @@ int sthip_trace_rays(sthip_ctx* ctx, const sthip_ray* rays, uint32_t ray_count, 
   return STHIP_OK;
 }
 
-int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf, const sthip_TransformData* inv, const sthip_TransformData* motion, uint32_t instance_count) {
-  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
-  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_NO_SCENE, "sthip_scene_update_transforms before sthip_scene_upload");
-  if (!xf || !inv) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_transforms: transforms and inverse transforms are required");
-  if (instance_count != ctx->instance_count) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the instance count changed: upload the scene again");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  sthip::TopLevelState next = ctx->top;  // nothing changes unless everything succeeds
-  std::vector<BvhNode> tlas;
-  uint32_t root_ref = 0, top_is_world = 1, stack_depth = 4;
-  float center[3] = {ctx->bvh.scene_cx, ctx->bvh.scene_cy, ctx->bvh.scene_cz}, radius = ctx->bvh.scene_radius;
-  std::string err;
-  if (!sthip::rebuild_top_level(next, xf, inv, instance_count, tlas, root_ref, top_is_world, stack_depth, center, radius, err)) {
-    // An instance of the merged world-space mesh (identity transform at upload) moved: the tree that is resident cannot follow,
-    // the scene is built again from the copy kept at upload, with the new transforms — the configured builder ("bvh_builder" = 1:
-    // ~10 ms per million triangles on the device), everything else as uploaded. Without the copy ("keep_scene" = 0) it is refused.
-    if (ctx->kept.valid && ctx->kept.instances.size() == instance_count) {
-      ctx->kept.xf.assign(xf, xf + instance_count);
-      ctx->kept.inv.assign(inv, inv + instance_count);
-      if (motion)
-        ctx->kept.motion.assign(motion, motion + instance_count);
-      else
-        ctx->kept.motion.clear();
-      const sthip_scene_desc d = ctx->kept.desc();
-      ctx->stats.full_rebuilds++;
-      return sthip_scene_upload(ctx, &d);
-    }
-    return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: " + err);
-  }
-  if (stack_depth > STHIP_MAX_STACK_DEPTH) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the new top level is too deep for the traversal stack");
-  if ((size_t)next.blas_nodes + tlas.size() > ctx->nodes.n) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the new top level does not fit: upload the scene again");
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old top level
-  HIP_TRY(ctx, drain_in_flight(ctx));               // (sthip_render_async: their copies too, so that their tickets are complete)
-  const uint32_t n = instance_count;
-  HIP_TRY(ctx, hipMemcpy(ctx->xf.p, xf, (size_t)n * 48, hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->inv_xf.p, inv, (size_t)n * 48, hipMemcpyHostToDevice));
-  if (motion) {
-    HIP_TRY(ctx, hipMemcpy(ctx->motion_xf.p, motion, (size_t)n * 48, hipMemcpyHostToDevice));
-  } else {
-    std::vector<sthip_TransformData> I(n);
-    memset(I.data(), 0, (size_t)n * 48);
-    for (auto& t : I) t.m[0][0] = t.m[1][1] = t.m[2][2] = 1;
-    HIP_TRY(ctx, hipMemcpy(ctx->motion_xf.p, I.data(), (size_t)n * 48, hipMemcpyHostToDevice));
-  }
+// A new top level over bottom levels that stay where they are (a transforms-only update; a refit, whose bottom levels have new
+// boxes): entries and top-level nodes into HBM, the scene bounds, and the forms derived from the binary tree made again.
+static int install_top_level(sthip_ctx* ctx, sthip::TopLevelState& next, const std::vector<BvhNode>& tlas, uint32_t root_ref, uint32_t top_is_world, uint32_t stack_depth, const float center[3],
+                             float radius) {
   if (!next.entries.empty()) HIP_TRY(ctx, hipMemcpy(ctx->entries.p, next.entries.data(), next.entries.size() * sizeof(TlasEntry), hipMemcpyHostToDevice));
   if (!tlas.empty()) HIP_TRY(ctx, upload_nodes(ctx, next.blas_nodes, tlas.data(), tlas.size()));
   ctx->bvh.root_ref = root_ref;
@@ -1496,6 +1483,221 @@ int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf,
     }
   }
   return configure_stack(ctx);
+}
+
+int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf, const sthip_TransformData* inv, const sthip_TransformData* motion, uint32_t instance_count) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_NO_SCENE, "sthip_scene_update_transforms before sthip_scene_upload");
+  if (!xf || !inv) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_transforms: transforms and inverse transforms are required");
+  if (instance_count != ctx->instance_count) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the instance count changed: upload the scene again");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  sthip::TopLevelState next = ctx->top;  // nothing changes unless everything succeeds
+  std::vector<BvhNode> tlas;
+  uint32_t root_ref = 0, top_is_world = 1, stack_depth = 4;
+  float center[3] = {ctx->bvh.scene_cx, ctx->bvh.scene_cy, ctx->bvh.scene_cz}, radius = ctx->bvh.scene_radius;
+  std::string err;
+  if (!sthip::rebuild_top_level(next, xf, inv, instance_count, tlas, root_ref, top_is_world, stack_depth, center, radius, err)) {
+    // An instance of the merged world-space mesh (identity transform at upload) moved: the tree that is resident cannot follow,
+    // the scene is built again from the copy kept at upload, with the new transforms — the configured builder ("bvh_builder" = 1:
+    // ~10 ms per million triangles on the device), everything else as uploaded. Without the copy ("keep_scene" = 0) it is refused.
+    if (ctx->kept.valid && ctx->kept.instances.size() == instance_count) {
+      ctx->kept.xf.assign(xf, xf + instance_count);
+      ctx->kept.inv.assign(inv, inv + instance_count);
+      if (motion)
+        ctx->kept.motion.assign(motion, motion + instance_count);
+      else
+        ctx->kept.motion.clear();
+      const sthip_scene_desc d = ctx->kept.desc();
+      ctx->stats.full_rebuilds++;
+      return sthip_scene_upload(ctx, &d);
+    }
+    return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: " + err);
+  }
+  if (stack_depth > STHIP_MAX_STACK_DEPTH) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the new top level is too deep for the traversal stack");
+  if ((size_t)next.blas_nodes + tlas.size() > ctx->nodes.n) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the new top level does not fit: upload the scene again");
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old top level
+  HIP_TRY(ctx, drain_in_flight(ctx));               // (sthip_render_async: their copies too, so that their tickets are complete)
+  const uint32_t n = instance_count;
+  HIP_TRY(ctx, hipMemcpy(ctx->xf.p, xf, (size_t)n * 48, hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->inv_xf.p, inv, (size_t)n * 48, hipMemcpyHostToDevice));
+  if (motion) {
+    HIP_TRY(ctx, hipMemcpy(ctx->motion_xf.p, motion, (size_t)n * 48, hipMemcpyHostToDevice));
+  } else {
+    std::vector<sthip_TransformData> I(n);
+    memset(I.data(), 0, (size_t)n * 48);
+    for (auto& t : I) t.m[0][0] = t.m[1][1] = t.m[2][2] = 1;
+    HIP_TRY(ctx, hipMemcpy(ctx->motion_xf.p, I.data(), (size_t)n * 48, hipMemcpyHostToDevice));
+  }
+  // the kept scene follows: a later rebuild from it (sthip_scene_update_vertices on a layout it does not refit) must find the
+  // instances where they are now, and the refit takes the transforms of its top level from here instead of from the device
+  if (ctx->kept.valid && ctx->kept.instances.size() == n) {
+    ctx->kept.xf.assign(xf, xf + n);
+    ctx->kept.inv.assign(inv, inv + n);
+    if (motion)
+      ctx->kept.motion.assign(motion, motion + n);
+    else
+      ctx->kept.motion.clear();
+  }
+  return install_top_level(ctx, next, tlas, root_ref, top_is_world, stack_depth, center, radius);
+}
+
+// The part of sthip_scene_update_vertices that changes the resident scene: the vertex range goes up, the leaf triangles are
+// gathered again, the bottom levels refitted and everything an upload derives from the meshes' bounds made again. A failure
+// in here leaves the scene half changed; the caller repairs that.
+static int refit_resident_scene(sthip_ctx* ctx, const sthip_PackedVertexData* vertices, uint32_t first_vertex, uint32_t vertex_count, bool kept, const sthip_TransformData* xf, const sthip_TransformData* inv,
+                                sthip::RefitResult& res, float& wide_ms) {
+  std::string err;
+  const uint32_t n = ctx->instance_count;
+  const std::vector<uint32_t>& root_of_entry = ctx->refit_root_of_entry;
+  if (vertex_count) HIP_TRY(ctx, hipMemcpyAsync(ctx->vertices.p + first_vertex, vertices, (size_t)vertex_count * sizeof(sthip_PackedVertexData), hipMemcpyHostToDevice, ctx->stream));
+  if (kept && vertex_count && vertices != ctx->kept.vertices.data() + first_vertex) memcpy(ctx->kept.vertices.data() + first_vertex, vertices, (size_t)vertex_count * sizeof(sthip_PackedVertexData));
+  ctx->reuse_grids_valid = false;
+  ctx->nodes_host.n = 0;  // (no layout that reads the host copy of the nodes comes this way; it must not outlive the boxes it holds)
+  if (!sthip::refit_gather(ctx->refit, ctx->tris.p, (uint32_t)ctx->bvh_tris, ctx->vertices.p, ctx->vertex_count, ctx->indices.p, ctx->indices_bytes, ctx->stream, err))
+    return fail(ctx, STHIP_ERR_HIP, "sthip_scene_update_vertices: " + err);
+  if (ctx->bvh_tris && ctx->vertex_count) {
+    hipLaunchKernelGGL(k_fill_tri_shade, dim3(grid_for_early(ctx, (size_t)ctx->bvh_tris)), dim3(STHIP_BLOCK), 0, ctx->stream, reinterpret_cast<const BvhTri*>(ctx->bvh.tris), (uint32_t)ctx->bvh_tris,
+                       (const uint8_t*)nullptr, ctx->vertices.p, ctx->vertex_count, ctx->indices.p, ctx->indices_bytes, ctx->tri_shade.p, ctx->has_alpha ? ctx->tri_uvs.p : nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  std::vector<uint32_t> emitter_instances;
+  for (uint32_t k = 0; k < ctx->emitter_count && k < ctx->emitters_host.size(); k++) emitter_instances.push_back(ctx->emitters_host[k].instance);
+  if (!sthip::refit_boxes(ctx->refit, ctx->nodes.p, ctx->tris.p, (uint32_t)ctx->bvh_tris, ctx->instances.p, emitter_instances, ctx->vertices.p, ctx->vertex_count, ctx->indices.p, ctx->indices_bytes,
+                          ctx->stream, res, err))
+    return fail(ctx, STHIP_ERR_HIP, "sthip_scene_update_vertices: " + err);
+  // what an upload derives from the meshes' bounds (bvh_build.cpp), with its arithmetic, from the roots' exact boxes
+  sthip::TopLevelState next = ctx->top;
+  for (size_t k = 0; k < next.entries.size(); k++) {
+    if (root_of_entry[k] == BVH_INVALID_REF) continue;
+    const float* lo = &res.root_boxes[8 * (size_t)root_of_entry[k]];
+    const float* hi = lo + 4;
+    if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) continue;
+    TlasEntry& e = next.entries[k];
+    for (int a = 0; a < 3; a++) e.center[a] = 0.5f * (lo[a] + hi[a]);
+    e.radius = 0.5f * sqrtf((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
+    if (e.identity == TLAS_ENTRY_IDENTITY) {
+      memcpy(next.merged_box, lo, 12);
+      memcpy(next.merged_box + 3, hi, 12);
+    } else {
+      memcpy(&next.obj_box[6 * k], lo, 12);
+      memcpy(&next.obj_box[6 * k + 3], hi, 12);
+    }
+  }
+  if (!emitter_instances.empty()) {
+    bool usable = true;
+    for (size_t k = 0; k < emitter_instances.size(); k++) {
+      EmitterBounds& b = ctx->emitters_host[k];
+      memcpy(b.lo, &res.emitter_boxes[8 * k], 12);
+      memcpy(b.hi, &res.emitter_boxes[8 * k + 4], 12);
+      if (!(b.lo[0] <= b.hi[0]) || !pad_emitter_bounds(b)) usable = false;
+    }
+    if (usable) {
+      HIP_TRY(ctx, hipMemcpy(ctx->emitters.p, ctx->emitters_host.data(), emitter_instances.size() * sizeof(EmitterBounds), hipMemcpyHostToDevice));
+    } else {  // (no bounds to aim at: every last ray is traced)
+      ctx->emitter_count = 0;
+      ctx->emitters_host.clear();
+    }
+  }
+  std::vector<BvhNode> tlas;
+  uint32_t root_ref = 0, top_is_world = 1, stack_depth = 4;
+  float center[3] = {ctx->bvh.scene_cx, ctx->bvh.scene_cy, ctx->bvh.scene_cz}, radius = ctx->bvh.scene_radius;
+  if (!sthip::rebuild_top_level(next, xf, inv, n, tlas, root_ref, top_is_world, stack_depth, center, radius, err)) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_vertices: " + err);
+  if (stack_depth > STHIP_MAX_STACK_DEPTH) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_vertices: the new top level is too deep for the traversal stack");
+  if ((size_t)next.blas_nodes + tlas.size() > ctx->nodes.n) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_vertices: the new top level does not fit");
+  const float wide_ms_before = ctx->stats.bvh_build_gpu_ms;
+  const int rc = install_top_level(ctx, next, tlas, root_ref, top_is_world, stack_depth, center, radius);
+  wide_ms = ctx->stats.bvh_build_gpu_ms - wide_ms_before;
+  return rc;
+}
+
+// sthip.h. The default layout is refitted where it lies (refit.hip); the layouts that keep more than the node and triangle
+// arrays of the tree (leaf triangles inside the node array, a treetop selected from a host copy of the nodes, the 8-wide form
+// with its permuted triangles) are built again from the kept scene.
+int sthip_scene_update_vertices(sthip_ctx* ctx, const sthip_PackedVertexData* vertices, uint32_t first_vertex, uint32_t vertex_count, sthip_refit_info* info) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (info) memset(info, 0, sizeof(*info));
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_vertices before sthip_scene_upload");
+  if (!vertices) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_vertices: vertices is NULL");
+  if ((uint64_t)first_vertex + vertex_count > ctx->vertex_count)
+    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_vertices: the range ends past the vertex_count of the uploaded scene");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const bool kept = ctx->kept.valid && ctx->kept.vertices.size() == ctx->vertex_count;
+  auto rebuild_from_kept = [&]() {  // (the kept vertices hold the new range already)
+    const sthip_scene_desc d = ctx->kept.desc();
+    ctx->stats.full_rebuilds++;
+    const int rc = sthip_scene_upload(ctx, &d);
+    if (info) {
+      info->rebuilt = 1;
+      info->device_ms = ctx->stats.bvh_build_gpu_ms;
+      info->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return rc;
+  };
+  if (ctx->embedded_resident || ctx->use_treetop || ctx->bvh.top_count || ctx->bvh.wide8_nodes || !ctx->wide8_host.empty()) {
+    if (!kept) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_vertices: this layout (embed_leaves, treetop, wide_bvh = 3) is not refitted and no scene was kept (keep_scene = 0): upload the scene again");
+    if (vertex_count) memcpy(ctx->kept.vertices.data() + first_vertex, vertices, (size_t)vertex_count * sizeof(sthip_PackedVertexData));
+    return rebuild_from_kept();
+  }
+  // everything that can fail for want of memory happens before anything of the resident scene changes
+  if (!ctx->refit_roots_valid || ctx->refit_root_of_entry.size() != ctx->top.entries.size()) {
+    std::unordered_map<uint32_t, uint32_t> place;  // (instances that share a mesh share its root)
+    ctx->refit_roots.clear();
+    ctx->refit_root_of_entry.assign(ctx->top.entries.size(), BVH_INVALID_REF);
+    for (size_t k = 0; k < ctx->top.entries.size(); k++) {
+      const TlasEntry& e = ctx->top.entries[k];
+      if ((e.identity != TLAS_ENTRY_IDENTITY && e.identity != TLAS_ENTRY_TRANSFORMED) || (e.root & BVH_LEAF_BIT) || e.root >= ctx->top.blas_nodes) continue;
+      const auto at = place.emplace(e.root, (uint32_t)ctx->refit_roots.size());
+      if (at.second) ctx->refit_roots.push_back(e.root);
+      ctx->refit_root_of_entry[k] = at.first->second;
+    }
+    ctx->refit_roots_valid = true;
+  }
+  if (!ctx->refit) ctx->refit = sthip::device_refit_create();
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old triangles and boxes
+  HIP_TRY(ctx, drain_in_flight(ctx));               // (sthip_render_async: their copies too, so that their tickets are complete)
+  std::string err;
+  if (!sthip::refit_prepare(ctx->refit, ctx->nodes.p, ctx->top.blas_nodes, ctx->refit_roots, ctx->top.blas_depth, ctx->tris.p, (uint32_t)ctx->bvh_tris, STHIP_MAX_EMITTER_BOUNDS, ctx->stream, err))
+    return fail(ctx, STHIP_ERR_HIP, "sthip_scene_update_vertices: " + err);
+  // the instances' transforms, for the top level: the kept scene has them (sthip_scene_update_transforms keeps it current);
+  // without one they are read back from the device
+  const uint32_t n = ctx->instance_count;
+  std::vector<sthip_TransformData> xf_read, inv_read;
+  const sthip_TransformData *xf = nullptr, *inv = nullptr;
+  if (ctx->kept.valid && ctx->kept.xf.size() == n && ctx->kept.inv.size() == n) {
+    xf = ctx->kept.xf.data();
+    inv = ctx->kept.inv.data();
+  } else {
+    xf_read.resize(n);
+    inv_read.resize(n);
+    HIP_TRY(ctx, hipMemcpy(xf_read.data(), ctx->xf.p, (size_t)n * 48, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(inv_read.data(), ctx->inv_xf.p, (size_t)n * 48, hipMemcpyDeviceToHost));
+    xf = xf_read.data();
+    inv = inv_read.data();
+  }
+  // ---- from here on the resident scene changes ----
+  sthip::RefitResult res;
+  float wide_ms = 0;
+  const int rc = refit_resident_scene(ctx, vertices, first_vertex, vertex_count, kept, xf, inv, res, wide_ms);
+  if (rc != STHIP_OK) {
+    // New triangles under old entries or an old top level would miss hits without a word. With a kept scene (it holds the new
+    // vertices by now) the scene is built again, as for the layouts above; without one no scene is resident any more, as after
+    // a failed sthip_scene_upload, and every call that needs one says so until the host uploads again.
+    if (kept) return rebuild_from_kept();
+    const std::string why = ctx->error;
+    ctx->has_scene = false;
+    sthip::device_refit_invalidate(ctx->refit);
+    ctx->refit_roots_valid = false;
+    return fail(ctx, rc, why + " (the resident scene was dropped half changed: upload the scene again)");
+  }
+  if (info) {
+    info->device_ms = res.gpu_ms + wide_ms;
+    info->sah_cost = (float)res.sah_cost;
+    info->sah_cost_at_build = (float)res.sah_cost_at_build;
+    info->rebuilt = 0;
+    info->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return STHIP_OK;
 }
 
 // One hash grid from one seed's staged appends (hashgrid.h): compact the stage in (path, vertex) order, hash the keys, build

@@ -348,6 +348,29 @@ void device_wide_scratch_destroy(DeviceWideScratch*);
 bool collapse_wide_device(DeviceWideScratch* scratch, const BvhNodeSlot* nodes, uint32_t node_count, const TlasEntry* entries, uint32_t entry_count, uint32_t root_ref, bool top_is_world_blas,
                           uint32_t max_levels, WideNode* wide_nodes, TlasEntry* wide_entries, void* stream, DeviceWideResult& result, std::string& err);
 
+// Deforming meshes (refit.hip): the leaf triangles gathered again from gVertices, the boxes of the bottom levels
+// [0, blas_nodes) refitted bottom-up in place, one launch per height over a schedule that is made once per resident tree.
+struct DeviceRefit;  // (the schedule, the scratch of exact boxes, the read-back buffer: kept between calls)
+struct RefitResult {
+  std::vector<float> root_boxes;     // 8 per root given to refit_prepare: lo.xyz, (subtree cost), hi.xyz, 0 — exact, as a build would bound the mesh
+  std::vector<float> emitter_boxes;  // 8 per emitter instance: lo.xyz, 0, hi.xyz, 0 of the vertices its triangles refer to
+  double sah_cost = 0;               // (sum over roots of: node areas + leaf areas x triangles) / (sum of the roots' areas)
+  double sah_cost_at_build = 0;      // the same figure of the tree as it was when the schedule was made
+  float gpu_ms = 0;                  // refit_gather .. refit_boxes on the stream
+};
+DeviceRefit* device_refit_create();
+void device_refit_destroy(DeviceRefit*);
+void device_refit_invalidate(DeviceRefit*);  // another tree is resident now: the schedule is made again at the next refit_prepare
+// Makes the schedule (if there is none for this tree) and every buffer a refit needs; `roots`: the distinct bottom-level
+// roots; max_levels: a bound of the bottom levels' height. Reads the tree and the triangles as they are (the cost at build).
+bool refit_prepare(DeviceRefit*, BvhNodeSlot* nodes, uint32_t blas_nodes, const std::vector<uint32_t>& roots, uint32_t max_levels, const BvhTri* tris, uint32_t tri_count, uint32_t max_emitters, void* stream,
+                   std::string& err);
+// Enqueues the gather (positions of every leaf triangle from `vertices`, through BvhTri::src_indices / src_vertex).
+bool refit_gather(DeviceRefit*, BvhTri* tris, uint32_t tri_count, const sthip_PackedVertexData* vertices, uint32_t vertex_count, const uint8_t* indices, uint64_t indices_bytes, void* stream, std::string& err);
+// Enqueues the refit and the emitter boxes, waits, and returns the roots' boxes and the costs.
+bool refit_boxes(DeviceRefit*, BvhNodeSlot* nodes, const BvhTri* tris, uint32_t tri_count, const sthip_InstanceData* instances, const std::vector<uint32_t>& emitter_instances,
+                 const sthip_PackedVertexData* vertices, uint32_t vertex_count, const uint8_t* indices, uint64_t indices_bytes, void* stream, RefitResult& result, std::string& err);
+
 // GPU LBVH of one mesh (lbvh.hip): appends nodes and leaf-ordered triangles to the outputs.
 bool lbvh_build_gpu(const std::vector<BvhTri>& tris_in, std::vector<BvhNode>& nodes_out, std::vector<BvhTri>& tris_out, uint32_t& root_ref, uint32_t& stack_need, float& gpu_ms,
                     std::string& err);

@@ -35,6 +35,9 @@
 #include <dlfcn.h>
 
 #include "../../include/sthip.h"
+// A library that cannot refit lacks this symbol (include/sthip.h): a weak reference, so that the host links against it
+// all the same and BDPT::update probes for the call before using it.
+#pragma weak sthip_scene_update_vertices
 #include "../../include/sthip_detmath.h"  // det_f16tof32: export_hdr of a half frame
 
 namespace stm {
@@ -459,6 +462,16 @@ struct Mesh {
 struct MeshPrimitive {
   component_ptr<Material> mMaterial;
   component_ptr<Mesh> mMesh;
+  // A deforming mesh (skinning, cloth, a morph): new vertex data, the same indices. The scene is told with
+  // Scene::mark_dirty() as after any other edit of the graph; BDPT::update then finds only vertex contents changed and
+  // refits the resident tree (last_update_was_vertices_only()).
+  void set_vertices(std::vector<float3> positions, std::vector<float3> normals = {}, std::vector<float2> uvs = {}) {
+    if (!mMesh) throw std::invalid_argument("MeshPrimitive::set_vertices: no mesh");
+    if (positions.size() != mMesh->positions.size()) throw std::invalid_argument("MeshPrimitive::set_vertices: the vertex count changed (topology must stay)");
+    mMesh->positions = std::move(positions);
+    if (!normals.empty()) mMesh->normals = std::move(normals);
+    if (!uvs.empty()) mMesh->uvs = std::move(uvs);
+  }
 };
 struct SpherePrimitive {  // Scene.hpp:34-37
   component_ptr<Material> mMaterial;
@@ -911,6 +924,7 @@ class BDPT {
   BDPTPushConstants& push_constants() { return mPushConstants; }
   const Frame& prev_result() const { return mPrevFrame; }  // BDPT.hpp:18
   bool last_update_was_transforms_only() const { return mLastUpdateWasTransformsOnly; }
+  bool last_update_was_vertices_only() const { return mLastUpdateWasVerticesOnly; }  // (no transform changed with them)
   // tone-map state the reference keeps on its pipeline objects (BDPT.cpp:44-54,190-193,304-309)
   uint32_t& tonemap_mode() { return mTonemapMode; }
   float& exposure() { return mExposure; }
@@ -950,12 +964,40 @@ class BDPT {
     // Only instances moved since the bound SceneData (same geometry, materials, images, volumes): the bottom levels in HBM
     // are still right, as the reference's cached BLASes are (Scene.cpp:435-459); rebuild the top level only.
     bool updated = false;
+    mLastUpdateWasVerticesOnly = false;
     if (mBoundData && same_geometry(*mBoundData, *scene->data())) {
       const int rc = sthip_scene_update_transforms(mCtx, d.gInstanceTransforms, d.gInstanceInverseTransforms, d.gInstanceMotionTransforms, d.instance_count);
       if (rc == STHIP_OK)
         updated = true;
       else if (rc != STHIP_ERR_UNSUPPORTED)
         throw std::runtime_error(std::string("sthip_scene_update_transforms: ") + sthip_last_error(mCtx));
+    } else if (mRefitDeformedMeshes && mBoundData && sthip_scene_update_vertices && same_topology(*mBoundData, *scene->data())) {
+      // A mesh deformed (same indices, instances, materials; only the contents of gVertices differ): the range that changed
+      // goes to the device and the resident bottom levels are refitted there (the reference rebuilds the BLAS of a dirty mesh,
+      // Scene.cpp:345,435-459). A layout the library does not refit without a kept scene answers UNSUPPORTED: upload.
+      const auto& a = mBoundData->mVertices;
+      const auto& b = scene->data()->mVertices;
+      size_t lo = 0, hi = b.size();
+      while (lo < hi && !std::memcmp(&a[lo], &b[lo], sizeof(PackedVertexData))) lo++;
+      while (hi > lo && !std::memcmp(&a[hi - 1], &b[hi - 1], sizeof(PackedVertexData))) hi--;
+      const bool moved = !same_bytes(mBoundData->mInstanceTransforms, scene->data()->mInstanceTransforms) ||
+                         !same_bytes(mBoundData->mInstanceInverseTransforms, scene->data()->mInstanceInverseTransforms) ||
+                         !same_bytes(mBoundData->mInstanceMotionTransforms, scene->data()->mInstanceMotionTransforms);
+      int rc = sthip_scene_update_vertices(mCtx, b.data() + lo, (uint32_t)lo, (uint32_t)(hi - lo), nullptr);
+      if (rc != STHIP_OK && rc != STHIP_ERR_UNSUPPORTED) throw std::runtime_error(std::string("sthip_scene_update_vertices: ") + sthip_last_error(mCtx));
+      if (rc == STHIP_OK && moved) {  // instances moved as well: the top level once more, over the refitted bottom levels
+        rc = sthip_scene_update_transforms(mCtx, d.gInstanceTransforms, d.gInstanceInverseTransforms, d.gInstanceMotionTransforms, d.instance_count);
+        if (rc != STHIP_OK && rc != STHIP_ERR_UNSUPPORTED) throw std::runtime_error(std::string("sthip_scene_update_transforms: ") + sthip_last_error(mCtx));
+      }
+      if (rc == STHIP_OK) {
+        mLastUpdateWasVerticesOnly = !moved;
+        mLastUpdateWasTransformsOnly = false;
+        mBound = scene->data().get();
+        mBoundData = scene->data();
+        mPushConstants.gLightCount = d.light_count;
+        mPushConstants.gEnvironmentMaterialAddress = scene->data()->mEnvironmentMaterialAddress;
+        return;
+      }
     }
     mLastUpdateWasTransformsOnly = updated;
     if (!updated && sthip_scene_upload(mCtx, &d) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_upload: ") + sthip_last_error(mCtx));
@@ -1231,13 +1273,18 @@ class BDPT {
   sthip_ctx* mCtx = nullptr;
   const void* mBound = nullptr;
   std::shared_ptr<Scene::SceneData> mBoundData;
-  bool mLastUpdateWasTransformsOnly = false;
+  bool mLastUpdateWasTransformsOnly = false, mLastUpdateWasVerticesOnly = false;
+  // false: a deformed mesh is uploaded like any other change. The multi-device driver clears it: its ranks must all walk the
+  // same tree form, and it sends them uploads or transforms-only updates, nothing else (stratum_hip_multi.hpp).
+  bool mRefitDeformedMeshes = true;
   template <typename T>
   static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
     return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
   }
-  static bool same_geometry(const Scene::SceneData& a, const Scene::SceneData& b) {
-    if (!same_bytes(a.mVertices, b.mVertices) || !same_bytes(a.mIndices, b.mIndices) || !same_bytes(a.mInstances, b.mInstances) || !same_bytes(a.mMaterialData, b.mMaterialData) ||
+  static bool same_geometry(const Scene::SceneData& a, const Scene::SceneData& b) { return same_bytes(a.mVertices, b.mVertices) && same_topology(a, b); }
+  // everything equal except the CONTENTS of the vertex array (and the transforms, which have update calls of their own)
+  static bool same_topology(const Scene::SceneData& a, const Scene::SceneData& b) {
+    if (a.mVertices.size() != b.mVertices.size() || !same_bytes(a.mIndices, b.mIndices) || !same_bytes(a.mInstances, b.mInstances) || !same_bytes(a.mMaterialData, b.mMaterialData) ||
         !same_bytes(a.mLightInstanceMap, b.mLightInstanceMap) || !same_bytes(a.mDistributionData, b.mDistributionData))
       return false;
     if (a.mResources.image4s != b.mResources.image4s || a.mResources.image1s != b.mResources.image1s || a.mResources.volumes != b.mResources.volumes) return false;  // the same objects

@@ -150,6 +150,7 @@ class MultiDeviceBDPT : public BDPT {
   explicit MultiDeviceBDPT(Node& node, const std::vector<int>& devices, uint32_t tile_w = 64, uint32_t tile_h = 32)
       : BDPT(node, devices.empty() ? 0 : devices[0]), mDevices(devices), mTileW(tile_w), mTileH(tile_h) {
     if (devices.empty()) throw std::invalid_argument("MultiDeviceBDPT: no devices");
+    mRefitDeformedMeshes = false;  // (update() below: a deformed mesh is a full upload on every rank, rank 0 included)
     mRanks.resize(devices.size());
     mCommMutex = std::vector<std::mutex>(devices.size());
     mRanks[0].ctx = mCtx;
@@ -213,6 +214,8 @@ class MultiDeviceBDPT : public BDPT {
 
   // the scene goes to every GPU (replicated: a 1M-triangle scene is < 200 MB of 288 GB), in parallel. Every rank takes the
   // SAME path — a transforms-only update everywhere or a full upload everywhere — so all of them walk the same tree form.
+  // A deformed mesh is a full upload everywhere: BDPT::update's vertices-only refit is switched off here (mRefitDeformedMeshes),
+  // so rank 0 never walks a refitted tree beside freshly built ones and last_update_was_vertices_only() stays false.
   void update(CommandBuffer& cb, float dt) override {
     auto scene = mNode.find_in_ancestor<Scene>();
     if (!scene) scene = mNode.root().find_in_descendants<Scene>();

@@ -99,6 +99,7 @@ class SceneData:
         self.distributions = np.zeros(0, np.float32)  # StructuredBuffer<float> gDistributions
         self.environment_address = 0xFFFFFFFF  # SceneData::mEnvironmentMaterialAddress, Scene.cpp:631-640
         self.volumes = []  # uint8 arrays: ByteAddressBuffer gVolumes[] (NanoVDB float grids)
+        self.dirty_vertices = None  # (begin, end) of the vertex records set_vertices changed and no update has sent yet
 
     @property
     def light_count(self):
@@ -127,6 +128,20 @@ class SceneData:
         self.transforms["m"][index] = m32
         self.inverse_transforms["m"][index] = transform_inverse(m32)
         self.motion_transforms["m"][index] = tmul(prev, self.inverse_transforms["m"][index])
+
+    def set_vertices(self, first, packed):
+        """A mesh deforms: replace the records [first, first + len(packed)) of gVertices (wire.PackedVertexData: position, u,
+        normal, v) and remember the range as dirty; BDPT.update_vertices sends it (sthip_scene_update_vertices). Topology — the
+        index buffer, the instances — stays."""
+        packed = np.ascontiguousarray(packed, dtype=wire.PackedVertexData).reshape(-1)
+        first = int(first)
+        if first < 0 or first + packed.shape[0] > self.vertices.shape[0]:
+            raise ValueError("set_vertices: [%d, %d) is not inside the %d vertices of the scene" % (first, first + packed.shape[0], self.vertices.shape[0]))
+        if packed.shape[0] == 0:
+            return
+        self.vertices[first : first + packed.shape[0]] = packed
+        lo, hi = self.dirty_vertices or (first, first + packed.shape[0])
+        self.dirty_vertices = (int(min(lo, first)), int(max(hi, first + packed.shape[0])))
 
     def view_medium_instances(self, view_transforms):
         """gViewMediumInstances (BDPT.cpp:456-466): per view the volume instance whose grid world box contains the camera."""

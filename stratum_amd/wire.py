@@ -240,6 +240,21 @@ class Stats(C.Structure):
     ]
 
 
+class RefitInfo(C.Structure):  # sthip_refit_info
+    _fields_ = [
+        ("device_ms", C.c_float),
+        ("total_ms", C.c_float),
+        ("sah_cost", C.c_float),
+        ("sah_cost_at_build", C.c_float),
+        ("rebuilt", C.c_uint32),
+        ("pad", C.c_uint32),
+    ]
+
+
+REFIT_INFO_BYTES = 24  # sizeof(sthip_refit_info), include/sthip.h
+assert C.sizeof(RefitInfo) == REFIT_INFO_BYTES
+
+
 def ptr(a):
     """void* of a C-contiguous numpy array (None -> NULL)."""
     if a is None:
