@@ -380,28 +380,39 @@ struct sthip_ctx {
 // again with a global-memory stack of the tree's full height — bounded here so that the spill buffer stays small
 #define STHIP_MAX_STACK_DEPTH 512u
 
-// k_trace's instantiations by (count_traversal, alpha / volumes, bounded stack, treetop)
-static const void* trace_kernel(bool count, bool alpha, bool bounded, bool top) {
-  static const void* const table[16] = {
-      (const void*)&k_trace<false, false, false, false>, (const void*)&k_trace<true, false, false, false>, (const void*)&k_trace<false, true, false, false>, (const void*)&k_trace<true, true, false, false>,
-      (const void*)&k_trace<false, false, true, false>,  (const void*)&k_trace<true, false, true, false>,  (const void*)&k_trace<false, true, true, false>,  (const void*)&k_trace<true, true, true, false>,
-      (const void*)&k_trace<false, false, false, true>,  (const void*)&k_trace<true, false, false, true>,  (const void*)&k_trace<false, true, false, true>,  (const void*)&k_trace<true, true, false, true>,
-      (const void*)&k_trace<false, false, true, true>,   (const void*)&k_trace<true, false, true, true>,   (const void*)&k_trace<false, true, true, true>,   (const void*)&k_trace<true, true, true, true>};
-  return table[(count ? 1 : 0) | (alpha ? 2 : 0) | (bounded ? 4 : 0) | (top ? 8 : 0)];
+// The instantiations that exist, by key (kernel_variants.h): made from the lists the definitions are compiled from, so that a
+// variant outside them has no entry here — a lookup that finds none is the caller's error, not an instantiation in this file
+struct KernelEntry {
+  uint32_t key;
+  const void* fn;
+};
+#define STHIP_SHADE_ENTRY(T, E, L, M, P, D) {sthip::shade_key(T, E, L, M, P, D), (const void*)&k_shade<T, E, L, M, P, D>},
+#define STHIP_TRACE_ENTRY(C, A, B, T, W) {sthip::trace_key(C, A, B, T, W), (const void*)&k_trace<C, A, B, T, W>},
+#define STHIP_LIGHT_ENTRY(T, E, M) {sthip::shade_light_key(T, E, M), (const void*)&k_shade_light<T, E, M>},
+static const KernelEntry g_shade_kernels[] = {STHIP_SHADE_ALL(STHIP_SHADE_ENTRY)};
+static const KernelEntry g_trace_kernels[] = {STHIP_TRACE_ALL(STHIP_TRACE_ENTRY)};
+static const KernelEntry g_shade_light_kernels[] = {STHIP_SHADE_LIGHT(STHIP_LIGHT_ENTRY)};
+
+template <size_t N>
+static const void* find_kernel(const KernelEntry (&table)[N], uint32_t key) {
+  for (const KernelEntry& e : table)
+    if (e.key == key) return e.fn;
+  return nullptr;
 }
-// ... over the 8-wide compressed tree ("wide_bvh" = 3)
-static const void* trace_kernel_wide8(bool count, bool alpha, bool bounded) {
-  static const void* const table[8] = {
-      (const void*)&k_trace<false, false, false, false, 2>, (const void*)&k_trace<true, false, false, false, 2>, (const void*)&k_trace<false, true, false, false, 2>, (const void*)&k_trace<true, true, false, false, 2>,
-      (const void*)&k_trace<false, false, true, false, 2>,  (const void*)&k_trace<true, false, true, false, 2>,  (const void*)&k_trace<false, true, true, false, 2>,  (const void*)&k_trace<true, true, true, false, 2>};
-  return table[(count ? 1 : 0) | (alpha ? 2 : 0) | (bounded ? 4 : 0)];
+// k_trace by (count_traversal, alpha masks / volumes, bounded stack) for the tree the scene is walked in: the 8-wide or 4-wide
+// form ("wide_bvh"; never with the treetop) or the binary one
+static const void* trace_kernel(const DeviceBvh& bvh, bool count, bool alpha, bool top) {
+  const int wide = bvh.wide8_nodes ? 2 : bvh.wide_nodes ? 1 : 0;
+  return find_kernel(g_trace_kernels, sthip::trace_key(count, alpha, bvh.spill != nullptr, top && wide == 0, wide));
 }
-// ... and over the 4-wide tree ("wide_bvh"; never with the treetop)
-static const void* trace_kernel_wide(bool count, bool alpha, bool bounded) {
-  static const void* const table[8] = {
-      (const void*)&k_trace<false, false, false, false, 1>, (const void*)&k_trace<true, false, false, false, 1>, (const void*)&k_trace<false, true, false, false, 1>, (const void*)&k_trace<true, true, false, false, 1>,
-      (const void*)&k_trace<false, false, true, false, 1>,  (const void*)&k_trace<true, false, true, false, 1>,  (const void*)&k_trace<false, true, true, false, 1>,  (const void*)&k_trace<true, true, true, false, 1>};
-  return table[(count ? 1 : 0) | (alpha ? 2 : 0) | (bounded ? 4 : 0)];
+// The kernels with two bool template arguments, all four instantiations of each compiled here
+#define STHIP_KERNEL2(K, a, b) ((a) ? ((b) ? (const void*)&K<true, true> : (const void*)&K<true, false>) : ((b) ? (const void*)&K<false, true> : (const void*)&K<false, false>))
+
+// One launch of a kernel that was picked at run time; `args` are the kernel's parameters, of exactly their types
+template <typename... A>
+static void launch_kernel(const void* fn, uint32_t grid, size_t lds, hipStream_t st, const A&... args) {
+  void* ptrs[] = {(void*)&args...};
+  (void)hipLaunchKernel(fn, dim3(grid), dim3(STHIP_BLOCK), ptrs, lds, st);
 }
 
 #define HIP_TRY(ctx, expr)                                                                            \
@@ -434,10 +445,7 @@ static void fill_counter_stats(sthip_ctx* ctx, const unsigned long long* c) {
   ctx->stats.tris_tested_primary = c[CNT_TRIS_PRIMARY];
 }
 
-static uint32_t grid_for_early(const sthip_ctx* ctx, size_t n) {  // (grid_for, for code above its definition)
-  const size_t blocks = (n + STHIP_BLOCK - 1) / STHIP_BLOCK;
-  return (uint32_t)std::max<size_t>(1, std::min(blocks, (size_t)ctx->cu_count * 32));
-}
+static uint32_t grid_for(const sthip_ctx* ctx, size_t n);
 
 static int fail(sthip_ctx* ctx, int code, const std::string& msg) {
   ctx->error = msg;
@@ -546,13 +554,8 @@ int sthip_create(int device, sthip_ctx** out_ctx) {
   (void)hipEventCreate(&ctx->ev[1]);
   {  // dynamic LDS beyond the 64 KB default for the kernels that carry the traversal stack
     const int lds_max = 160 * 1024;
-    for (int k = 0; k < 16; k++) (void)hipFuncSetAttribute(trace_kernel((k & 1) != 0, (k & 2) != 0, (k & 4) != 0, (k & 8) != 0), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    for (int k = 0; k < 8; k++) (void)hipFuncSetAttribute(trace_kernel_wide((k & 1) != 0, (k & 2) != 0, (k & 4) != 0), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    for (int k = 0; k < 8; k++) (void)hipFuncSetAttribute(trace_kernel_wide8((k & 1) != 0, (k & 2) != 0, (k & 4) != 0), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_batch<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_batch<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_batch<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_batch<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    for (const KernelEntry& e : g_trace_kernels) (void)hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    for (int k = 0; k < 4; k++) (void)hipFuncSetAttribute(STHIP_KERNEL2(k_trace_batch, (k & 2) != 0, (k & 1) != 0), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
   }
   ctx->stats.bvh_node_bytes = sizeof(BvhNodePacked);
   ctx->stats.bvh_tri_bytes = sizeof(BvhTri);
@@ -1266,7 +1269,7 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
         HIP_TRY(ctx, is_tri.ensure(units));
         HIP_TRY(ctx, hipMemcpy(is_tri.p, flags.data(), units, hipMemcpyHostToDevice));
       }
-      hipLaunchKernelGGL(k_fill_tri_shade, dim3(grid_for_early(ctx, units)), dim3(STHIP_BLOCK), 0, ctx->stream, reinterpret_cast<const BvhTri*>(ctx->bvh.tris), (uint32_t)units, is_tri.p, ctx->vertices.p, s->vertex_count,
+      hipLaunchKernelGGL(k_fill_tri_shade, dim3(grid_for(ctx, units)), dim3(STHIP_BLOCK), 0, ctx->stream, reinterpret_cast<const BvhTri*>(ctx->bvh.tris), (uint32_t)units, is_tri.p, ctx->vertices.p, s->vertex_count,
                          ctx->indices.p, (uint64_t)s->indices_bytes, ctx->tri_shade.p, ctx->has_alpha ? ctx->tri_uvs.p : nullptr);
       HIP_TRY(ctx, hipGetLastError());
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (`is_tri` goes out of scope)
@@ -1305,11 +1308,7 @@ static uint32_t grid_for(const sthip_ctx* ctx, size_t n) {
 static int trace_occupancy(const sthip_ctx* ctx, size_t lds_bytes) {  // resident k_trace blocks per CU with that much dynamic LDS
   int per_cu = 0;
   hipError_t e;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu,
-                                                   ctx->bvh.wide8_nodes  ? trace_kernel_wide8(false, false, ctx->bvh.spill != nullptr)
-                                                   : ctx->bvh.wide_nodes ? trace_kernel_wide(false, false, ctx->bvh.spill != nullptr)
-                                                                         : trace_kernel(false, false, ctx->bvh.spill != nullptr, ctx->use_treetop),
-                                                   STHIP_BLOCK, lds_bytes);
+  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_kernel(ctx->bvh, false, false, ctx->use_treetop), STHIP_BLOCK, lds_bytes);
   return e == hipSuccess ? per_cu : 0;
 }
 static uint32_t trace_grid(sthip_ctx* ctx, size_t lds_bytes) {
@@ -1406,17 +1405,7 @@ int sthip_trace_rays(sthip_ctx* ctx, const sthip_ray* rays, uint32_t ray_count, 
   bvh.alpha_test = (ctx->has_alpha && (any_hit & 2u)) ? 1u : 0u;
   bvh.flip_uvs = (any_hit & 4u) ? 1u : 0u;
   any_hit &= 1u;
-  if (any_hit) {
-    if (ctx->count_traversal)
-      hipLaunchKernelGGL((k_trace_batch<true, true>), dim3(grid), dim3(STHIP_BLOCK), lds, ctx->stream, bvh, d_rays, ray_count, d_hits, ctx->counters.p);
-    else
-      hipLaunchKernelGGL((k_trace_batch<true, false>), dim3(grid), dim3(STHIP_BLOCK), lds, ctx->stream, bvh, d_rays, ray_count, d_hits, ctx->counters.p);
-  } else {
-    if (ctx->count_traversal)
-      hipLaunchKernelGGL((k_trace_batch<false, true>), dim3(grid), dim3(STHIP_BLOCK), lds, ctx->stream, bvh, d_rays, ray_count, d_hits, ctx->counters.p);
-    else
-      hipLaunchKernelGGL((k_trace_batch<false, false>), dim3(grid), dim3(STHIP_BLOCK), lds, ctx->stream, bvh, d_rays, ray_count, d_hits, ctx->counters.p);
-  }
+  launch_kernel(STHIP_KERNEL2(k_trace_batch, any_hit != 0, ctx->count_traversal), grid, lds, ctx->stream, bvh, d_rays, ray_count, d_hits, ctx->counters.p);
   HIP_TRY(ctx, hipGetLastError());
   if (!device_ptrs) {
     HIP_TRY(ctx, hipMemcpyAsync(hits, hb.p, (size_t)ray_count * sizeof(sthip_hit), hipMemcpyDeviceToHost, ctx->stream));
@@ -1556,7 +1545,7 @@ static int refit_resident_scene(sthip_ctx* ctx, const sthip_PackedVertexData* ve
   if (!sthip::refit_gather(ctx->refit, ctx->tris.p, (uint32_t)ctx->bvh_tris, ctx->vertices.p, ctx->vertex_count, ctx->indices.p, ctx->indices_bytes, ctx->stream, err))
     return fail(ctx, STHIP_ERR_HIP, "sthip_scene_update_vertices: " + err);
   if (ctx->bvh_tris && ctx->vertex_count) {
-    hipLaunchKernelGGL(k_fill_tri_shade, dim3(grid_for_early(ctx, (size_t)ctx->bvh_tris)), dim3(STHIP_BLOCK), 0, ctx->stream, reinterpret_cast<const BvhTri*>(ctx->bvh.tris), (uint32_t)ctx->bvh_tris,
+    hipLaunchKernelGGL(k_fill_tri_shade, dim3(grid_for(ctx, (size_t)ctx->bvh_tris)), dim3(STHIP_BLOCK), 0, ctx->stream, reinterpret_cast<const BvhTri*>(ctx->bvh.tris), (uint32_t)ctx->bvh_tris,
                        (const uint8_t*)nullptr, ctx->vertices.p, ctx->vertex_count, ctx->indices.p, ctx->indices_bytes, ctx->tri_shade.p, ctx->has_alpha ? ctx->tri_uvs.p : nullptr);
     HIP_TRY(ctx, hipGetLastError());
   }
@@ -1762,20 +1751,921 @@ static void release_path_state(sthip_ctx* ctx) {
   ctx->deep_rays.release();
 }
 
+// ---- the render call: plan_render, reserve_render_buffers, bind_frame_params, run_batches, read_back ----
+
+static uint32_t owned_tiles(uint32_t tiles, uint32_t shard_rank, uint32_t shard_count) { return tiles > shard_rank ? (tiles - shard_rank + shard_count - 1) / shard_count : 0; }
+
+// What a render call resolves from its arguments and the context before it touches the device (plan_render): the resolved
+// flags and push constants, which techniques run, the sizes of the path state, the round counts, the kernels. Plain data that
+// the later phases read.
+struct RenderPlan {
+  sthip_BDPTPushConstants pc;
+  uint32_t sampling_flags, scene_flags, view_count, debug_mode;
+  bool has_env, media, inline_media, nee, connect_views, connect_paths, bdpt, light_tracing, lvc, lvc_reservoirs, nee_reuse, lvc_reuse;
+  bool coherent_rr, coherent_nee, coherent_lvc, presample, ext, shadow_debug, dev, out_packed, every_entry_written;
+  uint32_t W, H, tiles_x, tiles_y, paths_per_seed, path_count, batch, hg_buckets, light_threads, primary_rays, grid, lds_material_bytes;
+  uint32_t max_bounce_rounds, drain_rounds, max_shadow_round;
+  size_t pixels, P, P0, seg_stride, shadow_stride, shadow_entries, hg_slots, lvc_slots, vertices_per_seed, conn_per_path, radiance_entries, presample_n;
+  uint64_t reuse_key[3];
+  const void *k_trace[2], *k_shade, *k_probe, *k_shade_light;  // k_trace without / with traversal counters; the view pass's k_shade and its probe
+  uint32_t shade_lds, probe_lds;
+};
+
+// primary rays = owned pixels that lie inside the image and inside a view (known without asking the GPU)
+static uint32_t count_primary_rays(const RenderPlan& r, const sthip_ctx* ctx, const sthip_frame_desc* frame) {
+  uint32_t primary_rays = 0;
+  if (r.pc.gMaxPathVertices < 2) return 0;
+  for (uint32_t t = ctx->shard_rank; t < r.tiles_x * r.tiles_y; t += ctx->shard_count) {
+    const uint32_t ty = t / r.tiles_x, tx = t - ty * r.tiles_x;
+    const int x0 = (int)(tx * ctx->tile_w), y0 = (int)(ty * ctx->tile_h);
+    const int x1 = (int)std::min(r.W, (tx + 1) * ctx->tile_w), y1 = (int)std::min(r.H, (ty + 1) * ctx->tile_h);
+    if (r.view_count == 1) {
+      const int ax0 = std::max(x0, frame->gViews[0].image_min[0]), ay0 = std::max(y0, frame->gViews[0].image_min[1]);
+      const int ax1 = std::min(x1, frame->gViews[0].image_max[0]), ay1 = std::min(y1, frame->gViews[0].image_max[1]);
+      if (ax1 > ax0 && ay1 > ay0) primary_rays += (uint32_t)(ax1 - ax0) * (uint32_t)(ay1 - ay0);
+    } else {
+      for (int y = y0; y < y1; y++)
+        for (int x = x0; x < x1; x++)
+          for (uint32_t v = 0; v < r.view_count; v++) {
+            const sthip_ViewData& vw = frame->gViews[v];
+            if (x >= vw.image_min[0] && y >= vw.image_min[1] && x < vw.image_max[0] && y < vw.image_max[1]) {
+              primary_rays++;
+              break;
+            }
+          }
+    }
+  }
+  return primary_rays;
+}
+
+// Flag resolution and every argument check of a render call. No HIP call, no allocation, and the context is only read (but for
+// ctx->error and, once the plan is valid, the two stats the out-of-memory retry goes by): a rejected call leaves it as it was.
+static int plan_render(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc_in, uint32_t sampling_flags, uint32_t scene_flags, const sthip_frame_desc* frame, uint32_t seed_count, const sthip_outputs* out,
+                       RenderPlan& r) {
+  if (!pc_in || !frame || !out || !out->gRadiance || !frame->gViews || !frame->gViewTransforms || frame->view_count == 0 || seed_count == 0)
+    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: a required argument is NULL/zero");
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_NO_SCENE, "no scene uploaded");
+  if (pc_in->gViewCount != frame->view_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: gViewCount != frame.view_count");
+  if ((out->gDepth || out->gPrevUVs) && !frame->gInverseViewTransforms && !frame->gPrevInverseViewTransforms)
+    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: depth / prev-uv outputs need gInverseViewTransforms");
+  // BDPT_FLAG_TRACE_LIGHT is a per-kernel specialisation of the reference (sample_photons), never a caller's choice
+  if (scene_flags & STHIP_BDPT_FLAG_TRACE_LIGHT) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: BDPT_FLAG_TRACE_LIGHT is not a scene flag a caller sets");
+  const uint32_t unsupported = (1u << STHIP_eSampleLightPower);
+  if (sampling_flags & unsupported) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: a sampling flag outside the built hot path is set");
+  if (pc_in->gMaxPathVertices > 60 || pc_in->gMaxDiffuseVertices > 60) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: path length limits above 60");
+  if (pc_in->gLightCount > ctx->light_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: gLightCount exceeds the uploaded light list");
+
+  // flag resolution of BDPT::render (BDPT.cpp:486-523), idempotent if the host has done it already
+  memset(&r, 0, sizeof(r));
+  sthip_BDPTPushConstants& pcn = r.pc;
+  pcn = *pc_in;
+  if (pcn.gLightCount == 0) scene_flags &= ~STHIP_BDPT_FLAG_HAS_EMISSIVES;
+  const bool has_env = (scene_flags & STHIP_BDPT_FLAG_HAS_ENVIRONMENT) != 0, has_emissives = (scene_flags & STHIP_BDPT_FLAG_HAS_EMISSIVES) != 0;
+  if (!has_env) pcn.gEnvironmentSampleProbability = 0;
+  if (!has_emissives) pcn.gEnvironmentSampleProbability = 1;
+  if (!has_emissives && !has_env) sampling_flags &= ~((1u << STHIP_eNEE) | (1u << STHIP_eConnectToViews) | (1u << STHIP_eConnectToLightPaths));
+  if (!(sampling_flags & (1u << STHIP_eNEE))) sampling_flags &= ~((1u << STHIP_ePresampleLights) | (1u << STHIP_eNEEReservoirs) | (1u << STHIP_eNEEReservoirReuse));
+  if (!(sampling_flags & (1u << STHIP_eNEEReservoirs))) sampling_flags &= ~(1u << STHIP_eNEEReservoirReuse);  // only connect_light_reservoir touches the grid
+  if (!(sampling_flags & (1u << STHIP_eLVC))) sampling_flags &= ~((1u << STHIP_eLVCReservoirs) | (1u << STHIP_eLVCReservoirReuse));  // BDPT.cpp:517-520
+  if (!(sampling_flags & (1u << STHIP_eConnectToLightPaths))) sampling_flags &= ~((1u << STHIP_eLVC) | (1u << STHIP_eLVCReservoirs) | (1u << STHIP_eLVCReservoirReuse));  // only connect_lvc reads the cache
+  if (!(sampling_flags & (1u << STHIP_eLVCReservoirs))) sampling_flags &= ~(1u << STHIP_eLVCReservoirReuse);  // the reuse sits inside connect_lvc's reservoir branch
+  if (!(sampling_flags & ((1u << STHIP_eNEE) | (1u << STHIP_eLVC)))) sampling_flags &= ~(1u << STHIP_eDeferShadowRays);  // BDPT.cpp:522-523
+  // eCoherentSampling only touches the index of a presampled light (path.hlsli:317,379) and connect_lvc's (:688,703)
+  if (!(sampling_flags & ((1u << STHIP_ePresampleLights) | (1u << STHIP_eLVC)))) sampling_flags &= ~(1u << STHIP_eCoherentSampling);
+  const sthip_BDPTPushConstants* pc = &pcn;
+  r.sampling_flags = sampling_flags;
+  r.scene_flags = scene_flags;
+  r.has_env = has_env;
+  r.view_count = frame->view_count;
+  const auto flag = [&](uint32_t bit) { return (sampling_flags & (1u << bit)) != 0; };
+  if (has_env) {  // the Environment record (environment.h:17-22): ImageValue3, then 4 offsets into gDistributions when an image is bound
+    const size_t addr = pcn.gEnvironmentMaterialAddress;
+    if (addr + 16 > ctx->materials_host.size() || (addr & 3)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: gEnvironmentMaterialAddress is outside gMaterialData");
+    uint32_t rec[8] = {0};
+    memcpy(rec, ctx->materials_host.data() + addr, 16);
+    if (rec[3] < STHIP_IMAGE_COUNT) {
+      if (rec[3] >= ctx->image_count || addr + 32 > ctx->materials_host.size()) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: the environment refers to an image that is not in gImages");
+      memcpy(rec, ctx->materials_host.data() + addr, 32);
+      const size_t w = ctx->image_dims[rec[3]].first, h = ctx->image_dims[rec[3]].second;
+      const size_t need[4] = {h, w * h, h + 1, (w + 1) * h};  // marginal_pdf, row_pdf, marginal_cdf, row_cdf (dist2.h)
+      for (int k = 0; k < 4; k++)
+        if ((size_t)rec[4 + k] + need[k] > ctx->distribution_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: an environment distribution table lies outside gDistributions");
+    }
+  }
+
+  // participating media (BDPT_FLAG_HAS_MEDIA, BDPT.cpp:497-500)
+  if (ctx->has_volumes && !(scene_flags & STHIP_BDPT_FLAG_HAS_MEDIA)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: the scene has volume instances but BDPT_FLAG_HAS_MEDIA is not set");
+  const bool media = r.media = ctx->has_volumes;
+  if (media && flag(STHIP_eCoherentSampling)) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: eCoherentSampling with media (walks through volumes break the lockstep of a workgroup)");
+  // With media every visibility ray draws random numbers. A deferred NEE ray carries its own offset (k_shadow_media walks it);
+  // everything else draws from the path's own stream in the middle of a vertex — NEE without eDeferShadowRays, light tracing's
+  // connect_view, the connections to stored light vertices or to the light vertex cache — and k_shade / k_shade_light walk those
+  // themselves (visibility_walk_media).
+  if (!media) pcn.gMaxNullCollisions = 0;
+  const uint32_t W = r.W = pc->gOutputExtent[0], H = r.H = pc->gOutputExtent[1];
+  if (W == 0 || H == 0) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: empty output extent");
+  r.pixels = (size_t)W * H;
+  r.tiles_x = (W + ctx->tile_w - 1) / ctx->tile_w;
+  r.tiles_y = (H + ctx->tile_h - 1) / ctx->tile_h;
+  r.paths_per_seed = owned_tiles(r.tiles_x * r.tiles_y, ctx->shard_rank, ctx->shard_count) * ctx->tile_w * ctx->tile_h;
+  // Seeds traced together in one pass. A shard of a frame is small (1/8 of 1080p = 259 K paths does not fill
+  // 256 CUs of persistent waves), so several seeds of the owned pixels share the launches, up to ~4 M paths.
+  const uint32_t max_in_flight = (uint32_t)std::max<uint64_t>(1, (ctx->max_paths_in_flight) / std::max(1u, r.paths_per_seed));
+  // Reservoir reuse couples the seeds of a call: seed s looks into the hash grid seed s - 1 built (the reference's frame
+  // and previous frame), so they are traced one at a time and the grid is built between them.
+  const bool nee_reuse = r.nee_reuse = flag(STHIP_eNEEReservoirReuse);
+  const bool lvc_reuse = r.lvc_reuse = flag(STHIP_eLVCReservoirReuse);
+  // BDPTDebugMode: upstream's gDebugImage persists from frame to frame and most modes add to it or overwrite it: the seeds of a
+  // call are traced one after the other, as its frames are
+  const uint32_t debug_mode = r.debug_mode = out->gDebugImage ? out->debug_mode : 0u;
+  if (debug_mode >= STHIP_DEBUG_MODE_COUNT) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: debug_mode is not a BDPTDebugMode");
+  const uint32_t batch = r.batch = (nee_reuse || lvc_reuse || debug_mode) ? 1u : std::min(seed_count, max_in_flight);
+  r.path_count = batch * r.paths_per_seed;
+  // light tracing (eConnectToViews, BDPT.cpp:653-667): sample_photons' padded dispatch, dispatch_over(W, ceil(gLightPathCount / W))
+  const bool connect_views = r.connect_views = flag(STHIP_eConnectToViews);
+  const bool connect_paths = r.connect_paths = flag(STHIP_eConnectToLightPaths);  // light-subpath connections, no light vertex cache
+  const bool bdpt = r.bdpt = connect_views || connect_paths;
+  const bool light_tracing = r.light_tracing = bdpt && pc->gMaxPathVertices > 2;
+  if (bdpt) {
+    if (has_env) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: light subpaths with an environment (upstream starts environment light paths from an unset position, bdpt.hlsl:109-113)");
+    if (!frame->gInverseViewTransforms) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: eConnectToViews / eConnectToLightPaths need gInverseViewTransforms");
+    if (connect_paths && !flag(STHIP_eRemapThreads) && (W & 7u))
+      return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: eConnectToLightPaths without eRemapThreads needs a width that is a multiple of 8 (upstream's padding threads race on the vertex slots of the next row)");
+    if (connect_paths && pc->gMaxDiffuseVertices < 1) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: eConnectToLightPaths needs gMaxDiffuseVertices >= 1");
+  }
+  const bool lvc = r.lvc = connect_paths && flag(STHIP_eLVC);
+  r.lvc_reservoirs = lvc && flag(STHIP_eLVCReservoirs);
+  if (lvc) {
+    if (pc->gMaxDiffuseVertices < 2) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: eLVC needs gMaxDiffuseVertices >= 2 (a light path stores vertices 1 .. gMaxDiffuseVertices - 1)");
+    if (pc->gLightPathCount == 0 || (uint64_t)pc->gLightPathCount * pc->gMaxDiffuseVertices > (1ull << 28)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: eLVC needs 0 < gLightPathCount * gMaxDiffuseVertices <= 2^28");
+  }
+  const uint32_t light_rows = (pc->gLightPathCount + W - 1) / W;
+  const uint32_t light_threads = r.light_threads = light_tracing ? ((W + 7) / 8) * 8 * ((light_rows + 3) / 4) * 4 : 0;
+  if ((uint64_t)light_threads * batch > 0x7FFFFFFFull || (light_tracing && (uint64_t)batch * W * H > 0x7FFFFFFFull)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many light paths in flight");
+  const size_t P = r.P = std::max<size_t>(std::max<size_t>(1, r.path_count), (size_t)light_threads * batch);
+  r.P0 = std::max<size_t>(1, r.paths_per_seed);
+  r.vertices_per_seed = connect_paths ? (size_t)pc->gLightPathCount * pc->gMaxDiffuseVertices : 0;
+  const size_t conn_per_path = r.conn_per_path = connect_paths ? pc->gMaxDiffuseVertices - 1 : 0;
+  if (connect_paths && (uint64_t)P * std::max<size_t>(1, conn_per_path) >= 0x40000000ull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many connection entries in flight");
+  if (lvc) {
+    r.lvc_slots = (size_t)pc->gLightPathCount * (pc->gMaxDiffuseVertices - 1) * batch;
+    if (r.lvc_slots > 0x7FFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many light-vertex-cache slots in flight");
+  }
+
+  r.hg_buckets = (nee_reuse || lvc_reuse) ? pc->gHashGridBucketCount + 32u : 0u;  // probing does not wrap (hashgrid.h)
+  if (nee_reuse || lvc_reuse) {
+    if (has_env) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: eNEEReservoirReuse with an environment (a stored environment sample is read back as a surface point upstream: sample_Le leaves its pdfA positive)");
+    if (ctx->shard_count > 1) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: eNEEReservoirReuse on a pixel-tile shard (the grid is a whole-frame structure: render replicas and reduce)");
+    if (pc->gHashGridBucketCount == 0 || pc->gHashGridBucketCount > (1u << 28) || !(pc->gHashGridMinBucketRadius > 0)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: eNEEReservoirReuse needs 0 < gHashGridBucketCount <= 2^28 and gHashGridMinBucketRadius > 0");
+    r.hg_slots = (size_t)((W + 7) / 8) * ((H + 3) / 4) * 32 * std::max(1u, pc->gMaxDiffuseVertices);  // covers both map_pixel_coord forms
+    if (r.hg_slots > 0x7FFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many hash-grid append slots");
+  }
+  // what the grids of this call are built for: the first seed looks into the ones the previous call left only if the key is the same
+  r.reuse_key[0] = (uint64_t)(nee_reuse ? 1u : 0u) | (lvc_reuse ? 2u : 0u);
+  r.reuse_key[1] = r.hg_buckets;
+  r.reuse_key[2] = r.hg_slots;
+
+  // The queues are cut into QUEUE_SEGMENTS segments (traverse.h). A segment starts as a contiguous eighth of the
+  // slots and only shrinks from bounce to bounce, which bounds it and the distance between segments.
+  r.grid = std::max<uint32_t>(grid_for(ctx, P), QUEUE_SEGMENTS);
+  r.seg_stride = (((P + QUEUE_SEGMENTS - 1) / QUEUE_SEGMENTS) + 63) & ~(size_t)63;
+  if (r.seg_stride * QUEUE_SEGMENTS > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many paths in flight");
+  // a vertex queues at most one NEE ray, plus one visibility ray per stored light vertex it connects to
+  // (media: the walks of earlier vertices are still in the queue when a vertex adds its own — at most one per diffuse vertex and path)
+  r.shadow_stride = r.seg_stride * (media ? std::max<size_t>(1, pc->gMaxDiffuseVertices) : 1 + conn_per_path);
+  if (r.shadow_stride * QUEUE_SEGMENTS > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many shadow rays in flight");
+  r.shadow_entries = r.shadow_stride * QUEUE_SEGMENTS;  // per round; media ping-pong between two such regions
+  if (media && 2 * r.shadow_entries > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many shadow rays in flight");
+  // ePresampleLights (BDPT.cpp:644-651): gLightPresampleTileSize x TileCount light points per seed in flight
+  r.presample = flag(STHIP_ePresampleLights) && pc->gMaxPathVertices > 2;
+  r.presample_n = (size_t)pc->gLightPresampleTileSize * pc->gLightPresampleTileCount;
+  if (flag(STHIP_ePresampleLights)) {
+    if (has_env) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: ePresampleLights with an environment (upstream leaves the presampled environment direction unset, bdpt.hlsl:93)");
+    if (r.presample_n == 0 || r.presample_n > (1u << 24)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: gLightPresampleTileSize * gLightPresampleTileCount must be in 1 .. 2^24");
+  }
+  if (media && frame->gViewMediumInstances)
+    for (uint32_t v = 0; v < frame->view_count; v++) {
+      const uint32_t mi = frame->gViewMediumInstances[v];
+      if (mi != 0xFFFFu && (mi >= ctx->instance_count || !ctx->instance_is_volume[mi])) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: gViewMediumInstances entry is not a volume instance");
+    }
+  if (out->radiance_layout > STHIP_LAYOUT_SHARD_TILES) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: unknown radiance_layout");
+
+  // eCoherentRR takes effect in rounds in which a path can reach the roulette (shade_view_round); never with media
+  r.coherent_rr = flag(STHIP_eCoherentRR) && !media;
+  // eCoherentSampling: one probe per site and round (FrameParams::cs_nee / cs_lvc)
+  r.coherent_nee = flag(STHIP_eCoherentSampling) && flag(STHIP_ePresampleLights) && flag(STHIP_eNEE);
+  r.coherent_lvc = flag(STHIP_eCoherentSampling) && lvc;
+  r.nee = flag(STHIP_eNEE);
+  r.inline_media = media && r.nee && !flag(STHIP_eDeferShadowRays);
+  if (debug_mode) {
+    // inline shadow rays add to the debug image only where they are unoccluded: they are traced once more, with what they add
+    const bool inline_adds = (debug_mode == STHIP_DEBUG_RESERVOIR_WEIGHT || (debug_mode == STHIP_DEBUG_PATH_LENGTH_CONTRIBUTION && pc->gDebugLightPathLength == 1)) && r.nee &&
+                             !flag(STHIP_eDeferShadowRays) && !media;
+    // so do light-subpath connections (accumulate_contribution with the light vertex's length, path.hlsli:797,820); connect_lvc's
+    // deferred record (:781-789) adds to the radiance only
+    const bool connection_adds = debug_mode == STHIP_DEBUG_PATH_LENGTH_CONTRIBUTION && pc->gDebugLightPathLength >= 2 && connect_paths && !media && !(flag(STHIP_eLVC) && flag(STHIP_eDeferShadowRays));
+    r.shadow_debug = inline_adds || connection_adds;
+  }
+  r.dev = out->device_ptrs != 0;
+  r.out_packed = out->radiance_layout == STHIP_LAYOUT_SHARD_TILES;
+  r.radiance_entries = r.out_packed ? std::max<size_t>(1, r.paths_per_seed) : r.pixels;
+  r.primary_rays = count_primary_rays(r, ctx, frame);
+  // Pixels this shard does not own and pixels outside every view are zero (a sum-reduce over shards assembles the frame).
+  // When the shard is the whole frame and every pixel lies in a view, every output entry is written by the pass itself —
+  // the first vertex's G-buffer stores (hit or miss) and k_resolve — so the five fills (131 MB at 1080p) are left out.
+  r.every_entry_written = ctx->shard_count == 1 && !r.out_packed && !media && pc->gMaxPathVertices >= 2 && (size_t)r.primary_rays == r.pixels;
+  // closest-hit rays per path <= gMaxPathVertices - 1 (path.hlsli:960); without specular materials every scattering
+  // vertex counts as a diffuse vertex, so the path also ends after gMaxDiffuseVertices + 1 rays (path.hlsli:964-966):
+  // rounds beyond that would only be empty launches
+  r.max_bounce_rounds = pc->gMaxPathVertices >= 2 ? pc->gMaxPathVertices - 1 : 0;
+  if (!ctx->has_specular) r.max_bounce_rounds = std::min(r.max_bounce_rounds, pc->gMaxDiffuseVertices + 1);
+  // media: a trace() call walks from volume boundary to volume boundary, one k_trace round per segment (up to 2 per
+  // volume instance and ray); a shadow ray likewise, so its last segments need rounds of their own after the last bounce.
+  // The queue control words exist for 64 rounds; paths / shadow rays still walking after that are dropped.
+  if (media) {
+    r.drain_rounds = std::min(8u, 2 * ctx->volume_instances + 1);
+    r.max_bounce_rounds = std::min<uint64_t>(62 - r.drain_rounds, (uint64_t)r.max_bounce_rounds * (1 + 2 * ctx->volume_instances));
+  }
+  // The deepest round whose vertices can queue a visibility ray. Without specular materials the vertex shaded in round d is
+  // diffuse vertex d + 1, and the diffuse budget ends a path before NEE (path.hlsli:964-966 precede :978): rounds beyond
+  // gMaxDiffuseVertices - 1 leave their shadow queue empty, and the launch that would trace it is left out.
+  r.max_shadow_round = 0xFFFFFFFFu;
+  if (!ctx->has_specular && !media && !bdpt) r.max_shadow_round = pc->gMaxDiffuseVertices ? pc->gMaxDiffuseVertices - 1 : 0u;
+
+  // the kernels (kernel_variants.h): a variant that was never instantiated is an error of this call, not something to compile here
+  r.ext = ctx->has_spheres || has_env || bdpt || flag(STHIP_eNEEReservoirs) || flag(STHIP_eShadingNormalShadowFix);
+  r.lds_material_bytes = (ctx->lds_materials && !ctx->textured && ctx->materials_host.size() <= 32768) ? (uint32_t)(ctx->materials_host.size() & ~(size_t)3) : 0u;
+  const int media_mode = media ? (r.inline_media ? 2 : 1) : 0;
+  const bool alpha = (ctx->has_alpha && flag(STHIP_eAlphaTest)) || ctx->has_volumes;  // alpha masks under eAlphaTest, volume instances: the instantiation that carries them
+  char tuple[96];
+  const auto missing = [&]() { return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, std::string("render: no instantiation ") + tuple + " in kernel_variants.h"); };
+  for (int probe = 0; probe < 2; probe++) {
+    if (probe && !(r.coherent_rr || r.coherent_nee || r.coherent_lvc)) break;
+    const sthip::ShadeVariant v = sthip::select_shade_variant(ctx->textured, r.ext, bdpt, media_mode, probe != 0, debug_mode != 0);
+    snprintf(tuple, sizeof tuple, "k_shade<%d, %d, %d, %d, %d, %d>", v.textured, v.ext, v.lt, v.media, v.probe, v.debug);
+    if (!((probe ? r.k_probe : r.k_shade) = find_kernel(g_shade_kernels, sthip::shade_key(v.textured, v.ext, v.lt, v.media, v.probe, v.debug)))) return missing();
+    (probe ? r.probe_lds : r.shade_lds) = sthip::shade_lds_bytes(v, r.lds_material_bytes);
+  }
+  for (int count = 0; count < 2; count++) {
+    r.k_trace[count] = trace_kernel(ctx->bvh, count != 0, alpha, ctx->bvh.top_count != 0);
+    snprintf(tuple, sizeof tuple, "k_trace<%d, %d, %d, %d> of the resident tree", count, alpha, ctx->bvh.spill != nullptr, ctx->bvh.top_count != 0);
+    if (!r.k_trace[count]) return missing();
+  }
+  if (light_tracing) {
+    r.k_shade_light = find_kernel(g_shade_light_kernels, sthip::shade_light_key(ctx->textured, true, media));
+    snprintf(tuple, sizeof tuple, "k_shade_light<%d, 1, %d>", ctx->textured, media);
+    if (!r.k_shade_light) return missing();
+  }
+  ctx->stats.paths_per_seed = r.paths_per_seed;
+  ctx->stats.seeds_in_flight = batch;
+  return STHIP_OK;
+}
+
+// Every buffer the call needs, at the sizes of the plan (DevBuf::ensure keeps what is large enough), and the two temp-size queries
+static int reserve_render_buffers(sthip_ctx* ctx, const RenderPlan& r, const sthip_outputs* out, AsyncSlot* slot) {
+  const size_t P = r.P, hg_slots = r.hg_slots, shadow_entries = r.shadow_entries, queue_entries = r.seg_stride * QUEUE_SEGMENTS;
+  if (r.bdpt) {
+    HIP_TRY(ctx, ctx->bdpt.ensure(P));
+    if (r.light_tracing && r.connect_views) HIP_TRY(ctx, ctx->light_trace.ensure((size_t)r.batch * r.W * r.H * 4));
+    if (r.connect_paths) {
+      HIP_TRY(ctx, ctx->light_vertices.ensure(4 * std::max<size_t>(1, r.vertices_per_seed * r.batch)));
+      HIP_TRY(ctx, ctx->conn.ensure(std::max<size_t>(1, (size_t)r.path_count * r.conn_per_path)));
+    }
+    if (r.lvc) {
+      HIP_TRY(ctx, ctx->lvc_staging.ensure(4 * r.lvc_slots));
+      HIP_TRY(ctx, ctx->lvc_flags.ensure(r.lvc_slots));
+      HIP_TRY(ctx, ctx->lvc_offsets.ensure(r.lvc_slots));
+      HIP_TRY(ctx, ctx->lvc_count.ensure(r.batch));
+      size_t tmp_bytes = 0;
+      HIP_TRY(ctx, sthip::lvc_compact(nullptr, (uint32_t)(r.lvc_slots / r.batch), r.batch, 0, nullptr, nullptr, ctx->lvc_flags.p, ctx->lvc_offsets.p, nullptr, tmp_bytes, ctx->stream));
+      HIP_TRY(ctx, ctx->lvc_tmp.ensure(std::max<size_t>(16, tmp_bytes)));
+      if (r.lvc_reservoirs) HIP_TRY(ctx, ctx->path_contrib.ensure(P));
+    }
+  }
+  if (r.nee_reuse || r.lvc_reuse) {
+    if (r.nee_reuse) {
+      HIP_TRY(ctx, ctx->hg_appends.ensure(4 * hg_slots));
+      HIP_TRY(ctx, ctx->hg_compact.ensure(4 * hg_slots));
+      HIP_TRY(ctx, ctx->hg_data.ensure(3 * hg_slots));
+    }
+    if (r.lvc_reuse) {
+      HIP_TRY(ctx, ctx->lg_appends.ensure(6 * hg_slots));
+      HIP_TRY(ctx, ctx->lg_compact.ensure(6 * hg_slots));
+      HIP_TRY(ctx, ctx->lg_data.ensure(5 * hg_slots));
+      for (DevBuf<uint32_t>* b : {&ctx->lg_checksums, &ctx->lg_counters, &ctx->lg_indices}) HIP_TRY(ctx, b->ensure(r.hg_buckets));
+    }
+    for (DevBuf<uint32_t>* b : {&ctx->hg_flags, &ctx->hg_offsets, &ctx->hg_dest, &ctx->hg_bucket_of, &ctx->hg_append, &ctx->hg_sorted_bucket, &ctx->hg_sorted_append}) HIP_TRY(ctx, b->ensure(hg_slots));
+    for (DevBuf<unsigned long long>* b : {&ctx->hg_key64, &ctx->hg_sorted_key64}) HIP_TRY(ctx, b->ensure(hg_slots));
+    for (DevBuf<uint32_t>* b : {&ctx->hg_checksums, &ctx->hg_counters, &ctx->hg_indices}) HIP_TRY(ctx, b->ensure(r.hg_buckets));
+    HIP_TRY(ctx, ctx->hg_keys.ensure(hg_slots));
+    HIP_TRY(ctx, ctx->hg_count.ensure(1));
+    HIP_TRY(ctx, ctx->hg_owner.ensure(r.hg_buckets + 2 + 1024));  // (+ hashgrid.hip's control words and special-cell list)
+    size_t tmp_bytes = 0, build_bytes = 0;
+    HIP_TRY(ctx, sthip::lvc_compact(nullptr, (uint32_t)hg_slots, 1, 0, nullptr, nullptr, ctx->hg_flags.p, ctx->hg_offsets.p, nullptr, tmp_bytes, ctx->stream));
+    HIP_TRY(ctx, sthip::hashgrid_build_device(nullptr, nullptr, (uint32_t)hg_slots, r.hg_buckets, nullptr, ctx->hg_counters.p, ctx->hg_indices.p, nullptr, nullptr, ctx->hg_bucket_of.p, ctx->hg_append.p,
+                                              ctx->hg_sorted_bucket.p, ctx->hg_sorted_append.p, ctx->hg_key64.p, ctx->hg_sorted_key64.p, nullptr, build_bytes, ctx->stream));
+    HIP_TRY(ctx, ctx->hg_tmp.ensure(std::max<size_t>(16, std::max(tmp_bytes, build_bytes))));
+  }
+
+  for (DevBuf<float4>* b : {&ctx->ray_o, &ctx->ray_d, &ctx->hit, &ctx->beta, &ctx->radiance, &ctx->shadow_sum}) HIP_TRY(ctx, b->ensure(P));
+  HIP_TRY(ctx, ctx->hit_leaf.ensure(P));
+  HIP_TRY(ctx, ctx->accum.ensure(r.P0));
+  if (ctx->textured || r.debug_mode) HIP_TRY(ctx, ctx->cone.ensure(P));  // (a debug mode runs the general instantiation of k_shade)
+  if (r.debug_mode) HIP_TRY(ctx, ctx->debug.ensure(P));
+  HIP_TRY(ctx, ctx->shadow_rays.ensure(3 * shadow_entries * (r.media ? 2 : 1)));
+  if (ctx->bvh.spill) {  // bounded LDS stacks: room for every ray of a trace launch to overflow (4 x float4 each)
+    HIP_TRY(ctx, ctx->deep_rays.ensure(4 * (P + shadow_entries)));
+    if (ctx->deep_count.n < 2) {  // [0] rays in the deep queue, [1] k_trace_deep blocks that are through: both zero between launches (k_trace_deep resets them)
+      HIP_TRY(ctx, ctx->deep_count.ensure(2));
+      HIP_TRY(ctx, hipMemsetAsync(ctx->deep_count.p, 0, 8, ctx->stream));
+    }
+  }
+  if (r.media) {
+    HIP_TRY(ctx, ctx->media_state.ensure(2 * P));
+    HIP_TRY(ctx, ctx->shadow_hit.ensure(2 * shadow_entries));
+    HIP_TRY(ctx, ctx->shadow_ext.ensure(2 * shadow_entries));
+    HIP_TRY(ctx, ctx->shadow_result.ensure(P * std::max(1u, r.pc.gMaxDiffuseVertices)));
+    HIP_TRY(ctx, ctx->view_medium.ensure(std::max(1u, r.view_count)));
+  }
+  HIP_TRY(ctx, ctx->meta.ensure(P));
+  for (DevBuf<uint32_t>* b : {&ctx->queue0, &ctx->queue1, &ctx->queue_kept}) HIP_TRY(ctx, b->ensure(queue_entries));
+  HIP_TRY(ctx, ctx->counters.ensure(CNT_TOTAL));
+  HIP_TRY(ctx, ctx->qctl.ensure((size_t)3 * 64 * QUEUE_SEGMENTS * QCTL_STRIDE));  // path queues, shadow queues, and (BDPTDebugMode) the shadow rays' debug halves
+  if (r.sampling_flags & (1u << STHIP_ePresampleLights)) HIP_TRY(ctx, ctx->presampled.ensure(2 * r.presample_n * r.batch));
+  const size_t vbytes = (size_t)r.view_count * 48, params_bytes = 5 * vbytes + (size_t)r.view_count * 4;
+  HIP_TRY(ctx, ctx->views.ensure(5 * vbytes));
+  if (slot && slot->params_cap < params_bytes) {  // the pipelined form keeps the call's arrays in the slot's pinned block
+    if (slot->params) (void)hipHostFree(slot->params);
+    slot->params = nullptr;
+    slot->params_cap = 0;
+    HIP_TRY(ctx, hipHostMalloc((void**)&slot->params, params_bytes, hipHostMallocDefault));
+    slot->params_cap = params_bytes;
+  }
+  if (r.coherent_rr) HIP_TRY(ctx, ctx->rr.ensure(P));
+  if (r.coherent_nee) HIP_TRY(ctx, ctx->cs_nee.ensure(P));
+  if (r.coherent_lvc) HIP_TRY(ctx, ctx->cs_lvc.ensure(P));
+  if (r.inline_media || (r.media && r.bdpt))  // (light tracing's connect_view and the light-subpath connections walk inline whatever eDeferShadowRays says)
+    HIP_TRY(ctx, ctx->shade_stack.ensure((size_t)r.grid * STHIP_BLOCK * std::max(1u, ctx->bvh.stack_depth)));
+
+  // outputs: device pointers are written in place, host pointers go through staging buffers
+  const size_t cb = ctx->color_bytes(), pixels = r.pixels;  // bytes of one colour-image entry (radiance, albedo, debug)
+  const auto color_entries = [](size_t n, size_t bytes) { return (n * bytes + 15) / 16; };  // float4 entries of a staging buffer
+  if (r.debug_mode && !r.dev) HIP_TRY(ctx, ctx->out_debug.ensure(color_entries(pixels, cb)));
+  if (r.shadow_debug) HIP_TRY(ctx, ctx->shadow_debug.ensure(ctx->shadow_rays.n));
+  if (!r.dev) {
+    // the synchronous form has one staging set per context; a frame of sthip_render_async has its slot's, which the copy
+    // stream reads while the next frame renders into another (allocated at first use, released when the frame's size changes)
+    if (slot && (slot->key[0] != pixels || slot->key[1] != r.radiance_entries || slot->key[2] != cb)) {
+      slot->release_images();
+      slot->key[0] = pixels;
+      slot->key[1] = r.radiance_entries;
+      slot->key[2] = cb;
+    }
+    HIP_TRY(ctx, (slot ? slot->radiance : ctx->out_radiance).ensure(color_entries(r.radiance_entries, cb)));
+    if (out->gAlbedo) HIP_TRY(ctx, (slot ? slot->albedo : ctx->out_albedo).ensure(color_entries(pixels, cb)));
+    if (out->gVisibility) HIP_TRY(ctx, (slot ? slot->visibility : ctx->out_visibility).ensure(pixels));
+    if (out->gDepth) HIP_TRY(ctx, (slot ? slot->depth : ctx->out_depth).ensure(pixels));
+    if (out->gPrevUVs) HIP_TRY(ctx, (slot ? slot->prev_uv : ctx->out_prev_uv).ensure(pixels));
+    if (slot) HIP_TRY(ctx, slot->counters.ensure(CNT_TOTAL));
+  }
+  // half colour precision: k_shade writes the albedo in binary32 to a stage, k_resolve rounds it into the caller's image (or its staging)
+  if (ctx->half_color && out->gAlbedo) HIP_TRY(ctx, ctx->albedo_stage.ensure(pixels));
+  return STHIP_OK;
+}
+
+// Fills the kernels' parameter block from the plan and the reserved buffers, uploads the view arrays, and clears what of the
+// outputs the pass will not write itself. The first phase that enqueues work.
+static int bind_frame_params(sthip_ctx* ctx, const RenderPlan& r, const sthip_frame_desc* frame, const sthip_outputs* out, AsyncSlot* slot, FrameParams& p) {
+  hipStream_t st = ctx->stream;
+  const size_t pixels = r.pixels, cb = ctx->color_bytes(), vbytes = (size_t)r.view_count * 48;
+  memset(&p, 0, sizeof(p));
+  p.pc = r.pc;
+  p.sampling_flags = r.sampling_flags;
+  p.scene_flags = r.scene_flags;
+  p.shard_rank = ctx->shard_rank;
+  p.shard_count = ctx->shard_count;
+  p.tile_w = ctx->tile_w;
+  p.tile_h = ctx->tile_h;
+  p.tiles_x = r.tiles_x;
+  p.tiles_y = r.tiles_y;
+  p.paths_per_seed = r.paths_per_seed;
+  p.path_count = r.path_count;
+  {
+    std::vector<uint8_t> stack_copy(slot ? 0 : 5 * vbytes);
+    uint8_t* const host = slot ? slot->params : stack_copy.data();
+    const void* const arrays[5] = {frame->gViews, frame->gViewTransforms, frame->gPrevViews ? (const void*)frame->gPrevViews : frame->gViews,
+                                   frame->gPrevInverseViewTransforms ? frame->gPrevInverseViewTransforms : frame->gInverseViewTransforms, frame->gInverseViewTransforms};
+    for (int k = 0; k < 5; k++)  // (an array the caller left out is zero)
+      arrays[k] ? memcpy(host + k * vbytes, arrays[k], vbytes) : memset(host + k * vbytes, 0, vbytes);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->views.p, host, 5 * vbytes, hipMemcpyHostToDevice, st));
+    if (!slot) HIP_TRY(ctx, hipStreamSynchronize(st));  // `stack_copy` goes out of scope (the slot's block lives until the slot's next frame, which waits for this one)
+  }
+  p.views = reinterpret_cast<const sthip_ViewData*>(ctx->views.p);
+  p.view_xf = reinterpret_cast<const sthip_TransformData*>(ctx->views.p + vbytes);
+  p.prev_views = reinterpret_cast<const sthip_ViewData*>(ctx->views.p + 2 * vbytes);
+  p.prev_inv_view_xf = reinterpret_cast<const sthip_TransformData*>(ctx->views.p + 3 * vbytes);
+  p.inv_view_xf = reinterpret_cast<const sthip_TransformData*>(ctx->views.p + 4 * vbytes);
+  p.bdpt = r.bdpt ? ctx->bdpt.p : nullptr;
+  p.light_trace = r.light_tracing && r.connect_views ? ctx->light_trace.p : nullptr;
+  p.light_trace_empty = r.connect_views && !r.light_tracing ? 1u : 0u;
+  p.light_vertices = r.connect_paths ? ctx->light_vertices.p : nullptr;
+  p.conn = r.connect_paths && r.conn_per_path ? ctx->conn.p : nullptr;
+  p.lds_material_bytes = r.lds_material_bytes;
+  p.hg_checksums = ctx->hg_checksums.p;
+  p.hg_counters = ctx->hg_counters.p;
+  p.hg_indices = ctx->hg_indices.p;
+  p.hg_data = ctx->hg_data.p;
+  // the first seed of the call looks into the grids the previous call left, if it left them for the same estimator and table
+  p.hg_prev = ((r.nee_reuse || r.lvc_reuse) && ctx->reuse_persist && ctx->reuse_grids_valid && !memcmp(r.reuse_key, ctx->reuse_key, sizeof r.reuse_key)) ? 1u : 0u;
+  if (r.nee_reuse || r.lvc_reuse) ctx->reuse_grids_valid = false;  // (until this call has left its own)
+  p.hg_appends = r.nee_reuse ? ctx->hg_appends.p : nullptr;
+  p.lg_checksums = ctx->lg_checksums.p;
+  p.lg_counters = ctx->lg_counters.p;
+  p.lg_indices = ctx->lg_indices.p;
+  p.lg_data = ctx->lg_data.p;
+  p.lg_appends = r.lvc_reuse ? ctx->lg_appends.p : nullptr;
+  p.lvc_staging = r.lvc ? ctx->lvc_staging.p : nullptr;
+  p.lvc_count = r.lvc ? ctx->lvc_count.p : nullptr;
+  p.path_contrib = r.lvc_reservoirs ? ctx->path_contrib.p : nullptr;
+  p.light_threads = r.light_threads;
+  p.light_trace_quantization = 65536;  // BDPT.hpp:55 mLightTraceQuantization
+
+  p.bvh = ctx->bvh;
+  p.bvh.alpha_test = (ctx->has_alpha && (r.sampling_flags & (1u << STHIP_eAlphaTest))) ? 1u : 0u;  // intersection.hlsli:118
+  p.bvh.flip_uvs = (r.sampling_flags & (1u << STHIP_eFlipTriangleUVs)) ? 1u : 0u;
+  p.scene.vertices = ctx->vertices.p;
+  p.scene.indices = ctx->indices.p;
+  p.scene.instances = ctx->instances.p;
+  p.scene.xf = ctx->xf.p;
+  p.scene.inv_xf = ctx->inv_xf.p;
+  p.scene.motion_xf = ctx->motion_xf.p;
+  p.scene.materials = ctx->materials.p;
+  p.scene.lights = ctx->lights.p;
+  p.scene.instance_count = ctx->instance_count;
+  p.scene.light_count = ctx->light_count;
+  p.scene.images = ctx->images.p;
+  p.scene.image_texels = ctx->image_texels.p;
+  p.scene.image_count = ctx->image_count;
+  p.scene.distributions = ctx->distributions.p;
+  p.scene.distribution_count = ctx->distribution_count;
+  p.scene.volume_words = ctx->volume_words.p;
+  p.scene.volumes = ctx->volumes.p;
+  p.scene.volume_count = ctx->volume_count;
+  p.scene.leaf_tris = ctx->bvh.tris;
+  p.scene.leaf_shade = reinterpret_cast<const float4*>(ctx->tri_shade.p);
+  p.ray_o = ctx->ray_o.p;
+  p.ray_d = ctx->ray_d.p;
+  p.hit = ctx->hit.p;
+  p.hit_leaf = ctx->hit_leaf.p;
+  p.beta = ctx->beta.p;
+  p.meta = ctx->meta.p;
+  p.radiance = ctx->radiance.p;
+  p.shadow_sum = ctx->shadow_sum.p;
+  p.accum = ctx->accum.p;
+  p.cone = (ctx->textured || r.debug_mode) ? ctx->cone.p : nullptr;
+  p.queue[0] = ctx->queue0.p;
+  p.queue[1] = ctx->queue1.p;
+  p.shadow_rays = ctx->shadow_rays.p;
+  p.deep_rays = ctx->deep_rays.p;
+  p.deep_count = ctx->deep_count.p;
+  p.presampled = ctx->presampled.p;
+  p.counters = ctx->counters.p;
+  p.qctl = ctx->qctl.p;
+  p.seg_stride = (uint32_t)r.seg_stride;
+  p.shadow_stride = (uint32_t)r.shadow_stride;
+  p.media = r.media ? 1u : 0u;
+  p.inline_media = r.inline_media ? 1u : 0u;
+  if (r.inline_media || (r.media && r.bdpt)) p.shade_stack = ctx->shade_stack.p;
+  if (r.media) {
+    p.shadow_alt = (uint32_t)r.shadow_entries;
+    p.media_state = ctx->media_state.p;
+    p.shadow_hit = ctx->shadow_hit.p;
+    p.shadow_ext = ctx->shadow_ext.p;
+    p.shadow_result = ctx->shadow_result.p;
+    if (frame->gViewMediumInstances) {
+      if (slot) {  // (the caller's array is borrowed for the call only: the upload reads the slot's pinned copy)
+        memcpy(slot->params + 5 * vbytes, frame->gViewMediumInstances, (size_t)r.view_count * 4);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->view_medium.p, slot->params + 5 * vbytes, (size_t)r.view_count * 4, hipMemcpyHostToDevice, st));
+      } else {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->view_medium.p, frame->gViewMediumInstances, (size_t)r.view_count * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+      }
+      p.view_medium = ctx->view_medium.p;
+    }
+  }
+  p.count_traversal = ctx->count_traversal ? 1u : 0u;
+  p.refill_idle = ctx->refill_idle;
+  p.inst_flags = ctx->inst_flags.p;
+  p.emitters = ctx->emitters.p;
+  p.emitter_count = 0;  // (set where the view pass starts: only the plain pipeline answers last rays)
+  p.no_specular = ctx->has_specular ? 0u : 1u;
+  p.inner_min_lanes = ctx->inner_min_lanes;
+  p.rounds = r.max_bounce_rounds + r.drain_rounds;
+
+  p.out_half = ctx->half_color ? 1u : 0u;
+  p.debug_mode = r.debug_mode;
+  p.debug = r.debug_mode ? ctx->debug.p : nullptr;
+  if (r.debug_mode) {
+    if (r.dev) {
+      p.out_debug = out->gDebugImage;
+    } else {  // in / out: what the caller's image holds goes up first
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->out_debug.p, out->gDebugImage, pixels * cb, hipMemcpyHostToDevice, st));
+      p.out_debug = ctx->out_debug.p;
+    }
+    if (r.shadow_debug) p.shadow_debug = ctx->shadow_debug.p;
+  }
+  p.out_packed = r.out_packed ? 1u : 0u;
+  if (r.dev) {
+    p.out_radiance = out->gRadiance;
+    p.out_albedo = reinterpret_cast<float4*>(out->gAlbedo);
+    p.out_visibility = out->gVisibility;
+    p.out_depth = out->gDepth;
+    p.out_prev_uv = reinterpret_cast<float2*>(out->gPrevUVs);
+  } else {
+    p.out_radiance = slot ? slot->radiance.p : ctx->out_radiance.p;
+    if (out->gAlbedo) p.out_albedo = slot ? slot->albedo.p : ctx->out_albedo.p;
+    if (out->gVisibility) p.out_visibility = slot ? slot->visibility.p : ctx->out_visibility.p;
+    if (out->gDepth) p.out_depth = slot ? slot->depth.p : ctx->out_depth.p;
+    if (out->gPrevUVs) p.out_prev_uv = slot ? slot->prev_uv.p : ctx->out_prev_uv.p;
+  }
+  if (ctx->half_color && p.out_albedo) {
+    p.out_albedo16 = reinterpret_cast<Half4*>(p.out_albedo);
+    p.out_albedo = ctx->albedo_stage.p;
+  }
+  // The next writer of a staging set — the fills below or the first G-buffer store — runs after the copy of the frame that used
+  // the set before (a no-op for an event that was never recorded). The binary32 albedo stage of half colour precision is one
+  // per context: only k_shade and k_resolve touch it, in stream order; the copy reads the slot's RGBA16F image.
+  if (slot) HIP_TRY(ctx, hipStreamWaitEvent(st, slot->copied, 0));
+  if (!r.every_entry_written) {
+    HIP_TRY(ctx, hipMemsetAsync(p.out_radiance, 0, r.radiance_entries * cb, st));
+    if (p.out_albedo) HIP_TRY(ctx, hipMemsetAsync(p.out_albedo, 0, pixels * 16, st));
+    if (p.out_albedo16) HIP_TRY(ctx, hipMemsetAsync(p.out_albedo16, 0, pixels * 8, st));
+    if (p.out_visibility) HIP_TRY(ctx, hipMemsetAsync(p.out_visibility, 0, pixels * 8, st));
+    if (p.out_depth) HIP_TRY(ctx, hipMemsetAsync(p.out_depth, 0, pixels * 16, st));
+    if (p.out_prev_uv) HIP_TRY(ctx, hipMemsetAsync(p.out_prev_uv, 0, pixels * 8, st));
+  }
+  return STHIP_OK;
+}
+
+// What the launches of one render call share
+struct RenderRun {
+  sthip_ctx* ctx;
+  const RenderPlan& plan;
+  hipStream_t st;
+  uint32_t tgrid;  // blocks of a k_trace launch (persistent: what is resident at once)
+  size_t lds;      // ... and its dynamic LDS
+};
+
+// One k_trace launch over the path queue of round `dc` and the shadow queue of round `ds` (TRACE_NONE: none) and, for a tree
+// higher than the LDS stack (the bounded instantiation), k_trace_deep for the rays that overflowed
+static void launch_trace(const RenderRun& run, const FrameParams& p, uint32_t dc, uint32_t ds, bool count) {
+  launch_kernel(run.plan.k_trace[count ? 1 : 0], run.tgrid, run.lds, run.st, p, dc, ds);
+  if (p.bvh.spill) {
+    const bool alpha = p.bvh.alpha_test || run.ctx->has_volumes;
+    launch_kernel(STHIP_KERNEL2(k_trace_deep, count, alpha), (uint32_t)run.ctx->cu_count * 8u, 0, run.st, p);  // one spill column per thread (configure_stack)
+  }
+}
+
+// The view pass's shading of round `depth`: the probes of eCoherentRR / eCoherentSampling, then the round's k_shade
+static void shade_view_round(const RenderRun& run, FrameParams& p, uint32_t depth) {
+  sthip_ctx* ctx = run.ctx;
+  const RenderPlan& r = run.plan;
+  hipStream_t st = run.st;
+  // eCoherentRR: a vertex shaded in round `depth` has path_length depth + 2; the roulette runs for
+  // gMinPathVertices <= path_length < gMaxPathVertices at a non-specular vertex that is within the diffuse budget —
+  // without specular materials that is vertex number depth + 1 of at most gMaxDiffuseVertices. In such a round the
+  // paths first report their p (k_shade<PROBE>), the 8x4 groups agree (k_rr_reduce), then the round proper runs.
+  // A probe: the round's k_shade without any output, up to the statement `kind` names (FrameParams::probe_kind)
+  auto launch_probe = [&](uint32_t kind) {
+    FrameParams probe = p;
+    probe.probe_kind = kind;
+    probe.out_albedo = nullptr;
+    probe.out_visibility = nullptr;
+    probe.out_depth = nullptr;
+    probe.out_prev_uv = nullptr;
+    launch_kernel(r.k_probe, r.grid, r.probe_lds, st, probe, depth);
+  };
+  const unsigned reduce_grid = (unsigned)((p.path_count + STHIP_BLOCK - 1) / STHIP_BLOCK);
+  p.rr = nullptr;
+  if (r.coherent_rr && depth + 2 >= r.pc.gMinPathVertices && depth + 2 < r.pc.gMaxPathVertices && (ctx->has_specular || depth + 1 <= r.pc.gMaxDiffuseVertices)) {
+    p.rr = ctx->rr.p;
+    (void)hipMemsetAsync(ctx->rr.p, 0, (size_t)p.path_count * 16, st);
+    launch_probe(1);
+    hipLaunchKernelGGL(k_rr_reduce, dim3(reduce_grid), dim3(STHIP_BLOCK), 0, st, p);
+  }
+  // eCoherentSampling: the NEE index first (with the roulette's verdict known), then connect_lvc's (with the NEE index
+  // known: how many numbers a path draws in between depends on the candidates it looked at)
+  p.cs_nee = nullptr;
+  p.cs_lvc = nullptr;
+  if (r.coherent_nee) {
+    p.cs_nee = ctx->cs_nee.p;
+    (void)hipMemsetAsync(ctx->cs_nee.p, 0, (size_t)p.path_count * 8, st);
+    launch_probe(2);
+    hipLaunchKernelGGL(k_cs_reduce, dim3(reduce_grid), dim3(STHIP_BLOCK), 0, st, p.cs_nee, p.path_count);
+  }
+  if (r.coherent_lvc) {
+    p.cs_lvc = ctx->cs_lvc.p;
+    (void)hipMemsetAsync(ctx->cs_lvc.p, 0, (size_t)p.path_count * 8, st);
+    launch_probe(3);
+    hipLaunchKernelGGL(k_cs_reduce, dim3(reduce_grid), dim3(STHIP_BLOCK), 0, st, p.cs_lvc, p.path_count);
+  }
+  // untextured scenes, no light subpaths, no media, no debug mode. Where the path or diffuse budget can end at this round's
+  // vertex, only the paths that still have something to do reach k_shade (k_cull_terminal).
+  const bool plain = !ctx->textured && !r.bdpt && !r.media && !r.debug_mode;
+  if (plain && ctx->cull_terminal && depth >= 1 && !p.rr && !p.cs_nee && !p.cs_lvc && (depth + 2 >= r.pc.gMaxPathVertices || depth + 1 > r.pc.gMaxDiffuseVertices)) {
+    // a block keeps what it meets in LDS: as many blocks per segment as it takes for a segment's share to fit (16 KB at 1080p)
+    uint32_t per_segment = CULL_BLOCKS_PER_SEGMENT, per_block;
+    for (;; per_segment *= 2) {
+      per_block = (uint32_t)((((size_t)p.seg_stride + (size_t)per_segment * STHIP_BLOCK - 1) / ((size_t)per_segment * STHIP_BLOCK)) * STHIP_BLOCK);  // entries a block can meet
+      if ((size_t)(per_block + 2) * 4 <= 48 * 1024) break;
+    }
+    hipLaunchKernelGGL(k_cull_terminal, dim3(QUEUE_SEGMENTS * per_segment), dim3(STHIP_BLOCK), (size_t)(per_block + 2) * 4, st, p, depth, ctx->queue_kept.p, per_block);
+    FrameParams pk = p;
+    pk.queue[depth & 1u] = ctx->queue_kept.p;
+    pk.culled = 1;
+    launch_kernel(r.k_shade, r.grid, r.shade_lds, st, pk, depth);
+  } else {
+    launch_kernel(r.k_shade, r.grid, r.shade_lds, st, p, depth);
+  }
+}
+
+// The passes of every batch of seeds: the light pass (sample_photons), the compaction of the light vertex cache, the view pass,
+// k_resolve, and the hash grids the next seed looks into
+static int run_batches(const RenderRun& run, FrameParams& p, uint32_t seed_begin, uint32_t seed_count) {
+  sthip_ctx* ctx = run.ctx;
+  const RenderPlan& r = run.plan;
+  const sthip_BDPTPushConstants* pc = &r.pc;
+  hipStream_t st = run.st;
+  const uint32_t grid = r.grid;
+  const size_t pixels = r.pixels, hg_slots = r.hg_slots;
+  const bool timing = ctx->time_kernels;
+  float ms_trace = 0, ms_primary = 0, ms_shade = 0, ms_other = 0;
+  uint32_t launches_trace = 0, launches_primary = 0;
+  uint64_t rays_primary = 0;
+  auto timed = [&](float& acc, auto&& launch) -> int {
+    if (timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
+    launch();
+    HIP_TRY(ctx, hipGetLastError());
+    if (timing) {
+      HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
+      HIP_TRY(ctx, hipEventSynchronize(ctx->ev[1]));
+      float ms = 0;
+      HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+      acc += ms;
+    }
+    return STHIP_OK;
+  };
+  bool counters_cleared = false;  // (the first pass's k_clear takes the counters along with its queue control words)
+  for (uint32_t s = 0; s < seed_count; s += r.batch) {
+    const uint32_t in_flight = std::min(r.batch, seed_count - s);
+    p.seed = seed_begin + s;
+    p.seeds_in_flight = in_flight;
+    p.write_aov = s == 0 ? 1u : 0u;
+    int rc = STHIP_OK;
+    // queue sizes and heads are per pass; the ray / traversal counters run over the whole call
+    auto reset_queues = [&]() -> int {
+      const uint32_t per_depth = QUEUE_SEGMENTS * QCTL_STRIDE;  // 64-bit words
+      const uint32_t words = (r.max_bounce_rounds + r.drain_rounds + 1) * per_depth;  // the last round's shade appends to depth + 1; k_resolve sums p.rounds of them
+      hipLaunchKernelGGL(k_clear, dim3(std::max(1u, std::min(64u, (2 * words + CNT_TOTAL + STHIP_BLOCK - 1) / STHIP_BLOCK))), dim3(STHIP_BLOCK), 0, st, queue_ctl_host(ctx->qctl.p, 0, 0), words,
+                         queue_ctl_host(ctx->qctl.p, 1, 0), words, ctx->counters.p, counters_cleared ? 0u : (uint32_t)CNT_TOTAL);
+      counters_cleared = true;
+      if (p.shadow_debug) HIP_TRY(ctx, hipMemsetAsync(queue_ctl_host(ctx->qctl.p, 2, 0), 0, (size_t)words * 8, st));  // the debug halves' queues (BDPTDebugMode)
+      HIP_TRY(ctx, hipGetLastError());
+      return STHIP_OK;
+    };
+    auto trace = [&](uint32_t dc, uint32_t ds) -> int {
+      if (dc == TRACE_NONE && ds == TRACE_NONE) return STHIP_OK;
+      launches_trace++;
+      return timed(ms_trace, [&]() {
+        launch_trace(run, p, dc, ds, ctx->count_traversal);
+        if (p.shadow_debug && ds != TRACE_NONE) {
+          // BDPTDebugMode: the same shadow rays once more, carrying what each adds to the debug image, accumulated into the paths'
+          // debug pixels the way the first pass accumulated their contributions into the radiance (finish_ray)
+          FrameParams q = p;
+          q.shadow_rays = p.shadow_debug;
+          q.radiance = p.debug;
+          q.shadow_sum = p.debug;  // (a connection's debug half exists while NEE's rays are deferred: finish_ray's target either way)
+          q.qctl = p.qctl + (size_t)64 * QUEUE_SEGMENTS * QCTL_STRIDE;  // its "shadow queues" (kind 1) are the debug queues (kind 2) k_shade filled
+          launch_trace(run, q, TRACE_NONE, ds, false);
+        }
+      });
+    };
+    // the first bounce as wave packets (k_trace_primary): one 8x8 pixel block per wave
+    auto trace_primary = [&]() -> int {
+      launches_primary++;
+      rays_primary += (uint64_t)r.primary_rays * in_flight;
+      const uint32_t packets = (p.path_count + 63) / 64;
+      const unsigned pgrid = std::max(1u, std::min((packets + 3) / 4, (uint32_t)ctx->cu_count * 64u));
+      const size_t plds = ((size_t)ctx->bvh.stack_depth * (STHIP_BLOCK / 64) + 13 * STHIP_BLOCK) * sizeof(uint32_t);  // the per-wave stacks + every lane's saved world-space ray constants
+      return timed(ms_primary, [&]() { launch_kernel(STHIP_KERNEL2(k_trace_primary, ctx->count_traversal, p.bvh.alpha_test != 0), pgrid, plds, st, p); });
+    };
+    // Round r traces the paths entering bounce r together with the shadow rays bounce r - 1 produced (one launch,
+    // k_trace), then shades bounce r; a last launch traces the shadow rays of the last bounce. `shade(depth)` is the
+    // pass's shading kernel; the light pass (sample_photons) has visibility rays to the camera in place of NEE rays.
+    auto run_rounds = [&](bool light, bool shadow_rays, auto&& shade) -> int {
+      for (uint32_t depth = 0; depth <= r.max_bounce_rounds; depth++) {
+        const uint32_t dc = depth < r.max_bounce_rounds ? depth : TRACE_NONE;
+        const uint32_t ds = depth >= 1 && shadow_rays && depth - 1 <= r.max_shadow_round ? depth - 1 : TRACE_NONE;
+        int e;
+        if (!light && depth == 0 && dc == 0 && ctx->packet_primary && !ctx->has_volumes) {
+          e = trace_primary();
+        } else if (ctx->fuse_trace) {
+          e = trace(dc, ds);
+        } else {  // analysis: the two ray kinds in launches of their own
+          e = trace(TRACE_NONE, ds);
+          if (!e) e = trace(dc, TRACE_NONE);
+        }
+        if (e) return e;
+        if (r.media && ds != TRACE_NONE) {
+          e = timed(ms_shade, [&]() { hipLaunchKernelGGL(k_shadow_media, dim3(grid), dim3(STHIP_BLOCK), 0, st, p, ds); });
+          if (e) return e;
+        }
+        if (dc == TRACE_NONE) break;
+        e = timed(ms_shade, [&]() { shade(depth); });
+        if (e) return e;
+      }
+      if (r.media && shadow_rays)  // the shadow rays still walking after the last bounce
+        for (uint32_t ds = r.max_bounce_rounds; ds < r.max_bounce_rounds + r.drain_rounds; ds++) {
+          int e = trace(TRACE_NONE, ds);
+          if (!e) e = timed(ms_shade, [&]() { hipLaunchKernelGGL(k_shadow_media, dim3(grid), dim3(STHIP_BLOCK), 0, st, p, ds); });
+          if (e) return e;
+        }
+      return STHIP_OK;
+    };
+
+    if (r.connect_paths) {  // BDPT.cpp:655-659; `conn` holds no pending entries when a pass starts
+      HIP_TRY(ctx, hipMemsetAsync(ctx->light_vertices.p, 0, std::max<size_t>(1, r.vertices_per_seed * in_flight) * 64, st));
+      if (r.lvc) HIP_TRY(ctx, hipMemsetAsync(ctx->lvc_staging.p, 0, (size_t)in_flight * pc->gLightPathCount * (pc->gMaxDiffuseVertices - 1) * 64, st));
+      if (p.conn) HIP_TRY(ctx, hipMemsetAsync(ctx->conn.p, 0, (size_t)in_flight * p.paths_per_seed * r.conn_per_path * 16, st));
+    }
+    if (r.light_tracing) {  // sample_photons before the view paths, BDPT.cpp:653-667
+      if (r.connect_views) HIP_TRY(ctx, hipMemsetAsync(ctx->light_trace.p, 0, (size_t)in_flight * r.W * r.H * 16, st));
+      p.light_pass = 1;
+      p.path_count = in_flight * r.light_threads;
+      rc = reset_queues();
+      if (rc) return rc;
+      rc = timed(ms_other, [&]() { launch_kernel(ctx->textured ? (const void*)&k_generate_light<true, true> : (const void*)&k_generate_light<false, true>, grid_for(ctx, p.path_count), 0, st, p); });
+      if (rc) return rc;
+      rc = run_rounds(true, !r.media, [&](uint32_t depth) { launch_kernel(r.k_shade_light, grid, 0, st, p, depth); });  // (media: connect_view walks its ray itself: nothing is queued)
+      if (rc) return rc;
+      rc = timed(ms_other, [&]() { hipLaunchKernelGGL(k_count_rays, dim3(1), dim3(1), 0, st, p); });
+      if (rc) return rc;
+      p.light_pass = 0;
+    }
+    if (r.lvc) {  // the cache in its defined order: compact the staged vertices of every seed in flight (lvc.hip)
+      const uint32_t slots_per_seed = pc->gLightPathCount * (pc->gMaxDiffuseVertices - 1);
+      size_t tmp_bytes = ctx->lvc_tmp.n;
+      if (r.light_tracing)
+        HIP_TRY(ctx, sthip::lvc_compact(ctx->lvc_staging.p, slots_per_seed, in_flight, (uint32_t)r.vertices_per_seed, ctx->light_vertices.p, ctx->lvc_count.p, ctx->lvc_flags.p, ctx->lvc_offsets.p,
+                                        ctx->lvc_tmp.p, tmp_bytes, st));
+      else
+        HIP_TRY(ctx, hipMemsetAsync(ctx->lvc_count.p, 0, (size_t)in_flight * 4, st));
+    }
+
+    if (r.nee_reuse) HIP_TRY(ctx, hipMemsetAsync(ctx->hg_appends.p, 0, hg_slots * 64, st));
+    if (r.lvc_reuse) HIP_TRY(ctx, hipMemsetAsync(ctx->lg_appends.p, 0, hg_slots * 96, st));
+    p.path_count = in_flight * p.paths_per_seed;
+    rc = reset_queues();
+    if (rc) return rc;
+    rc = timed(ms_other, [&]() { hipLaunchKernelGGL(k_generate, dim3(grid), dim3(STHIP_BLOCK), 0, st, p); });
+    if (rc) return rc;
+    if (r.debug_mode == STHIP_DEBUG_ENVIRONMENT_SAMPLE_TEST || r.debug_mode == STHIP_DEBUG_ENVIRONMENT_SAMPLE_PDF) {
+      // bdpt.hlsl:190-205: sample_visibility returns before it traces anything; the frame stays (0, 0, 0, 1), no ray is counted
+      // (the G-buffer outputs are not written upstream either: they are left zero here)
+      if (s == 0) {
+        if (p.out_albedo) HIP_TRY(ctx, hipMemsetAsync(p.out_albedo, 0, pixels * 16, st));  // (the binary32 stage with half colour precision)
+        if (p.out_visibility) HIP_TRY(ctx, hipMemsetAsync(p.out_visibility, 0, pixels * 8, st));
+        if (p.out_depth) HIP_TRY(ctx, hipMemsetAsync(p.out_depth, 0, pixels * 16, st));
+        if (p.out_prev_uv) HIP_TRY(ctx, hipMemsetAsync(p.out_prev_uv, 0, pixels * 8, st));
+      }
+      rc = timed(ms_other, [&]() {
+        hipLaunchKernelGGL(k_debug_environment, dim3(grid), dim3(STHIP_BLOCK), 0, st, p);
+        hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(STHIP_BLOCK), 0, st, p, s == 0 ? 1u : 0u, s + in_flight == seed_count ? 1u : 0u, 0u);
+      });
+      if (rc) return rc;
+      rays_primary = 0;
+      continue;
+    }
+    if (r.presample) {
+      const unsigned pgrid = (unsigned)((r.presample_n * in_flight + STHIP_BLOCK - 1) / STHIP_BLOCK);
+      rc = timed(ms_other, [&]() { launch_kernel(STHIP_KERNEL2(k_presample_lights, ctx->textured, ctx->has_spheres || r.has_env), pgrid, 0, st, p); });
+      if (rc) return rc;
+    }
+    p.emitter_count = ctx->answer_last_rays ? ctx->emitter_count : 0u;  // (only the plain k_shade instantiation looks at it)
+    rc = run_rounds(false, (r.nee || r.connect_paths) && !r.inline_media, [&](uint32_t depth) { shade_view_round(run, p, depth); });  // (inline walks through media: nothing is queued)
+    if (rc) return rc;
+    rc = timed(ms_other, [&]() { hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(STHIP_BLOCK), 0, st, p, s == 0 ? 1u : 0u, s + in_flight == seed_count ? 1u : 0u, r.primary_rays * in_flight); });
+    if (rc) return rc;
+    if ((r.nee_reuse || r.lvc_reuse) && (s + in_flight < seed_count || ctx->reuse_persist)) {
+      // This seed's appends become the grids the next seed looks up (hashgrid.h)
+      if (r.nee_reuse) {
+        const int rc2 = build_hash_grid(ctx, st, ctx->hg_appends.p, ctx->hg_compact.p, ctx->hg_data.p, hg_slots, 4, 2, false, pc->gHashGridBucketCount, ctx->hg_checksums, ctx->hg_counters, ctx->hg_indices);
+        if (rc2) return rc2;
+      }
+      if (r.lvc_reuse) {
+        const int rc2 = build_hash_grid(ctx, st, ctx->lg_appends.p, ctx->lg_compact.p, ctx->lg_data.p, hg_slots, 6, 0, true, pc->gHashGridBucketCount, ctx->lg_checksums, ctx->lg_counters, ctx->lg_indices);
+        if (rc2) return rc2;
+      }
+      p.hg_prev = 1;
+    }
+  }
+  if (timing) {
+    ctx->stats.ms_trace = ms_trace;
+    ctx->stats.ms_shade = ms_shade;
+    ctx->stats.ms_total = ms_trace + ms_primary + ms_shade + ms_other;
+    ctx->stats.launches_trace = launches_trace;
+    ctx->stats.ms_trace_primary = ms_primary;
+    ctx->stats.launches_primary = launches_primary;
+  }
+  ctx->stats.rays_primary_packets = rays_primary;
+  return STHIP_OK;
+}
+
+// The staged images to the caller's host memory, on stream `s` (the render stream, or the copy stream of the pipelined form)
+static int read_back(sthip_ctx* ctx, const RenderPlan& r, const FrameParams& p, const sthip_outputs* out, hipStream_t s) {
+  const size_t pixels = r.pixels, cb = ctx->color_bytes();
+  HIP_TRY(ctx, hipMemcpyAsync(out->gRadiance, p.out_radiance, r.radiance_entries * cb, hipMemcpyDeviceToHost, s));
+  if (out->gAlbedo) HIP_TRY(ctx, hipMemcpyAsync(out->gAlbedo, p.out_albedo16 ? (const void*)p.out_albedo16 : (const void*)p.out_albedo, pixels * cb, hipMemcpyDeviceToHost, s));
+  if (out->gVisibility) HIP_TRY(ctx, hipMemcpyAsync(out->gVisibility, p.out_visibility, pixels * 8, hipMemcpyDeviceToHost, s));
+  if (out->gDepth) HIP_TRY(ctx, hipMemcpyAsync(out->gDepth, p.out_depth, pixels * 16, hipMemcpyDeviceToHost, s));
+  if (out->gPrevUVs) HIP_TRY(ctx, hipMemcpyAsync(out->gPrevUVs, p.out_prev_uv, pixels * 8, hipMemcpyDeviceToHost, s));
+  return STHIP_OK;
+}
+
+// One attempt at a render call. `slot`: the frame of sthip_render_async whose staging set and events the call uses (nullptr:
+// the synchronous form).
 static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32_t sampling_flags, uint32_t scene_flags, const sthip_frame_desc* frame, uint32_t seed_begin, uint32_t seed_count,
-                       const sthip_outputs* out, AsyncSlot* slot);
+                       const sthip_outputs* out, AsyncSlot* slot) {
+  RenderPlan plan;
+  int rc = plan_render(ctx, pc, sampling_flags, scene_flags, frame, seed_count, out, plan);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = reserve_render_buffers(ctx, plan, out, slot);
+  if (rc) return rc;
+  FrameParams p;
+  rc = bind_frame_params(ctx, plan, frame, out, slot, p);
+  if (rc) return rc;
+  hipStream_t st = ctx->stream;
+  RenderRun run{ctx, plan, st, 0, trace_lds_bytes(ctx)};
+  run.tgrid = std::min<uint32_t>(trace_grid(ctx, run.lds), (uint32_t)((plan.P + STHIP_BLOCK - 1) / STHIP_BLOCK));
+  if (ctx->bvh.spill) run.tgrid = std::min<uint32_t>(run.tgrid, (uint32_t)ctx->cu_count * 8u);  // what the spill buffer has columns for (configure_stack)
+
+  ctx->render_launched = true;  // everything the call needs is allocated: from here on work is enqueued
+  // the deep queue's control words: k_trace_deep leaves them at zero, but a call that was cut short between k_trace and
+  // k_trace_deep (a failed launch, an error return) would not have: one 8-byte fill per call keeps every call self-contained
+  if (ctx->bvh.spill && ctx->deep_count.p) HIP_TRY(ctx, hipMemsetAsync(ctx->deep_count.p, 0, 8, st));
+  rc = run_batches(run, p, seed_begin, seed_count);
+  if (rc) return rc;
+  if ((plan.nee_reuse || plan.lvc_reuse) && ctx->reuse_persist) {  // what the next call's first seed may look into
+    memcpy(ctx->reuse_key, plan.reuse_key, sizeof plan.reuse_key);
+    ctx->reuse_grids_valid = true;
+  }
+
+  if (slot) {
+    // The read-back of the pipelined form: on the copy stream, behind the "rendered" event, so that the runtime moves this frame
+    // (a copy engine, or its copy kernel on a hardware queue of its own: ~0.6 ms per 33 MB image) while the next one is traced. ctx->counters is rewritten by the next frame's k_clear: its read-out into
+    // the slot is a device-to-device copy ON THE RENDER STREAM, ordered before that rewrite; the copy stream then takes the
+    // slot's counters to the pinned record. Nothing waits on the host, nothing spins on the device: events only.
+    hipStream_t cs = ctx->copy_stream;
+    HIP_TRY(ctx, hipMemcpyAsync(slot->counters.p, ctx->counters.p, CNT_TOTAL * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, hipEventRecord(slot->rendered, st));
+    HIP_TRY(ctx, hipStreamWaitEvent(cs, slot->rendered, 0));
+    rc = read_back(ctx, plan, p, out, cs);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(slot->record, slot->counters.p, CNT_TOTAL * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipEventRecord(slot->copied, cs));
+    slot->ray_count = out->gRayCount;
+    ctx->stats_pending = true;  // (until the ticket is retired, sthip_get_stats reads the counters of the last frame enqueued)
+  } else if (!plan.dev) {
+    rc = read_back(ctx, plan, p, out, st);
+    if (rc) return rc;
+    if (plan.debug_mode) HIP_TRY(ctx, hipMemcpyAsync(out->gDebugImage, p.out_debug, plan.pixels * ctx->color_bytes(), hipMemcpyDeviceToHost, st));
+    unsigned long long c[CNT_TOTAL];
+    HIP_TRY(ctx, hipMemcpyAsync(c, ctx->counters.p, sizeof(c), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (out->gRayCount) {
+      out->gRayCount[0] = c[CNT_RAYS_CLOSEST] + c[CNT_RAYS_SHADOW];
+      out->gRayCount[1] = c[CNT_RAYS_CLOSEST] - c[CNT_CROSSINGS];
+    }
+    fill_counter_stats(ctx, c);
+    ctx->stats_pending = false;
+  } else {
+    if (out->gRayCount) hipLaunchKernelGGL(k_write_ray_count, dim3(1), dim3(1), 0, st, ctx->counters.p, reinterpret_cast<unsigned long long*>(out->gRayCount));
+    ctx->stats_pending = true;
+  }
+  return STHIP_OK;
+}
 
 // A render allocates its path state (~330 B per path in flight at the default flags) before it enqueues anything. Should the
 // device not have that much left — a host application that holds memory of its own, several contexts on one device — the
 // batch is halved (fewer seeds traced together: the same frame, a little slower) and the call tried again, down to one seed;
 // the smaller batch stays for the calls that follow (stats: max_paths_in_flight, batch_halvings).
-int sthip_render(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32_t sampling_flags, uint32_t scene_flags, const sthip_frame_desc* frame, uint32_t seed_begin,
-                 uint32_t seed_count, const sthip_outputs* out) {
-  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+static int render_with_retry(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32_t sampling_flags, uint32_t scene_flags, const sthip_frame_desc* frame, uint32_t seed_begin, uint32_t seed_count,
+                             const sthip_outputs* out, AsyncSlot* slot) {
   for (;;) {
     ctx->last_hip_error = hipSuccess;
     ctx->render_launched = false;
-    const int rc = render_once(ctx, pc, sampling_flags, scene_flags, frame, seed_begin, seed_count, out, nullptr);
+    const int rc = render_once(ctx, pc, sampling_flags, scene_flags, frame, seed_begin, seed_count, out, slot);
     ctx->stats.max_paths_in_flight = ctx->max_paths_in_flight;
     if (rc != STHIP_ERR_HIP || ctx->last_hip_error != hipErrorOutOfMemory || ctx->render_launched) return rc;
     (void)hipGetLastError();  // (the allocation's error is not sticky, but it is the "last error" until read)
@@ -1787,6 +2677,12 @@ int sthip_render(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32_t sam
     ctx->stats.batch_halvings++;
     if (getenv("STHIP_VERBOSE")) fprintf(stderr, "[sthip] out of device memory (%s): max_paths_in_flight -> %llu\n", ctx->error.c_str(), (unsigned long long)ctx->max_paths_in_flight);
   }
+}
+
+int sthip_render(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32_t sampling_flags, uint32_t scene_flags, const sthip_frame_desc* frame, uint32_t seed_begin,
+                 uint32_t seed_count, const sthip_outputs* out) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  return render_with_retry(ctx, pc, sampling_flags, scene_flags, frame, seed_begin, seed_count, out, nullptr);
 }
 
 // ---- pipelined host outputs (sthip.h: sthip_render_async) ----
@@ -1847,21 +2743,8 @@ int sthip_render_async(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32
     slot->ticket = 0;
     slot->ray_count = nullptr;
   }
-  for (;;) {
-    ctx->last_hip_error = hipSuccess;
-    ctx->render_launched = false;
-    const int rc = render_once(ctx, pc, sampling_flags, scene_flags, frame, seed_begin, seed_count, out, slot);
-    ctx->stats.max_paths_in_flight = ctx->max_paths_in_flight;
-    if (rc == STHIP_OK) break;
-    if (rc != STHIP_ERR_HIP || ctx->last_hip_error != hipErrorOutOfMemory || ctx->render_launched) return rc;
-    (void)hipGetLastError();
-    const uint64_t per_seed = std::max<uint64_t>(1, ctx->stats.paths_per_seed);
-    if (ctx->max_paths_in_flight <= per_seed || ctx->max_paths_in_flight <= 1) return rc;
-    (void)drain_in_flight(ctx);  // the out-of-memory retry of sthip_render: every frame in flight completes before its path state goes
-    release_path_state(ctx);
-    ctx->max_paths_in_flight = std::max<uint64_t>(per_seed, ctx->max_paths_in_flight / 2);
-    ctx->stats.batch_halvings++;
-  }
+  const int rc = render_with_retry(ctx, pc, sampling_flags, scene_flags, frame, seed_begin, seed_count, out, slot);
+  if (rc != STHIP_OK) return rc;
   slot->ticket = t;
   ctx->next_ticket = t + 1;
   *ticket = t;
@@ -1891,946 +2774,12 @@ int sthip_wait_outputs(sthip_ctx* ctx, uint64_t ticket) {
   return STHIP_OK;
 }
 
-static int render_once(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc, uint32_t sampling_flags, uint32_t scene_flags, const sthip_frame_desc* frame, uint32_t seed_begin, uint32_t seed_count,
-                       const sthip_outputs* out, AsyncSlot* slot) {
-  if (!pc || !frame || !out || !out->gRadiance || !frame->gViews || !frame->gViewTransforms || frame->view_count == 0 || seed_count == 0)
-    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: a required argument is NULL/zero");
-  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_NO_SCENE, "no scene uploaded");
-  if (pc->gViewCount != frame->view_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: gViewCount != frame.view_count");
-  if ((out->gDepth || out->gPrevUVs) && !frame->gInverseViewTransforms && !frame->gPrevInverseViewTransforms)
-    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: depth / prev-uv outputs need gInverseViewTransforms");
-  // BDPT_FLAG_TRACE_LIGHT is a per-kernel specialisation of the reference (sample_photons), never a caller's choice
-  if (scene_flags & STHIP_BDPT_FLAG_TRACE_LIGHT) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: BDPT_FLAG_TRACE_LIGHT is not a scene flag a caller sets");
-  const uint32_t unsupported = (1u << STHIP_eSampleLightPower);
-  if (sampling_flags & unsupported) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: a sampling flag outside the built hot path is set");
-  if (pc->gMaxPathVertices > 60 || pc->gMaxDiffuseVertices > 60) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: path length limits above 60");
-  if (pc->gLightCount > ctx->light_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: gLightCount exceeds the uploaded light list");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-
-  // flag resolution of BDPT::render (BDPT.cpp:486-523), idempotent if the host has done it already
-  sthip_BDPTPushConstants pcn = *pc;
-  if (pcn.gLightCount == 0) scene_flags &= ~STHIP_BDPT_FLAG_HAS_EMISSIVES;
-  const bool has_env = (scene_flags & STHIP_BDPT_FLAG_HAS_ENVIRONMENT) != 0, has_emissives = (scene_flags & STHIP_BDPT_FLAG_HAS_EMISSIVES) != 0;
-  if (!has_env) pcn.gEnvironmentSampleProbability = 0;
-  if (!has_emissives) pcn.gEnvironmentSampleProbability = 1;
-  if (!has_emissives && !has_env) sampling_flags &= ~((1u << STHIP_eNEE) | (1u << STHIP_eConnectToViews) | (1u << STHIP_eConnectToLightPaths));
-  if (!(sampling_flags & (1u << STHIP_eNEE))) sampling_flags &= ~((1u << STHIP_ePresampleLights) | (1u << STHIP_eNEEReservoirs) | (1u << STHIP_eNEEReservoirReuse));
-  if (!(sampling_flags & (1u << STHIP_eNEEReservoirs))) sampling_flags &= ~(1u << STHIP_eNEEReservoirReuse);  // only connect_light_reservoir touches the grid
-  if (!(sampling_flags & (1u << STHIP_eLVC))) sampling_flags &= ~((1u << STHIP_eLVCReservoirs) | (1u << STHIP_eLVCReservoirReuse));  // BDPT.cpp:517-520
-  if (!(sampling_flags & (1u << STHIP_eConnectToLightPaths))) sampling_flags &= ~((1u << STHIP_eLVC) | (1u << STHIP_eLVCReservoirs) | (1u << STHIP_eLVCReservoirReuse));  // only connect_lvc reads the cache
-  if (!(sampling_flags & (1u << STHIP_eLVCReservoirs))) sampling_flags &= ~(1u << STHIP_eLVCReservoirReuse);  // the reuse sits inside connect_lvc's reservoir branch
-  if (!(sampling_flags & ((1u << STHIP_eNEE) | (1u << STHIP_eLVC)))) sampling_flags &= ~(1u << STHIP_eDeferShadowRays);  // BDPT.cpp:522-523
-  // eCoherentSampling only touches the index of a presampled light (path.hlsli:317,379) and connect_lvc's (:688,703)
-  if (!(sampling_flags & ((1u << STHIP_ePresampleLights) | (1u << STHIP_eLVC)))) sampling_flags &= ~(1u << STHIP_eCoherentSampling);
-  pc = &pcn;
-  if (has_env) {  // the Environment record (environment.h:17-22): ImageValue3, then 4 offsets into gDistributions when an image is bound
-    const size_t addr = pcn.gEnvironmentMaterialAddress;
-    if (addr + 16 > ctx->materials_host.size() || (addr & 3)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: gEnvironmentMaterialAddress is outside gMaterialData");
-    uint32_t rec[8] = {0};
-    memcpy(rec, ctx->materials_host.data() + addr, 16);
-    if (rec[3] < STHIP_IMAGE_COUNT) {
-      if (rec[3] >= ctx->image_count || addr + 32 > ctx->materials_host.size()) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: the environment refers to an image that is not in gImages");
-      memcpy(rec, ctx->materials_host.data() + addr, 32);
-      const size_t w = ctx->image_dims[rec[3]].first, h = ctx->image_dims[rec[3]].second;
-      const size_t need[4] = {h, w * h, h + 1, (w + 1) * h};  // marginal_pdf, row_pdf, marginal_cdf, row_cdf (dist2.h)
-      for (int k = 0; k < 4; k++)
-        if ((size_t)rec[4 + k] + need[k] > ctx->distribution_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: an environment distribution table lies outside gDistributions");
-    }
-  }
-
-  // participating media (BDPT_FLAG_HAS_MEDIA, BDPT.cpp:497-500)
-  if (ctx->has_volumes && !(scene_flags & STHIP_BDPT_FLAG_HAS_MEDIA)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: the scene has volume instances but BDPT_FLAG_HAS_MEDIA is not set");
-  const bool media = ctx->has_volumes;
-  if (media && (sampling_flags & (1u << STHIP_eCoherentSampling))) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: eCoherentSampling with media (walks through volumes break the lockstep of a workgroup)");
-  // With media every visibility ray draws random numbers. A deferred NEE ray carries its own offset (k_shadow_media walks it);
-  // everything else draws from the path's own stream in the middle of a vertex — NEE without eDeferShadowRays, light tracing's
-  // connect_view, the connections to stored light vertices or to the light vertex cache — and k_shade / k_shade_light walk those
-  // themselves (visibility_walk_media).
-  if (!media) pcn.gMaxNullCollisions = 0;
-  const uint32_t W = pc->gOutputExtent[0], H = pc->gOutputExtent[1];
-  if (W == 0 || H == 0) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: empty output extent");
-  const size_t pixels = (size_t)W * H;
-  FrameParams p;
-  memset(&p, 0, sizeof(p));
-  p.pc = *pc;
-  p.sampling_flags = sampling_flags;
-  p.scene_flags = scene_flags;
-  p.shard_rank = ctx->shard_rank;
-  p.shard_count = ctx->shard_count;
-  p.tile_w = ctx->tile_w;
-  p.tile_h = ctx->tile_h;
-  p.tiles_x = (W + p.tile_w - 1) / p.tile_w;
-  p.tiles_y = (H + p.tile_h - 1) / p.tile_h;
-  const uint32_t tiles = p.tiles_x * p.tiles_y;
-  const uint32_t owned = tiles > p.shard_rank ? (tiles - p.shard_rank + p.shard_count - 1) / p.shard_count : 0;
-  p.paths_per_seed = owned * p.tile_w * p.tile_h;
-  // Seeds traced together in one pass. A shard of a frame is small (1/8 of 1080p = 259 K paths does not fill
-  // 256 CUs of persistent waves), so several seeds of the owned pixels share the launches, up to ~4 M paths.
-  const uint32_t max_in_flight = (uint32_t)std::max<uint64_t>(1, (ctx->max_paths_in_flight) / std::max(1u, p.paths_per_seed));
-  // Reservoir reuse couples the seeds of a call: seed s looks into the hash grid seed s - 1 built (the reference's frame
-  // and previous frame), so they are traced one at a time and the grid is built between them.
-  const bool nee_reuse = (sampling_flags & (1u << STHIP_eNEEReservoirReuse)) != 0;
-  const bool lvc_reuse = (sampling_flags & (1u << STHIP_eLVCReservoirReuse)) != 0;
-  // BDPTDebugMode: upstream's gDebugImage persists from frame to frame and most modes add to it or overwrite it: the seeds of a
-  // call are traced one after the other, as its frames are
-  const uint32_t debug_mode = out->gDebugImage ? out->debug_mode : 0u;
-  if (debug_mode >= STHIP_DEBUG_MODE_COUNT) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: debug_mode is not a BDPTDebugMode");
-  if (debug_mode && out->radiance_layout == STHIP_LAYOUT_SHARD_TILES && false) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: debug image with packed tiles");
-  const uint32_t batch = (nee_reuse || lvc_reuse || debug_mode) ? 1u : std::min(seed_count, max_in_flight);
-  p.path_count = batch * p.paths_per_seed;
-  ctx->stats.paths_per_seed = p.paths_per_seed;
-  ctx->stats.seeds_in_flight = batch;
-  // light tracing (eConnectToViews, BDPT.cpp:653-667): sample_photons' padded dispatch, dispatch_over(W, ceil(gLightPathCount / W))
-  const bool connect_views = (sampling_flags & (1u << STHIP_eConnectToViews)) != 0;
-  const bool connect_paths = (sampling_flags & (1u << STHIP_eConnectToLightPaths)) != 0;  // light-subpath connections, no light vertex cache
-  const bool bdpt = connect_views || connect_paths;
-  const bool light_tracing = bdpt && pc->gMaxPathVertices > 2;
-  if (bdpt) {
-    if (has_env) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: light subpaths with an environment (upstream starts environment light paths from an unset position, bdpt.hlsl:109-113)");
-    if (!frame->gInverseViewTransforms) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: eConnectToViews / eConnectToLightPaths need gInverseViewTransforms");
-    if (connect_paths && !(sampling_flags & (1u << STHIP_eRemapThreads)) && (W & 7u))
-      return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: eConnectToLightPaths without eRemapThreads needs a width that is a multiple of 8 (upstream's padding threads race on the vertex slots of the next row)");
-    if (connect_paths && pc->gMaxDiffuseVertices < 1) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: eConnectToLightPaths needs gMaxDiffuseVertices >= 1");
-  }
-  const bool lvc = connect_paths && (sampling_flags & (1u << STHIP_eLVC));
-  const bool lvc_reservoirs = lvc && (sampling_flags & (1u << STHIP_eLVCReservoirs));
-  if (lvc) {
-    if (pc->gMaxDiffuseVertices < 2) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: eLVC needs gMaxDiffuseVertices >= 2 (a light path stores vertices 1 .. gMaxDiffuseVertices - 1)");
-    if (pc->gLightPathCount == 0 || (uint64_t)pc->gLightPathCount * pc->gMaxDiffuseVertices > (1ull << 28)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: eLVC needs 0 < gLightPathCount * gMaxDiffuseVertices <= 2^28");
-  }
-  const uint32_t light_rows = (pc->gLightPathCount + W - 1) / W;
-  const uint32_t light_threads = light_tracing ? ((W + 7) / 8) * 8 * ((light_rows + 3) / 4) * 4 : 0;
-  if ((uint64_t)light_threads * batch > 0x7FFFFFFFull || (light_tracing && (uint64_t)batch * W * H > 0x7FFFFFFFull)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many light paths in flight");
-  const size_t P = std::max<size_t>(std::max<size_t>(1, p.path_count), (size_t)light_threads * batch);
-  const size_t P0 = std::max<size_t>(1, p.paths_per_seed);
-  const size_t vertices_per_seed = connect_paths ? (size_t)pc->gLightPathCount * pc->gMaxDiffuseVertices : 0;
-  const size_t conn_per_path = connect_paths ? pc->gMaxDiffuseVertices - 1 : 0;
-  if (bdpt) {
-    HIP_TRY(ctx, ctx->bdpt.ensure(P));
-    if (light_tracing && connect_views) HIP_TRY(ctx, ctx->light_trace.ensure((size_t)batch * W * H * 4));
-    if (connect_paths) {
-      if ((uint64_t)P * std::max<size_t>(1, conn_per_path) >= 0x40000000ull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many connection entries in flight");
-      HIP_TRY(ctx, ctx->light_vertices.ensure(4 * std::max<size_t>(1, vertices_per_seed * batch)));
-      HIP_TRY(ctx, ctx->conn.ensure(std::max<size_t>(1, (size_t)p.path_count * conn_per_path)));
-    }
-    if (lvc) {
-      const size_t slots = (size_t)pc->gLightPathCount * (pc->gMaxDiffuseVertices - 1) * batch;
-      if (slots > 0x7FFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many light-vertex-cache slots in flight");
-      HIP_TRY(ctx, ctx->lvc_staging.ensure(4 * slots));
-      HIP_TRY(ctx, ctx->lvc_flags.ensure(slots));
-      HIP_TRY(ctx, ctx->lvc_offsets.ensure(slots));
-      HIP_TRY(ctx, ctx->lvc_count.ensure(batch));
-      size_t tmp_bytes = 0;
-      HIP_TRY(ctx, sthip::lvc_compact(nullptr, (uint32_t)(slots / batch), batch, 0, nullptr, nullptr, ctx->lvc_flags.p, ctx->lvc_offsets.p, nullptr, tmp_bytes, ctx->stream));
-      HIP_TRY(ctx, ctx->lvc_tmp.ensure(std::max<size_t>(16, tmp_bytes)));
-      if (lvc_reservoirs) HIP_TRY(ctx, ctx->path_contrib.ensure(P));
-    }
-  }
-
-  size_t hg_slots = 0;
-  const uint32_t hg_buckets = (nee_reuse || lvc_reuse) ? pc->gHashGridBucketCount + 32u : 0u;  // probing does not wrap (hashgrid.h)
-  if (nee_reuse || lvc_reuse) {
-    if (has_env) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: eNEEReservoirReuse with an environment (a stored environment sample is read back as a surface point upstream: sample_Le leaves its pdfA positive)");
-    if (ctx->shard_count > 1) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: eNEEReservoirReuse on a pixel-tile shard (the grid is a whole-frame structure: render replicas and reduce)");
-    if (pc->gHashGridBucketCount == 0 || pc->gHashGridBucketCount > (1u << 28) || !(pc->gHashGridMinBucketRadius > 0)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: eNEEReservoirReuse needs 0 < gHashGridBucketCount <= 2^28 and gHashGridMinBucketRadius > 0");
-    hg_slots = (size_t)((W + 7) / 8) * ((H + 3) / 4) * 32 * std::max(1u, pc->gMaxDiffuseVertices);  // covers both map_pixel_coord forms
-    if (hg_slots > 0x7FFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many hash-grid append slots");
-    if (nee_reuse) {
-      HIP_TRY(ctx, ctx->hg_appends.ensure(4 * hg_slots));
-      HIP_TRY(ctx, ctx->hg_compact.ensure(4 * hg_slots));
-      HIP_TRY(ctx, ctx->hg_data.ensure(3 * hg_slots));
-    }
-    if (lvc_reuse) {
-      HIP_TRY(ctx, ctx->lg_appends.ensure(6 * hg_slots));
-      HIP_TRY(ctx, ctx->lg_compact.ensure(6 * hg_slots));
-      HIP_TRY(ctx, ctx->lg_data.ensure(5 * hg_slots));
-      HIP_TRY(ctx, ctx->lg_checksums.ensure(hg_buckets));
-      HIP_TRY(ctx, ctx->lg_counters.ensure(hg_buckets));
-      HIP_TRY(ctx, ctx->lg_indices.ensure(hg_buckets));
-    }
-    HIP_TRY(ctx, ctx->hg_flags.ensure(hg_slots));
-    HIP_TRY(ctx, ctx->hg_offsets.ensure(hg_slots));
-    HIP_TRY(ctx, ctx->hg_dest.ensure(hg_slots));
-    HIP_TRY(ctx, ctx->hg_keys.ensure(hg_slots));
-    HIP_TRY(ctx, ctx->hg_count.ensure(1));
-    HIP_TRY(ctx, ctx->hg_checksums.ensure(hg_buckets));
-    HIP_TRY(ctx, ctx->hg_counters.ensure(hg_buckets));
-    HIP_TRY(ctx, ctx->hg_indices.ensure(hg_buckets));
-    HIP_TRY(ctx, ctx->hg_owner.ensure(hg_buckets + 2 + 1024));  // (+ hashgrid.hip's control words and special-cell list)
-    HIP_TRY(ctx, ctx->hg_key64.ensure(hg_slots));
-    HIP_TRY(ctx, ctx->hg_sorted_key64.ensure(hg_slots));
-    HIP_TRY(ctx, ctx->hg_bucket_of.ensure(hg_slots));
-    HIP_TRY(ctx, ctx->hg_append.ensure(hg_slots));
-    HIP_TRY(ctx, ctx->hg_sorted_bucket.ensure(hg_slots));
-    HIP_TRY(ctx, ctx->hg_sorted_append.ensure(hg_slots));
-    size_t tmp_bytes = 0, build_bytes = 0;
-    HIP_TRY(ctx, sthip::lvc_compact(nullptr, (uint32_t)hg_slots, 1, 0, nullptr, nullptr, ctx->hg_flags.p, ctx->hg_offsets.p, nullptr, tmp_bytes, ctx->stream));
-    HIP_TRY(ctx, sthip::hashgrid_build_device(nullptr, nullptr, (uint32_t)hg_slots, hg_buckets, nullptr, ctx->hg_counters.p, ctx->hg_indices.p, nullptr, nullptr, ctx->hg_bucket_of.p, ctx->hg_append.p,
-                                              ctx->hg_sorted_bucket.p, ctx->hg_sorted_append.p, ctx->hg_key64.p, ctx->hg_sorted_key64.p, nullptr, build_bytes, ctx->stream));
-    HIP_TRY(ctx, ctx->hg_tmp.ensure(std::max<size_t>(16, std::max(tmp_bytes, build_bytes))));
-  }
-
-  HIP_TRY(ctx, ctx->ray_o.ensure(P));
-  HIP_TRY(ctx, ctx->ray_d.ensure(P));
-  HIP_TRY(ctx, ctx->hit.ensure(P));
-  HIP_TRY(ctx, ctx->hit_leaf.ensure(P));
-  HIP_TRY(ctx, ctx->beta.ensure(P));
-  HIP_TRY(ctx, ctx->radiance.ensure(P));
-  HIP_TRY(ctx, ctx->shadow_sum.ensure(P));
-  HIP_TRY(ctx, ctx->accum.ensure(P0));
-  if (ctx->textured || debug_mode) HIP_TRY(ctx, ctx->cone.ensure(P));  // (a debug mode runs the general instantiation of k_shade)
-  if (debug_mode) HIP_TRY(ctx, ctx->debug.ensure(P));
-  // The queues are cut into QUEUE_SEGMENTS segments (traverse.h). A segment starts as a contiguous eighth of the
-  // slots and only shrinks from bounce to bounce, which bounds it and the distance between segments.
-  const uint32_t shade_grid = std::max<uint32_t>(grid_for(ctx, P), QUEUE_SEGMENTS);
-  const size_t seg_stride = (((P + QUEUE_SEGMENTS - 1) / QUEUE_SEGMENTS) + 63) & ~(size_t)63;
-  if (seg_stride * QUEUE_SEGMENTS > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many paths in flight");
-  // a vertex queues at most one NEE ray, plus one visibility ray per stored light vertex it connects to
-  // (media: the walks of earlier vertices are still in the queue when a vertex adds its own — at most one per diffuse vertex and path)
-  const size_t shadow_stride = seg_stride * (media ? std::max<size_t>(1, pc->gMaxDiffuseVertices) : 1 + conn_per_path);
-  if (shadow_stride * QUEUE_SEGMENTS > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many shadow rays in flight");
-  const size_t shadow_entries = shadow_stride * QUEUE_SEGMENTS;  // per round; media ping-pong between two such regions
-  HIP_TRY(ctx, ctx->shadow_rays.ensure(3 * shadow_entries * (media ? 2 : 1)));
-  if (ctx->bvh.spill) {  // bounded LDS stacks: room for every ray of a trace launch to overflow (4 x float4 each)
-    HIP_TRY(ctx, ctx->deep_rays.ensure(4 * (P + shadow_entries)));
-    if (ctx->deep_count.n < 2) {  // [0] rays in the deep queue, [1] k_trace_deep blocks that are through: both zero between launches (k_trace_deep resets them)
-      HIP_TRY(ctx, ctx->deep_count.ensure(2));
-      HIP_TRY(ctx, hipMemsetAsync(ctx->deep_count.p, 0, 8, ctx->stream));
-    }
-  }
-  if (media) {
-    if (2 * shadow_entries > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: too many shadow rays in flight");
-    HIP_TRY(ctx, ctx->media_state.ensure(2 * P));
-    HIP_TRY(ctx, ctx->shadow_hit.ensure(2 * shadow_entries));
-    HIP_TRY(ctx, ctx->shadow_ext.ensure(2 * shadow_entries));
-    HIP_TRY(ctx, ctx->shadow_result.ensure(P * std::max(1u, pc->gMaxDiffuseVertices)));
-    HIP_TRY(ctx, ctx->view_medium.ensure(std::max(1u, frame->view_count)));
-  }
-  HIP_TRY(ctx, ctx->meta.ensure(P));
-  HIP_TRY(ctx, ctx->queue0.ensure(seg_stride * QUEUE_SEGMENTS));
-  HIP_TRY(ctx, ctx->queue1.ensure(seg_stride * QUEUE_SEGMENTS));
-  HIP_TRY(ctx, ctx->queue_kept.ensure(seg_stride * QUEUE_SEGMENTS));
-  HIP_TRY(ctx, ctx->counters.ensure(CNT_TOTAL));
-  HIP_TRY(ctx, ctx->qctl.ensure((size_t)3 * 64 * QUEUE_SEGMENTS * QCTL_STRIDE));  // path queues, shadow queues, and (BDPTDebugMode) the shadow rays' debug halves
-  // ePresampleLights (BDPT.cpp:644-651): gLightPresampleTileSize x TileCount light points per seed in flight
-  const bool presample = (sampling_flags & (1u << STHIP_ePresampleLights)) && pc->gMaxPathVertices > 2;
-  const size_t presample_n = (size_t)pc->gLightPresampleTileSize * pc->gLightPresampleTileCount;
-  if (sampling_flags & (1u << STHIP_ePresampleLights)) {
-    if (has_env) return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: ePresampleLights with an environment (upstream leaves the presampled environment direction unset, bdpt.hlsl:93)");
-    if (presample_n == 0 || presample_n > (1u << 24)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: gLightPresampleTileSize * gLightPresampleTileCount must be in 1 .. 2^24");
-    HIP_TRY(ctx, ctx->presampled.ensure(2 * presample_n * batch));
-  }
-
-  // views
-  const uint32_t nv = frame->view_count;
-  const size_t vbytes = (size_t)nv * 48;
-  HIP_TRY(ctx, ctx->views.ensure(5 * vbytes));
-  if (slot && slot->params_cap < 5 * vbytes + (size_t)nv * 4) {  // the pipelined form keeps the call's arrays in the slot's pinned block
-    if (slot->params) (void)hipHostFree(slot->params);
-    slot->params = nullptr;
-    slot->params_cap = 0;
-    HIP_TRY(ctx, hipHostMalloc((void**)&slot->params, 5 * vbytes + (size_t)nv * 4, hipHostMallocDefault));
-    slot->params_cap = 5 * vbytes + (size_t)nv * 4;
-  }
-  {
-    std::vector<uint8_t> stack_copy(slot ? 0 : 5 * vbytes);
-    uint8_t* const host = slot ? slot->params : stack_copy.data();
-    if (frame->gInverseViewTransforms)
-      memcpy(host + 4 * vbytes, frame->gInverseViewTransforms, vbytes);
-    else
-      memset(host + 4 * vbytes, 0, vbytes);
-    memcpy(host, frame->gViews, vbytes);
-    memcpy(host + vbytes, frame->gViewTransforms, vbytes);
-    memcpy(host + 2 * vbytes, frame->gPrevViews ? frame->gPrevViews : frame->gViews, vbytes);
-    const sthip_TransformData* piv = frame->gPrevInverseViewTransforms ? frame->gPrevInverseViewTransforms : frame->gInverseViewTransforms;
-    if (piv)
-      memcpy(host + 3 * vbytes, piv, vbytes);
-    else
-      memset(host + 3 * vbytes, 0, vbytes);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->views.p, host, 5 * vbytes, hipMemcpyHostToDevice, st));
-    if (!slot) HIP_TRY(ctx, hipStreamSynchronize(st));  // `stack_copy` goes out of scope (the slot's block lives until the slot's next frame, which waits for this one)
-  }
-  p.views = reinterpret_cast<const sthip_ViewData*>(ctx->views.p);
-  p.view_xf = reinterpret_cast<const sthip_TransformData*>(ctx->views.p + vbytes);
-  p.prev_views = reinterpret_cast<const sthip_ViewData*>(ctx->views.p + 2 * vbytes);
-  p.prev_inv_view_xf = reinterpret_cast<const sthip_TransformData*>(ctx->views.p + 3 * vbytes);
-  p.inv_view_xf = reinterpret_cast<const sthip_TransformData*>(ctx->views.p + 4 * vbytes);
-  p.bdpt = bdpt ? ctx->bdpt.p : nullptr;
-  p.light_trace = light_tracing && connect_views ? ctx->light_trace.p : nullptr;
-  p.light_trace_empty = connect_views && !light_tracing ? 1u : 0u;
-  p.light_vertices = connect_paths ? ctx->light_vertices.p : nullptr;
-  p.conn = connect_paths && conn_per_path ? ctx->conn.p : nullptr;
-  // eCoherentRR takes effect in rounds in which a path can reach the roulette (see run below); never with media
-  const bool coherent_rr = (sampling_flags & (1u << STHIP_eCoherentRR)) && !media;
-  if (coherent_rr) HIP_TRY(ctx, ctx->rr.ensure(P));
-  p.rr = nullptr;
-  // eCoherentSampling: one probe per site and round (FrameParams::cs_nee / cs_lvc)
-  const bool coherent_nee = (sampling_flags & (1u << STHIP_eCoherentSampling)) && (sampling_flags & (1u << STHIP_ePresampleLights)) && (sampling_flags & (1u << STHIP_eNEE));
-  const bool coherent_lvc = (sampling_flags & (1u << STHIP_eCoherentSampling)) && lvc;
-  if (coherent_nee) HIP_TRY(ctx, ctx->cs_nee.ensure(P));
-  if (coherent_lvc) HIP_TRY(ctx, ctx->cs_lvc.ensure(P));
-  p.cs_nee = nullptr;
-  p.cs_lvc = nullptr;
-  p.probe_kind = 0;
-  p.lds_material_bytes = (ctx->lds_materials && !ctx->textured && ctx->materials_host.size() <= 32768) ? (uint32_t)(ctx->materials_host.size() & ~(size_t)3) : 0u;
-  const size_t shade_lds = p.lds_material_bytes;
-  p.hg_checksums = ctx->hg_checksums.p;
-  p.hg_counters = ctx->hg_counters.p;
-  p.hg_indices = ctx->hg_indices.p;
-  p.hg_data = ctx->hg_data.p;
-  // the first seed of the call looks into the grids the previous call left, if it left them for the same estimator and table
-  const uint64_t reuse_key[3] = {(uint64_t)(nee_reuse ? 1u : 0u) | (lvc_reuse ? 2u : 0u), hg_buckets, hg_slots};
-  p.hg_prev = ((nee_reuse || lvc_reuse) && ctx->reuse_persist && ctx->reuse_grids_valid && !memcmp(reuse_key, ctx->reuse_key, sizeof reuse_key)) ? 1u : 0u;
-  if (nee_reuse || lvc_reuse) ctx->reuse_grids_valid = false;  // (until this call has left its own)
-  p.hg_appends = nee_reuse ? ctx->hg_appends.p : nullptr;
-  p.lg_checksums = ctx->lg_checksums.p;
-  p.lg_counters = ctx->lg_counters.p;
-  p.lg_indices = ctx->lg_indices.p;
-  p.lg_data = ctx->lg_data.p;
-  p.lg_appends = lvc_reuse ? ctx->lg_appends.p : nullptr;
-  p.lvc_staging = lvc ? ctx->lvc_staging.p : nullptr;
-  p.lvc_count = lvc ? ctx->lvc_count.p : nullptr;
-  p.path_contrib = lvc_reservoirs ? ctx->path_contrib.p : nullptr;
-  p.light_threads = light_threads;
-  p.light_trace_quantization = 65536;  // BDPT.hpp:55 mLightTraceQuantization
-
-  p.bvh = ctx->bvh;
-  p.bvh.alpha_test = (ctx->has_alpha && (sampling_flags & (1u << STHIP_eAlphaTest))) ? 1u : 0u;  // intersection.hlsli:118
-  p.bvh.flip_uvs = (sampling_flags & (1u << STHIP_eFlipTriangleUVs)) ? 1u : 0u;
-  p.scene.vertices = ctx->vertices.p;
-  p.scene.indices = ctx->indices.p;
-  p.scene.instances = ctx->instances.p;
-  p.scene.xf = ctx->xf.p;
-  p.scene.inv_xf = ctx->inv_xf.p;
-  p.scene.motion_xf = ctx->motion_xf.p;
-  p.scene.materials = ctx->materials.p;
-  p.scene.lights = ctx->lights.p;
-  p.scene.instance_count = ctx->instance_count;
-  p.scene.light_count = ctx->light_count;
-  p.scene.images = ctx->images.p;
-  p.scene.image_texels = ctx->image_texels.p;
-  p.scene.image_count = ctx->image_count;
-  p.scene.distributions = ctx->distributions.p;
-  p.scene.distribution_count = ctx->distribution_count;
-  p.scene.volume_words = ctx->volume_words.p;
-  p.scene.volumes = ctx->volumes.p;
-  p.scene.volume_count = ctx->volume_count;
-  p.scene.leaf_tris = ctx->bvh.tris;
-  p.scene.leaf_shade = reinterpret_cast<const float4*>(ctx->tri_shade.p);
-  p.ray_o = ctx->ray_o.p;
-  p.ray_d = ctx->ray_d.p;
-  p.hit = ctx->hit.p;
-  p.hit_leaf = ctx->hit_leaf.p;
-  p.beta = ctx->beta.p;
-  p.meta = ctx->meta.p;
-  p.radiance = ctx->radiance.p;
-  p.shadow_sum = ctx->shadow_sum.p;
-  p.accum = ctx->accum.p;
-  p.cone = (ctx->textured || debug_mode) ? ctx->cone.p : nullptr;
-  p.queue[0] = ctx->queue0.p;
-  p.queue[1] = ctx->queue1.p;
-  p.shadow_rays = ctx->shadow_rays.p;
-  p.deep_rays = ctx->deep_rays.p;
-  p.deep_count = ctx->deep_count.p;
-  p.presampled = ctx->presampled.p;
-  p.counters = ctx->counters.p;
-  p.qctl = ctx->qctl.p;
-  p.seg_stride = (uint32_t)seg_stride;
-  p.shadow_stride = (uint32_t)shadow_stride;
-  p.media = media ? 1u : 0u;
-  const bool inline_media = media && (sampling_flags & (1u << STHIP_eNEE)) && !(sampling_flags & (1u << STHIP_eDeferShadowRays));
-  p.inline_media = inline_media ? 1u : 0u;
-  if (inline_media || (media && bdpt)) {  // (light tracing's connect_view and the light-subpath connections walk inline whatever eDeferShadowRays says)
-    HIP_TRY(ctx, ctx->shade_stack.ensure((size_t)shade_grid * STHIP_BLOCK * std::max(1u, ctx->bvh.stack_depth)));
-    p.shade_stack = ctx->shade_stack.p;
-  }
-  if (media) {
-    p.shadow_alt = (uint32_t)shadow_entries;
-    p.media_state = ctx->media_state.p;
-    p.shadow_hit = ctx->shadow_hit.p;
-    p.shadow_ext = ctx->shadow_ext.p;
-    p.shadow_result = ctx->shadow_result.p;
-    p.view_medium = nullptr;
-    if (frame->gViewMediumInstances) {
-      for (uint32_t v = 0; v < frame->view_count; v++) {
-        const uint32_t mi = frame->gViewMediumInstances[v];
-        if (mi != 0xFFFFu && (mi >= ctx->instance_count || !ctx->instance_is_volume[mi]))
-          return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: gViewMediumInstances entry is not a volume instance");
-      }
-      if (slot) {  // (the caller's array is borrowed for the call only: the upload reads the slot's pinned copy)
-        memcpy(slot->params + 5 * vbytes, frame->gViewMediumInstances, (size_t)frame->view_count * 4);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->view_medium.p, slot->params + 5 * vbytes, (size_t)frame->view_count * 4, hipMemcpyHostToDevice, st));
-      } else {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->view_medium.p, frame->gViewMediumInstances, (size_t)frame->view_count * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-      }
-      p.view_medium = ctx->view_medium.p;
-    }
-  }
-  p.count_traversal = ctx->count_traversal ? 1u : 0u;
-  p.refill_idle = ctx->refill_idle;
-  p.culled = 0;
-  p.inst_flags = ctx->inst_flags.p;
-  p.emitters = ctx->emitters.p;
-  p.emitter_count = 0;  // (set where the view pass starts: only the plain pipeline answers last rays)
-  p.no_specular = ctx->has_specular ? 0u : 1u;
-  p.inner_min_lanes = ctx->inner_min_lanes;
-
-  // outputs: device pointers are written in place, host pointers go through staging buffers
-  const bool dev = out->device_ptrs != 0;
-  const size_t cb = ctx->color_bytes();  // bytes of one colour-image entry (radiance, albedo, debug)
-  const auto color_entries = [](size_t n, size_t bytes) { return (n * bytes + 15) / 16; };  // float4 entries of a staging buffer
-  p.out_half = ctx->half_color ? 1u : 0u;
-  p.debug_mode = debug_mode;
-  p.debug = debug_mode ? ctx->debug.p : nullptr;
-  p.out_debug = nullptr;
-  p.shadow_debug = nullptr;
-  if (debug_mode) {
-    if (dev) {
-      p.out_debug = out->gDebugImage;
-    } else {  // in / out: what the caller's image holds goes up first
-      HIP_TRY(ctx, ctx->out_debug.ensure(color_entries(pixels, cb)));
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->out_debug.p, out->gDebugImage, pixels * cb, hipMemcpyHostToDevice, st));
-      p.out_debug = ctx->out_debug.p;
-    }
-    // inline shadow rays add to the debug image only where they are unoccluded: they are traced once more, with what they add
-    const bool inline_adds = (debug_mode == STHIP_DEBUG_RESERVOIR_WEIGHT || (debug_mode == STHIP_DEBUG_PATH_LENGTH_CONTRIBUTION && pc->gDebugLightPathLength == 1)) &&
-                             (sampling_flags & (1u << STHIP_eNEE)) && !(sampling_flags & (1u << STHIP_eDeferShadowRays)) && !media;
-    // so do light-subpath connections (accumulate_contribution with the light vertex's length, path.hlsli:797,820); connect_lvc's
-    // deferred record (:781-789) adds to the radiance only
-    const bool connection_adds = debug_mode == STHIP_DEBUG_PATH_LENGTH_CONTRIBUTION && pc->gDebugLightPathLength >= 2 && connect_paths && !media &&
-                                 !((sampling_flags & (1u << STHIP_eLVC)) && (sampling_flags & (1u << STHIP_eDeferShadowRays)));
-    if (inline_adds || connection_adds) {
-      HIP_TRY(ctx, ctx->shadow_debug.ensure(ctx->shadow_rays.n));
-      p.shadow_debug = ctx->shadow_debug.p;
-    }
-  }
-  p.out_packed = out->radiance_layout == STHIP_LAYOUT_SHARD_TILES ? 1u : 0u;
-  if (out->radiance_layout > STHIP_LAYOUT_SHARD_TILES) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: unknown radiance_layout");
-  const size_t radiance_entries = p.out_packed ? std::max<size_t>(1, p.paths_per_seed) : pixels;
-  if (dev) {
-    p.out_radiance = out->gRadiance;
-    p.out_albedo = reinterpret_cast<float4*>(out->gAlbedo);
-    p.out_visibility = out->gVisibility;
-    p.out_depth = out->gDepth;
-    p.out_prev_uv = reinterpret_cast<float2*>(out->gPrevUVs);
-  } else {
-    // the synchronous form has one staging set per context; a frame of sthip_render_async has its slot's, which the copy
-    // stream reads while the next frame renders into another (allocated at first use, released when the frame's size changes)
-    if (slot && (slot->key[0] != pixels || slot->key[1] != radiance_entries || slot->key[2] != cb)) {
-      slot->release_images();
-      slot->key[0] = pixels;
-      slot->key[1] = radiance_entries;
-      slot->key[2] = cb;
-    }
-    DevBuf<float4>& s_radiance = slot ? slot->radiance : ctx->out_radiance;
-    DevBuf<float4>& s_albedo = slot ? slot->albedo : ctx->out_albedo;
-    DevBuf<sthip_VisibilityInfo>& s_visibility = slot ? slot->visibility : ctx->out_visibility;
-    DevBuf<sthip_DepthInfo>& s_depth = slot ? slot->depth : ctx->out_depth;
-    DevBuf<float2>& s_prev_uv = slot ? slot->prev_uv : ctx->out_prev_uv;
-    HIP_TRY(ctx, s_radiance.ensure(color_entries(radiance_entries, cb)));
-    p.out_radiance = s_radiance.p;
-    if (out->gAlbedo) {
-      HIP_TRY(ctx, s_albedo.ensure(color_entries(pixels, cb)));
-      p.out_albedo = s_albedo.p;
-    }
-    if (out->gVisibility) {
-      HIP_TRY(ctx, s_visibility.ensure(pixels));
-      p.out_visibility = s_visibility.p;
-    }
-    if (out->gDepth) {
-      HIP_TRY(ctx, s_depth.ensure(pixels));
-      p.out_depth = s_depth.p;
-    }
-    if (out->gPrevUVs) {
-      HIP_TRY(ctx, s_prev_uv.ensure(pixels));
-      p.out_prev_uv = s_prev_uv.p;
-    }
-    if (slot) HIP_TRY(ctx, slot->counters.ensure(CNT_TOTAL));
-  }
-  // primary rays = owned pixels that lie inside the image and inside a view (known without asking the GPU)
-  uint32_t primary_rays = 0;
-  if (pc->gMaxPathVertices >= 2) {
-    for (uint32_t t = p.shard_rank; t < tiles; t += p.shard_count) {
-      const uint32_t ty = t / p.tiles_x, tx = t - ty * p.tiles_x;
-      const int x0 = (int)(tx * p.tile_w), y0 = (int)(ty * p.tile_h);
-      const int x1 = (int)std::min(W, (tx + 1) * p.tile_w), y1 = (int)std::min(H, (ty + 1) * p.tile_h);
-      if (nv == 1) {
-        const int ax0 = std::max(x0, frame->gViews[0].image_min[0]), ay0 = std::max(y0, frame->gViews[0].image_min[1]);
-        const int ax1 = std::min(x1, frame->gViews[0].image_max[0]), ay1 = std::min(y1, frame->gViews[0].image_max[1]);
-        if (ax1 > ax0 && ay1 > ay0) primary_rays += (uint32_t)(ax1 - ax0) * (uint32_t)(ay1 - ay0);
-      } else {
-        for (int y = y0; y < y1; y++)
-          for (int x = x0; x < x1; x++)
-            for (uint32_t v = 0; v < nv; v++) {
-              const sthip_ViewData& vw = frame->gViews[v];
-              if (x >= vw.image_min[0] && y >= vw.image_min[1] && x < vw.image_max[0] && y < vw.image_max[1]) {
-                primary_rays++;
-                break;
-              }
-            }
-      }
-    }
-  }
-  // half colour precision: k_shade writes the albedo in binary32 to a stage, k_resolve rounds it into the caller's image (or its staging)
-  p.out_albedo16 = nullptr;
-  if (ctx->half_color && p.out_albedo) {
-    p.out_albedo16 = reinterpret_cast<Half4*>(p.out_albedo);
-    HIP_TRY(ctx, ctx->albedo_stage.ensure(pixels));
-    p.out_albedo = ctx->albedo_stage.p;
-  }
-  // Pixels this shard does not own and pixels outside every view are zero (a sum-reduce over shards assembles the frame).
-  // When the shard is the whole frame and every pixel lies in a view, every output entry is written by the pass itself —
-  // the first vertex's G-buffer stores (hit or miss) and k_resolve — so the five fills (131 MB at 1080p) are left out.
-  const bool every_entry_written = p.shard_count == 1 && !p.out_packed && !media && pc->gMaxPathVertices >= 2 && (size_t)primary_rays == pixels;
-  // The next writer of a staging set — the fills below or the first G-buffer store — runs after the copy of the frame that used
-  // the set before (a no-op for an event that was never recorded). The binary32 albedo stage of half colour precision is one
-  // per context: only k_shade and k_resolve touch it, in stream order; the copy reads the slot's RGBA16F image.
-  if (slot) HIP_TRY(ctx, hipStreamWaitEvent(st, slot->copied, 0));
-  if (!every_entry_written) {
-    HIP_TRY(ctx, hipMemsetAsync(p.out_radiance, 0, radiance_entries * cb, st));
-    if (p.out_albedo) HIP_TRY(ctx, hipMemsetAsync(p.out_albedo, 0, pixels * 16, st));
-    if (p.out_albedo16) HIP_TRY(ctx, hipMemsetAsync(p.out_albedo16, 0, pixels * 8, st));
-    if (p.out_visibility) HIP_TRY(ctx, hipMemsetAsync(p.out_visibility, 0, pixels * 8, st));
-    if (p.out_depth) HIP_TRY(ctx, hipMemsetAsync(p.out_depth, 0, pixels * 16, st));
-    if (p.out_prev_uv) HIP_TRY(ctx, hipMemsetAsync(p.out_prev_uv, 0, pixels * 8, st));
-  }
-  const uint32_t grid = shade_grid;
-  const size_t lds = trace_lds_bytes(ctx);
-  uint32_t tgrid = std::min<uint32_t>(trace_grid(ctx, lds), (uint32_t)((P + STHIP_BLOCK - 1) / STHIP_BLOCK));
-  if (ctx->bvh.spill) tgrid = std::min<uint32_t>(tgrid, (uint32_t)ctx->cu_count * 8u);  // what the spill buffer has columns for (configure_stack)
-  // closest-hit rays per path <= gMaxPathVertices - 1 (path.hlsli:960); without specular materials every scattering
-  // vertex counts as a diffuse vertex, so the path also ends after gMaxDiffuseVertices + 1 rays (path.hlsli:964-966):
-  // rounds beyond that would only be empty launches
-  uint32_t max_bounce_rounds = pc->gMaxPathVertices >= 2 ? pc->gMaxPathVertices - 1 : 0;
-  if (!ctx->has_specular) max_bounce_rounds = std::min(max_bounce_rounds, pc->gMaxDiffuseVertices + 1);
-  // media: a trace() call walks from volume boundary to volume boundary, one k_trace round per segment (up to 2 per
-  // volume instance and ray); a shadow ray likewise, so its last segments need rounds of their own after the last bounce.
-  // The queue control words exist for 64 rounds; paths / shadow rays still walking after that are dropped.
-  uint32_t drain_rounds = 0;
-  if (media) {
-    drain_rounds = std::min(8u, 2 * ctx->volume_instances + 1);
-    max_bounce_rounds = std::min<uint64_t>(62 - drain_rounds, (uint64_t)max_bounce_rounds * (1 + 2 * ctx->volume_instances));
-  }
-  p.rounds = max_bounce_rounds + drain_rounds;
-  // The deepest round whose vertices can queue a visibility ray. Without specular materials the vertex shaded in round d is
-  // diffuse vertex d + 1, and the diffuse budget ends a path before NEE (path.hlsli:964-966 precede :978): rounds beyond
-  // gMaxDiffuseVertices - 1 leave their shadow queue empty, and the launch that would trace it is left out.
-  uint32_t max_shadow_round = 0xFFFFFFFFu;
-  if (!ctx->has_specular && !media && !bdpt) max_shadow_round = pc->gMaxDiffuseVertices ? pc->gMaxDiffuseVertices - 1 : 0u;
-  const bool timing = ctx->time_kernels;
-  float ms_trace = 0, ms_primary = 0, ms_shade = 0, ms_other = 0;
-  uint32_t launches_trace = 0, launches_primary = 0;
-  uint64_t rays_primary = 0;
-  auto timed = [&](float& acc, auto&& launch) -> int {
-    if (timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
-    launch();
-    HIP_TRY(ctx, hipGetLastError());
-    if (timing) {
-      HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-      HIP_TRY(ctx, hipEventSynchronize(ctx->ev[1]));
-      float ms = 0;
-      HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      acc += ms;
-    }
-    return STHIP_OK;
-  };
-
-  ctx->render_launched = true;  // everything the call needs is allocated: from here on work is enqueued
-  // the deep queue's control words: k_trace_deep leaves them at zero, but a call that was cut short between k_trace and
-  // k_trace_deep (a failed launch, an error return) would not have: one 8-byte fill per call keeps every call self-contained
-  if (ctx->bvh.spill && ctx->deep_count.p) HIP_TRY(ctx, hipMemsetAsync(ctx->deep_count.p, 0, 8, st));
-  bool counters_cleared = false;  // (the first pass's k_clear takes the counters along with its queue control words)
-  const bool nee = (sampling_flags & (1u << STHIP_eNEE)) != 0;
-  const bool ext = ctx->has_spheres || has_env || bdpt || (sampling_flags & ((1u << STHIP_eNEEReservoirs) | (1u << STHIP_eShadingNormalShadowFix)));
-  for (uint32_t s = 0; s < seed_count; s += batch) {
-    const uint32_t in_flight = std::min(batch, seed_count - s);
-    p.seed = seed_begin + s;
-    p.seeds_in_flight = in_flight;
-    p.write_aov = s == 0 ? 1u : 0u;
-    int rc = STHIP_OK;
-    // queue sizes and heads are per pass; the ray / traversal counters run over the whole call
-    auto reset_queues = [&]() -> int {
-      const uint32_t per_depth = QUEUE_SEGMENTS * QCTL_STRIDE;  // 64-bit words
-      const uint32_t words = (max_bounce_rounds + drain_rounds + 1) * per_depth;  // the last round's shade appends to depth + 1; k_resolve sums p.rounds of them
-      hipLaunchKernelGGL(k_clear, dim3(std::max(1u, std::min(64u, (2 * words + CNT_TOTAL + STHIP_BLOCK - 1) / STHIP_BLOCK))), dim3(STHIP_BLOCK), 0, st, queue_ctl_host(ctx->qctl.p, 0, 0), words,
-                         queue_ctl_host(ctx->qctl.p, 1, 0), words, ctx->counters.p, counters_cleared ? 0u : (uint32_t)CNT_TOTAL);
-      counters_cleared = true;
-      if (p.shadow_debug) HIP_TRY(ctx, hipMemsetAsync(queue_ctl_host(ctx->qctl.p, 2, 0), 0, (size_t)words * 8, st));  // the debug halves' queues (BDPTDebugMode)
-      HIP_TRY(ctx, hipGetLastError());
-      return STHIP_OK;
-    };
-    auto trace = [&](uint32_t dc, uint32_t ds) -> int {
-      if (dc == TRACE_NONE && ds == TRACE_NONE) return STHIP_OK;
-      launches_trace++;
-      return timed(ms_trace, [&]() {
-        const bool alpha = p.bvh.alpha_test || ctx->has_volumes;  // alpha masks under eAlphaTest, volume instances: the instantiation that carries them
-        void* kargs[3] = {(void*)&p, (void*)&dc, (void*)&ds};
-        (void)hipLaunchKernel(p.bvh.wide8_nodes  ? trace_kernel_wide8(ctx->count_traversal, alpha, p.bvh.spill != nullptr)
-                              : p.bvh.wide_nodes ? trace_kernel_wide(ctx->count_traversal, alpha, p.bvh.spill != nullptr)
-                                                 : trace_kernel(ctx->count_traversal, alpha, p.bvh.spill != nullptr, p.bvh.top_count != 0),
-                              dim3(tgrid), dim3(STHIP_BLOCK), kargs, lds, st);
-        if (p.bvh.spill) {  // a tree higher than the LDS stack ran the bounded instantiation: now the rays that overflowed
-          const uint32_t dgrid = (uint32_t)ctx->cu_count * 8u;  // one spill column per thread (configure_stack)
-          if (alpha) {
-            if (ctx->count_traversal)
-              hipLaunchKernelGGL((k_trace_deep<true, true>), dim3(dgrid), dim3(STHIP_BLOCK), 0, st, p);
-            else
-              hipLaunchKernelGGL((k_trace_deep<false, true>), dim3(dgrid), dim3(STHIP_BLOCK), 0, st, p);
-          } else if (ctx->count_traversal)
-            hipLaunchKernelGGL((k_trace_deep<true, false>), dim3(dgrid), dim3(STHIP_BLOCK), 0, st, p);
-          else
-            hipLaunchKernelGGL((k_trace_deep<false, false>), dim3(dgrid), dim3(STHIP_BLOCK), 0, st, p);
-        }
-        if (p.shadow_debug && ds != TRACE_NONE) {
-          // BDPTDebugMode: the same shadow rays once more, carrying what each adds to the debug image, accumulated into the paths'
-          // debug pixels the way the first pass accumulated their contributions into the radiance (finish_ray)
-          FrameParams q = p;
-          q.shadow_rays = p.shadow_debug;
-          q.radiance = p.debug;
-          q.shadow_sum = p.debug;  // (a connection's debug half exists while NEE's rays are deferred: finish_ray's target either way)
-          q.qctl = p.qctl + (size_t)64 * QUEUE_SEGMENTS * QCTL_STRIDE;  // its "shadow queues" (kind 1) are the debug queues (kind 2) k_shade filled
-          const uint32_t none = TRACE_NONE;
-          void* qargs[3] = {(void*)&q, (void*)&none, (void*)&ds};
-          (void)hipLaunchKernel(p.bvh.wide8_nodes  ? trace_kernel_wide8(false, alpha, p.bvh.spill != nullptr)
-                                : p.bvh.wide_nodes ? trace_kernel_wide(false, alpha, p.bvh.spill != nullptr)
-                                                   : trace_kernel(false, alpha, p.bvh.spill != nullptr, p.bvh.top_count != 0),
-                                dim3(tgrid), dim3(STHIP_BLOCK), qargs, lds, st);
-          if (p.bvh.spill) {
-            const uint32_t dgrid = (uint32_t)ctx->cu_count * 8u;
-            if (alpha)
-              hipLaunchKernelGGL((k_trace_deep<false, true>), dim3(dgrid), dim3(STHIP_BLOCK), 0, st, q);
-            else
-              hipLaunchKernelGGL((k_trace_deep<false, false>), dim3(dgrid), dim3(STHIP_BLOCK), 0, st, q);
-          }
-        }
-      });
-    };
-    // the first bounce as wave packets (k_trace_primary): one 8x8 pixel block per wave
-    auto trace_primary = [&]() -> int {
-      launches_primary++;
-      rays_primary += (uint64_t)primary_rays * in_flight;
-      const uint32_t packets = (p.path_count + 63) / 64;
-      const unsigned pgrid = std::max(1u, std::min((packets + 3) / 4, (uint32_t)ctx->cu_count * 64u));
-      const size_t plds = ((size_t)ctx->bvh.stack_depth * (STHIP_BLOCK / 64) + 13 * STHIP_BLOCK) * sizeof(uint32_t);  // the per-wave stacks + every lane's saved world-space ray constants
-      return timed(ms_primary, [&]() {
-        if (p.bvh.alpha_test) {
-          if (ctx->count_traversal)
-            hipLaunchKernelGGL((k_trace_primary<true, true>), dim3(pgrid), dim3(STHIP_BLOCK), plds, st, p);
-          else
-            hipLaunchKernelGGL((k_trace_primary<false, true>), dim3(pgrid), dim3(STHIP_BLOCK), plds, st, p);
-        } else if (ctx->count_traversal)
-          hipLaunchKernelGGL((k_trace_primary<true, false>), dim3(pgrid), dim3(STHIP_BLOCK), plds, st, p);
-        else
-          hipLaunchKernelGGL((k_trace_primary<false, false>), dim3(pgrid), dim3(STHIP_BLOCK), plds, st, p);
-      });
-    };
-    // Round r traces the paths entering bounce r together with the shadow rays bounce r - 1 produced (one launch,
-    // k_trace), then shades bounce r; a last launch traces the shadow rays of the last bounce. `shade(depth)` is the
-    // pass's shading kernel; the light pass (sample_photons) has visibility rays to the camera in place of NEE rays.
-    auto run_rounds = [&](bool light, bool shadow_rays, auto&& shade) -> int {
-      for (uint32_t depth = 0; depth <= max_bounce_rounds; depth++) {
-        const uint32_t dc = depth < max_bounce_rounds ? depth : TRACE_NONE;
-        const uint32_t ds = depth >= 1 && shadow_rays && depth - 1 <= max_shadow_round ? depth - 1 : TRACE_NONE;
-        int r;
-        if (!light && depth == 0 && dc == 0 && ctx->packet_primary && !ctx->has_volumes) {
-          r = trace_primary();
-        } else if (ctx->fuse_trace) {
-          r = trace(dc, ds);
-        } else {  // analysis: the two ray kinds in launches of their own
-          r = trace(TRACE_NONE, ds);
-          if (!r) r = trace(dc, TRACE_NONE);
-        }
-        if (r) return r;
-        if (media && ds != TRACE_NONE) {
-          r = timed(ms_shade, [&]() { hipLaunchKernelGGL(k_shadow_media, dim3(grid), dim3(STHIP_BLOCK), 0, st, p, ds); });
-          if (r) return r;
-        }
-        if (dc == TRACE_NONE) break;
-        r = timed(ms_shade, [&]() { shade(depth); });
-        if (r) return r;
-      }
-      if (media && shadow_rays)  // the shadow rays still walking after the last bounce
-        for (uint32_t ds = max_bounce_rounds; ds < max_bounce_rounds + drain_rounds; ds++) {
-          int r = trace(TRACE_NONE, ds);
-          if (!r) r = timed(ms_shade, [&]() { hipLaunchKernelGGL(k_shadow_media, dim3(grid), dim3(STHIP_BLOCK), 0, st, p, ds); });
-          if (r) return r;
-        }
-      return STHIP_OK;
-    };
-
-    if (connect_paths) {  // BDPT.cpp:655-659; `conn` holds no pending entries when a pass starts
-      HIP_TRY(ctx, hipMemsetAsync(ctx->light_vertices.p, 0, std::max<size_t>(1, vertices_per_seed * in_flight) * 64, st));
-      if (lvc) HIP_TRY(ctx, hipMemsetAsync(ctx->lvc_staging.p, 0, (size_t)in_flight * pc->gLightPathCount * (pc->gMaxDiffuseVertices - 1) * 64, st));
-      if (p.conn) HIP_TRY(ctx, hipMemsetAsync(ctx->conn.p, 0, (size_t)in_flight * p.paths_per_seed * conn_per_path * 16, st));
-    }
-    if (light_tracing) {  // sample_photons before the view paths, BDPT.cpp:653-667
-      if (connect_views) HIP_TRY(ctx, hipMemsetAsync(ctx->light_trace.p, 0, (size_t)in_flight * W * H * 16, st));
-      p.light_pass = 1;
-      p.path_count = in_flight * light_threads;
-      rc = reset_queues();
-      if (rc) return rc;
-      const uint32_t lgrid = grid_for(ctx, p.path_count);
-      rc = timed(ms_other, [&]() {
-        if (ctx->textured)
-          hipLaunchKernelGGL((k_generate_light<true, true>), dim3(lgrid), dim3(STHIP_BLOCK), 0, st, p);
-        else
-          hipLaunchKernelGGL((k_generate_light<false, true>), dim3(lgrid), dim3(STHIP_BLOCK), 0, st, p);
-      });
-      if (rc) return rc;
-      rc = run_rounds(true, !media, [&](uint32_t depth) {  // (media: connect_view walks its ray itself: nothing is queued)
-        if (media && ctx->textured)
-          hipLaunchKernelGGL((k_shade_light<true, true, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else if (media)
-          hipLaunchKernelGGL((k_shade_light<false, true, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else if (ctx->textured)
-          hipLaunchKernelGGL((k_shade_light<true, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else
-          hipLaunchKernelGGL((k_shade_light<false, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-      });
-      if (rc) return rc;
-      rc = timed(ms_other, [&]() { hipLaunchKernelGGL(k_count_rays, dim3(1), dim3(1), 0, st, p); });
-      if (rc) return rc;
-      p.light_pass = 0;
-    }
-    if (lvc) {  // the cache in its defined order: compact the staged vertices of every seed in flight (lvc.hip)
-      const uint32_t slots_per_seed = pc->gLightPathCount * (pc->gMaxDiffuseVertices - 1);
-      size_t tmp_bytes = ctx->lvc_tmp.n;
-      if (light_tracing)
-        HIP_TRY(ctx, sthip::lvc_compact(ctx->lvc_staging.p, slots_per_seed, in_flight, (uint32_t)vertices_per_seed, ctx->light_vertices.p, ctx->lvc_count.p, ctx->lvc_flags.p, ctx->lvc_offsets.p,
-                                        ctx->lvc_tmp.p, tmp_bytes, st));
-      else
-        HIP_TRY(ctx, hipMemsetAsync(ctx->lvc_count.p, 0, (size_t)in_flight * 4, st));
-    }
-
-    if (nee_reuse) HIP_TRY(ctx, hipMemsetAsync(ctx->hg_appends.p, 0, hg_slots * 64, st));
-    if (lvc_reuse) HIP_TRY(ctx, hipMemsetAsync(ctx->lg_appends.p, 0, hg_slots * 96, st));
-    p.path_count = in_flight * p.paths_per_seed;
-    rc = reset_queues();
-    if (rc) return rc;
-    rc = timed(ms_other, [&]() { hipLaunchKernelGGL(k_generate, dim3(grid), dim3(STHIP_BLOCK), 0, st, p); });
-    if (rc) return rc;
-    if (debug_mode == STHIP_DEBUG_ENVIRONMENT_SAMPLE_TEST || debug_mode == STHIP_DEBUG_ENVIRONMENT_SAMPLE_PDF) {
-      // bdpt.hlsl:190-205: sample_visibility returns before it traces anything; the frame stays (0, 0, 0, 1), no ray is counted
-      // (the G-buffer outputs are not written upstream either: they are left zero here)
-      if (s == 0) {
-        if (p.out_albedo) HIP_TRY(ctx, hipMemsetAsync(p.out_albedo, 0, pixels * 16, st));  // (the binary32 stage with half colour precision)
-        if (p.out_visibility) HIP_TRY(ctx, hipMemsetAsync(p.out_visibility, 0, pixels * 8, st));
-        if (p.out_depth) HIP_TRY(ctx, hipMemsetAsync(p.out_depth, 0, pixels * 16, st));
-        if (p.out_prev_uv) HIP_TRY(ctx, hipMemsetAsync(p.out_prev_uv, 0, pixels * 8, st));
-      }
-      rc = timed(ms_other, [&]() {
-        hipLaunchKernelGGL(k_debug_environment, dim3(grid), dim3(STHIP_BLOCK), 0, st, p);
-        hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(STHIP_BLOCK), 0, st, p, s == 0 ? 1u : 0u, s + in_flight == seed_count ? 1u : 0u, 0u);
-      });
-      if (rc) return rc;
-      rays_primary = 0;
-      continue;
-    }
-    if (presample) {
-      const unsigned pgrid = (unsigned)((presample_n * in_flight + STHIP_BLOCK - 1) / STHIP_BLOCK);
-      const bool pext = ctx->has_spheres || has_env;
-      rc = timed(ms_other, [&]() {
-        if (ctx->textured && pext)
-          hipLaunchKernelGGL((k_presample_lights<true, true>), dim3(pgrid), dim3(STHIP_BLOCK), 0, st, p);
-        else if (ctx->textured)
-          hipLaunchKernelGGL((k_presample_lights<true, false>), dim3(pgrid), dim3(STHIP_BLOCK), 0, st, p);
-        else if (pext)
-          hipLaunchKernelGGL((k_presample_lights<false, true>), dim3(pgrid), dim3(STHIP_BLOCK), 0, st, p);
-        else
-          hipLaunchKernelGGL((k_presample_lights<false, false>), dim3(pgrid), dim3(STHIP_BLOCK), 0, st, p);
-      });
-      if (rc) return rc;
-    }
-    p.emitter_count = ctx->answer_last_rays ? ctx->emitter_count : 0u;  // (only the plain k_shade instantiation looks at it)
-    rc = run_rounds(false, (nee || connect_paths) && !inline_media, [&](uint32_t depth) {  // (inline walks through media: nothing is queued)
-      // eCoherentRR: a vertex shaded in round `depth` has path_length depth + 2; the roulette runs for
-      // gMinPathVertices <= path_length < gMaxPathVertices at a non-specular vertex that is within the diffuse budget —
-      // without specular materials that is vertex number depth + 1 of at most gMaxDiffuseVertices. In such a round the
-      // paths first report their p (k_shade<PROBE>), the 8x4 groups agree (k_rr_reduce), then the round proper runs.
-      // A probe: the round's k_shade without any output, up to the statement `kind` names (FrameParams::probe_kind)
-      auto launch_probe = [&](uint32_t kind) {
-        FrameParams probe = p;
-        probe.probe_kind = kind;
-        probe.out_albedo = nullptr;
-        probe.out_visibility = nullptr;
-        probe.out_depth = nullptr;
-        probe.out_prev_uv = nullptr;
-        if (bdpt) {
-          if (ctx->textured)
-            hipLaunchKernelGGL((k_shade<true, true, true, false, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, probe, depth);
-          else
-            hipLaunchKernelGGL((k_shade<false, true, true, false, true>), dim3(grid), dim3(STHIP_BLOCK), shade_lds, st, probe, depth);
-        } else if (ctx->textured)
-          hipLaunchKernelGGL((k_shade<true, true, false, false, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, probe, depth);
-        else
-          hipLaunchKernelGGL((k_shade<false, true, false, false, true>), dim3(grid), dim3(STHIP_BLOCK), shade_lds, st, probe, depth);
-      };
-      const unsigned reduce_grid = (unsigned)((p.path_count + STHIP_BLOCK - 1) / STHIP_BLOCK);
-      p.rr = nullptr;
-      if (coherent_rr && depth + 2 >= pc->gMinPathVertices && depth + 2 < pc->gMaxPathVertices && (ctx->has_specular || depth + 1 <= pc->gMaxDiffuseVertices)) {
-        p.rr = ctx->rr.p;
-        (void)hipMemsetAsync(ctx->rr.p, 0, (size_t)p.path_count * 16, st);
-        launch_probe(1);
-        hipLaunchKernelGGL(k_rr_reduce, dim3(reduce_grid), dim3(STHIP_BLOCK), 0, st, p);
-      }
-      // eCoherentSampling: the NEE index first (with the roulette's verdict known), then connect_lvc's (with the NEE index
-      // known: how many numbers a path draws in between depends on the candidates it looked at)
-      p.cs_nee = nullptr;
-      p.cs_lvc = nullptr;
-      if (coherent_nee) {
-        p.cs_nee = ctx->cs_nee.p;
-        (void)hipMemsetAsync(ctx->cs_nee.p, 0, (size_t)p.path_count * 8, st);
-        launch_probe(2);
-        hipLaunchKernelGGL(k_cs_reduce, dim3(reduce_grid), dim3(STHIP_BLOCK), 0, st, p.cs_nee, p.path_count);
-      }
-      if (coherent_lvc) {
-        p.cs_lvc = ctx->cs_lvc.p;
-        (void)hipMemsetAsync(ctx->cs_lvc.p, 0, (size_t)p.path_count * 8, st);
-        launch_probe(3);
-        hipLaunchKernelGGL(k_cs_reduce, dim3(reduce_grid), dim3(STHIP_BLOCK), 0, st, p.cs_lvc, p.path_count);
-      }
-      if (debug_mode) {  // BDPTDebugMode: the general instantiation with the statements that feed gDebugImage
-        if (media && bdpt && inline_media)
-          hipLaunchKernelGGL((k_shade<true, true, true, 2, false, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else if (media && bdpt)
-          hipLaunchKernelGGL((k_shade<true, true, true, 1, false, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else if (media && inline_media)
-          hipLaunchKernelGGL((k_shade<true, true, false, 2, false, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else if (media)
-          hipLaunchKernelGGL((k_shade<true, true, false, 1, false, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else if (bdpt)
-          hipLaunchKernelGGL((k_shade<true, true, true, false, false, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else
-          hipLaunchKernelGGL((k_shade<true, true, false, false, false, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-      } else if (media && bdpt) {  // light tracing through media: the view paths carry the BDPT quantities
-        if (ctx->textured && inline_media)
-          hipLaunchKernelGGL((k_shade<true, true, true, 2>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else if (ctx->textured)
-          hipLaunchKernelGGL((k_shade<true, true, true, 1>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else if (inline_media)
-          hipLaunchKernelGGL((k_shade<false, true, true, 2>), dim3(grid), dim3(STHIP_BLOCK), shade_lds, st, p, depth);
-        else
-          hipLaunchKernelGGL((k_shade<false, true, true, 1>), dim3(grid), dim3(STHIP_BLOCK), shade_lds, st, p, depth);
-      } else if (media && inline_media) {
-        if (ctx->textured)
-          hipLaunchKernelGGL((k_shade<true, true, false, 2>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else
-          hipLaunchKernelGGL((k_shade<false, true, false, 2>), dim3(grid), dim3(STHIP_BLOCK), shade_lds, st, p, depth);
-      } else if (media) {
-        if (ctx->textured)
-          hipLaunchKernelGGL((k_shade<true, true, false, 1>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else
-          hipLaunchKernelGGL((k_shade<false, true, false, 1>), dim3(grid), dim3(STHIP_BLOCK), shade_lds, st, p, depth);
-      } else if (bdpt) {
-        if (ctx->textured)
-          hipLaunchKernelGGL((k_shade<true, true, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-        else
-          hipLaunchKernelGGL((k_shade<false, true, true>), dim3(grid), dim3(STHIP_BLOCK), shade_lds, st, p, depth);
-      } else if (ctx->textured && ext)
-        hipLaunchKernelGGL((k_shade<true, true>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-      else if (ctx->textured)
-        hipLaunchKernelGGL((k_shade<true, false>), dim3(grid), dim3(STHIP_BLOCK), 0, st, p, depth);
-      else {
-        // untextured scenes, no light subpaths, no media. Where the path or diffuse budget can end at this round's vertex, only
-        // the paths that still have something to do reach k_shade (k_cull_terminal).
-        FrameParams pk = p;
-        if (ctx->cull_terminal && depth >= 1 && !p.rr && !p.cs_nee && !p.cs_lvc && (depth + 2 >= pc->gMaxPathVertices || depth + 1 > pc->gMaxDiffuseVertices)) {
-          // a block keeps what it meets in LDS: as many blocks per segment as it takes for a segment's share to fit (16 KB at 1080p)
-          uint32_t per_segment = CULL_BLOCKS_PER_SEGMENT, per_block;
-          for (;; per_segment *= 2) {
-            per_block = (uint32_t)((((size_t)p.seg_stride + (size_t)per_segment * STHIP_BLOCK - 1) / ((size_t)per_segment * STHIP_BLOCK)) * STHIP_BLOCK);  // entries a block can meet
-            if ((size_t)(per_block + 2) * 4 <= 48 * 1024) break;
-          }
-          hipLaunchKernelGGL(k_cull_terminal, dim3(QUEUE_SEGMENTS * per_segment), dim3(STHIP_BLOCK), (size_t)(per_block + 2) * 4, st, p, depth, ctx->queue_kept.p, per_block);
-          pk.queue[depth & 1u] = ctx->queue_kept.p;
-          pk.culled = 1;
-        }
-        if (ext)
-          hipLaunchKernelGGL((k_shade<false, true>), dim3(grid), dim3(STHIP_BLOCK), shade_lds, st, pk, depth);
-        else
-          hipLaunchKernelGGL((k_shade<false, false>), dim3(grid), dim3(STHIP_BLOCK), shade_lds, st, pk, depth);
-      }
-    });
-    if (rc) return rc;
-    rc = timed(ms_other, [&]() { hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(STHIP_BLOCK), 0, st, p, s == 0 ? 1u : 0u, s + in_flight == seed_count ? 1u : 0u, primary_rays * in_flight); });
-    if (rc) return rc;
-    if ((nee_reuse || lvc_reuse) && (s + in_flight < seed_count || ctx->reuse_persist)) {
-      // This seed's appends become the grids the next seed looks up (hashgrid.h)
-      if (nee_reuse) {
-        const int rc2 = build_hash_grid(ctx, st, ctx->hg_appends.p, ctx->hg_compact.p, ctx->hg_data.p, hg_slots, 4, 2, false, pc->gHashGridBucketCount, ctx->hg_checksums, ctx->hg_counters, ctx->hg_indices);
-        if (rc2) return rc2;
-      }
-      if (lvc_reuse) {
-        const int rc2 = build_hash_grid(ctx, st, ctx->lg_appends.p, ctx->lg_compact.p, ctx->lg_data.p, hg_slots, 6, 0, true, pc->gHashGridBucketCount, ctx->lg_checksums, ctx->lg_counters, ctx->lg_indices);
-        if (rc2) return rc2;
-      }
-      p.hg_prev = 1;
-    }
-  }
-  if ((nee_reuse || lvc_reuse) && ctx->reuse_persist) {  // what the next call's first seed may look into
-    memcpy(ctx->reuse_key, reuse_key, sizeof reuse_key);
-    ctx->reuse_grids_valid = true;
-  }
-
-  if (slot) {
-    // The read-back of the pipelined form: on the copy stream, behind the "rendered" event, so that the runtime moves this frame
-    // (a copy engine, or its copy kernel on a hardware queue of its own: ~0.6 ms per 33 MB image) while the next one is traced. ctx->counters is rewritten by the next frame's k_clear: its read-out into
-    // the slot is a device-to-device copy ON THE RENDER STREAM, ordered before that rewrite; the copy stream then takes the
-    // slot's counters to the pinned record. Nothing waits on the host, nothing spins on the device: events only.
-    hipStream_t cs = ctx->copy_stream;
-    HIP_TRY(ctx, hipMemcpyAsync(slot->counters.p, ctx->counters.p, CNT_TOTAL * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(ctx, hipEventRecord(slot->rendered, st));
-    HIP_TRY(ctx, hipStreamWaitEvent(cs, slot->rendered, 0));
-    HIP_TRY(ctx, hipMemcpyAsync(out->gRadiance, p.out_radiance, radiance_entries * cb, hipMemcpyDeviceToHost, cs));
-    if (out->gAlbedo) HIP_TRY(ctx, hipMemcpyAsync(out->gAlbedo, p.out_albedo16 ? (const void*)p.out_albedo16 : (const void*)p.out_albedo, pixels * cb, hipMemcpyDeviceToHost, cs));
-    if (out->gVisibility) HIP_TRY(ctx, hipMemcpyAsync(out->gVisibility, p.out_visibility, pixels * 8, hipMemcpyDeviceToHost, cs));
-    if (out->gDepth) HIP_TRY(ctx, hipMemcpyAsync(out->gDepth, p.out_depth, pixels * 16, hipMemcpyDeviceToHost, cs));
-    if (out->gPrevUVs) HIP_TRY(ctx, hipMemcpyAsync(out->gPrevUVs, p.out_prev_uv, pixels * 8, hipMemcpyDeviceToHost, cs));
-    HIP_TRY(ctx, hipMemcpyAsync(slot->record, slot->counters.p, CNT_TOTAL * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
-    HIP_TRY(ctx, hipEventRecord(slot->copied, cs));
-    slot->ray_count = out->gRayCount;
-    ctx->stats_pending = true;  // (until the ticket is retired, sthip_get_stats reads the counters of the last frame enqueued)
-  } else if (!dev) {
-    HIP_TRY(ctx, hipMemcpyAsync(out->gRadiance, p.out_radiance, radiance_entries * cb, hipMemcpyDeviceToHost, st));
-    if (out->gAlbedo) HIP_TRY(ctx, hipMemcpyAsync(out->gAlbedo, p.out_albedo16 ? (const void*)p.out_albedo16 : (const void*)p.out_albedo, pixels * cb, hipMemcpyDeviceToHost, st));
-    if (out->gVisibility) HIP_TRY(ctx, hipMemcpyAsync(out->gVisibility, p.out_visibility, pixels * 8, hipMemcpyDeviceToHost, st));
-    if (out->gDepth) HIP_TRY(ctx, hipMemcpyAsync(out->gDepth, p.out_depth, pixels * 16, hipMemcpyDeviceToHost, st));
-    if (out->gPrevUVs) HIP_TRY(ctx, hipMemcpyAsync(out->gPrevUVs, p.out_prev_uv, pixels * 8, hipMemcpyDeviceToHost, st));
-    if (debug_mode) HIP_TRY(ctx, hipMemcpyAsync(out->gDebugImage, p.out_debug, pixels * cb, hipMemcpyDeviceToHost, st));
-    unsigned long long c[CNT_TOTAL];
-    HIP_TRY(ctx, hipMemcpyAsync(c, ctx->counters.p, sizeof(c), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (out->gRayCount) {
-      out->gRayCount[0] = c[CNT_RAYS_CLOSEST] + c[CNT_RAYS_SHADOW];
-      out->gRayCount[1] = c[CNT_RAYS_CLOSEST] - c[CNT_CROSSINGS];
-    }
-    fill_counter_stats(ctx, c);
-    ctx->stats_pending = false;
-  } else {
-    if (out->gRayCount) hipLaunchKernelGGL(k_write_ray_count, dim3(1), dim3(1), 0, st, ctx->counters.p, reinterpret_cast<unsigned long long*>(out->gRayCount));
-    ctx->stats_pending = true;
-  }
-  if (timing) {
-    ctx->stats.ms_trace = ms_trace;
-    ctx->stats.ms_shade = ms_shade;
-    ctx->stats.ms_total = ms_trace + ms_primary + ms_shade + ms_other;
-    ctx->stats.launches_trace = launches_trace;
-    ctx->stats.ms_trace_primary = ms_primary;
-    ctx->stats.launches_primary = launches_primary;
-  }
-  ctx->stats.rays_primary_packets = rays_primary;
-  return STHIP_OK;
-}
-
 // ---- multi-GPU assembly: the packed tiles of every shard -> the frame ----
 
 uint32_t sthip_shard_slot_count(uint32_t width, uint32_t height, uint32_t shard_rank, uint32_t shard_count, uint32_t tile_w, uint32_t tile_h) {
   if (!width || !height || !shard_count || !tile_w || !tile_h || shard_rank >= shard_count) return 0;
   const uint32_t tiles = ((width + tile_w - 1) / tile_w) * ((height + tile_h - 1) / tile_h);
-  const uint32_t owned = tiles > shard_rank ? (tiles - shard_rank + shard_count - 1) / shard_count : 0;
-  return owned * tile_w * tile_h;
+  return owned_tiles(tiles, shard_rank, shard_count) * tile_w * tile_h;
 }
 
 int sthip_assemble_tiles_bytes(sthip_ctx* ctx, const void* packed, uint64_t rank_stride, uint32_t shard_count, uint32_t tile_w, uint32_t tile_h, uint32_t width, uint32_t height,

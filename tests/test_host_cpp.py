@@ -213,6 +213,16 @@ def test_packed_node_planes_are_conservative(tmp_path):
     assert out.returncode == 0 and out.stdout.startswith("PACK OK"), out.stdout + out.stderr
 
 
+def test_shade_variant_rule_matches_the_instantiation_lists(tmp_path):
+    """csrc/kernel_variants.h: the rule that picks k_shade's template arguments selects only listed instantiations, every
+    listed one is selected by some reachable input, and rule and LDS size agree with the former if/else ladders written out
+    in tests/cpp/kernel_variants_check.cpp (host only: the header has no HIP in it)."""
+    exe = str(tmp_path / "kernel_variants_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-o", exe, os.path.join(ROOT, "tests", "cpp", "kernel_variants_check.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("VARIANTS OK: 24 listed, 24 selected"), out.stdout + out.stderr
+
+
 # ---- the multi-GPU driver of the C++ host (host/stratum_hip_multi.hpp) ----
 def _multi_host(built):
     import __graft_entry__ as g
