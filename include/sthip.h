@@ -222,6 +222,71 @@ typedef struct sthip_refit_info { /* optional out-parameter, may be NULL */
 } sthip_refit_info;
 int sthip_scene_update_vertices(sthip_ctx* ctx, const sthip_PackedVertexData* vertices, uint32_t first_vertex, uint32_t vertex_count, sthip_refit_info* info);
 
+/* ---- rigs: a mesh animated on the device (kernels/anim.hlsl: `blend` :53-86, `skin` :27-51; no upstream host calls them) ----
+ * sthip_scene_update_vertices needs the host to compute every deformed vertex and to send it up on each frame. Almost every
+ * moving mesh is a rig: a rest pose, a few blend targets, four bone weights per vertex. With the calls below the rig stays
+ * resident and a frame sends only its pose: four blend factors and bone_count matrices per rig. One kernel (animate.hip)
+ * writes the rig's records of gVertices on the device; the gather, the refit, the top level and everything else
+ * sthip_scene_update_vertices derives follow unchanged, so the frame is the one a fresh upload of the posed vertices gives,
+ * bit for bit.
+ *
+ * The arithmetic is part of the contract (sthip_detmath.h: binary32, no contraction, left to right). Per vertex, rest record r:
+ *   blend, only if blend_target_count > 0 (anim.hlsl:59-81):
+ *     f = fmaxf(0, 1 - (((|b0| + |b1|) + |b2|) + |b3|));  p = f * r.position;  for k = 0 .. count - 1: p = p + bk * Tk.position;
+ *     n the same from the normals, then n = normalize3(n) (1 / sqrt of the dot product, times each component). Without targets
+ *     p and n are bit copies of the rest.
+ *   skin, only if bone_count > 0 (anim.hlsl:31-45):
+ *     M = +0;  for j = 0 .. 3: M = M + bones[indices[j]] * weights[j], elementwise;
+ *     p' = M[r][0] * p.x + M[r][1] * p.y + M[r][2] * p.z + M[r][3];  n' the 3x3 part the same way; not renormalised (as upstream).
+ *   u and v are bit copies of the rest. Upstream's tangent has no field in PackedVertexData and is not carried.
+ *
+ * sthip_scene_set_rigs: `rigs` and everything they point to are host arrays, copied during the call. Validated on the host:
+ * STHIP_ERR_INVALID_ARGUMENT with a message, and nothing changes (rigs set before stay), when no scene is resident, a range
+ * runs past the uploaded vertex_count, two ranges overlap, blend_target_count > 4 or bone_count > 1024, a pointer the counts
+ * require is NULL (`weights` is NULL if and only if bone_count == 0), or some indices[k] >= bone_count. Then the REST POSE of
+ * each rig is taken on the device: a copy of the records of its range as they are resident at this moment, whatever the last
+ * upload, sthip_scene_update_vertices or sthip_scene_animate left there; targets and weights go up once. A later
+ * sthip_scene_update_vertices over a rigged range changes the resident records until the next sthip_scene_animate but does
+ * NOT change the rest pose: set the rigs again for that. rig_count = 0 drops all rigs; so does every sthip_scene_upload.
+ *
+ * sthip_scene_animate: pose_count must be the rig_count of the last sthip_scene_set_rigs, poses[i] belongs to rigs[i].
+ * Refused on the host (STHIP_ERR_INVALID_ARGUMENT, nothing changes): no scene, no rigs, a wrong pose_count, `bones` NULL for a
+ * rig with bones, a factor of a present target or a bone entry that is not finite. Then it does what
+ * sthip_scene_update_vertices does with the upload replaced by the kernel: waits for the stream and completes the frames in
+ * flight, sends the bones (the only host-to-device traffic of the call), launches k_animate once per rig, gathers, refits
+ * and installs the new top level. sthip_refit_info as for the vertex call; device_ms includes k_animate.
+ * Measured on the 1M-triangle atrium (profiles/r07/animate.json, medians of 9 calls, device-built tree): a rig over all
+ * 408 970 vertices with 4 targets and 64 bones, 0.86 ms for the call (0.73 ms of it on the stream, k_animate included; 3 KB go
+ * up) against 1.32 ms for sthip_scene_update_vertices with the same vertices in the same process (0.71 ms on the stream; 13 MB
+ * go up); a rig over one instance's mesh (5 440 vertices) 0.83 ms against 0.84 ms.
+ * The copy of the scene "keep_scene" keeps is NOT updated per call (that would bring the transfer back in the other
+ * direction): its rigged ranges are marked stale and read back from the device immediately before anything is built again
+ * from the kept scene — the rebuild inside sthip_scene_update_transforms when a merged instance moved, the failure fallback,
+ * and the layouts the refit does not serve ("embed_leaves", "treetop", "wide_bvh" = 3), for which this call runs the kernel,
+ * reads the ranges back and builds the scene again (rebuilt = 1). A sthip_scene_update_vertices over records of a stale range
+ * makes those records current again. Failures follow the vertex call's rules: everything that can be refused or can run out
+ * of memory happens before gVertices is touched; after that a failure ends in a rebuild from the kept scene, or with
+ * "keep_scene" = 0 in no resident scene (layouts the refit serves) — layouts it does not serve return STHIP_ERR_UNSUPPORTED
+ * with "keep_scene" = 0 and change nothing.
+ *
+ * sthip_scene_read_vertices: the resident records [first_vertex, first_vertex + vertex_count) of gVertices, copied to host
+ * memory after the work on the stream has finished (what a host that wants the posed mesh back calls; tests).
+ * A library without the feature lacks the three symbols. */
+typedef struct sthip_rig_desc {
+  uint32_t first_vertex, vertex_count;            /* the records of gVertices this rig drives */
+  uint32_t blend_target_count;                    /* 0..4 */
+  uint32_t bone_count;                            /* 0: no skinning; at most 1024 */
+  const sthip_PackedVertexData* blend_targets[4]; /* vertex_count records each; position and normal are read, u / v ignored */
+  const sthip_VertexWeight* weights;              /* vertex_count records, or NULL iff bone_count == 0 */
+} sthip_rig_desc;
+typedef struct sthip_rig_pose {
+  float blend_factors[4];           /* factors of absent targets are taken as 0 */
+  const sthip_TransformData* bones; /* bone_count matrices (row-major 3x4), NULL iff the rig has no bones */
+} sthip_rig_pose;
+int sthip_scene_set_rigs(sthip_ctx* ctx, const sthip_rig_desc* rigs, uint32_t rig_count);
+int sthip_scene_animate(sthip_ctx* ctx, const sthip_rig_pose* poses, uint32_t pose_count, sthip_refit_info* info);
+int sthip_scene_read_vertices(sthip_ctx* ctx, uint32_t first_vertex, uint32_t vertex_count, sthip_PackedVertexData* out);
+
 /* ---- frame: replaces the dispatch sequence of BDPT::render (BDPT.cpp:607-720) ----
  * Renders seeds seed_begin .. seed_begin+seed_count-1 (gRandomSeed = seed, BDPT.cpp:480), one
  * sample per pixel centre per seed (bdpt.hlsl:167), and averages them with the running mean of

@@ -47,6 +47,12 @@ typedef struct sthip_TransformData {
   float m[3][4];
 } sthip_TransformData;
 
+/* VertexWeight, kernels/anim.hlsl:6-9: the four bones of a skinned vertex and their weights (sthip_scene_set_rigs) */
+typedef struct sthip_VertexWeight {
+  float weights[4];
+  uint32_t indices[4];
+} sthip_VertexWeight;
+
 /* W6 — ProjectionData, transform.h:109-148 */
 typedef struct sthip_ProjectionData {
   float scale[2];
@@ -189,6 +195,7 @@ enum sthip_BDPTFlagBits {
 static_assert(sizeof(sthip_InstanceData) == 16, "InstanceData");
 static_assert(sizeof(sthip_PackedVertexData) == 32, "PackedVertexData");
 static_assert(sizeof(sthip_TransformData) == 48, "TransformData");
+static_assert(sizeof(sthip_VertexWeight) == 32, "VertexWeight");
 static_assert(sizeof(sthip_ViewData) == 48, "ViewData");
 static_assert(sizeof(sthip_VisibilityInfo) == 8, "VisibilityInfo");
 static_assert(sizeof(sthip_DepthInfo) == 16, "DepthInfo");

@@ -24,6 +24,9 @@ EXPORTS = [
     "sthip_scene_upload",
     "sthip_scene_update_transforms",
     "sthip_scene_update_vertices",
+    "sthip_scene_set_rigs",
+    "sthip_scene_animate",
+    "sthip_scene_read_vertices",
     "sthip_render",
     "sthip_host_alloc",
     "sthip_host_free",
@@ -100,6 +103,12 @@ def lib():
     L.sthip_scene_upload.argtypes = [C.c_void_p, C.POINTER(wire.SceneDesc)]
     L.sthip_scene_update_vertices.restype = C.c_int
     L.sthip_scene_update_vertices.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(wire.RefitInfo)]
+    L.sthip_scene_set_rigs.restype = C.c_int
+    L.sthip_scene_set_rigs.argtypes = [C.c_void_p, C.POINTER(wire.RigDesc), C.c_uint32]
+    L.sthip_scene_animate.restype = C.c_int
+    L.sthip_scene_animate.argtypes = [C.c_void_p, C.POINTER(wire.RigPose), C.c_uint32, C.POINTER(wire.RefitInfo)]
+    L.sthip_scene_read_vertices.restype = C.c_int
+    L.sthip_scene_read_vertices.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.sthip_render.restype = C.c_int
     L.sthip_render.argtypes = [
         C.c_void_p,

@@ -161,6 +161,60 @@ class BDPT:
         self._scene = scene
         return {f: getattr(info, f) for f, _ in wire.RefitInfo._fields_ if f != "pad"}
 
+    def set_rigs(self, rigs):
+        """Make rigs resident (sthip_scene_set_rigs). `rigs`: a list of dicts with "first_vertex", "vertex_count", optionally
+        "blend_targets" (up to 4 wire.PackedVertexData arrays of vertex_count records), and "weights" (a wire.VertexWeight
+        array of vertex_count records) with "bone_count". The rest pose of each rig is the resident records of its range as
+        they are now. An empty list drops the rigs; so does update()."""
+        n = len(rigs)
+        descs = (wire.RigDesc * max(1, n))()
+        keep = []  # (the arrays the descriptors point into, alive for the call)
+        for d, rig in zip(descs, rigs):
+            d.first_vertex, d.vertex_count = int(rig["first_vertex"]), int(rig["vertex_count"])
+            targets = list(rig.get("blend_targets") or [])
+            d.blend_target_count = len(targets)
+            for k, t in enumerate(targets[:4]):
+                t = np.ascontiguousarray(t, dtype=wire.PackedVertexData)
+                if t.shape[0] != d.vertex_count:
+                    raise ValueError("a blend target has %d records, the rig %d" % (t.shape[0], d.vertex_count))
+                keep.append(t)
+                d.blend_targets[k] = t.ctypes.data
+            d.bone_count = int(rig.get("bone_count", 0))
+            w = rig.get("weights")
+            if w is not None:
+                w = np.ascontiguousarray(w, dtype=wire.VertexWeight)
+                if w.shape[0] != d.vertex_count:
+                    raise ValueError("weights has %d records, the rig %d" % (w.shape[0], d.vertex_count))
+                keep.append(w)
+                d.weights = w.ctypes.data
+        self._check(self._lib.sthip_scene_set_rigs(self._h, descs, n), "sthip_scene_set_rigs")
+
+    def animate(self, poses):
+        """Pose the resident rigs on the device and refit (sthip_scene_animate). `poses`: one dict per rig with optionally
+        "blend_factors" (up to 4 floats) and "bones" (a wire.TransformData array, or float32 of shape (bone_count, 3, 4)).
+        Only the pose crosses to the device. Returns sthip_refit_info as a dict, as update_vertices does."""
+        n = len(poses)
+        c_poses = (wire.RigPose * max(1, n))()
+        keep = []
+        for c, pose in zip(c_poses, poses):
+            for k, f in enumerate(list(pose.get("blend_factors", ()))[:4]):
+                c.blend_factors[k] = float(f)
+            b = pose.get("bones")
+            if b is not None:
+                b = np.asarray(b)
+                b = np.ascontiguousarray(b["m"] if b.dtype == wire.TransformData else b, dtype=np.float32).reshape(-1, 3, 4)
+                keep.append(b)
+                c.bones = b.ctypes.data
+        info = wire.RefitInfo()
+        self._check(self._lib.sthip_scene_animate(self._h, c_poses, n, C.byref(info)), "sthip_scene_animate")
+        return {f: getattr(info, f) for f, _ in wire.RefitInfo._fields_ if f != "pad"}
+
+    def read_vertices(self, first, count):
+        """The resident vertex records [first, first + count) as a wire.PackedVertexData array (sthip_scene_read_vertices)."""
+        out = np.zeros(int(count), dtype=wire.PackedVertexData)
+        self._check(self._lib.sthip_scene_read_vertices(self._h, int(first), int(count), wire.ptr(out)), "sthip_scene_read_vertices")
+        return out
+
     def set_stream(self, stream_handle):
         self._check(self._lib.sthip_set_stream(self._h, C.c_void_p(stream_handle)), "sthip_set_stream")
 

@@ -10,13 +10,16 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
+#include <cmath>
 #include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/sthip.h"
+#include "animate.h"
 #include "bvh_build.h"
 #include "kernel_instances.h"  // kernels.h + the instantiations that live in shade_*.hip / trace_kernels.hip
 #include "post.h"
@@ -271,6 +274,23 @@ struct sthip_ctx {
   bool refit_roots_valid = false;
   uint32_t vertex_count = 0;
   uint64_t indices_bytes = 0;
+  // sthip_scene_set_rigs / sthip_scene_animate (animate.hip): the rigs as they are resident — per rig its range of gVertices
+  // and where its records start in the arrays below (rest poses and weights: one record per rigged vertex, in rig order;
+  // targets: target_count x vertex_count records per rig; bones: bone_count per rig, staged on the host by every animate call)
+  struct ResidentRig {
+    uint32_t first = 0, count = 0, target_count = 0, bone_count = 0;
+    size_t at = 0, targets_at = 0, bones_at = 0;
+  };
+  std::vector<ResidentRig> rigs;
+  DevBuf<sthip_PackedVertexData> rig_rest, rig_targets;
+  DevBuf<sthip_VertexWeight> rig_weights;
+  DevBuf<sthip_TransformData> rig_bones;
+  std::vector<sthip_TransformData> rig_bones_host;
+  std::vector<std::array<float, 4>> rig_factors;  // of the animate call in progress
+  hipEvent_t rig_ev[2] = {nullptr, nullptr};      // around the k_animate launches of a call (sthip_refit_info::device_ms)
+  // ranges [first, end) of the kept scene's vertices that an animate call left behind the device's: read back before anything
+  // is built from the kept scene (sync_kept_vertices)
+  std::vector<std::pair<uint32_t, uint32_t>> kept_stale;
   bool embedded_resident = false;  // the leaf triangles lie in the node array (BuiltBvh::embedded)
   bool want_wide = false;                            // the current scene is walked in its 4-wide form (decided at upload)
   bool lds_materials = true;  // k_shade stages gMaterialData in LDS when it fits 32 KB
@@ -575,6 +595,8 @@ void sthip_destroy(sthip_ctx* ctx) {
   ctx->wide_scratch = nullptr;
   sthip::device_refit_destroy(ctx->refit);
   ctx->refit = nullptr;
+  for (int k = 0; k < 2; k++)
+    if (ctx->rig_ev[k]) (void)hipEventDestroy(ctx->rig_ev[k]);
   ctx->vertices.release();
   ctx->volume_words.release();
   ctx->volumes.release();
@@ -814,6 +836,79 @@ static int collapse_resident_tree(sthip_ctx* ctx) {
   return STHIP_OK;
 }
 
+// ---- rigs (sthip_scene_set_rigs / sthip_scene_animate) ----
+static void drop_rigs(sthip_ctx* ctx) {
+  ctx->rigs.clear();
+  ctx->rig_rest.release();
+  ctx->rig_targets.release();
+  ctx->rig_weights.release();
+  ctx->rig_bones.release();
+  ctx->rig_bones_host.clear();
+  ctx->rig_factors.clear();
+}
+
+// The kept scene's vertices are current again: the ranges an animate call wrote on the device come back to the host. Called
+// immediately before anything is built from the kept scene.
+static int sync_kept_vertices(sthip_ctx* ctx) {
+  if (ctx->kept_stale.empty()) return STHIP_OK;
+  if (ctx->kept.valid && ctx->kept.vertices.size() == ctx->vertex_count && ctx->vertices.p) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (k_animate runs on the stream; the copy below does not wait for a non-blocking one)
+    for (const auto& r : ctx->kept_stale)
+      if (r.first < r.second && r.second <= ctx->vertex_count)
+        HIP_TRY(ctx, hipMemcpy(ctx->kept.vertices.data() + r.first, ctx->vertices.p + r.first, (size_t)(r.second - r.first) * sizeof(sthip_PackedVertexData), hipMemcpyDeviceToHost));
+  }
+  ctx->kept_stale.clear();
+  return STHIP_OK;
+}
+// The host wrote the kept records [first, first + count): they are not stale any more
+static void kept_vertices_written(sthip_ctx* ctx, uint32_t first, uint32_t count) {
+  if (ctx->kept_stale.empty() || !count) return;
+  const uint32_t end = first + count;
+  std::vector<std::pair<uint32_t, uint32_t>> left;
+  for (const auto& r : ctx->kept_stale) {
+    if (end <= r.first || r.second <= first) {
+      left.push_back(r);
+      continue;
+    }
+    if (r.first < first) left.emplace_back(r.first, first);
+    if (end < r.second) left.emplace_back(end, r.second);
+  }
+  ctx->kept_stale.swap(left);
+}
+
+// The k_animate launches of an animate call: the bones staged in rig_bones_host go up, then one launch per rig. From the
+// first launch on the kept vertices of the rigs' ranges are behind the device's.
+static int pose_rigs(sthip_ctx* ctx, const char* call) {
+  if (!ctx->rig_bones_host.empty())
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->rig_bones.p, ctx->rig_bones_host.data(), ctx->rig_bones_host.size() * sizeof(sthip_TransformData), hipMemcpyHostToDevice, ctx->stream));
+  if (ctx->kept.valid)
+    for (const auto& r : ctx->rigs) {
+      if (!r.count) continue;
+      kept_vertices_written(ctx, r.first, r.count);  // (what is left of the range from earlier calls: one entry per range, however often it is posed)
+      ctx->kept_stale.emplace_back(r.first, r.first + r.count);
+    }
+  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[0], ctx->stream));
+  for (size_t k = 0; k < ctx->rigs.size(); k++) {
+    const sthip_ctx::ResidentRig& r = ctx->rigs[k];
+    sthip::AnimateRig a;
+    a.vertices = ctx->vertices.p + r.first;
+    a.rest = ctx->rig_rest.p + r.at;
+    for (uint32_t t = 0; t < r.target_count; t++) {
+      a.targets[t] = ctx->rig_targets.p + r.targets_at + (size_t)t * r.count;
+      a.factors[t] = ctx->rig_factors[k][t];
+    }
+    a.weights = r.bone_count ? ctx->rig_weights.p + r.at : nullptr;
+    a.bones = r.bone_count ? ctx->rig_bones.p + r.bones_at : nullptr;
+    a.vertex_count = r.count;
+    a.target_count = r.target_count;
+    a.bone_count = r.bone_count;
+    std::string err;
+    if (!sthip::animate_launch(a, ctx->cu_count, ctx->stream, err)) return fail(ctx, STHIP_ERR_HIP, std::string(call) + ": " + err);
+  }
+  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[1], ctx->stream));
+  return STHIP_OK;
+}
+
 int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
   if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
   if (!s || !s->gInstances || !s->gInstanceTransforms || !s->gInstanceInverseTransforms || !s->gMaterialData || s->instance_count == 0)
@@ -830,6 +925,11 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
   ctx->has_scene = false;
   sthip::device_refit_invalidate(ctx->refit);  // (the schedule of a refit belongs to the tree that goes away now)
   ctx->refit_roots_valid = false;
+  // the rigs name vertex ranges of the scene that goes away; a rebuild from the kept copy is the same scene and keeps them
+  if (!(ctx->kept.valid && s->gVertices && s->gVertices == ctx->kept.vertices.data())) {
+    drop_rigs(ctx);
+    ctx->kept_stale.clear();
+  }
   for (uint32_t i = 0; i < s->light_count; i++)
     if (s->gLightInstances[i] >= s->instance_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: gLightInstances entry out of range");
   bool any_specular = false, any_image = false, any_alpha = false;
@@ -1490,6 +1590,10 @@ int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf,
     // the scene is built again from the copy kept at upload, with the new transforms — the configured builder ("bvh_builder" = 1:
     // ~10 ms per million triangles on the device), everything else as uploaded. Without the copy ("keep_scene" = 0) it is refused.
     if (ctx->kept.valid && ctx->kept.instances.size() == instance_count) {
+      {  // (ranges an animate call posed on the device: the rebuild must see them)
+        const int rc = sync_kept_vertices(ctx);
+        if (rc != STHIP_OK) return rc;
+      }
       ctx->kept.xf.assign(xf, xf + instance_count);
       ctx->kept.inv.assign(inv, inv + instance_count);
       if (motion)
@@ -1530,20 +1634,37 @@ int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf,
   return install_top_level(ctx, next, tlas, root_ref, top_is_world, stack_depth, center, radius);
 }
 
-// The part of sthip_scene_update_vertices that changes the resident scene: the vertex range goes up, the leaf triangles are
-// gathered again, the bottom levels refitted and everything an upload derives from the meshes' bounds made again. A failure
-// in here leaves the scene half changed; the caller repairs that.
-static int refit_resident_scene(sthip_ctx* ctx, const sthip_PackedVertexData* vertices, uint32_t first_vertex, uint32_t vertex_count, bool kept, const sthip_TransformData* xf, const sthip_TransformData* inv,
-                                sthip::RefitResult& res, float& wide_ms) {
+// Where the new vertex records of a refit come from: a range of host records that goes up (sthip_scene_update_vertices), or
+// the resident rigs in the pose an animate call staged, written on the device (sthip_scene_animate: `vertices` is NULL)
+struct VertexSource {
+  const char* call;  // the entry point, for messages
+  const sthip_PackedVertexData* vertices;
+  uint32_t first_vertex, vertex_count;
+  bool posed() const { return vertices == nullptr; }
+};
+
+// The part of a vertex update that changes the resident scene: the vertex range goes up or the rigs are posed, the leaf
+// triangles are gathered again, the bottom levels refitted and everything an upload derives from the meshes' bounds made again.
+// A failure in here leaves the scene half changed; the caller repairs that.
+static int refit_resident_scene(sthip_ctx* ctx, const VertexSource& src, bool kept, const sthip_TransformData* xf, const sthip_TransformData* inv, sthip::RefitResult& res, float& wide_ms) {
   std::string err;
+  const std::string call = std::string(src.call) + ": ";
   const uint32_t n = ctx->instance_count;
   const std::vector<uint32_t>& root_of_entry = ctx->refit_root_of_entry;
-  if (vertex_count) HIP_TRY(ctx, hipMemcpyAsync(ctx->vertices.p + first_vertex, vertices, (size_t)vertex_count * sizeof(sthip_PackedVertexData), hipMemcpyHostToDevice, ctx->stream));
-  if (kept && vertex_count && vertices != ctx->kept.vertices.data() + first_vertex) memcpy(ctx->kept.vertices.data() + first_vertex, vertices, (size_t)vertex_count * sizeof(sthip_PackedVertexData));
+  if (src.posed()) {
+    const int rc = pose_rigs(ctx, src.call);
+    if (rc != STHIP_OK) return rc;
+  } else if (src.vertex_count) {
+    const sthip_PackedVertexData* vertices = src.vertices;
+    const uint32_t first_vertex = src.first_vertex, vertex_count = src.vertex_count;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->vertices.p + first_vertex, vertices, (size_t)vertex_count * sizeof(sthip_PackedVertexData), hipMemcpyHostToDevice, ctx->stream));
+    if (kept && vertices != ctx->kept.vertices.data() + first_vertex) memcpy(ctx->kept.vertices.data() + first_vertex, vertices, (size_t)vertex_count * sizeof(sthip_PackedVertexData));
+    if (kept) kept_vertices_written(ctx, first_vertex, vertex_count);
+  }
   ctx->reuse_grids_valid = false;
   ctx->nodes_host.n = 0;  // (no layout that reads the host copy of the nodes comes this way; it must not outlive the boxes it holds)
   if (!sthip::refit_gather(ctx->refit, ctx->tris.p, (uint32_t)ctx->bvh_tris, ctx->vertices.p, ctx->vertex_count, ctx->indices.p, ctx->indices_bytes, ctx->stream, err))
-    return fail(ctx, STHIP_ERR_HIP, "sthip_scene_update_vertices: " + err);
+    return fail(ctx, STHIP_ERR_HIP, call + err);
   if (ctx->bvh_tris && ctx->vertex_count) {
     hipLaunchKernelGGL(k_fill_tri_shade, dim3(grid_for(ctx, (size_t)ctx->bvh_tris)), dim3(STHIP_BLOCK), 0, ctx->stream, reinterpret_cast<const BvhTri*>(ctx->bvh.tris), (uint32_t)ctx->bvh_tris,
                        (const uint8_t*)nullptr, ctx->vertices.p, ctx->vertex_count, ctx->indices.p, ctx->indices_bytes, ctx->tri_shade.p, ctx->has_alpha ? ctx->tri_uvs.p : nullptr);
@@ -1553,7 +1674,7 @@ static int refit_resident_scene(sthip_ctx* ctx, const sthip_PackedVertexData* ve
   for (uint32_t k = 0; k < ctx->emitter_count && k < ctx->emitters_host.size(); k++) emitter_instances.push_back(ctx->emitters_host[k].instance);
   if (!sthip::refit_boxes(ctx->refit, ctx->nodes.p, ctx->tris.p, (uint32_t)ctx->bvh_tris, ctx->instances.p, emitter_instances, ctx->vertices.p, ctx->vertex_count, ctx->indices.p, ctx->indices_bytes,
                           ctx->stream, res, err))
-    return fail(ctx, STHIP_ERR_HIP, "sthip_scene_update_vertices: " + err);
+    return fail(ctx, STHIP_ERR_HIP, call + err);
   // what an upload derives from the meshes' bounds (bvh_build.cpp), with its arithmetic, from the roots' exact boxes
   sthip::TopLevelState next = ctx->top;
   for (size_t k = 0; k < next.entries.size(); k++) {
@@ -1590,32 +1711,28 @@ static int refit_resident_scene(sthip_ctx* ctx, const sthip_PackedVertexData* ve
   std::vector<BvhNode> tlas;
   uint32_t root_ref = 0, top_is_world = 1, stack_depth = 4;
   float center[3] = {ctx->bvh.scene_cx, ctx->bvh.scene_cy, ctx->bvh.scene_cz}, radius = ctx->bvh.scene_radius;
-  if (!sthip::rebuild_top_level(next, xf, inv, n, tlas, root_ref, top_is_world, stack_depth, center, radius, err)) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_vertices: " + err);
-  if (stack_depth > STHIP_MAX_STACK_DEPTH) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_vertices: the new top level is too deep for the traversal stack");
-  if ((size_t)next.blas_nodes + tlas.size() > ctx->nodes.n) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_vertices: the new top level does not fit");
+  if (!sthip::rebuild_top_level(next, xf, inv, n, tlas, root_ref, top_is_world, stack_depth, center, radius, err)) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + err);
+  if (stack_depth > STHIP_MAX_STACK_DEPTH) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "the new top level is too deep for the traversal stack");
+  if ((size_t)next.blas_nodes + tlas.size() > ctx->nodes.n) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "the new top level does not fit");
   const float wide_ms_before = ctx->stats.bvh_build_gpu_ms;
   const int rc = install_top_level(ctx, next, tlas, root_ref, top_is_world, stack_depth, center, radius);
   wide_ms = ctx->stats.bvh_build_gpu_ms - wide_ms_before;
   return rc;
 }
 
-// sthip.h. The default layout is refitted where it lies (refit.hip); the layouts that keep more than the node and triangle
-// arrays of the tree (leaf triangles inside the node array, a treetop selected from a host copy of the nodes, the 8-wide form
-// with its permuted triangles) are built again from the kept scene.
-int sthip_scene_update_vertices(sthip_ctx* ctx, const sthip_PackedVertexData* vertices, uint32_t first_vertex, uint32_t vertex_count, sthip_refit_info* info) {
-  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
-  const auto t0 = std::chrono::steady_clock::now();
-  if (info) memset(info, 0, sizeof(*info));
-  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_vertices before sthip_scene_upload");
-  if (!vertices) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_vertices: vertices is NULL");
-  if ((uint64_t)first_vertex + vertex_count > ctx->vertex_count)
-    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_vertices: the range ends past the vertex_count of the uploaded scene");
+// sthip.h, for both sources of new vertices. The default layout is refitted where it lies (refit.hip); the layouts that keep
+// more than the node and triangle arrays of the tree (leaf triangles inside the node array, a treetop selected from a host
+// copy of the nodes, the 8-wide form with its permuted triangles) are built again from the kept scene.
+static int update_resident_vertices(sthip_ctx* ctx, const VertexSource& src, sthip_refit_info* info, std::chrono::steady_clock::time_point t0) {
+  const std::string call = std::string(src.call) + ": ";
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const bool kept = ctx->kept.valid && ctx->kept.vertices.size() == ctx->vertex_count;
-  auto rebuild_from_kept = [&]() {  // (the kept vertices hold the new range already)
+  auto rebuild_from_kept = [&]() {  // (the kept vertices hold the new range already, or get the posed ranges back from the device here)
+    int rc = sync_kept_vertices(ctx);
+    if (rc != STHIP_OK) return rc;
     const sthip_scene_desc d = ctx->kept.desc();
     ctx->stats.full_rebuilds++;
-    const int rc = sthip_scene_upload(ctx, &d);
+    rc = sthip_scene_upload(ctx, &d);
     if (info) {
       info->rebuilt = 1;
       info->device_ms = ctx->stats.bvh_build_gpu_ms;
@@ -1623,9 +1740,21 @@ int sthip_scene_update_vertices(sthip_ctx* ctx, const sthip_PackedVertexData* ve
     }
     return rc;
   };
+  if (src.posed())
+    for (int k = 0; k < 2; k++)
+      if (!ctx->rig_ev[k]) HIP_TRY(ctx, hipEventCreate(&ctx->rig_ev[k]));
   if (ctx->embedded_resident || ctx->use_treetop || ctx->bvh.top_count || ctx->bvh.wide8_nodes || !ctx->wide8_host.empty()) {
-    if (!kept) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_vertices: this layout (embed_leaves, treetop, wide_bvh = 3) is not refitted and no scene was kept (keep_scene = 0): upload the scene again");
-    if (vertex_count) memcpy(ctx->kept.vertices.data() + first_vertex, vertices, (size_t)vertex_count * sizeof(sthip_PackedVertexData));
+    if (!kept) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "this layout (embed_leaves, treetop, wide_bvh = 3) is not refitted and no scene was kept (keep_scene = 0): upload the scene again");
+    if (src.posed()) {  // the kernel, then the rebuild reads its ranges back
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      HIP_TRY(ctx, drain_in_flight(ctx));
+      const int rc = pose_rigs(ctx, src.call);
+      if (rc != STHIP_OK) return rc;
+    } else if (src.vertex_count) {
+      const int rc = sync_kept_vertices(ctx);  // (before the host's records go in: they are the newer ones)
+      if (rc != STHIP_OK) return rc;
+      memcpy(ctx->kept.vertices.data() + src.first_vertex, src.vertices, (size_t)src.vertex_count * sizeof(sthip_PackedVertexData));
+    }
     return rebuild_from_kept();
   }
   // everything that can fail for want of memory happens before anything of the resident scene changes
@@ -1647,7 +1776,7 @@ int sthip_scene_update_vertices(sthip_ctx* ctx, const sthip_PackedVertexData* ve
   HIP_TRY(ctx, drain_in_flight(ctx));               // (sthip_render_async: their copies too, so that their tickets are complete)
   std::string err;
   if (!sthip::refit_prepare(ctx->refit, ctx->nodes.p, ctx->top.blas_nodes, ctx->refit_roots, ctx->top.blas_depth, ctx->tris.p, (uint32_t)ctx->bvh_tris, STHIP_MAX_EMITTER_BOUNDS, ctx->stream, err))
-    return fail(ctx, STHIP_ERR_HIP, "sthip_scene_update_vertices: " + err);
+    return fail(ctx, STHIP_ERR_HIP, call + err);
   // the instances' transforms, for the top level: the kept scene has them (sthip_scene_update_transforms keeps it current);
   // without one they are read back from the device
   const uint32_t n = ctx->instance_count;
@@ -1667,11 +1796,11 @@ int sthip_scene_update_vertices(sthip_ctx* ctx, const sthip_PackedVertexData* ve
   // ---- from here on the resident scene changes ----
   sthip::RefitResult res;
   float wide_ms = 0;
-  const int rc = refit_resident_scene(ctx, vertices, first_vertex, vertex_count, kept, xf, inv, res, wide_ms);
+  const int rc = refit_resident_scene(ctx, src, kept, xf, inv, res, wide_ms);
   if (rc != STHIP_OK) {
     // New triangles under old entries or an old top level would miss hits without a word. With a kept scene (it holds the new
-    // vertices by now) the scene is built again, as for the layouts above; without one no scene is resident any more, as after
-    // a failed sthip_scene_upload, and every call that needs one says so until the host uploads again.
+    // vertices by now, or reads the posed ones back) the scene is built again, as for the layouts above; without one no scene
+    // is resident any more, as after a failed sthip_scene_upload, and every call that needs one says so until the host uploads again.
     if (kept) return rebuild_from_kept();
     const std::string why = ctx->error;
     ctx->has_scene = false;
@@ -1680,12 +1809,136 @@ int sthip_scene_update_vertices(sthip_ctx* ctx, const sthip_PackedVertexData* ve
     return fail(ctx, rc, why + " (the resident scene was dropped half changed: upload the scene again)");
   }
   if (info) {
-    info->device_ms = res.gpu_ms + wide_ms;
+    float pose_ms = 0;  // (refit_boxes has waited for the stream: the events around k_animate have been reached)
+    if (src.posed()) (void)hipEventElapsedTime(&pose_ms, ctx->rig_ev[0], ctx->rig_ev[1]);
+    info->device_ms = pose_ms + res.gpu_ms + wide_ms;
     info->sah_cost = (float)res.sah_cost;
     info->sah_cost_at_build = (float)res.sah_cost_at_build;
     info->rebuilt = 0;
     info->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
+  return STHIP_OK;
+}
+
+int sthip_scene_update_vertices(sthip_ctx* ctx, const sthip_PackedVertexData* vertices, uint32_t first_vertex, uint32_t vertex_count, sthip_refit_info* info) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (info) memset(info, 0, sizeof(*info));
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_vertices before sthip_scene_upload");
+  if (!vertices) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_vertices: vertices is NULL");
+  if ((uint64_t)first_vertex + vertex_count > ctx->vertex_count)
+    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_vertices: the range ends past the vertex_count of the uploaded scene");
+  return update_resident_vertices(ctx, VertexSource{"sthip_scene_update_vertices", vertices, first_vertex, vertex_count}, info, t0);
+}
+
+// sthip.h: validated on the host, then the rest poses are taken on the device and targets and weights go up once. Everything is
+// made beside the resident rigs and swapped in at the end, so a refused or failed call leaves them as they were.
+int sthip_scene_set_rigs(sthip_ctx* ctx, const sthip_rig_desc* rigs, uint32_t rig_count) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  const std::string call = "sthip_scene_set_rigs: ";
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_set_rigs before sthip_scene_upload");
+  if (rig_count && !rigs) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "rigs is NULL");
+  std::vector<sthip_ctx::ResidentRig> next(rig_count);
+  size_t records = 0, target_records = 0, bones = 0;
+  for (uint32_t i = 0; i < rig_count; i++) {
+    const sthip_rig_desc& d = rigs[i];
+    const std::string rig = call + "rig " + std::to_string(i) + ": ";
+    if ((uint64_t)d.first_vertex + d.vertex_count > ctx->vertex_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, rig + "the range ends past the vertex_count of the uploaded scene");
+    if (d.blend_target_count > sthip::ANIMATE_MAX_TARGETS) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, rig + "blend_target_count is more than 4");
+    if (d.bone_count > sthip::ANIMATE_MAX_BONES) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, rig + "bone_count is more than 1024");
+    for (uint32_t t = 0; t < d.blend_target_count; t++)
+      if (!d.blend_targets[t]) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, rig + "a blend target that blend_target_count requires is NULL");
+    if (d.bone_count && !d.weights) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, rig + "bone_count > 0 but weights is NULL");
+    for (uint32_t j = 0; j < i; j++)
+      if (d.vertex_count && rigs[j].vertex_count && d.first_vertex < rigs[j].first_vertex + rigs[j].vertex_count && rigs[j].first_vertex < d.first_vertex + d.vertex_count)
+        return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, rig + "its range overlaps the range of rig " + std::to_string(j));
+    if (d.bone_count)
+      for (uint32_t v = 0; v < d.vertex_count; v++)
+        for (int k = 0; k < 4; k++)
+          if (d.weights[v].indices[k] >= d.bone_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, rig + "a bone index of vertex " + std::to_string(v) + " is not below bone_count");
+    sthip_ctx::ResidentRig& r = next[i];
+    r.first = d.first_vertex;
+    r.count = d.vertex_count;
+    r.target_count = d.blend_target_count;
+    r.bone_count = d.bone_count;
+    r.at = records;
+    r.targets_at = target_records;
+    r.bones_at = bones;
+    records += d.vertex_count;
+    target_records += (size_t)d.blend_target_count * d.vertex_count;
+    bones += d.bone_count;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!rig_count) {
+    drop_rigs(ctx);
+    return STHIP_OK;
+  }
+  DevBuf<sthip_PackedVertexData> rest, targets;
+  DevBuf<sthip_VertexWeight> weights;
+  DevBuf<sthip_TransformData> bone_buf;
+  HIP_TRY(ctx, rest.ensure(records));
+  HIP_TRY(ctx, targets.ensure(target_records));
+  HIP_TRY(ctx, weights.ensure(bones ? records : 0));  // (one place per rigged vertex, so that a rig's weights lie where its rest pose does)
+  HIP_TRY(ctx, bone_buf.ensure(bones));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (an animate call before this one wrote the records the rest pose is taken from)
+  for (uint32_t i = 0; i < rig_count; i++) {
+    const sthip_ctx::ResidentRig& r = next[i];
+    if (!r.count) continue;
+    const size_t bytes = (size_t)r.count * sizeof(sthip_PackedVertexData);
+    HIP_TRY(ctx, hipMemcpy(rest.p + r.at, ctx->vertices.p + r.first, bytes, hipMemcpyDeviceToDevice));
+    for (uint32_t t = 0; t < r.target_count; t++) HIP_TRY(ctx, hipMemcpy(targets.p + r.targets_at + (size_t)t * r.count, rigs[i].blend_targets[t], bytes, hipMemcpyHostToDevice));
+    if (r.bone_count) HIP_TRY(ctx, hipMemcpy(weights.p + r.at, rigs[i].weights, (size_t)r.count * sizeof(sthip_VertexWeight), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  std::swap(ctx->rig_rest.p, rest.p), std::swap(ctx->rig_rest.n, rest.n);
+  std::swap(ctx->rig_targets.p, targets.p), std::swap(ctx->rig_targets.n, targets.n);
+  std::swap(ctx->rig_weights.p, weights.p), std::swap(ctx->rig_weights.n, weights.n);
+  std::swap(ctx->rig_bones.p, bone_buf.p), std::swap(ctx->rig_bones.n, bone_buf.n);
+  ctx->rigs.swap(next);
+  ctx->rig_bones_host.assign(bones, sthip_TransformData{});
+  ctx->rig_factors.assign(rig_count, std::array<float, 4>{{0, 0, 0, 0}});
+  return STHIP_OK;
+}
+
+// sthip.h: the pose is checked and staged on the host; from there on the call is a vertex update whose records are written by
+// k_animate instead of coming up from the host.
+int sthip_scene_animate(sthip_ctx* ctx, const sthip_rig_pose* poses, uint32_t pose_count, sthip_refit_info* info) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (info) memset(info, 0, sizeof(*info));
+  const std::string call = "sthip_scene_animate: ";
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_animate before sthip_scene_upload");
+  if (ctx->rigs.empty()) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_animate before sthip_scene_set_rigs: no rigs are resident");
+  if (pose_count != ctx->rigs.size()) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "pose_count is not the rig_count of sthip_scene_set_rigs");
+  if (!poses) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "poses is NULL");
+  for (uint32_t i = 0; i < pose_count; i++) {
+    const sthip_ctx::ResidentRig& r = ctx->rigs[i];
+    const std::string rig = call + "pose " + std::to_string(i) + ": ";
+    for (uint32_t t = 0; t < r.target_count; t++)
+      if (!std::isfinite(poses[i].blend_factors[t])) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, rig + "a blend factor is not finite");
+    if (r.bone_count && !poses[i].bones) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, rig + "the rig has bones but bones is NULL");
+    for (uint32_t b = 0; b < r.bone_count; b++)
+      for (int e = 0; e < 12; e++)
+        if (!std::isfinite(poses[i].bones[b].m[e / 4][e % 4])) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, rig + "an entry of bone " + std::to_string(b) + " is not finite");
+  }
+  for (uint32_t i = 0; i < pose_count; i++) {  // (nothing is staged from a call that is refused)
+    const sthip_ctx::ResidentRig& r = ctx->rigs[i];
+    for (uint32_t t = 0; t < 4; t++) ctx->rig_factors[i][t] = t < r.target_count ? poses[i].blend_factors[t] : 0.0f;
+    if (r.bone_count) memcpy(ctx->rig_bones_host.data() + r.bones_at, poses[i].bones, (size_t)r.bone_count * sizeof(sthip_TransformData));
+  }
+  return update_resident_vertices(ctx, VertexSource{"sthip_scene_animate", nullptr, 0, 0}, info, t0);
+}
+
+int sthip_scene_read_vertices(sthip_ctx* ctx, uint32_t first_vertex, uint32_t vertex_count, sthip_PackedVertexData* out) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_vertices before sthip_scene_upload");
+  if ((uint64_t)first_vertex + vertex_count > ctx->vertex_count)
+    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_vertices: the range ends past the vertex_count of the uploaded scene");
+  if (!vertex_count) return STHIP_OK;
+  if (!out) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_vertices: out is NULL");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(out, ctx->vertices.p + first_vertex, (size_t)vertex_count * sizeof(sthip_PackedVertexData), hipMemcpyDeviceToHost));
   return STHIP_OK;
 }
 

@@ -17,6 +17,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -38,6 +39,10 @@
 // A library that cannot refit lacks this symbol (include/sthip.h): a weak reference, so that the host links against it
 // all the same and BDPT::update probes for the call before using it.
 #pragma weak sthip_scene_update_vertices
+// ... and one that cannot pose rigs on the device lacks these: Scene::update then poses them on the host
+#pragma weak sthip_scene_set_rigs
+#pragma weak sthip_scene_animate
+#pragma weak sthip_scene_read_vertices
 #include "../../include/sthip_detmath.h"  // det_f16tof32: export_hdr of a half frame
 
 namespace stm {
@@ -458,7 +463,57 @@ struct Mesh {
   std::vector<float2> uvs;
   std::vector<uint32_t> indices;
   uint32_t index_stride = 4;  // 2 or 4 bytes
+  // a rig over the mesh (MeshPrimitive::set_rig / set_pose): positions / normals above are its rest pose
+  struct BlendTarget {
+    std::vector<float3> positions, normals;
+  };
+  std::vector<BlendTarget> blend_targets;  // at most 4
+  std::vector<sthip_VertexWeight> weights;  // one per vertex, or none (bone_count = 0)
+  uint32_t bone_count = 0;
+  bool posed = false;  // set_pose was called: until then the mesh is shown in its rest pose, bit for bit
+  float blend_factors[4] = {0, 0, 0, 0};
+  std::vector<TransformData> bones;
+  bool rigged() const { return !blend_targets.empty() || bone_count; }
 };
+// One vertex of a rig in a pose, on the host: the arithmetic of sthip_scene_animate (include/sthip.h; compile with
+// -ffp-contract=off), for a library that lacks the call and for drivers that upload posed meshes in full.
+inline PackedVertexData pose_rig_vertex(PackedVertexData r, const PackedVertexData* const* targets, uint32_t target_count, size_t i, const float factors[4], const sthip_VertexWeight* weights,
+                                        const TransformData* bones, uint32_t bone_count) {
+  float p[3] = {r.position[0], r.position[1], r.position[2]}, n[3] = {r.normal[0], r.normal[1], r.normal[2]};
+  if (target_count) {
+    const float b[4] = {target_count > 0 ? factors[0] : 0.f, target_count > 1 ? factors[1] : 0.f, target_count > 2 ? factors[2] : 0.f, target_count > 3 ? factors[3] : 0.f};
+    const float f = std::fmax(0.f, 1.f - (((std::fabs(b[0]) + std::fabs(b[1])) + std::fabs(b[2])) + std::fabs(b[3])));
+    for (int a = 0; a < 3; a++) p[a] = f * p[a], n[a] = f * n[a];
+    for (uint32_t k = 0; k < target_count; k++)
+      for (int a = 0; a < 3; a++) {
+        const float tp = b[k] * targets[k][i].position[a], tn = b[k] * targets[k][i].normal[a];
+        p[a] = p[a] + tp;
+        n[a] = n[a] + tn;
+      }
+    const float d0 = n[0] * n[0], d1 = n[1] * n[1], d2 = n[2] * n[2];
+    const float inv = 1.0f / std::sqrt((d0 + d1) + d2);
+    for (int a = 0; a < 3; a++) n[a] = n[a] * inv;
+  }
+  if (bone_count) {
+    float m[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    for (int j = 0; j < 4; j++)
+      for (int row = 0; row < 3; row++)
+        for (int c = 0; c < 4; c++) {
+          const float t = bones[weights[i].indices[j]].m[row][c] * weights[i].weights[j];
+          m[row][c] = m[row][c] + t;
+        }
+    float q[3], w[3];
+    for (int row = 0; row < 3; row++) {
+      const float a0 = m[row][0] * p[0], a1 = m[row][1] * p[1], a2 = m[row][2] * p[2];
+      q[row] = ((a0 + a1) + a2) + m[row][3];
+      const float c0 = m[row][0] * n[0], c1 = m[row][1] * n[1], c2 = m[row][2] * n[2];
+      w[row] = (c0 + c1) + c2;
+    }
+    for (int a = 0; a < 3; a++) p[a] = q[a], n[a] = w[a];
+  }
+  for (int a = 0; a < 3; a++) r.position[a] = p[a], r.normal[a] = n[a];
+  return r;
+}
 struct MeshPrimitive {
   component_ptr<Material> mMaterial;
   component_ptr<Mesh> mMesh;
@@ -471,6 +526,36 @@ struct MeshPrimitive {
     mMesh->positions = std::move(positions);
     if (!normals.empty()) mMesh->normals = std::move(normals);
     if (!uvs.empty()) mMesh->uvs = std::move(uvs);
+  }
+  // A rig over the mesh (kernels/anim.hlsl): up to 4 blend targets (positions and normals, one per vertex) and four bone
+  // weights per vertex over bone_count bones (none: blend shapes only). The mesh's own vertices are the rest pose. With a
+  // library that has sthip_scene_animate the rig goes to the device once after the next upload and set_pose then costs a
+  // frame its bones and factors only (BDPT::update: last_update_was_vertices_only()); without it the host poses the mesh.
+  void set_rig(std::vector<Mesh::BlendTarget> targets, std::vector<sthip_VertexWeight> weights = {}, uint32_t bone_count = 0) {
+    if (!mMesh) throw std::invalid_argument("MeshPrimitive::set_rig: no mesh");
+    const size_t n = mMesh->positions.size();
+    if (targets.size() > 4) throw std::invalid_argument("MeshPrimitive::set_rig: more than 4 blend targets");
+    for (const auto& t : targets)
+      if (t.positions.size() != n || t.normals.size() != n) throw std::invalid_argument("MeshPrimitive::set_rig: a blend target has another vertex count than the mesh");
+    if (bone_count > 1024) throw std::invalid_argument("MeshPrimitive::set_rig: more than 1024 bones");
+    if ((bone_count != 0) != !weights.empty() || (bone_count && weights.size() != n)) throw std::invalid_argument("MeshPrimitive::set_rig: one weight record per vertex if and only if there are bones");
+    for (const auto& w : weights)
+      for (uint32_t index : w.indices)
+        if (index >= bone_count) throw std::invalid_argument("MeshPrimitive::set_rig: a bone index is not below bone_count");
+    mMesh->blend_targets = std::move(targets);
+    mMesh->weights = std::move(weights);
+    mMesh->bone_count = bone_count;
+    mMesh->posed = false;
+    mMesh->bones.clear();
+  }
+  // The pose of the rig: factors of the blend targets (absent ones ignored) and bone_count final matrices (the host has
+  // applied hierarchy and keyframes). Scene::mark_dirty() tells the scene, as after any other edit.
+  void set_pose(const std::array<float, 4>& factors, std::vector<TransformData> bones = {}) {
+    if (!mMesh || !mMesh->rigged()) throw std::invalid_argument("MeshPrimitive::set_pose: the mesh has no rig");
+    if (bones.size() != mMesh->bone_count) throw std::invalid_argument("MeshPrimitive::set_pose: the rig has another bone count");
+    for (int k = 0; k < 4; k++) mMesh->blend_factors[k] = factors[k];
+    mMesh->bones = std::move(bones);
+    mMesh->posed = true;
   }
 };
 struct SpherePrimitive {  // Scene.hpp:34-37
@@ -644,6 +729,19 @@ class Scene {
     uint32_t mEnvironmentMaterialAddress = ~0u;
     uint32_t mMaterialCount = 0;
     uint32_t mEmissivePrimitiveCount = 0;
+    // rigs posed on the device (Scene::pose_on_device()): mVertices holds their rest poses; mPoses[i] belongs to mRigs[i]
+    struct Rig {
+      uint32_t first_vertex = 0, vertex_count = 0, bone_count = 0;
+      std::vector<std::vector<PackedVertexData>> targets;
+      std::vector<sthip_VertexWeight> weights;
+    };
+    struct Pose {
+      bool posed = false;
+      float factors[4] = {0, 0, 0, 0};
+      std::vector<TransformData> bones;
+    };
+    std::vector<Rig> mRigs;
+    std::vector<Pose> mPoses;
     sthip_scene_desc desc() const {
       sthip_scene_desc d{};
       d.gVertices = mVertices.data();
@@ -677,6 +775,15 @@ class Scene {
   Node& node() const { return mNode; }
   const std::shared_ptr<SceneData>& data() const { return mSceneData; }
   void mark_dirty() { mDirty = true; }
+  // true (the default with a library that has sthip_scene_animate): rigged meshes are packed in their rest pose with their
+  // rigs beside them, and BDPT::update poses them on the device. false: update() below poses them on the host, and everything
+  // downstream sees a deformed mesh like any other (the multi-device driver, which uploads deformed meshes in full).
+  bool pose_on_device() const { return mPoseOnDevice; }
+  void set_pose_on_device(bool on) {
+    on = on && sthip_scene_set_rigs && sthip_scene_animate;
+    if (on != mPoseOnDevice) mDirty = true;
+    mPoseOnDevice = on;
+  }
 
   // Scene.cpp:299-684 for MeshPrimitive instances: same traversal order (breadth-first), same packing
   void update(CommandBuffer&, float) {
@@ -713,6 +820,33 @@ class Scene {
           if (i < mesh.normals.size()) v.normal[0] = mesh.normals[i].x, v.normal[1] = mesh.normals[i].y, v.normal[2] = mesh.normals[i].z;
           if (i < mesh.uvs.size()) v.u = mesh.uvs[i].x, v.v = mesh.uvs[i].y;
           sd->mVertices.push_back(v);
+        }
+        if (mesh.rigged() && (mPoseOnDevice || mesh.posed)) {
+          const uint32_t first = meshit->second.first, count = (uint32_t)mesh.positions.size();
+          SceneData::Rig rig;
+          rig.first_vertex = first, rig.vertex_count = count, rig.bone_count = mesh.bone_count;
+          for (const auto& t : mesh.blend_targets) {
+            rig.targets.emplace_back(count, PackedVertexData{});
+            for (uint32_t i = 0; i < count; i++) {
+              PackedVertexData& v = rig.targets.back()[i];
+              v.position[0] = t.positions[i].x, v.position[1] = t.positions[i].y, v.position[2] = t.positions[i].z;
+              v.normal[0] = t.normals[i].x, v.normal[1] = t.normals[i].y, v.normal[2] = t.normals[i].z;
+            }
+          }
+          rig.weights = mesh.weights;
+          if (mPoseOnDevice) {
+            SceneData::Pose pose;
+            pose.posed = mesh.posed;
+            std::memcpy(pose.factors, mesh.blend_factors, sizeof(pose.factors));
+            pose.bones = mesh.bones;
+            sd->mRigs.push_back(std::move(rig));
+            sd->mPoses.push_back(std::move(pose));
+          } else {  // posed here, with the arithmetic of the device's kernel
+            const PackedVertexData* targets[4] = {nullptr, nullptr, nullptr, nullptr};
+            for (size_t k = 0; k < rig.targets.size(); k++) targets[k] = rig.targets[k].data();
+            for (uint32_t i = 0; i < count; i++)
+              sd->mVertices[first + i] = pose_rig_vertex(sd->mVertices[first + i], targets, (uint32_t)rig.targets.size(), i, mesh.blend_factors, rig.weights.data(), mesh.bones.data(), rig.bone_count);
+          }
         }
         for (uint32_t idx : mesh.indices) {
           if (mesh.index_stride == 2) {
@@ -820,6 +954,7 @@ class Scene {
   Node& mNode;
   std::shared_ptr<SceneData> mSceneData;
   bool mDirty = true;
+  bool mPoseOnDevice = sthip_scene_set_rigs && sthip_scene_animate;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -965,13 +1100,34 @@ class BDPT {
     // are still right, as the reference's cached BLASes are (Scene.cpp:435-459); rebuild the top level only.
     bool updated = false;
     mLastUpdateWasVerticesOnly = false;
-    if (mBoundData && same_geometry(*mBoundData, *scene->data())) {
+    const Scene::SceneData& sd = *scene->data();
+    const bool rigs = !sd.mRigs.empty();  // (packed only with a library that has the calls: Scene::pose_on_device())
+    if (rigs && mRigsResident && mBoundData && same_geometry(*mBoundData, sd) && !same_poses(*mBoundData, sd)) {
+      // Only poses changed (and perhaps transforms): the rigs are resident, the bones and factors go to the device and the
+      // meshes are posed and the tree refitted there. A layout the library cannot serve without a kept scene answers UNSUPPORTED: upload.
+      const bool moved = !same_bytes(mBoundData->mInstanceTransforms, sd.mInstanceTransforms) || !same_bytes(mBoundData->mInstanceInverseTransforms, sd.mInstanceInverseTransforms) ||
+                         !same_bytes(mBoundData->mInstanceMotionTransforms, sd.mInstanceMotionTransforms);
+      int rc = animate(sd);
+      if (rc == STHIP_OK && moved) {
+        rc = sthip_scene_update_transforms(mCtx, d.gInstanceTransforms, d.gInstanceInverseTransforms, d.gInstanceMotionTransforms, d.instance_count);
+        if (rc != STHIP_OK && rc != STHIP_ERR_UNSUPPORTED) throw std::runtime_error(std::string("sthip_scene_update_transforms: ") + sthip_last_error(mCtx));
+      }
+      if (rc == STHIP_OK) {
+        mLastUpdateWasVerticesOnly = !moved;
+        mLastUpdateWasTransformsOnly = false;
+        mBound = scene->data().get();
+        mBoundData = scene->data();
+        mPushConstants.gLightCount = d.light_count;
+        mPushConstants.gEnvironmentMaterialAddress = sd.mEnvironmentMaterialAddress;
+        return;
+      }
+    } else if (mBoundData && same_geometry(*mBoundData, *scene->data()) && (!rigs || (mRigsResident && same_poses(*mBoundData, sd)))) {
       const int rc = sthip_scene_update_transforms(mCtx, d.gInstanceTransforms, d.gInstanceInverseTransforms, d.gInstanceMotionTransforms, d.instance_count);
       if (rc == STHIP_OK)
         updated = true;
       else if (rc != STHIP_ERR_UNSUPPORTED)
         throw std::runtime_error(std::string("sthip_scene_update_transforms: ") + sthip_last_error(mCtx));
-    } else if (mRefitDeformedMeshes && mBoundData && sthip_scene_update_vertices && same_topology(*mBoundData, *scene->data())) {
+    } else if (mRefitDeformedMeshes && mBoundData && sthip_scene_update_vertices && !rigs && same_topology(*mBoundData, *scene->data())) {  // (a new rest pose of a rig: an upload)
       // A mesh deformed (same indices, instances, materials; only the contents of gVertices differ): the range that changed
       // goes to the device and the resident bottom levels are refitted there (the reference rebuilds the BLAS of a dirty mesh,
       // Scene.cpp:345,435-459). A layout the library does not refit without a kept scene answers UNSUPPORTED: upload.
@@ -1001,6 +1157,25 @@ class BDPT {
     }
     mLastUpdateWasTransformsOnly = updated;
     if (!updated && sthip_scene_upload(mCtx, &d) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_upload: ") + sthip_last_error(mCtx));
+    if (!updated) {  // the upload dropped the rigs: they go up once, over the rest poses that just went up, and take their pose
+      mRigsResident = false;
+      if (rigs) {
+        std::vector<sthip_rig_desc> descs(sd.mRigs.size());
+        bool posed = false;
+        for (size_t i = 0; i < descs.size(); i++) {
+          const Scene::SceneData::Rig& r = sd.mRigs[i];
+          descs[i] = sthip_rig_desc{};
+          descs[i].first_vertex = r.first_vertex, descs[i].vertex_count = r.vertex_count;
+          descs[i].blend_target_count = (uint32_t)r.targets.size(), descs[i].bone_count = r.bone_count;
+          for (size_t k = 0; k < r.targets.size(); k++) descs[i].blend_targets[k] = r.targets[k].data();
+          descs[i].weights = r.bone_count ? r.weights.data() : nullptr;
+          posed = posed || sd.mPoses[i].posed;
+        }
+        if (sthip_scene_set_rigs(mCtx, descs.data(), (uint32_t)descs.size()) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_set_rigs: ") + sthip_last_error(mCtx));
+        mRigsResident = true;
+        if (posed && animate(sd) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_animate: ") + sthip_last_error(mCtx));
+      }
+    }
     mBound = scene->data().get();
     mBoundData = scene->data();
     mPushConstants.gLightCount = d.light_count;                    // BDPT.cpp:396
@@ -1281,9 +1456,49 @@ class BDPT {
   static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
     return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
   }
+  bool mRigsResident = false;  // the rigs of mBoundData are on the device (sthip_scene_set_rigs after the last upload)
+  // sthip_scene_animate with the poses of `sd`. The call poses every rig; one whose mesh never got a pose is sent zero factors
+  // and identity bones (its positions stay the rest pose's; its normals are normalised again if it has blend targets).
+  int animate(const Scene::SceneData& sd) {
+    std::vector<sthip_rig_pose> poses(sd.mPoses.size());
+    std::vector<std::vector<TransformData>> identity(sd.mPoses.size());
+    for (size_t i = 0; i < poses.size(); i++) {
+      poses[i] = sthip_rig_pose{};
+      std::memcpy(poses[i].blend_factors, sd.mPoses[i].factors, sizeof(poses[i].blend_factors));
+      const uint32_t bone_count = sd.mRigs[i].bone_count;
+      if (sd.mPoses[i].bones.size() == bone_count) {
+        poses[i].bones = bone_count ? sd.mPoses[i].bones.data() : nullptr;
+      } else {  // (never posed: identity bones)
+        TransformData I{};
+        I.m[0][0] = I.m[1][1] = I.m[2][2] = 1;
+        identity[i].assign(bone_count, I);
+        poses[i].bones = identity[i].data();
+      }
+    }
+    const int rc = sthip_scene_animate(mCtx, poses.data(), (uint32_t)poses.size(), nullptr);
+    if (rc != STHIP_OK && rc != STHIP_ERR_UNSUPPORTED) throw std::runtime_error(std::string("sthip_scene_animate: ") + sthip_last_error(mCtx));
+    return rc;
+  }
+  static bool same_poses(const Scene::SceneData& a, const Scene::SceneData& b) {
+    if (a.mPoses.size() != b.mPoses.size()) return false;
+    for (size_t i = 0; i < a.mPoses.size(); i++)
+      if (a.mPoses[i].posed != b.mPoses[i].posed || std::memcmp(a.mPoses[i].factors, b.mPoses[i].factors, sizeof(a.mPoses[i].factors)) || !same_bytes(a.mPoses[i].bones, b.mPoses[i].bones)) return false;
+    return true;
+  }
+  static bool same_rigs(const Scene::SceneData& a, const Scene::SceneData& b) {
+    if (a.mRigs.size() != b.mRigs.size()) return false;
+    for (size_t i = 0; i < a.mRigs.size(); i++) {
+      const Scene::SceneData::Rig &x = a.mRigs[i], &y = b.mRigs[i];
+      if (x.first_vertex != y.first_vertex || x.vertex_count != y.vertex_count || x.bone_count != y.bone_count || x.targets.size() != y.targets.size() || !same_bytes(x.weights, y.weights)) return false;
+      for (size_t k = 0; k < x.targets.size(); k++)
+        if (!same_bytes(x.targets[k], y.targets[k])) return false;
+    }
+    return true;
+  }
   static bool same_geometry(const Scene::SceneData& a, const Scene::SceneData& b) { return same_bytes(a.mVertices, b.mVertices) && same_topology(a, b); }
   // everything equal except the CONTENTS of the vertex array (and the transforms, which have update calls of their own)
   static bool same_topology(const Scene::SceneData& a, const Scene::SceneData& b) {
+    if (!same_rigs(a, b)) return false;
     if (a.mVertices.size() != b.mVertices.size() || !same_bytes(a.mIndices, b.mIndices) || !same_bytes(a.mInstances, b.mInstances) || !same_bytes(a.mMaterialData, b.mMaterialData) ||
         !same_bytes(a.mLightInstanceMap, b.mLightInstanceMap) || !same_bytes(a.mDistributionData, b.mDistributionData))
       return false;

@@ -219,6 +219,10 @@ class MultiDeviceBDPT : public BDPT {
   void update(CommandBuffer& cb, float dt) override {
     auto scene = mNode.find_in_ancestor<Scene>();
     if (!scene) scene = mNode.root().find_in_descendants<Scene>();
+    if (scene && scene->pose_on_device()) {  // rigs are posed on the host here: a posed mesh is a deformed mesh, uploaded in full on every rank
+      scene->set_pose_on_device(false);
+      scene->update(cb, dt);
+    }
     if (!scene || !scene->data() || scene->data().get() == mBound) return;
     flush();
     BDPT::update(cb, dt);  // rank 0, and the bookkeeping (mBound, light count, environment)

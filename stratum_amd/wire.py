@@ -11,6 +11,7 @@ import numpy as np
 InstanceData = np.dtype([("packed", "<u4", (4,))])
 PackedVertexData = np.dtype([("position", "<f4", (3,)), ("u", "<f4"), ("normal", "<f4", (3,)), ("v", "<f4")])
 TransformData = np.dtype([("m", "<f4", (3, 4))])
+VertexWeight = np.dtype([("weights", "<f4", (4,)), ("indices", "<u4", (4,))])  # sthip_VertexWeight (kernels/anim.hlsl:6-9)
 ProjectionData = np.dtype(
     [
         ("scale", "<f4", (2,)),
@@ -44,7 +45,7 @@ MaterialRecord = np.dtype(
 Ray = np.dtype([("origin", "<f4", (3,)), ("tmin", "<f4"), ("direction", "<f4", (3,)), ("tmax", "<f4")])
 Hit = np.dtype([("t", "<f4"), ("b1", "<f4"), ("b2", "<f4"), ("instance_primitive_index", "<u4")])
 
-assert InstanceData.itemsize == 16 and PackedVertexData.itemsize == 32 and TransformData.itemsize == 48
+assert InstanceData.itemsize == 16 and PackedVertexData.itemsize == 32 and TransformData.itemsize == 48 and VertexWeight.itemsize == 32
 assert ViewData.itemsize == 48 and VisibilityInfo.itemsize == 8 and DepthInfo.itemsize == 16
 assert ShadingData.itemsize == 48 and MaterialRecord.itemsize == 72 and Ray.itemsize == 32 and Hit.itemsize == 16
 
@@ -253,6 +254,25 @@ class RefitInfo(C.Structure):  # sthip_refit_info
 
 REFIT_INFO_BYTES = 24  # sizeof(sthip_refit_info), include/sthip.h
 assert C.sizeof(RefitInfo) == REFIT_INFO_BYTES
+
+
+class RigDesc(C.Structure):  # sthip_rig_desc
+    _fields_ = [
+        ("first_vertex", C.c_uint32),
+        ("vertex_count", C.c_uint32),
+        ("blend_target_count", C.c_uint32),
+        ("bone_count", C.c_uint32),
+        ("blend_targets", C.c_void_p * 4),
+        ("weights", C.c_void_p),
+    ]
+
+
+class RigPose(C.Structure):  # sthip_rig_pose
+    _fields_ = [("blend_factors", C.c_float * 4), ("bones", C.c_void_p)]
+
+
+RIG_DESC_BYTES, RIG_POSE_BYTES, VERTEX_WEIGHT_BYTES = 56, 24, 32  # sizeof of the C structs, include/sthip.h and sthip_wire.h
+assert C.sizeof(RigDesc) == RIG_DESC_BYTES and C.sizeof(RigPose) == RIG_POSE_BYTES
 
 
 def ptr(a):
