@@ -520,11 +520,13 @@ int sthip_measure_ceiling(sthip_ctx* ctx, uint32_t kind, double* gbytes_per_s);
  *
  * An option that DOES change results: "half_color_precision" (0 = default, 1; other values are refused). While it is 1
  * the colour images of sthip_render (gRadiance, gAlbedo, gDebugImage; see sthip_outputs), sthip_tonemap (gInput,
- * gAlbedo, gOutput), sthip_accumulate (gRadiance, gAlbedo, gPrevAccumColor, gAccumColor), sthip_image_compare (both
+ * gAlbedo, gOutput), sthip_accumulate (gRadiance, gAlbedo, gPrevAccumColor, gAccumColor), sthip_denoise_filter (gAccumColor, gFilterImages), sthip_image_compare (both
  * images) and sthip_assemble_tiles (8-byte entries) are RGBA16F; every other buffer keeps its type. It takes effect at
  * the next call. A library without the feature answers STHIP_ERR_INVALID_ARGUMENT (unknown option): a host may probe
  * with it.
- * "output_ring" (1..8, default 2): see sthip_render_async. */
+ * "output_ring" (1..8, default 2): see sthip_render_async.
+ * "denoise_block" (0 = default, 1): the lanes of a block of sthip_denoise_filter's kernels cover 32x8 or 16x16 pixels; never
+ * changes results. */
 int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value);
 
 /* ---- after the path: display transform, image metric, HDR export ---- */
@@ -562,6 +564,96 @@ typedef struct sthip_accumulate_desc {
   float* gAccumMoments;                        /* out, RG32F */
 } sthip_accumulate_desc;
 int sthip_accumulate(sthip_ctx* ctx, const sthip_accumulate_desc* desc);
+
+/* FilterKernelType, src/Shaders/filter_type.h:8-16 */
+enum {
+  STHIP_FILTER_ATROUS = 0,
+  STHIP_FILTER_BOX3,
+  STHIP_FILTER_BOX5,
+  STHIP_FILTER_SUBSAMPLED,
+  STHIP_FILTER_BOX3_SUBSAMPLED,
+  STHIP_FILTER_BOX5_SUBSAMPLED,
+  STHIP_FILTER_TYPE_COUNT
+};
+
+/* The filter of the denoiser: what Denoiser::denoise dispatches after the temporal accumulation when mAtrousIterations > 0
+ * (src/Node/Denoiser.cpp:215-265): estimate_variance (kernels/estimate_variance.hlsl:51-103) into gFilterImages[0], then
+ * `iterations` passes of the edge-stopping filter (kernels/atrous.hlsl:211-262), pass i reading gFilterImages[i % 2] and
+ * writing gFilterImages[(i + 1) % 2] with step 1 << i, and copy_rgb (:266-271) after pass history_tap - 1. The result
+ * upstream returns is gFilterImages[iterations % 2]; after the call both images hold what upstream's ping-pong images hold.
+ * Pixels outside every view are written by no pass (copy_rgb alone covers the whole extent).
+ *
+ * THE ARITHMETIC CONTRACT of the three passes. Everything is binary32, unfused, in the order written in the shaders
+ * (include/sthip_detmath.h), with these decisions:
+ *   max / saturate   max(a, K) with a constant K is `a > K ? a : K` (a NaN gives K); saturate(a) is `a > 0 ? (a < 1 ? a : 1) : 0`.
+ *   length           length(v) of a float2 is sqrtf(v.x * v.x + v.y * v.y).
+ *   powers           pow(d, 256) (atrous) and pow(d, 128) (variance) of the clamped normal dot product d are 8 and 7
+ *                    successive squarings d = d * d. They are not det_powf: the base may be 0.
+ *   exponential      a = -(w_l * w_l) - w_z (atrous) or a = -w_z (variance). A NaN `a` skips the tap. a < -87 makes w = 0:
+ *                    the tap adds nothing (it is skipped: nothing is multiplied by that 0). Otherwise e = det_expf(a) and
+ *                    w = e * kernel_weight * w_n, multiplied left to right (variance: w = e * w_n); then the shader's own
+ *                    isinf(w) || isnan(w) skip.
+ *   constants        kernel weights are the binary32 quotients of the literals: 2.0f/3.0f, 1.0f/6.0f, 4.0f/9.0f, 1.0f/9.0f,
+ *                    1.0f/36.0f; the boxes and the subsampled kernel weigh every tap 1; compute_sigma_luminance's table
+ *                    is {{1/4, 1/8}, {1/8, 1/16}}.
+ *   helpers          luminance is dot(rgb, (0.2126, 0.7152, 0.0722)) added left to right; normals are bitfield.h's octahedral
+ *                    unpack (det_f16tof32, the fold for z < 0, one division and three multiplies to normalise); a pixel's view
+ *                    is the first whose [image_min, image_max) holds it, test_inside the same test — all as sthip_accumulate.
+ *   tap order        sums are taken in the source order of atrous(), box3(), box5(), subsampled() (atrous.hlsl:121-207) and in
+ *                    the yy-outer, xx-inner loops of estimate_variance and compute_sigma_luminance.
+ *   accumulation     sum_color += color_p * (w, w, w, w * w); the result is sum_color * (1/sum_w, 1/sum_w, 1/sum_w,
+ *                    (1/sum_w) * (1/sum_w)) with one division 1/sum_w.
+ * Kept as upstream wrote it:
+ *   - tap() receives an offset already multiplied by the step and multiplies it by the step again inside w_z's length(...)
+ *     (atrous.hlsl:109). The product offset * step * step is taken as a SIGNED integer before the conversion to float (the
+ *     unsigned reading of int * uint would make the filter asymmetric).
+ *   - compute_sigma_luminance weighs the centre with kernel[1][1] = 1/16 (atrous.hlsl:87), and its 3x3 footprint does not
+ *     scale with the step.
+ *   - copy_rgb always reads gFilterImages[0], whichever image the tapped iteration wrote (atrous.hlsl:270).
+ *   - estimate_variance maps the centre's instance index through gInstanceIndexMap but compares it with a neighbour of the
+ *     CURRENT frame (estimate_variance.hlsl:83). An index beyond instance_count maps to 0xFFFFFFFF (matches nothing).
+ *   - pixels whose z is infinite (misses: the renderer writes inf) go through sigma_l and the division by sum_w = 1 only.
+ *   - a tap whose w is 0 through w_n = 0 is NOT skipped: 0 * (a NaN or inf colour) reaches the sum, as upstream.
+ * Upstream defect, noted only: Denoiser.cpp:225 pushes the TEMPORAL pipeline's constants to the variance dispatch, so
+ * gVarianceBoostLength never reaches the shader (and gHistoryLimit does only because the offsets coincide). Here
+ * variance_boost_length is an explicit field, 0 = off.
+ *
+ * gViews is always a host pointer. Host form (device_ptrs = 0): the inputs are staged, both filter images are copied back,
+ * gAccumColor too when the tap fired (1 <= history_tap <= iterations), and the call returns synchronised. Device form: the
+ * passes are only enqueued on the context's stream, one after another (the kernel boundary is their only synchronisation);
+ * with up to 4 views nothing is staged or waited for. The filter taps read a per-pixel guide image {n.x, n.y, n.z, z} (16 B:
+ * the unpacked normal and the depth, exactly the values named above) that estimate_variance writes; it is scratch the context
+ * owns and the one allocation the device form can make: it grows only when the extent exceeds every earlier call's.
+ * With "half_color_precision" gAccumColor and both filter images are RGBA16F, as upstream's are (Denoiser.cpp:160-163): every
+ * pass reads halves exactly, computes in binary32 and rounds to nearest even at its one store; gAccumMoments, gVisibility and
+ * gDepth keep their types.
+ * Refused with STHIP_ERR_INVALID_ARGUMENT, the message naming the field: a NULL gViews / gVisibility / gDepth / gAccumColor /
+ * gAccumMoments / gFilterImages[k], view_count = 0, iterations outside 1..8, filter_type >= 6, an empty extent or one of more
+ * than 2^31 - 1 pixels, a view of gViews whose [image_min, image_max) leaves the extent (the taps are bounded by their view). */
+typedef struct sthip_denoise_desc {
+  uint32_t width, height;
+  uint32_t view_count;         /* gViewCount */
+  uint32_t device_ptrs;
+  uint32_t instance_count;     /* entries of gInstanceIndexMap */
+  uint32_t iterations;         /* mAtrousIterations, 1..8; pass i has gIteration = i, gStepSize = 1 << i */
+  uint32_t filter_type;        /* specialisation constant gFilterKernelType (STHIP_FILTER_*; upstream's default is BOX3) */
+  uint32_t history_tap;        /* mHistoryTap: copy_rgb after pass history_tap - 1; 0 or > iterations: never */
+  float history_limit;         /* gHistoryLimit of estimate_variance: pixels with at least this many samples take their own moments */
+  float variance_boost_length; /* gVarianceBoostLength, 0 = off */
+  float sigma_luminance_boost; /* gSigmaLuminanceBoost (upstream's default: 3, Denoiser.cpp:75) */
+  uint32_t pad_;
+  const sthip_ViewData* gViews;
+  const sthip_VisibilityInfo* gVisibility;
+  const sthip_DepthInfo* gDepth;
+  const uint32_t* gInstanceIndexMap; /* NULL = identity */
+  float* gAccumColor;                /* in; out as well when the tap fires. RGBA32F (RGBA16F) */
+  const float* gAccumMoments;        /* in, RG32F */
+  float* gFilterImages[2];           /* out, RGBA32F (RGBA16F): rgb = colour, a = variance */
+  /* optional, host memory, 10 floats, for measurements: when not NULL every pass is bracketed by events and the call waits
+   * for them: milliseconds of [0] estimate_variance, [1 + i] pass i, [9] copy_rgb (0 for passes that did not run) */
+  float* pass_ms;
+} sthip_denoise_desc;
+int sthip_denoise_filter(sthip_ctx* ctx, const sthip_denoise_desc* desc);
 
 /* TonemapMode, src/Shaders/tonemap.h:8-21 */
 enum {

@@ -43,6 +43,7 @@ EXPORTS = [
     "sthip_pack_tiles",
     "sthip_radiance_to_sums",
     "sthip_accumulate",
+    "sthip_denoise_filter",
     "sthip_tonemap",
     "sthip_image_compare",
     "sthip_write_hdr",
@@ -150,6 +151,8 @@ def lib():
     L.sthip_pack_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     L.sthip_accumulate.restype = C.c_int
     L.sthip_accumulate.argtypes = [C.c_void_p, C.POINTER(wire.AccumulateDesc)]
+    L.sthip_denoise_filter.restype = C.c_int
+    L.sthip_denoise_filter.argtypes = [C.c_void_p, C.POINTER(wire.DenoiseDesc)]
     L.sthip_tonemap.restype = C.c_int
     L.sthip_tonemap.argtypes = [C.c_void_p, C.POINTER(wire.TonemapDesc)]
     L.sthip_image_compare.restype = C.c_int

@@ -20,6 +20,7 @@
 
 #include "../../include/sthip.h"
 #include "animate.h"
+#include "denoise.h"
 #include "bvh_build.h"
 #include "kernel_instances.h"  // kernels.h + the instantiations that live in shade_*.hip / trace_kernels.hip
 #include "post.h"
@@ -339,6 +340,8 @@ struct sthip_ctx {
   uint32_t emitter_count = 0;  // 0: not applicable to this scene (no or too many emissive triangle instances)
   DevBuf<unsigned long long> qctl;  // queue control lines (queue_ctl)
   DevBuf<uint32_t> post_scratch;  // maxima / metric accumulator of post.h
+  DevBuf<float4> denoise_guide;   // sthip_denoise_filter: {n.x, n.y, n.z, z} per pixel, grows with the largest extent seen
+  uint32_t denoise_block = 0;     // "denoise_block": 0 = 32x8 lanes per block, 1 = 16x16
   DevBuf<sthip_ray> ray_staging;  // sthip_trace_rays with host pointers
   DevBuf<sthip_hit> hit_staging;
   DevBuf<float4> out_radiance, out_albedo;  // staging of the colour images (out_debug too): color_bytes() per entry, so 16 B entries hold 1 or 2
@@ -751,6 +754,9 @@ int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value) {
       release_ring(ctx);
       ctx->output_ring = (uint32_t)value;
     }
+  } else if (!strcmp(name, "denoise_block")) {
+    if (value != 0 && value != 1) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "denoise_block: 0 (32x8) or 1 (16x16)");
+    ctx->denoise_block = (uint32_t)value;
   } else if (!strcmp(name, "inner_min_lanes"))
     ctx->inner_min_lanes = (uint32_t)std::min<int64_t>(64, std::max<int64_t>(1, value));
   else
@@ -3170,6 +3176,114 @@ int sthip_accumulate(sthip_ctx* ctx, const sthip_accumulate_desc* d) {
   const hipError_t es = staged.empty() ? hipSuccess : hipStreamSynchronize(st);
   release();
   if (e != hipSuccess || es != hipSuccess) return fail(ctx, STHIP_ERR_HIP, std::string("sthip_accumulate: ") + hipGetErrorString(e != hipSuccess ? e : es));
+  return STHIP_OK;
+}
+
+// The filter of the denoiser (denoise.hip): estimate_variance, the a-trous passes and the history tap, enqueued in order.
+int sthip_denoise_filter(sthip_ctx* ctx, const sthip_denoise_desc* d) {
+  if (!ctx || !d) return STHIP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const char* field, const char* why) { return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, std::string("sthip_denoise_filter: ") + field + " " + why); };
+  if (!d->width) return refuse("width", "is 0");
+  if (!d->height) return refuse("height", "is 0");
+  if ((uint64_t)d->width * d->height > 0x7FFFFFFFull) return refuse("width x height", "is too large (more than 2^31 - 1 pixels)");
+  if (!d->view_count) return refuse("view_count", "is 0");
+  if (d->iterations < 1 || d->iterations > sthip::DENOISE_MAX_ITERATIONS) return refuse("iterations", "must be 1 .. 8");
+  if (d->filter_type >= STHIP_FILTER_TYPE_COUNT) return refuse("filter_type", "must be below 6 (STHIP_FILTER_*)");
+  if (!d->gViews) return refuse("gViews", "is NULL");
+  if (!d->gVisibility) return refuse("gVisibility", "is NULL");
+  if (!d->gDepth) return refuse("gDepth", "is NULL");
+  if (!d->gAccumColor) return refuse("gAccumColor", "is NULL");
+  if (!d->gAccumMoments) return refuse("gAccumMoments", "is NULL");
+  if (!d->gFilterImages[0]) return refuse("gFilterImages[0]", "is NULL");
+  if (!d->gFilterImages[1]) return refuse("gFilterImages[1]", "is NULL");
+  if (d->gInstanceIndexMap && !d->instance_count) return refuse("instance_count", "is 0 with a gInstanceIndexMap");
+  for (uint32_t v = 0; v < d->view_count; v++) {  // the taps are bounded by their view: a view must lie inside the images
+    const sthip_ViewData& vw = d->gViews[v];
+    if (vw.image_min[0] < 0 || vw.image_min[1] < 0 || vw.image_max[0] > (int64_t)d->width || vw.image_max[1] > (int64_t)d->height)
+      return refuse("gViews", ("holds a view that leaves the extent (view " + std::to_string(v) + ")").c_str());
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t n = (size_t)d->width * d->height, cb = ctx->color_bytes();
+  const bool tapped = d->history_tap >= 1 && d->history_tap <= d->iterations;
+  HIP_TRY(ctx, ctx->denoise_guide.ensure(n));  // (no allocation unless the extent exceeds every earlier call's)
+  std::vector<void*> staged;  // device copies of host arrays, freed on return
+  auto release = [&]() {
+    for (void* q : staged) (void)hipFree(q);
+  };
+  bool bad = false;
+  // a host array on the device: its contents when `copy` (inputs; outputs too — pixels outside every view keep the caller's)
+  auto stage = [&](const void* host, size_t bytes) -> void* {
+    if (!host || d->device_ptrs) return const_cast<void*>(host);
+    void* q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) {
+      bad = true;
+      return nullptr;
+    }
+    staged.push_back(q);
+    if (hipMemcpyAsync(q, host, bytes, hipMemcpyHostToDevice, st) != hipSuccess) bad = true;
+    return q;
+  };
+  sthip::DenoiseParams p{};
+  p.width = d->width;
+  p.height = d->height;
+  p.view_count = d->view_count;
+  p.instance_count = d->instance_count;
+  p.history_limit = d->history_limit;
+  p.variance_boost_length = d->variance_boost_length;
+  p.sigma_luminance_boost = d->sigma_luminance_boost;
+  if (d->view_count <= sthip::DENOISE_INLINE_VIEWS) {  // gViews is a host array in either form
+    p.views = nullptr;
+    memcpy(p.inline_views, d->gViews, (size_t)d->view_count * sizeof(sthip_ViewData));
+  } else {
+    void* q = nullptr;
+    if (hipMalloc(&q, (size_t)d->view_count * sizeof(sthip_ViewData)) != hipSuccess)
+      bad = true;
+    else {
+      staged.push_back(q);
+      if (hipMemcpyAsync(q, d->gViews, (size_t)d->view_count * sizeof(sthip_ViewData), hipMemcpyHostToDevice, st) != hipSuccess) bad = true;
+    }
+    p.views = (const sthip_ViewData*)q;
+  }
+  p.visibility = (const sthip_VisibilityInfo*)stage(d->gVisibility, n * sizeof(sthip_VisibilityInfo));
+  p.depth = (const sthip_DepthInfo*)stage(d->gDepth, n * sizeof(sthip_DepthInfo));
+  p.instance_index_map = (const uint32_t*)stage(d->gInstanceIndexMap, (size_t)d->instance_count * 4);
+  p.accum_color = stage(d->gAccumColor, n * cb);
+  p.accum_moments = stage(d->gAccumMoments, n * 8);
+  p.filter[0] = stage(d->gFilterImages[0], n * cb);
+  p.filter[1] = stage(d->gFilterImages[1], n * cb);
+  p.guide = ctx->denoise_guide.p;
+  if (bad) {
+    (void)hipStreamSynchronize(st);
+    release();
+    return fail(ctx, STHIP_ERR_HIP, "sthip_denoise_filter: staging the host images on the device failed");
+  }
+  hipEvent_t ev[20] = {};
+  bool ran[10] = {};
+  hipError_t e = hipSuccess;
+  if (d->pass_ms)
+    for (int k = 0; k < 20 && e == hipSuccess; k++) e = hipEventCreate(&ev[k]);
+  std::string err;
+  const bool ok = e == hipSuccess && sthip::denoise_launch(p, d->iterations, d->filter_type, d->history_tap, ctx->half_color, ctx->denoise_block, st,
+                                                           d->pass_ms ? reinterpret_cast<void* const*>(ev) : nullptr, ran, err);
+  if (ok && !d->device_ptrs) {
+    e = hipMemcpyAsync(d->gFilterImages[0], p.filter[0], n * cb, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d->gFilterImages[1], p.filter[1], n * cb, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && tapped) e = hipMemcpyAsync(d->gAccumColor, p.accum_color, n * cb, hipMemcpyDeviceToHost, st);
+  }
+  // staged copies must outlive the kernels, and the timings need them finished; the device form with inline views only enqueues
+  const hipError_t es = (staged.empty() && !d->pass_ms) ? hipSuccess : hipStreamSynchronize(st);
+  if (d->pass_ms) {
+    for (int k = 0; k < 10; k++) {
+      d->pass_ms[k] = 0;
+      if (ok && e == hipSuccess && es == hipSuccess && ran[k]) (void)hipEventElapsedTime(&d->pass_ms[k], ev[2 * k], ev[2 * k + 1]);
+    }
+    for (int k = 0; k < 20; k++)
+      if (ev[k]) (void)hipEventDestroy(ev[k]);
+  }
+  release();
+  if (!ok && e == hipSuccess) return fail(ctx, STHIP_ERR_HIP, "sthip_denoise_filter: " + err);
+  if (e != hipSuccess || es != hipSuccess) return fail(ctx, STHIP_ERR_HIP, std::string("sthip_denoise_filter: ") + hipGetErrorString(e != hipSuccess ? e : es));
   return STHIP_OK;
 }
 

@@ -8,6 +8,7 @@
 //   stm::node_to_world                                         src/Node/Scene.cpp:108-117
 //   stm::Application (OnUpdate / OnRenderWindow only)          src/Node/Application.hpp:11-29
 //   stm::Scene  (update() packs SceneData, data())             src/Node/Scene.hpp:44-69, Scene.cpp:299-684
+//   stm::Denoiser (denoise(), reset_accumulation())            src/Node/Denoiser.hpp:9-60, Denoiser.cpp:117-274
 //   stm::BDPT   (update(), render(), prev_result())            src/Node/BDPT.hpp:13-24, BDPT.cpp:35-127,341-838
 //
 // What is NOT here: Vulkan (Device, CommandBuffer, Image, Buffer), loaders, GUI, window. The
@@ -43,6 +44,9 @@
 #pragma weak sthip_scene_set_rigs
 #pragma weak sthip_scene_animate
 #pragma weak sthip_scene_read_vertices
+// ... and one without the post block lacks these: Denoiser::denoise then throws
+#pragma weak sthip_accumulate
+#pragma weak sthip_denoise_filter
 #include "../../include/sthip_detmath.h"  // det_f16tof32: export_hdr of a half frame
 
 namespace stm {
@@ -958,6 +962,99 @@ class Scene {
 };
 
 // ------------------------------------------------------------------------------------------------
+// Denoiser: Denoiser.hpp:9-60. The node BDPT::render hands its frame to when one is in the graph (BDPT.cpp:472-473,767-781):
+// temporal accumulation (sthip_accumulate), then — with atrous_iterations() > 0 — the variance estimate, the filter passes and
+// the history tap (sthip_denoise_filter). The state and its defaults are upstream's (Denoiser.cpp:73-77, Denoiser.hpp:56-57,
+// gFilterKernelType = 1). The images live in host memory between frames, as the Frame's do (host form of both calls).
+// Upstream's first frame, and one after reset_accumulation(), returns the radiance and accumulates nothing (Denoiser.cpp:267-271);
+// here such a frame accumulates into an empty history — sample count 0 everywhere — as the Python host's does.
+// gInstanceIndexMap is the identity: this host's Scene keeps an instance's index from frame to frame.
+// ------------------------------------------------------------------------------------------------
+class Denoiser {
+ public:
+  explicit Denoiser(Node& node) : mNode(node) {}
+  Node& node() const { return mNode; }
+  bool& reprojection() { return mReprojection; }
+  bool& demodulate_albedo() { return mDemodulateAlbedo; }
+  float& history_limit() { return mHistoryLimit; }                    // gHistoryLimit: "Target Sample Count"
+  uint32_t& atrous_iterations() { return mAtrousIterations; }         // "Filter Iterations"
+  uint32_t& filter_type() { return mFilterType; }                     // STHIP_FILTER_*
+  uint32_t& history_tap() { return mHistoryTap; }                     // "History Tap Iteration"
+  float& variance_boost_length() { return mVarianceBoostLength; }     // "Variance Boost Frames"
+  float& sigma_luminance_boost() { return mSigmaLuminanceBoost; }
+  void reset_accumulation() { mResetAccumulation = true; }
+  uint32_t accumulated_frames() const { return mAccumulatedFrames; }
+
+  // Denoiser::denoise (Denoiser.cpp:117-274). The colour images are RGBA32F, or RGBA16F when `half` (the context's
+  // "half_color_precision"). Returns the image upstream returns — the accumulated colour, or gFilterImages[iterations % 2] —
+  // which stays valid until the next call.
+  const void* denoise(sthip_ctx* ctx, bool half, uint32_t width, uint32_t height, const void* radiance, const void* albedo, const std::vector<ViewData>& views,
+                      const std::vector<VisibilityInfo>& visibility, const std::vector<DepthInfo>& depth, const std::vector<float>& prev_uvs) {
+    const size_t n = (size_t)width * height, cb = half ? 8 : 16;
+    if (mResetAccumulation || mWidth != width || mHeight != height || mHalf != half || mAccumColor.size() != n * cb) {
+      mAccumColor.assign(n * cb, 0);
+      mAccumMoments.assign(2 * n, 0.f);
+      VisibilityInfo miss{};
+      miss.instance_primitive_index = 0xFFFFFFFFu;
+      mPrevVisibility.assign(n, miss);
+      mPrevDepth.assign(n, DepthInfo{});
+      mWidth = width, mHeight = height, mHalf = half;
+      mResetAccumulation = false;
+      mAccumulatedFrames = 0;
+    }
+    std::vector<uint8_t> color(n * cb, 0);
+    std::vector<float> moments(2 * n, 0.f);
+    sthip_accumulate_desc a{};
+    a.width = width, a.height = height, a.view_count = (uint32_t)views.size();
+    a.reprojection = mReprojection ? 1u : 0u, a.demodulate_albedo = mDemodulateAlbedo ? 1u : 0u;
+    a.history_limit = mHistoryLimit;
+    a.gViews = views.data();
+    a.gRadiance = static_cast<const float*>(radiance), a.gAlbedo = static_cast<const float*>(albedo);
+    a.gVisibility = visibility.data(), a.gDepth = depth.data(), a.gPrevUVs = prev_uvs.data();
+    a.gPrevVisibility = mPrevVisibility.data(), a.gPrevDepth = mPrevDepth.data();
+    a.gPrevAccumColor = reinterpret_cast<const float*>(mAccumColor.data()), a.gPrevAccumMoments = mAccumMoments.data();
+    a.gAccumColor = reinterpret_cast<float*>(color.data()), a.gAccumMoments = moments.data();
+    if (!sthip_accumulate) throw std::runtime_error("Denoiser::denoise: this libstratum_hip has no sthip_accumulate");
+    if (sthip_accumulate(ctx, &a) != STHIP_OK) throw std::runtime_error(std::string("sthip_accumulate: ") + sthip_last_error(ctx));
+    mAccumColor.swap(color);
+    mAccumMoments.swap(moments);
+    mPrevVisibility = visibility;
+    mPrevDepth = depth;
+    mAccumulatedFrames++;
+    if (mAtrousIterations == 0) return mAccumColor.data();
+    if (!sthip_denoise_filter) throw std::runtime_error("Denoiser::denoise: this libstratum_hip has no sthip_denoise_filter (filter iterations need it)");
+    for (auto& f : mFilterImages) f.assign(n * cb, 0);
+    sthip_denoise_desc d{};
+    d.width = width, d.height = height, d.view_count = (uint32_t)views.size();
+    d.iterations = mAtrousIterations, d.filter_type = mFilterType, d.history_tap = mHistoryTap;
+    d.history_limit = mHistoryLimit;  // (one set of push constants serves both dispatches, Denoiser.cpp:225)
+    d.variance_boost_length = mVarianceBoostLength, d.sigma_luminance_boost = mSigmaLuminanceBoost;
+    d.gViews = views.data(), d.gVisibility = visibility.data(), d.gDepth = depth.data();
+    d.gAccumColor = reinterpret_cast<float*>(mAccumColor.data());  // (the tapped colour is the history)
+    d.gAccumMoments = mAccumMoments.data();
+    d.gFilterImages[0] = reinterpret_cast<float*>(mFilterImages[0].data()), d.gFilterImages[1] = reinterpret_cast<float*>(mFilterImages[1].data());
+    if (sthip_denoise_filter(ctx, &d) != STHIP_OK) throw std::runtime_error(std::string("sthip_denoise_filter: ") + sthip_last_error(ctx));
+    return mFilterImages[mAtrousIterations % 2].data();
+  }
+
+ private:
+  Node& mNode;
+  bool mReprojection = true, mDemodulateAlbedo = true;  // Denoiser.cpp:76-77
+  float mHistoryLimit = 0;                              // :73
+  uint32_t mAtrousIterations = 0, mHistoryTap = 0;      // Denoiser.hpp:56-57
+  uint32_t mFilterType = STHIP_FILTER_BOX3;             // atrous.hlsl:55,59
+  float mVarianceBoostLength = 0, mSigmaLuminanceBoost = 3;  // Denoiser.cpp:75
+  bool mResetAccumulation = false;
+  uint32_t mAccumulatedFrames = 0;
+  uint32_t mWidth = 0, mHeight = 0;
+  bool mHalf = false;
+  std::vector<uint8_t> mAccumColor, mFilterImages[2];
+  std::vector<float> mAccumMoments;
+  std::vector<VisibilityInfo> mPrevVisibility;
+  std::vector<DepthInfo> mPrevDepth;
+};
+
+// ------------------------------------------------------------------------------------------------
 // BDPT: BDPT.hpp:13-24. Errors surface as exceptions like in the reference (Shader.cpp:115, Instance.cpp:25).
 // ------------------------------------------------------------------------------------------------
 class BDPT {
@@ -974,6 +1071,9 @@ class BDPT {
     // with set_half_color_precision(true) (mHalfColorPrecision, BDPT.cpp:231,553-558) these RGBA16F images (IEEE binary16 bits)
     // are filled instead of mRadiance / mAlbedo / mTonemapResult / mDebugImage, which then stay empty
     std::vector<uint16_t> mRadiance16, mAlbedo16, mTonemapResult16, mDebugImage16;
+    // mDenoiseResult (BDPT.cpp:769): what the Denoiser returned and the tone map read; only with a Denoiser in the graph
+    std::vector<float> mDenoiseResult;
+    std::vector<uint16_t> mDenoiseResult16;
   };
 
   explicit BDPT(Node& node, int device = 0) : mNode(node) {
@@ -1290,7 +1390,9 @@ class BDPT {
     // BDPT.cpp:474,482-483: a frame whose first camera moved since the last one reuses nothing (gReservoirSpatialM = 0) unless the
     // denoiser reprojects; setting the option drops the grids the last frame left (include/sthip.h)
     const bool changed = !mPrevInverseViewTransforms.empty() && !fs.ti.empty() && std::memcmp(&mPrevInverseViewTransforms[0], &fs.ti[0], sizeof(TransformData)) != 0;
+    if (auto denoiser = mNode.find<Denoiser>()) mReprojection = denoiser->reprojection();  // BDPT.cpp:472-473
     if (changed && !mReprojection) (void)sthip_set_option(mCtx, "reuse_grids_persist", 1);
+    mChanged = changed;
     if (sthip_render(mCtx, &pc, mSamplingFlags, scene_flags, &f, mFrameNumber, seed_count, &o) != STHIP_OK)
       throw std::runtime_error(std::string("sthip_render: ") + sthip_last_error(mCtx));
     if (mDebugMode != STHIP_DEBUG_NONE) {
@@ -1311,6 +1413,7 @@ class BDPT {
   // bytes themselves reads them through the ABI. Non-virtual, and the only code that refers to the pipelined entry points.
   uint64_t submit(CommandBuffer& cb, uint32_t width, uint32_t height, const std::vector<std::pair<ViewData, TransformData>>& views, uint32_t seed_count = 1) {
     if (mDebugMode != STHIP_DEBUG_NONE) throw std::runtime_error("BDPT::submit: not with a debug mode: use render()");
+    if (mDenoise && mNode.find<Denoiser>()) throw std::runtime_error("BDPT::submit: not with a Denoiser in the graph (its history chains through host memory): use render()");
     FrameSetup fs;
     prepare_frame(width, height, views, fs);
     if (!mAsync) {
@@ -1395,7 +1498,9 @@ class BDPT {
   }
   uint32_t debug_mode() const { return mDebugMode; }
   // Denoiser::reprojection() (BDPT.cpp:472-473): with it a moving camera keeps the previous frame's reuse grids
+  // (with a Denoiser in the graph render() takes it from the component instead)
   void set_reprojection(bool on) { mReprojection = on; }
+  bool& denoise() { return mDenoise; }  // "Enable denoiser" (BDPT.cpp:302): whether a Denoiser in the graph is used
 
  protected:
   uint32_t frame_number() const { return mFrameNumber; }
@@ -1411,7 +1516,7 @@ class BDPT {
   void finish_frame(Frame fr, const FrameSetup& fs, uint32_t seed_count, bool noted_at_submit = false) {
     const uint32_t width = fr.width, height = fr.height;
     const size_t n = (size_t)width * height;
-    // tone map (BDPT.cpp:783-815); without a denoiser gModulateAlbedo stays off (:779-780 only run when one exists)
+    // tone map (BDPT.cpp:783-815); without a Denoiser in the graph gModulateAlbedo stays off (:779-780 only run when one exists)
     sthip_tonemap_desc tm{};
     if (mHalfColorPrecision) {  // (the context's option makes all three images RGBA16F)
       if (fr.mAlbedo16.size() != 4 * n) fr.mAlbedo16.assign(4 * n, 0);
@@ -1430,6 +1535,17 @@ class BDPT {
     tm.height = height;
     tm.mode = mTonemapMode;
     tm.modulate_albedo = 0;
+    if (auto denoiser = mDenoise ? mNode.find<Denoiser>() : component_ptr<Denoiser>()) {  // accumulate / denoise, BDPT.cpp:767-781
+      if (mChanged && !denoiser->reprojection()) denoiser->reset_accumulation();
+      const void* albedo = mHalfColorPrecision ? static_cast<const void*>(fr.mAlbedo16.data()) : static_cast<const void*>(fr.mAlbedo.data());
+      const void* result = denoiser->denoise(mCtx, mHalfColorPrecision, width, height, tm.gInput, albedo, fs.v, fr.mVisibility, fr.mDepth, fr.mPrevUVs);
+      if (mHalfColorPrecision)
+        fr.mDenoiseResult16.assign(static_cast<const uint16_t*>(result), static_cast<const uint16_t*>(result) + 4 * n);
+      else
+        fr.mDenoiseResult.assign(static_cast<const float*>(result), static_cast<const float*>(result) + 4 * n);
+      tm.gInput = mHalfColorPrecision ? reinterpret_cast<const float*>(fr.mDenoiseResult16.data()) : fr.mDenoiseResult.data();
+      tm.modulate_albedo = denoiser->demodulate_albedo() ? 1u : 0u;
+    }
     tm.gamma_correction = mGammaCorrection ? 1u : 0u;
     tm.exposure = mExposure;
     tm.exposure_alpha = mExposureAlpha;       // gExposureAlpha, BDPT.cpp:51,192,307
@@ -1510,6 +1626,8 @@ class BDPT {
   uint32_t mFrameNumber = 0;
   uint32_t mDebugMode = STHIP_DEBUG_NONE;
   bool mReprojection = false;
+  bool mDenoise = true;   // BDPT.hpp: mDenoise = true
+  bool mChanged = false;  // the frame being rendered moved its first camera (render() -> finish_frame)
   std::vector<float> mDebugImage;
   bool mHalfColorPrecision = false;  // BDPT.cpp:231
   std::vector<uint16_t> mDebugImage16;  // mDebugImage while mHalfColorPrecision is on

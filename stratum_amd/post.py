@@ -1,4 +1,5 @@
-"""What the reference does with the renderer's output, on the GPU: the tone-map block of BDPT::render
+"""What the reference does with the renderer's output, on the GPU: the Denoiser node (src/Node/Denoiser.cpp: temporal
+accumulation, variance estimate and edge-stopping filter -> sthip_accumulate / sthip_denoise_filter), the tone-map block of BDPT::render
 (src/Node/BDPT.cpp:783-815 -> kernels/tonemap.hlsl), the ImageComparer node (src/Node/ImageComparer.cpp:61-90 ->
 kernels/image_compare.hlsl) and the "Export HDR" button (BDPT.cpp:313-337). Thin host code over the C ABI
 (sthip_tonemap / sthip_image_compare / sthip_write_hdr); there is no CPU implementation behind it.
@@ -94,6 +95,96 @@ class TemporalAccumulation:
         self._bdpt._check(_lib.lib().sthip_accumulate(self._bdpt._h, C.byref(d)), "sthip_accumulate")
         self.history = {"accum_color": out_c, "accum_moments": out_m, "visibility": frame_out.get("visibility"), "depth": frame_out.get("depth")}
         return out_c, out_m
+
+
+def denoise_desc(views, visibility, depth, accum_color, accum_moments, iterations, filter_type="Box3", history_tap=0, history_limit=0.0, variance_boost_length=0.0,
+                 sigma_luminance_boost=3.0, instance_index_map=None, filter_images=None, keep=None, color_dtype=np.float32):
+    """Fills a wire.DenoiseDesc (host form) from arrays. accum_color is used in place when it already is a contiguous array of
+    color_dtype: the history tap writes into it. filter_images: what the two images hold before the call (pixels outside every view
+    keep it), default zeros. `keep` receives the arrays the descriptor points at. Returns (desc, filter0, filter1, accum_color)."""
+    acc = _rgba(accum_color, "accum_color", color_dtype)
+    H, W = acc.shape[0], acc.shape[1]
+    d = wire.DenoiseDesc()
+    d.width, d.height = W, H
+    v = np.ascontiguousarray(views, dtype=wire.ViewData)
+    d.view_count = v.shape[0]
+    d.device_ptrs = 0
+    d.iterations = int(iterations)
+    d.filter_type = _mode(wire.FILTER, filter_type)
+    d.history_tap = int(history_tap)
+    d.history_limit = float(history_limit)
+    d.variance_boost_length = float(variance_boost_length)
+    d.sigma_luminance_boost = float(sigma_luminance_boost)
+    f = [np.zeros((H, W, 4), color_dtype) if filter_images is None else np.array(_rgba(filter_images[k], "filter_images[%d]" % k, color_dtype)) for k in range(2)]
+    arrays = {
+        "gViews": v,
+        "gVisibility": np.ascontiguousarray(visibility, wire.VisibilityInfo) if visibility is not None else None,
+        "gDepth": np.ascontiguousarray(depth, wire.DepthInfo) if depth is not None else None,
+        "gInstanceIndexMap": np.ascontiguousarray(instance_index_map, np.uint32) if instance_index_map is not None else None,
+        "gAccumColor": acc,
+        "gAccumMoments": np.ascontiguousarray(accum_moments, np.float32),
+    }
+    for k, a in arrays.items():
+        setattr(d, k, a.ctypes.data if a is not None else None)
+    d.instance_count = arrays["gInstanceIndexMap"].shape[0] if instance_index_map is not None else 0
+    d.gFilterImages[0], d.gFilterImages[1] = f[0].ctypes.data, f[1].ctypes.data
+    if keep is not None:
+        keep.append((arrays, f))
+    return d, f[0], f[1], acc
+
+
+class Denoiser:
+    """The Denoiser node (src/Node/Denoiser.cpp:117-274): temporal accumulation, then — with iterations > 0 — the variance
+    estimate, `iterations` passes of the edge-stopping filter and the history tap. The defaults are upstream's
+    (Denoiser.cpp:73-77, Denoiser.hpp:56-57, gFilterKernelType = 1). Calling it returns what Denoiser::denoise returns: the
+    accumulated colour, or gFilterImages[iterations % 2]. (Upstream's first frame and a frame after a reset return the radiance
+    and accumulate nothing; here, as with TemporalAccumulation, they accumulate into an empty history.)"""
+
+    def __init__(self, bdpt, reprojection=True, demodulate_albedo=True, history_limit=0, iterations=0, filter_type="Box3", history_tap=0, variance_boost_length=0, sigma_luminance_boost=3):
+        self._bdpt = bdpt
+        self.accumulation = TemporalAccumulation(bdpt, reprojection, demodulate_albedo, history_limit)
+        self.iterations = iterations  # mAtrousIterations
+        self.filter_type = filter_type
+        self.history_tap = history_tap  # mHistoryTap
+        self.variance_boost_length = variance_boost_length
+        self.sigma_luminance_boost = sigma_luminance_boost
+        self.filter_images = None  # both ping-pong images after the last filtered frame
+
+    reprojection = property(lambda self: self.accumulation.reprojection, lambda self, v: setattr(self.accumulation, "reprojection", v))
+    demodulate_albedo = property(lambda self: self.accumulation.demodulate_albedo, lambda self, v: setattr(self.accumulation, "demodulate_albedo", v))
+    history_limit = property(lambda self: self.accumulation.history_limit, lambda self, v: setattr(self.accumulation, "history_limit", v))
+
+    def reset(self):  # Denoiser::reset_accumulation
+        self.accumulation.reset()
+
+    def __call__(self, frame_out, views, instance_index_map=None):
+        out_c, out_m = self.accumulation(frame_out, views, instance_index_map)
+        if not self.iterations:
+            return out_c
+        keep = []
+        # out_c IS the history's accumulated colour: the tapped colour lands in the history (the one history_limit serves both
+        # dispatches, as upstream's one set of push constants does, Denoiser.cpp:225)
+        d, f0, f1, _ = denoise_desc(views, frame_out.get("visibility"), frame_out.get("depth"), out_c, out_m, self.iterations, self.filter_type, self.history_tap,
+                                    self.history_limit, self.variance_boost_length, self.sigma_luminance_boost, instance_index_map, None, keep, self._bdpt.color_dtype)
+        assert d.gAccumColor == out_c.ctypes.data
+        self._bdpt._check(_lib.lib().sthip_denoise_filter(self._bdpt._h, C.byref(d)), "sthip_denoise_filter")
+        self.filter_images = (f0, f1)
+        return self.filter_images[self.iterations % 2]
+
+    def device(self, width, height, views, visibility_ptr, depth_ptr, accum_color_ptr, accum_moments_ptr, filter0_ptr, filter1_ptr, instance_index_map_ptr=None, instance_count=0):
+        """The filter alone in its device-pointer form (buffers in HBM; the colour images RGBA16F with half_color_precision):
+        enqueues the passes on the context's stream and returns. The result is filter<iterations % 2>."""
+        v = np.ascontiguousarray(views, dtype=wire.ViewData)
+        d = wire.DenoiseDesc()
+        d.width, d.height, d.view_count, d.device_ptrs = width, height, v.shape[0], 1
+        d.instance_count = instance_count
+        d.iterations, d.filter_type, d.history_tap = int(self.iterations), _mode(wire.FILTER, self.filter_type), int(self.history_tap)
+        d.history_limit, d.variance_boost_length, d.sigma_luminance_boost = float(self.history_limit), float(self.variance_boost_length), float(self.sigma_luminance_boost)
+        d.gViews = v.ctypes.data
+        d.gVisibility, d.gDepth, d.gInstanceIndexMap = visibility_ptr, depth_ptr, instance_index_map_ptr
+        d.gAccumColor, d.gAccumMoments = accum_color_ptr, accum_moments_ptr
+        d.gFilterImages[0], d.gFilterImages[1] = filter0_ptr, filter1_ptr
+        self._bdpt._check(_lib.lib().sthip_denoise_filter(self._bdpt._h, C.byref(d)), "sthip_denoise_filter")
 
 
 class Tonemapper:

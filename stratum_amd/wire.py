@@ -373,3 +373,32 @@ class AccumulateDesc(C.Structure):
         ("gAccumMoments", C.c_void_p),
     ]
 
+
+
+FILTER_TYPES = ["Atrous", "Box3", "Box5", "Subsampled", "Box3Subsampled", "Box5Subsampled"]  # FilterKernelType, filter_type.h:8-16
+FILTER = {n: i for i, n in enumerate(FILTER_TYPES)}
+
+
+class DenoiseDesc(C.Structure):
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("view_count", C.c_uint32),
+        ("device_ptrs", C.c_uint32),
+        ("instance_count", C.c_uint32),
+        ("iterations", C.c_uint32),
+        ("filter_type", C.c_uint32),
+        ("history_tap", C.c_uint32),
+        ("history_limit", C.c_float),
+        ("variance_boost_length", C.c_float),
+        ("sigma_luminance_boost", C.c_float),
+        ("pad_", C.c_uint32),
+        ("gViews", C.c_void_p),
+        ("gVisibility", C.c_void_p),
+        ("gDepth", C.c_void_p),
+        ("gInstanceIndexMap", C.c_void_p),
+        ("gAccumColor", C.c_void_p),
+        ("gAccumMoments", C.c_void_p),
+        ("gFilterImages", C.c_void_p * 2),
+        ("pass_ms", C.c_void_p),
+    ]
