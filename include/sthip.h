@@ -452,7 +452,10 @@ typedef struct sthip_stats {
   uint64_t busy_rounds[2];
   /* the first bounce runs as wave packets in a kernel of its own (k_trace_primary, "packet_primary" = 1): its share of
    * rays_path / nodes_visited / tris_tested, its launches and its time, all of which are NOT part of ms_trace /
-   * launches_trace (so those describe k_trace alone) */
+   * launches_trace (so those describe k_trace alone). rays_primary_packets is what the packet kernel TRACED in the last
+   * render: with "reuse_first_hits" it runs over one seed's paths when the kept hits do not fit the call, and not at all
+   * when they do — 0 for a call served entirely from kept hits. Such rays are trace_ray calls of the reference all the
+   * same: rays_total / rays_path / gRayCount count them as before */
   uint64_t rays_primary_packets;
   uint64_t nodes_visited_primary;
   uint64_t tris_tested_primary;
@@ -513,7 +516,15 @@ int sthip_measure_ceiling(sthip_ctx* ctx, uint32_t kind, double* gbytes_per_s);
  * path or diffuse budget can end, only the paths that still have something to do reach the shading kernel), "answer_last_rays"
  * (default 1: a path's last ray is traced only if it can reach the bounds of an emissive instance; sthip_stats::rays_answered;
  * identical results for rays that start within a few scene sizes of the scene — as every path ray does — which is also what
- * the hit contract itself needs),
+ * the hit contract itself needs), "reuse_first_hits" (default 1: the primary ray of a pixel goes through its centre whatever the
+ * seed, so the hits of the first bounce are kept on the device — 20 bytes per path of one seed, allocated at first use; a
+ * device without room for them renders as with 0 — and traced again only when something they depend on changed: the views or
+ * their transforms, the extent, the shard, whether gMaxPathVertices >= 2, eAlphaTest / eFlipTriangleUVs, or the scene, by any
+ * of sthip_scene_upload, sthip_scene_update_transforms, sthip_scene_update_vertices, sthip_scene_animate, sthip_scene_set_rigs.
+ * A host that renders one frame per call under a still camera traces the first bounce once; the seeds in flight of one call
+ * share one trace. Frames, gRayCount and every stat but rays_primary_packets are the same either way. Setting the option, to
+ * either value, drops the kept hits, and so do sthip_set_shard and a change of stream by sthip_set_stream. Not used under
+ * "count_traversal" / "time_kernels", with volumes, or with "packet_primary" = 0),
  * "keep_scene" (default 1: a host copy of the uploaded arrays, see sthip_scene_update_transforms), "treetop" (default 0), "embed_leaves" (default 0), "lds_materials" (default 1), "lds_stack_levels" (4..150: LDS levels of the traversal stack; a higher
  * tree runs the bounded kernels, default: bounded at 32 levels beyond a height of 40): layout / scheduling options that
  * never change results, read at the next sthip_scene_upload / sthip_scene_update_transforms.

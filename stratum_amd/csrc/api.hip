@@ -22,6 +22,7 @@
 #include "animate.h"
 #include "denoise.h"
 #include "bvh_build.h"
+#include "first_hits.h"
 #include "kernel_instances.h"  // kernels.h + the instantiations that live in shade_*.hip / trace_kernels.hip
 #include "post.h"
 #include "ceilings.h"
@@ -364,6 +365,16 @@ struct sthip_ctx {
   uint64_t max_paths_in_flight = 1ull << 22;  // (sthip_create sizes it to the device: 2^26 on a 288 GB MI355X — launches large enough that their
                                               // tails stop mattering: atrium x 8 seeds +7 %, forest at 4K x 16 +38 % over 2^22; tools/in_flight_sweep.py)
   bool packet_primary = true;  // the first bounce is traced as wave packets (k_trace_primary)
+  // "reuse_first_hits" (first_hits.h): the hits of the first bounce do not depend on the seed, so the packet kernel's output
+  // for ONE seed's paths is kept here (20 B per path, allocated at first use; a call renders without them if that fails) and
+  // the kernel runs again only when the key of a call differs from the key they were traced for. `scene_serial` counts the
+  // calls that can move a triangle, an instance or an alpha mask. The pair (valid, key) changes only where the launch that
+  // fills the buffers is enqueued (run_batches: past the point where a render is tried again), or where the hits are dropped.
+  bool reuse_first_hits = true, first_hits_valid = false;
+  uint64_t scene_serial = 0;
+  sthip::FirstHitKey first_hit_key{};
+  DevBuf<float4> first_hit;
+  DevBuf<uint32_t> first_hit_leaf;
   bool fuse_trace = true;  // closest-hit rays of a bounce and the shadow rays of the previous one in one launch
   int bvh_builder = 0;  // sthip::BvhBuilderKind
   uint32_t sah_top_size = 64;  // "sah_top" (measured 32 .. 16384: 64 traces fastest): the GPU builder's subtrees of at most this many triangles get a host-built SAH top (0: off)
@@ -621,6 +632,8 @@ void sthip_destroy(sthip_ctx* ctx) {
   ctx->ray_d.release();
   ctx->hit.release();
   ctx->hit_leaf.release();
+  ctx->first_hit.release();
+  ctx->first_hit_leaf.release();
   ctx->debug.release();
   ctx->shadow_debug.release();
   ctx->beta.release();
@@ -672,6 +685,7 @@ int sthip_set_stream(sthip_ctx* ctx, void* hip_stream) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, drain_in_flight(ctx));
   }
+  if ((hipStream_t)hip_stream != ctx->stream) ctx->first_hits_valid = false;  // (nothing orders the new stream behind the launch that filled them)
   ctx->stream = (hipStream_t)hip_stream;
   return STHIP_OK;
 }
@@ -684,6 +698,7 @@ int sthip_set_shard(sthip_ctx* ctx, uint32_t shard_rank, uint32_t shard_count, u
   ctx->shard_count = shard_count;
   ctx->tile_w = tile_w;
   ctx->tile_h = tile_h;
+  ctx->first_hits_valid = false;
   return STHIP_OK;
 }
 
@@ -699,6 +714,10 @@ int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value) {
     ctx->packet_primary = value != 0;
   else if (!strcmp(name, "answer_last_rays"))
     ctx->answer_last_rays = value != 0;
+  else if (!strcmp(name, "reuse_first_hits")) {  // setting it (to either value) also drops the hits kept so far
+    ctx->reuse_first_hits = value != 0;
+    ctx->first_hits_valid = false;
+  }
   else if (!strcmp(name, "cull_terminal"))
     ctx->cull_terminal = value != 0;
   else if (!strcmp(name, "refill_idle"))
@@ -929,6 +948,7 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, drain_in_flight(ctx));  // ... and the copy stream of sthip_render_async still reads the staging sets of its frames
   ctx->has_scene = false;
+  ctx->scene_serial++;  // (first_hits.h: from here on the resident triangles are not the ones kept hits were traced against)
   sthip::device_refit_invalidate(ctx->refit);  // (the schedule of a refit belongs to the tree that goes away now)
   ctx->refit_roots_valid = false;
   // the rigs name vertex ranges of the scene that goes away; a rebuild from the kept copy is the same scene and keeps them
@@ -1586,6 +1606,7 @@ int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf,
   if (!xf || !inv) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_transforms: transforms and inverse transforms are required");
   if (instance_count != ctx->instance_count) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the instance count changed: upload the scene again");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->scene_serial++;  // (first_hits.h; a refused call costs one trace of the first bounce)
   sthip::TopLevelState next = ctx->top;  // nothing changes unless everything succeeds
   std::vector<BvhNode> tlas;
   uint32_t root_ref = 0, top_is_world = 1, stack_depth = 4;
@@ -1732,6 +1753,7 @@ static int refit_resident_scene(sthip_ctx* ctx, const VertexSource& src, bool ke
 static int update_resident_vertices(sthip_ctx* ctx, const VertexSource& src, sthip_refit_info* info, std::chrono::steady_clock::time_point t0) {
   const std::string call = std::string(src.call) + ": ";
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->scene_serial++;  // (first_hits.h: sthip_scene_update_vertices and sthip_scene_animate both come this way)
   const bool kept = ctx->kept.valid && ctx->kept.vertices.size() == ctx->vertex_count;
   auto rebuild_from_kept = [&]() {  // (the kept vertices hold the new range already, or get the posed ranges back from the device here)
     int rc = sync_kept_vertices(ctx);
@@ -1875,6 +1897,7 @@ int sthip_scene_set_rigs(sthip_ctx* ctx, const sthip_rig_desc* rigs, uint32_t ri
     bones += d.bone_count;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->scene_serial++;  // (first_hits.h)
   if (!rig_count) {
     drop_rigs(ctx);
     return STHIP_OK;
@@ -2008,6 +2031,10 @@ static void release_path_state(sthip_ctx* ctx) {
   ctx->light_trace.release();
   ctx->presampled.release();
   ctx->deep_rays.release();
+  // the kept first hits are a cache: the device is short of memory, so they go too (the next attempt traces the first bounce)
+  ctx->first_hit.release();
+  ctx->first_hit_leaf.release();
+  ctx->first_hits_valid = false;
 }
 
 // ---- the render call: plan_render, reserve_render_buffers, bind_frame_params, run_batches, read_back ----
@@ -2028,6 +2055,10 @@ struct RenderPlan {
   uint64_t reuse_key[3];
   const void *k_trace[2], *k_shade, *k_probe, *k_shade_light;  // k_trace without / with traversal counters; the view pass's k_shade and its probe
   uint32_t shade_lds, probe_lds;
+  // "reuse_first_hits": the call's first bounce may be served from / kept in the context's buffers, and what for (first_hits.h).
+  // plan_render says whether the call is of that kind; reserve_render_buffers withdraws it if the buffers cannot be had.
+  bool keep_first_hits;
+  sthip::FirstHitKey first_hit_key;
 };
 
 // primary rays = owned pixels that lie inside the image and inside a view (known without asking the GPU)
@@ -2275,13 +2306,20 @@ static int plan_render(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc_in, uin
     snprintf(tuple, sizeof tuple, "k_shade_light<%d, 1, %d>", ctx->textured, media);
     if (!r.k_shade_light) return missing();
   }
+  // The first bounce from kept hits: only where run_batches traces it with the packet kernel (no volumes, a path budget of two
+  // vertices or more, no debug mode that returns before tracing), and never under the diagnostic options, whose passes
+  // describe the kernels (ms_trace_primary, nodes_visited_primary, rays_primary_packets of a traced first bounce)
+  r.keep_first_hits = ctx->reuse_first_hits && ctx->packet_primary && !ctx->has_volumes && !ctx->count_traversal && !ctx->time_kernels && r.max_bounce_rounds >= 1 && r.paths_per_seed > 0 &&
+                      debug_mode != STHIP_DEBUG_ENVIRONMENT_SAMPLE_TEST && debug_mode != STHIP_DEBUG_ENVIRONMENT_SAMPLE_PDF &&
+                      sthip::first_hit_key_make(r.first_hit_key, ctx->scene_serial, pc->gOutputExtent, r.view_count, pc->gMaxPathVertices, ctx->shard_rank, ctx->shard_count, ctx->tile_w, ctx->tile_h,
+                                                r.paths_per_seed, ctx->has_alpha && flag(STHIP_eAlphaTest), flag(STHIP_eFlipTriangleUVs), frame->gViews, frame->gViewTransforms);
   ctx->stats.paths_per_seed = r.paths_per_seed;
   ctx->stats.seeds_in_flight = batch;
   return STHIP_OK;
 }
 
 // Every buffer the call needs, at the sizes of the plan (DevBuf::ensure keeps what is large enough), and the two temp-size queries
-static int reserve_render_buffers(sthip_ctx* ctx, const RenderPlan& r, const sthip_outputs* out, AsyncSlot* slot) {
+static int reserve_render_buffers(sthip_ctx* ctx, RenderPlan& r, const sthip_outputs* out, AsyncSlot* slot) {
   const size_t P = r.P, hg_slots = r.hg_slots, shadow_entries = r.shadow_entries, queue_entries = r.seg_stride * QUEUE_SEGMENTS;
   if (r.bdpt) {
     HIP_TRY(ctx, ctx->bdpt.ensure(P));
@@ -2389,6 +2427,21 @@ static int reserve_render_buffers(sthip_ctx* ctx, const RenderPlan& r, const sth
   }
   // half colour precision: k_shade writes the albedo in binary32 to a stage, k_resolve rounds it into the caller's image (or its staging)
   if (ctx->half_color && out->gAlbedo) HIP_TRY(ctx, ctx->albedo_stage.ensure(pixels));
+  // Last, when everything the call cannot do without is there: the kept first hits of one seed's paths. A device that cannot
+  // hold them renders as without the option: no error, and nothing for the out-of-memory retry to halve a batch over.
+  if (r.keep_first_hits && (ctx->first_hit.n < r.paths_per_seed || ctx->first_hit_leaf.n < r.paths_per_seed)) {
+    ctx->first_hits_valid = false;  // (the buffers they are in go away)
+    hipError_t e = ctx->first_hit.ensure(r.paths_per_seed);
+    if (e == hipSuccess) e = ctx->first_hit_leaf.ensure(r.paths_per_seed);
+    // (the leaf of an all-dead packet's slot is never written by the packet kernel and never used: only read, behind `ip != miss`)
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->first_hit_leaf.p, 0xFF, (size_t)r.paths_per_seed * sizeof(uint32_t), ctx->stream);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->first_hit.release();
+      ctx->first_hit_leaf.release();
+      r.keep_first_hits = false;
+    }
+  }
   return STHIP_OK;
 }
 
@@ -2709,14 +2762,48 @@ static int run_batches(const RenderRun& run, FrameParams& p, uint32_t seed_begin
         }
       });
     };
-    // the first bounce as wave packets (k_trace_primary): one 8x8 pixel block per wave
-    auto trace_primary = [&]() -> int {
+    // the first bounce as wave packets (k_trace_primary): one 8x8 pixel block per wave, over the first `seeds` seeds in flight of `q`
+    auto launch_primary = [&](const FrameParams& q, uint32_t seeds) -> int {
       launches_primary++;
-      rays_primary += (uint64_t)r.primary_rays * in_flight;
-      const uint32_t packets = (p.path_count + 63) / 64;
+      rays_primary += (uint64_t)r.primary_rays * seeds;
+      const uint32_t packets = (q.path_count + 63) / 64;
       const unsigned pgrid = std::max(1u, std::min((packets + 3) / 4, (uint32_t)ctx->cu_count * 64u));
       const size_t plds = ((size_t)ctx->bvh.stack_depth * (STHIP_BLOCK / 64) + 13 * STHIP_BLOCK) * sizeof(uint32_t);  // the per-wave stacks + every lane's saved world-space ray constants
-      return timed(ms_primary, [&]() { launch_kernel(STHIP_KERNEL2(k_trace_primary, ctx->count_traversal, p.bvh.alpha_test != 0), pgrid, plds, st, p); });
+      return timed(ms_primary, [&]() { launch_kernel(STHIP_KERNEL2(k_trace_primary, ctx->count_traversal, q.bvh.alpha_test != 0), pgrid, plds, st, q); });
+    };
+    // "reuse_first_hits" (first_hits.h): the hits of the first bounce are those of seed 0's slots for every seed, and for every
+    // call of the same key. They are traced into the context's kept buffers, once per change of key (slots are seed x
+    // paths_per_seed + pixel slot, and k_generate has written every seed's rays by now: seed 0's are as good as any). With one
+    // seed in flight round 0 is shaded straight from the kept buffers (shade_first_round); with several, a streaming kernel
+    // writes the kept hits to every seed's slots of p.hit / p.hit_leaf.
+    const bool from_kept = r.keep_first_hits;
+    auto trace_primary = [&]() -> int {
+      if (!from_kept) return launch_primary(p, in_flight);
+      if (!(ctx->first_hits_valid && sthip::first_hit_key_equal(ctx->first_hit_key, r.first_hit_key))) {
+        ctx->first_hits_valid = false;
+        FrameParams q = p;
+        q.path_count = p.paths_per_seed;
+        q.hit = ctx->first_hit.p;
+        q.hit_leaf = ctx->first_hit_leaf.p;
+        const int e = launch_primary(q, 1);
+        if (e) return e;
+        ctx->first_hit_key = r.first_hit_key;  // (valid only now that the launch that fills them is enqueued)
+        ctx->first_hits_valid = true;
+      }
+      if (in_flight > 1)
+        return timed(ms_primary, [&]() {
+          hipLaunchKernelGGL(k_replicate_first_hits, dim3(grid_for(ctx, p.paths_per_seed)), dim3(STHIP_BLOCK), 0, st, (const float4*)ctx->first_hit.p, (const uint32_t*)ctx->first_hit_leaf.p, p.hit,
+                             p.hit_leaf, p.paths_per_seed, in_flight);
+        });
+      return STHIP_OK;
+    };
+    // round 0 of the view pass: its hits are the kept ones where they were not copied (k_shade and its probes are their only
+    // readers: k_cull_terminal runs from round 1 on, and k_trace writes p.hit afresh for every later round)
+    auto shade_first_round = [&]() {
+      FrameParams q = p;
+      q.hit = ctx->first_hit.p;
+      q.hit_leaf = ctx->first_hit_leaf.p;
+      shade_view_round(run, q, 0);
     };
     // Round r traces the paths entering bounce r together with the shadow rays bounce r - 1 produced (one launch,
     // k_trace), then shades bounce r; a last launch traces the shadow rays of the last bounce. `shade(depth)` is the
@@ -2811,7 +2898,12 @@ static int run_batches(const RenderRun& run, FrameParams& p, uint32_t seed_begin
       if (rc) return rc;
     }
     p.emitter_count = ctx->answer_last_rays ? ctx->emitter_count : 0u;  // (only the plain k_shade instantiation looks at it)
-    rc = run_rounds(false, (r.nee || r.connect_paths) && !r.inline_media, [&](uint32_t depth) { shade_view_round(run, p, depth); });  // (inline walks through media: nothing is queued)
+    rc = run_rounds(false, (r.nee || r.connect_paths) && !r.inline_media, [&](uint32_t depth) {  // (inline walks through media: nothing is queued)
+      if (depth == 0 && from_kept && in_flight == 1)
+        shade_first_round();
+      else
+        shade_view_round(run, p, depth);
+    });
     if (rc) return rc;
     rc = timed(ms_other, [&]() { hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(STHIP_BLOCK), 0, st, p, s == 0 ? 1u : 0u, s + in_flight == seed_count ? 1u : 0u, r.primary_rays * in_flight); });
     if (rc) return rc;

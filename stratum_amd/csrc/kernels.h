@@ -3325,6 +3325,24 @@ inline __global__ void __launch_bounds__(STHIP_BLOCK) k_resolve(FrameParams p, u
 }
 #endif
 
+// "reuse_first_hits" with several seeds in flight: the kept hits of one seed's slots (first_hits.h) to the slots of every seed in
+// flight, seed x paths + slot. Streaming, 16 bytes per lane and access: 20 B read per slot, 20 B written per slot and seed. The
+// leaf indices move four slots at a time (paths is a multiple of 64: slots are whole 8x8 blocks).
+#ifndef STHIP_TEMPLATE_INSTANCES_ONLY
+inline __global__ void __launch_bounds__(STHIP_BLOCK) k_replicate_first_hits(const float4* kept_hit, const uint32_t* kept_leaf, float4* hit, uint32_t* hit_leaf, uint32_t paths, uint32_t seeds) {
+  const uint32_t first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+  for (uint32_t i = first; i < paths; i += stride) {
+    const float4 h = kept_hit[i];
+    for (uint32_t s = 0; s < seeds; s++) hit[(size_t)s * paths + i] = h;
+  }
+  const uint4* kept_leaf4 = reinterpret_cast<const uint4*>(kept_leaf);
+  for (uint32_t q = first; q < (paths >> 2); q += stride) {
+    const uint4 leaf = kept_leaf4[q];
+    for (uint32_t s = 0; s < seeds; s++) *reinterpret_cast<uint4*>(hit_leaf + (size_t)s * paths + 4 * (size_t)q) = leaf;
+  }
+}
+#endif
+
 // the zero fills a pass starts with, as one launch: up to three ranges of 64-bit words
 #ifndef STHIP_TEMPLATE_INSTANCES_ONLY
 inline __global__ void __launch_bounds__(STHIP_BLOCK) k_clear(unsigned long long* a, uint32_t na, unsigned long long* b, uint32_t nb, unsigned long long* c, uint32_t nc) {
