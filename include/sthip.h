@@ -42,9 +42,49 @@ enum sthip_status {
 };
 
 typedef struct sthip_image_desc {
-  const float* pixels; /* width * height * 4 floats */
+  const float* pixels; /* width * height * 4 floats (gImage1s: width * height floats); bytes instead with an 8-bit format
+                          of sthip_scene_upload_formats, see sthip_image_format */
   uint32_t width, height;
 } sthip_image_desc;
+
+/* ---- resident texel formats (sthip_scene_upload_formats) ----
+ * Every texture the reference renders from is 8 bits per channel (Scene.cpp:178,229 create the material images as
+ * R8G8B8A8Unorm, :182,233 the alpha masks as R8Unorm). An image may be handed over and kept resident in that form: a
+ * quarter of the bytes on the host link, in HBM and per texel fetch. The format is chosen per image; format 0 is the
+ * binary32 form sthip_scene_upload has always taken, stored and sampled exactly as before.
+ *
+ * Formats of gImages:  STHIP_IMAGE_FORMAT_RGBA32F (0): `pixels` points at width * height * 4 floats.
+ *                      STHIP_IMAGE_FORMAT_RGBA8_UNORM (1): `pixels` points at width * height * 4 BYTES, row 0 first, R G B A.
+ * Formats of gImage1s: STHIP_IMAGE_FORMAT_R32F (0): width * height floats.
+ *                      STHIP_IMAGE_FORMAT_R8_UNORM (1): width * height BYTES.
+ * sRGB formats are out of scope: the images the reference binds after material_convert are all Unorm, and a byte is
+ * never passed through a transfer curve here.
+ *
+ * Decode: a byte b is the binary32 quotient (float)b / 255.0f, correctly rounded (IEEE division; the build has no
+ * fast-math and no contraction).
+ * Mip chain of an RGBA8 image: the shape of the float chain — level k + 1 has max(1, dim / 2) texels per side, at most
+ * STHIP_MAX_MIPS (16) levels, down to 1 x 1 — and each channel of texel (x, y) of level k + 1 is the integer
+ *   (a + b + c + d + 2) >> 2
+ * over the texels (min(2x, w - 1) | min(2x + 1, w - 1), min(2y, h - 1) | min(2y + 1, h - 1)) of level k, the four clamped
+ * source texels of the float chain. Levels are stored as bytes; they are built on the device from the uploaded level 0
+ * (one launch per level), so only level 0 crosses the host link. (An alpha mask has no chain: only level 0 is sampled.)
+ * Filtering is unchanged: repeat addressing, bilinear taps, the trilinear blend between two levels, the same arithmetic
+ * in the same order, applied to decoded texels.
+ *
+ * What follows for results: wherever only level 0 is read — without eRayCones (lod = 0), and in the alpha test — an 8-bit
+ * image gives, bit for bit, what the float image pixels = bytes / 255.0f gives; and so at every level for an image whose
+ * float chain ((a + b) + (c + d)) * 0.25f equals its decoded byte chain. Elsewhere the two chains differ by the rounding
+ * of the integer mean (at most half a step of 1 / 255 per level).
+ *
+ * An 8-bit image bound as the environment map is refused by sthip_render and sthip_render_async with
+ * STHIP_ERR_UNSUPPORTED and a message (an HDR environment in 8 bits is nobody's use case). */
+#define STHIP_MAX_MIPS 16 /* levels of a mip chain at most, float or 8-bit */
+enum sthip_image_format {
+  STHIP_IMAGE_FORMAT_RGBA32F = 0,
+  STHIP_IMAGE_FORMAT_RGBA8_UNORM = 1,
+  STHIP_IMAGE_FORMAT_R32F = 0,
+  STHIP_IMAGE_FORMAT_R8_UNORM = 1
+};
 
 typedef struct sthip_volume_desc {
   const void* data; /* the NanoVDB grid buffer */
@@ -176,6 +216,21 @@ int sthip_set_stream(sthip_ctx* ctx, void* hip_stream);
  * were rendered with device output pointers), then replace the resident arrays: a caller never has to synchronise
  * before re-uploading. */
 int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* scene);
+
+/* sthip_scene_upload with a resident format per image (sthip_image_format above): image_formats has scene->image_count
+ * entries for gImages, image1_formats scene->image1_count entries for gImage1s; a NULL array means all 0, and
+ * sthip_scene_upload IS this call with both arrays NULL. An entry that is not a format of its array returns
+ * STHIP_ERR_INVALID_ARGUMENT. The formats belong to the scene: the copy "keep_scene" keeps holds 8-bit images as bytes
+ * with their formats, and everything built again from it (a moved instance of the merged mesh, a layout the refit does
+ * not serve, the failure fallback) is built with them.
+ *
+ * sthip_scene_read_image: the stored texels of level `level` of gImages[image_index] in the image's resident format,
+ * copied to host memory after the work on the stream has finished: w * h * 16 bytes (RGBA32F) or w * h * 4 bytes
+ * (RGBA8) with w = max(1, width >> level), h = max(1, height >> level). out_bytes must be exactly that. It is how a
+ * host (or a test) sees the mip chain. STHIP_ERR_INVALID_ARGUMENT: no scene, an index or a level out of range, a NULL
+ * `out`, a wrong out_bytes. A library without the feature lacks the two symbols. */
+int sthip_scene_upload_formats(sthip_ctx* ctx, const sthip_scene_desc* scene, const uint8_t* image_formats, const uint8_t* image1_formats);
+int sthip_scene_read_image(sthip_ctx* ctx, uint32_t image_index, uint32_t level, void* out, uint64_t out_bytes);
 
 /* Instances moved, nothing else changed (Scene::update with cached BLASes, Scene.cpp:435-459,614-629: only the TLAS is
  * rebuilt): new gInstanceTransforms / gInstanceInverseTransforms / gInstanceMotionTransforms (may be NULL: identity) for

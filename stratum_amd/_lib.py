@@ -22,6 +22,8 @@ EXPORTS = [
     "sthip_last_error",
     "sthip_set_stream",
     "sthip_scene_upload",
+    "sthip_scene_upload_formats",
+    "sthip_scene_read_image",
     "sthip_scene_update_transforms",
     "sthip_scene_update_vertices",
     "sthip_scene_set_rigs",
@@ -102,6 +104,11 @@ def lib():
     L.sthip_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.sthip_scene_upload.restype = C.c_int
     L.sthip_scene_upload.argtypes = [C.c_void_p, C.POINTER(wire.SceneDesc)]
+    if hasattr(L, "sthip_scene_upload_formats"):  # (an older build named by STHIP_LIB lacks the two: calling them raises)
+        L.sthip_scene_upload_formats.restype = C.c_int
+        L.sthip_scene_upload_formats.argtypes = [C.c_void_p, C.POINTER(wire.SceneDesc), C.c_void_p, C.c_void_p]
+        L.sthip_scene_read_image.restype = C.c_int
+        L.sthip_scene_read_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]
     L.sthip_scene_update_vertices.restype = C.c_int
     L.sthip_scene_update_vertices.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(wire.RefitInfo)]
     L.sthip_scene_set_rigs.restype = C.c_int

@@ -133,7 +133,12 @@ class BDPT:
     # ---- BDPT::update: (re)bind the scene ----
     def update(self, scene):
         d = scene.desc()
-        self._check(self._lib.sthip_scene_upload(self._h, C.byref(d)), "sthip_scene_upload")
+        formats, formats1 = scene.formats()
+        if formats.any() or formats1.any():  # some image is a uint8 array: it goes up, and stays resident, as 8-bit texels
+            rc = self._lib.sthip_scene_upload_formats(self._h, C.byref(d), wire.ptr(formats) if formats.size else None, wire.ptr(formats1) if formats1.size else None)
+            self._check(rc, "sthip_scene_upload_formats")
+        else:
+            self._check(self._lib.sthip_scene_upload(self._h, C.byref(d)), "sthip_scene_upload")
         scene.dirty_vertices = None  # (the whole vertex array went up)
         self._scene = scene
 
@@ -213,6 +218,15 @@ class BDPT:
         """The resident vertex records [first, first + count) as a wire.PackedVertexData array (sthip_scene_read_vertices)."""
         out = np.zeros(int(count), dtype=wire.PackedVertexData)
         self._check(self._lib.sthip_scene_read_vertices(self._h, int(first), int(count), wire.ptr(out)), "sthip_scene_read_vertices")
+        return out
+
+    def read_image(self, index, level=0):
+        """The stored texels of one level of gImages[index] in the image's resident format (sthip_scene_read_image): a
+        float32 array (h, w, 4) of an RGBA32F image, a uint8 array (h, w, 4) of an RGBA8_UNORM one."""
+        im = self._scene.images[int(index)]
+        h, w = max(1, im.shape[0] >> int(level)), max(1, im.shape[1] >> int(level))
+        out = np.zeros((h, w, 4), im.dtype)
+        self._check(self._lib.sthip_scene_read_image(self._h, int(index), int(level), wire.ptr(out), out.nbytes), "sthip_scene_read_image")
         return out
 
     def set_stream(self, stream_handle):

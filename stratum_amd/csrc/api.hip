@@ -24,6 +24,7 @@
 #include "bvh_build.h"
 #include "first_hits.h"
 #include "kernel_instances.h"  // kernels.h + the instantiations that live in shade_*.hip / trace_kernels.hip
+#include "mips.h"
 #include "post.h"
 #include "ceilings.h"
 
@@ -107,12 +108,14 @@ struct KeptScene {
   std::vector<sthip_TransformData> xf, inv, motion;
   std::vector<uint32_t> lights;
   std::vector<std::vector<float>> image_pixels, image1_pixels;
+  std::vector<std::vector<uint8_t>> image_bytes, image1_bytes;  // the 8-bit images, as they came: bytes (the float vector of such an image stays empty)
+  std::vector<uint8_t> image_formats, image1_formats;           // sthip_image_format per image (sthip_scene_upload_formats)
   std::vector<sthip_image_desc> images, images1;
   std::vector<float> distributions;
   std::vector<std::vector<uint8_t>> volume_bytes;
   std::vector<sthip_volume_desc> volumes;
   bool valid = false;
-  void keep(const sthip_scene_desc& s) {
+  void keep(const sthip_scene_desc& s, const uint8_t* formats, const uint8_t* formats1) {
     vertices.assign(s.gVertices, s.gVertices + (s.gVertices ? s.vertex_count : 0));
     indices.assign((const uint8_t*)s.gIndices, (const uint8_t*)s.gIndices + (s.gIndices ? s.indices_bytes : 0));
     materials.assign((const uint8_t*)s.gMaterialData, (const uint8_t*)s.gMaterialData + (s.gMaterialData ? s.material_bytes : 0));
@@ -122,16 +125,27 @@ struct KeptScene {
     motion.clear();
     if (s.gInstanceMotionTransforms) motion.assign(s.gInstanceMotionTransforms, s.gInstanceMotionTransforms + s.instance_count);
     lights.assign(s.gLightInstances, s.gLightInstances + (s.gLightInstances ? s.light_count : 0));
-    auto take = [](const sthip_image_desc* in, uint32_t n, size_t channels, std::vector<std::vector<float>>& px, std::vector<sthip_image_desc>& d) {
+    auto take = [](const sthip_image_desc* in, uint32_t n, size_t channels, const uint8_t* formats, std::vector<std::vector<float>>& px, std::vector<std::vector<uint8_t>>& bytes, std::vector<uint8_t>& fmt,
+                   std::vector<sthip_image_desc>& d) {
       px.assign(n, {});
+      bytes.assign(n, {});
+      fmt.assign(n, 0);
       d.assign(n, sthip_image_desc{});
       for (uint32_t i = 0; i < n; i++) {
-        px[i].assign(in[i].pixels, in[i].pixels + (size_t)in[i].width * in[i].height * channels);
-        d[i] = sthip_image_desc{px[i].data(), in[i].width, in[i].height};
+        const size_t count = (size_t)in[i].width * in[i].height * channels;
+        fmt[i] = formats ? formats[i] : 0;
+        if (fmt[i]) {  // 8-bit: `pixels` points at bytes
+          const uint8_t* b = reinterpret_cast<const uint8_t*>(in[i].pixels);
+          bytes[i].assign(b, b + count);
+          d[i] = sthip_image_desc{reinterpret_cast<const float*>(bytes[i].data()), in[i].width, in[i].height};
+        } else {
+          px[i].assign(in[i].pixels, in[i].pixels + count);
+          d[i] = sthip_image_desc{px[i].data(), in[i].width, in[i].height};
+        }
       }
     };
-    take(s.gImages, s.gImages ? s.image_count : 0, 4, image_pixels, images);
-    take(s.gImage1s, s.gImage1s ? s.image1_count : 0, 1, image1_pixels, images1);
+    take(s.gImages, s.gImages ? s.image_count : 0, 4, formats, image_pixels, image_bytes, image_formats, images);
+    take(s.gImage1s, s.gImage1s ? s.image1_count : 0, 1, formats1, image1_pixels, image1_bytes, image1_formats, images1);
     distributions.assign(s.gDistributions, s.gDistributions + (s.gDistributions ? s.distribution_count : 0));
     volume_bytes.assign(s.gVolumes ? s.volume_count : 0, {});
     volumes.assign(volume_bytes.size(), sthip_volume_desc{});
@@ -234,6 +248,8 @@ struct sthip_ctx {
   DevBuf<uint32_t> lights;
   DevBuf<DeviceImage> images;
   DevBuf<float4> image_texels;
+  DevBuf<uint32_t> image_texels8;        // the RGBA8 images' texels (a word per texel), every level; DeviceImage::offset indexes it for them
+  std::vector<DeviceImage> images_host;  // the table as uploaded (sthip_scene_read_image; the environment's format at render)
   uint32_t image_count = 0;
   DevBuf<float2> cone;
   uint32_t instance_count = 0, light_count = 0;
@@ -325,6 +341,7 @@ struct sthip_ctx {
   DevBuf<uint32_t> light_trace; // gLightTraceSamples
   DevBuf<DeviceImage1> images1;  // gImage1s (alpha masks)
   DevBuf<float> image1_texels;
+  DevBuf<uint8_t> image1_texels8;  // the R8 masks' texels
   DevBuf<BvhTriUv> tri_uvs;
   DevBuf<BvhTriShade> tri_shade;  // beside the leaf triangles: their vertices' normals and uvs (k_fill_tri_shade)
   DevBuf<uint32_t> hit_leaf;      // per path: the leaf triangle of its hit
@@ -623,6 +640,7 @@ void sthip_destroy(sthip_ctx* ctx) {
   ctx->lights.release();
   ctx->images.release();
   ctx->image_texels.release();
+  ctx->image_texels8.release();
   ctx->cone.release();
   ctx->nodes.release();
   ctx->tris.release();
@@ -659,6 +677,7 @@ void sthip_destroy(sthip_ctx* ctx) {
   ctx->light_trace.release();
   ctx->images1.release();
   ctx->image1_texels.release();
+  ctx->image1_texels8.release();
   ctx->tri_uvs.release();
   ctx->tri_shade.release();
   ctx->hit_leaf.release();
@@ -934,7 +953,17 @@ static int pose_rigs(sthip_ctx* ctx, const char* call) {
   return STHIP_OK;
 }
 
-int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
+// What the kept copy is built again from: the kept arrays with the formats their images were uploaded in.
+static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats);
+static int upload_kept_scene(sthip_ctx* ctx) {
+  const sthip_scene_desc d = ctx->kept.desc();
+  return scene_upload(ctx, &d, ctx->kept.image_formats.empty() ? nullptr : ctx->kept.image_formats.data(), ctx->kept.image1_formats.empty() ? nullptr : ctx->kept.image1_formats.data());
+}
+
+int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) { return scene_upload(ctx, s, nullptr, nullptr); }
+int sthip_scene_upload_formats(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats) { return scene_upload(ctx, s, image_formats, image1_formats); }
+
+static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats) {
   if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
   if (!s || !s->gInstances || !s->gInstanceTransforms || !s->gInstanceInverseTransforms || !s->gMaterialData || s->instance_count == 0)
     return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: a required array is NULL or there are no instances");
@@ -942,6 +971,10 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
     return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: vertex_count / indices_bytes > 0 but the array is NULL");
   if (s->instance_count > 0xFFFF) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: more than 65535 instances (16-bit instance index, scene.h:23)");
   if (s->light_count && !s->gLightInstances) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: light_count > 0 but gLightInstances is NULL");
+  for (uint32_t i = 0; image_formats && s->gImages && i < s->image_count; i++)
+    if (image_formats[i] > STHIP_IMAGE_FORMAT_RGBA8_UNORM) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: image_formats[" + std::to_string(i) + "] = " + std::to_string(image_formats[i]) + " is not a format of gImages");
+  for (uint32_t i = 0; image1_formats && s->gImage1s && i < s->image1_count; i++)
+    if (image1_formats[i] > STHIP_IMAGE_FORMAT_R8_UNORM) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: image1_formats[" + std::to_string(i) + "] = " + std::to_string(image1_formats[i]) + " is not a format of gImage1s");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // frames of the previous scene may still be in flight on the caller's stream (device output pointers: sthip_render only
   // enqueues), and the copies below go through the null stream, which a non-blocking stream does not wait for
@@ -968,12 +1001,13 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
   auto image_range = [&](uint32_t index, int channel, float& lo, float& hi) {
     if (!scanned[index]) {
       const float* px = s->gImages[index].pixels;
+      const uint8_t* px8 = image_formats && image_formats[index] ? reinterpret_cast<const uint8_t*>(px) : nullptr;  // RGBA8: the decoded bytes
       const size_t count = (size_t)s->gImages[index].width * s->gImages[index].height;
       for (int c = 0; c < 4; c++) {
         float a = __builtin_inff(), b = -__builtin_inff();
         bool nan = false;
         for (size_t k = 0; px && k < count; k++) {
-          const float t = px[4 * k + c];
+          const float t = px8 ? (float)px8[4 * k + c] / 255.0f : px[4 * k + c];
           if (t != t) nan = true;
           a = std::min(a, t);
           b = std::max(b, t);
@@ -1194,14 +1228,32 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
   ctx->image_dims.clear();
   for (uint32_t i = 0; i < s->image_count; i++) ctx->image_dims.emplace_back(s->gImages[i].width, s->gImages[i].height);
   // images: mip chain by 2x2 box filter, level k+1 = max(1, floor(dim / 2)), ((a + b) + (c + d)) * 0.25
+  // (RGBA8 images, sthip_scene_upload_formats: the same shape in an array of their own, (a + b + c + d + 2) >> 2 per channel,
+  // made on the device from level 0 — mips.hip)
   {
     std::vector<DeviceImage> table(s->image_count);
     std::vector<float> texels;
+    size_t texels8 = 0;  // words of image_texels8
     for (uint32_t i = 0; i < s->image_count; i++) {
       uint32_t w = s->gImages[i].width, h = s->gImages[i].height;
       if (!s->gImages[i].pixels || w == 0 || h == 0 || w > 0xFFFF || h > 0xFFFF) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: bad image");
       DeviceImage& im = table[i];
       memset(&im, 0, sizeof(im));
+      if (image_formats && image_formats[i] == STHIP_IMAGE_FORMAT_RGBA8_UNORM) {  // the layout only: the texels go up below
+        im.format = STHIP_IMAGE_FORMAT_RGBA8_UNORM;
+        for (uint32_t level = 0;; level++) {
+          im.offset[level] = (uint32_t)texels8;
+          im.w[level] = (uint16_t)w;
+          im.h[level] = (uint16_t)h;
+          im.levels = level + 1;
+          texels8 += (size_t)w * h;
+          if ((w == 1 && h == 1) || level + 1 == STHIP_MAX_MIPS) break;
+          w = std::max(1u, w / 2);
+          h = std::max(1u, h / 2);
+        }
+        if (texels8 > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_UNSUPPORTED, "scene: the RGBA8 images exceed 2^32 texels (32-bit texel offsets)");
+        continue;
+      }
       size_t level_start = texels.size();
       texels.insert(texels.end(), s->gImages[i].pixels, s->gImages[i].pixels + (size_t)w * h * 4);
       for (uint32_t level = 0;; level++) {
@@ -1233,7 +1285,17 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
     HIP_TRY(ctx, ctx->image_texels.ensure(std::max<size_t>(1, texels.size() / 4)));
     if (!table.empty()) HIP_TRY(ctx, hipMemcpy(ctx->images.p, table.data(), table.size() * sizeof(DeviceImage), hipMemcpyHostToDevice));
     if (!texels.empty()) HIP_TRY(ctx, hipMemcpy(ctx->image_texels.p, texels.data(), texels.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, ctx->image_texels8.ensure(std::max<size_t>(1, texels8)));
+    for (uint32_t i = 0; i < s->image_count; i++) {  // RGBA8: level 0 goes up as it is, each further level is one launch over the level before it, in stream order
+      const DeviceImage& im = table[i];
+      if (im.format != STHIP_IMAGE_FORMAT_RGBA8_UNORM) continue;
+      HIP_TRY(ctx, hipMemcpy(ctx->image_texels8.p + im.offset[0], s->gImages[i].pixels, (size_t)im.w[0] * im.h[0] * 4, hipMemcpyHostToDevice));
+      for (uint32_t level = 0; level + 1 < im.levels; level++)
+        if (!sthip::mip_rgba8_launch(ctx->image_texels8.p + im.offset[level], im.w[level], im.h[level], ctx->image_texels8.p + im.offset[level + 1], ctx->cu_count, ctx->stream, err)) return fail(ctx, STHIP_ERR_HIP, "scene: " + err);
+    }
+    if (texels8) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->image_count = s->image_count;
+    ctx->images_host = std::move(table);
   }
 
   // the 8-wide form permutes the leaf triangles (bvh_build.h): made before anything of the tree is uploaded
@@ -1303,13 +1365,22 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
   {  // alpha masks: one-channel images and the per-triangle uvs the traversal interpolates
     std::vector<DeviceImage1> table(s->image1_count);
     std::vector<float> texels;
+    std::vector<uint8_t> texels8;  // the R8 masks (sthip_scene_upload_formats), in an array of their own
     for (uint32_t i = 0; i < s->image1_count; i++) {
       const sthip_image_desc& im = s->gImage1s[i];
       if (!im.pixels || im.width == 0 || im.height == 0 || im.width > 0xFFFF || im.height > 0xFFFF) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: bad alpha-mask image");
-      table[i].offset = (uint32_t)texels.size();
       table[i].w = im.width;
       table[i].h = im.height;
-      table[i].pad = 0;
+      if (image1_formats && image1_formats[i] == STHIP_IMAGE_FORMAT_R8_UNORM) {
+        const uint8_t* bytes = reinterpret_cast<const uint8_t*>(im.pixels);
+        table[i].offset = (uint32_t)texels8.size();
+        table[i].format = STHIP_IMAGE_FORMAT_R8_UNORM;
+        texels8.insert(texels8.end(), bytes, bytes + (size_t)im.width * im.height);
+        if (texels8.size() > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_UNSUPPORTED, "scene: the R8 alpha masks exceed 2^32 texels (32-bit texel offsets)");
+        continue;
+      }
+      table[i].offset = (uint32_t)texels.size();
+      table[i].format = STHIP_IMAGE_FORMAT_R32F;
       texels.insert(texels.end(), im.pixels, im.pixels + (size_t)im.width * im.height);
     }
     HIP_TRY(ctx, ctx->images1.ensure(std::max<size_t>(1, table.size())));
@@ -1317,6 +1388,8 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
     HIP_TRY(ctx, ctx->tri_uvs.ensure(1));  // (sized and filled with the shading records further down, once the triangles are resident)
     if (!table.empty()) HIP_TRY(ctx, hipMemcpy(ctx->images1.p, table.data(), table.size() * sizeof(DeviceImage1), hipMemcpyHostToDevice));
     if (!texels.empty()) HIP_TRY(ctx, hipMemcpy(ctx->image1_texels.p, texels.data(), texels.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, ctx->image1_texels8.ensure(std::max<size_t>(1, texels8.size())));
+    if (!texels8.empty()) HIP_TRY(ctx, hipMemcpy(ctx->image1_texels8.p, texels8.data(), texels8.size(), hipMemcpyHostToDevice));
     HIP_TRY(ctx, ctx->inst_alpha.ensure(std::max<size_t>(1, built.inst_alpha.size())));
     if (!built.inst_alpha.empty()) HIP_TRY(ctx, hipMemcpy(ctx->inst_alpha.p, built.inst_alpha.data(), built.inst_alpha.size() * 4, hipMemcpyHostToDevice));
     ctx->bvh.inst_alpha = ctx->inst_alpha.p;
@@ -1324,6 +1397,7 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
     ctx->bvh.tri_uv = reinterpret_cast<const float2*>(ctx->tri_uvs.p);
     ctx->bvh.images1 = ctx->images1.p;
     ctx->bvh.image1_texels = ctx->image1_texels.p;
+    ctx->bvh.image1_texels8 = ctx->image1_texels8.p;
     ctx->bvh.alpha_test = 0;
     ctx->bvh.flip_uvs = 0;
   }
@@ -1408,7 +1482,7 @@ int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) {
   ctx->has_scene = true;
   ctx->reuse_grids_valid = false;  // (stored samples name materials and lights of the scene they were taken in)
   if (ctx->keep_scene) {
-    if (s->gVertices != ctx->kept.vertices.data() || !ctx->kept.valid) ctx->kept.keep(*s);  // (a rebuild from the kept copy itself keeps nothing anew)
+    if (s->gVertices != ctx->kept.vertices.data() || !ctx->kept.valid) ctx->kept.keep(*s, image_formats, image1_formats);  // (a rebuild from the kept copy itself keeps nothing anew)
   } else {
     ctx->kept = KeptScene();
   }
@@ -1627,9 +1701,8 @@ int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf,
         ctx->kept.motion.assign(motion, motion + instance_count);
       else
         ctx->kept.motion.clear();
-      const sthip_scene_desc d = ctx->kept.desc();
       ctx->stats.full_rebuilds++;
-      return sthip_scene_upload(ctx, &d);
+      return upload_kept_scene(ctx);
     }
     return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: " + err);
   }
@@ -1758,9 +1831,8 @@ static int update_resident_vertices(sthip_ctx* ctx, const VertexSource& src, sth
   auto rebuild_from_kept = [&]() {  // (the kept vertices hold the new range already, or get the posed ranges back from the device here)
     int rc = sync_kept_vertices(ctx);
     if (rc != STHIP_OK) return rc;
-    const sthip_scene_desc d = ctx->kept.desc();
     ctx->stats.full_rebuilds++;
-    rc = sthip_scene_upload(ctx, &d);
+    rc = upload_kept_scene(ctx);
     if (info) {
       info->rebuilt = 1;
       info->device_ms = ctx->stats.bvh_build_gpu_ms;
@@ -1958,6 +2030,22 @@ int sthip_scene_animate(sthip_ctx* ctx, const sthip_rig_pose* poses, uint32_t po
   return update_resident_vertices(ctx, VertexSource{"sthip_scene_animate", nullptr, 0, 0}, info, t0);
 }
 
+int sthip_scene_read_image(sthip_ctx* ctx, uint32_t image_index, uint32_t level, void* out, uint64_t out_bytes) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_image before sthip_scene_upload");
+  if (image_index >= ctx->image_count || image_index >= ctx->images_host.size()) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_image: image_index is not in gImages");
+  const DeviceImage& im = ctx->images_host[image_index];
+  if (level >= im.levels) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_image: the image has " + std::to_string(im.levels) + " levels");
+  const bool bytes = im.format == STHIP_IMAGE_FORMAT_RGBA8_UNORM;
+  const uint64_t want = (uint64_t)im.w[level] * im.h[level] * (bytes ? 4u : 16u);
+  if (!out || out_bytes != want) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_image: the level holds " + std::to_string(want) + " bytes; out is NULL or out_bytes differs");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const void* src = bytes ? (const void*)(ctx->image_texels8.p + im.offset[level]) : (const void*)(ctx->image_texels.p + im.offset[level]);
+  HIP_TRY(ctx, hipMemcpy(out, src, (size_t)want, hipMemcpyDeviceToHost));
+  return STHIP_OK;
+}
+
 int sthip_scene_read_vertices(sthip_ctx* ctx, uint32_t first_vertex, uint32_t vertex_count, sthip_PackedVertexData* out) {
   if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
   if (!ctx->has_scene) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_vertices before sthip_scene_upload");
@@ -2135,6 +2223,9 @@ static int plan_render(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc_in, uin
     memcpy(rec, ctx->materials_host.data() + addr, 16);
     if (rec[3] < STHIP_IMAGE_COUNT) {
       if (rec[3] >= ctx->image_count || addr + 32 > ctx->materials_host.size()) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "render: the environment refers to an image that is not in gImages");
+      // (the environment's lookups and its texel descent read the float array at every level: shading.h, Environment)
+      if (rec[3] < ctx->images_host.size() && ctx->images_host[rec[3]].format != STHIP_IMAGE_FORMAT_RGBA32F)
+        return fail(ctx, STHIP_ERR_UNSUPPORTED, "render: the environment map is an 8-bit image (gImages[" + std::to_string(rec[3]) + "] is RGBA8_UNORM): upload it as RGBA32F");
       memcpy(rec, ctx->materials_host.data() + addr, 32);
       const size_t w = ctx->image_dims[rec[3]].first, h = ctx->image_dims[rec[3]].second;
       const size_t need[4] = {h, w * h, h + 1, (w + 1) * h};  // marginal_pdf, row_pdf, marginal_cdf, row_cdf (dist2.h)
@@ -2517,6 +2608,7 @@ static int bind_frame_params(sthip_ctx* ctx, const RenderPlan& r, const sthip_fr
   p.scene.light_count = ctx->light_count;
   p.scene.images = ctx->images.p;
   p.scene.image_texels = ctx->image_texels.p;
+  p.scene.image_texels8 = ctx->image_texels8.p;
   p.scene.image_count = ctx->image_count;
   p.scene.distributions = ctx->distributions.p;
   p.scene.distribution_count = ctx->distribution_count;

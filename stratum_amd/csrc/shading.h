@@ -21,6 +21,7 @@ struct DeviceScene {
   // Texture2D<float4> gImages[] (bdpt.hlsl:33): mip chains packed into one float4 buffer
   const struct DeviceImage* images;
   const float4* image_texels;
+  const uint32_t* image_texels8;  // the texels of the RGBA8 images (DeviceImage::format): one word per texel, R in the low byte
   uint32_t image_count;
   const float* distributions;  // StructuredBuffer<float> gDistributions (environment map tables, dist2.h)
   uint32_t distribution_count;
@@ -34,13 +35,20 @@ struct DeviceScene {
   const float4* leaf_shade;
 };
 
+#ifndef STHIP_MAX_MIPS
 #define STHIP_MAX_MIPS 16
+#endif
 struct DeviceImage {
-  uint32_t offset[STHIP_MAX_MIPS];  // first texel of each level in image_texels
+  uint32_t offset[STHIP_MAX_MIPS];  // first texel of each level in image_texels (format 0) or in image_texels8 (format 1)
   uint16_t w[STHIP_MAX_MIPS], h[STHIP_MAX_MIPS];
   uint32_t levels;
-  uint32_t pad[3];
+  uint32_t format;  // sthip_image_format: STHIP_IMAGE_FORMAT_RGBA32F / STHIP_IMAGE_FORMAT_RGBA8_UNORM, uniform per image
+  uint32_t pad[2];
 };
+// an RGBA8 texel decoded: each byte b is the correctly rounded quotient (float)b / 255.0f (sthip.h; IEEE division)
+DEV float4 decode_rgba8(uint32_t t) {
+  return make_float4((float)(t & 0xFFu) / 255.0f, (float)((t >> 8) & 0xFFu) / 255.0f, (float)((t >> 16) & 0xFFu) / 255.0f, (float)(t >> 24) / 255.0f);
+}
 
 // scene.h:29-47
 struct Inst {
@@ -419,19 +427,25 @@ struct DisneyMaterial {
 
   // sample_image, image_value.h:81-97: SampleLevel(gStaticSampler, uv, lod) as repeat addressing + trilinear
   // filtering over the box-filtered mip chain
+  // RGBA8: the image's texels are bytes (DeviceImage::format, STHIP_IMAGE_FORMAT_RGBA8_UNORM): one dword per texel, decoded
+  // after the load. The format is uniform per image, so sample_image branches once per lookup and each side is straight-line code.
+  template <bool RGBA8>
   static DEV float4 texel(const DeviceScene& sc, const DeviceImage& im, uint32_t level, int x, int y) {
     const int w = (int)im.w[level], h = (int)im.h[level];
     x = ((x % w) + w) % w;
     y = ((y % h) + h) % h;
-    return sc.image_texels[im.offset[level] + (uint32_t)y * (uint32_t)w + (uint32_t)x];
+    const uint32_t at = im.offset[level] + (uint32_t)y * (uint32_t)w + (uint32_t)x;
+    if (RGBA8) return decode_rgba8(sc.image_texels8[at]);
+    return sc.image_texels[at];
   }
+  template <bool RGBA8>
   static DEV float4 bilinear(const DeviceScene& sc, const DeviceImage& im, uint32_t level, float u, float v) {
     const float x = u * (float)im.w[level] - 0.5f, y = v * (float)im.h[level] - 0.5f;
     const float x0 = floorf(x), y0 = floorf(y);
     const float fx = x - x0, fy = y - y0;
     const int ix = (int)x0, iy = (int)y0;
-    const float4 c00 = texel(sc, im, level, ix, iy), c10 = texel(sc, im, level, ix + 1, iy);
-    const float4 c01 = texel(sc, im, level, ix, iy + 1), c11 = texel(sc, im, level, ix + 1, iy + 1);
+    const float4 c00 = texel<RGBA8>(sc, im, level, ix, iy), c10 = texel<RGBA8>(sc, im, level, ix + 1, iy);
+    const float4 c01 = texel<RGBA8>(sc, im, level, ix, iy + 1), c11 = texel<RGBA8>(sc, im, level, ix + 1, iy + 1);
     float4 r;
     r.x = lerp1(lerp1(c00.x, c10.x, fx), lerp1(c01.x, c11.x, fx), fy);
     r.y = lerp1(lerp1(c00.y, c10.y, fx), lerp1(c01.y, c11.y, fx), fy);
@@ -448,7 +462,12 @@ struct DisneyMaterial {
     const float l0 = floorf(lod);
     const uint32_t i0 = (uint32_t)l0, i1 = min(i0 + 1, im.levels - 1);
     const float f = lod - l0;
-    const float4 a = bilinear(sc, im, i0, u, v), b = bilinear(sc, im, i1, u, v);
+    float4 a, b;
+    if (im.format) {
+      a = bilinear<true>(sc, im, i0, u, v), b = bilinear<true>(sc, im, i1, u, v);
+    } else {
+      a = bilinear<false>(sc, im, i0, u, v), b = bilinear<false>(sc, im, i1, u, v);
+    }
     return make_float4(lerp1(a.x, b.x, f), lerp1(a.y, b.y, f), lerp1(a.z, b.z, f), lerp1(a.w, b.w, f));
   }
   static DEV float4 eval_image_value4(const DeviceScene& sc, const float* p, float u, float v, float uvs, bool ray_cones) {  // image_value.h:194-198

@@ -33,6 +33,7 @@ struct DeviceBvh {
   const uint32_t* inst_alpha;   // per instance: gImage1s index of its material's mask, BVH_NO_ALPHA if none
   const struct DeviceImage1* images1;
   const float* image1_texels;
+  const uint8_t* image1_texels8;  // the texels of the R8 masks (DeviceImage1::format)
   uint32_t alpha_test;
   uint32_t flip_uvs;            // gFlipTriangleUVs for the mask lookup
   const DeviceVolume* volumes;  // gVolumes headers (volume instances are top-level entries tested in place, like spheres)
@@ -63,7 +64,8 @@ struct DeviceBvh {
   uint32_t wide8_tri_min;  // the leaf phase of the 8-wide walk goes on while at least this many lanes of the wave hold a triangle ("tri_min_lanes")
 };
 struct DeviceImage1 {
-  uint32_t offset, w, h, pad;
+  uint32_t offset, w, h;  // offset: first texel in image1_texels (format 0) or in image1_texels8 (format 1)
+  uint32_t format;        // sthip_image_format: STHIP_IMAGE_FORMAT_R32F / STHIP_IMAGE_FORMAT_R8_UNORM
 };
 // level-0 lookup of a one-channel image: bilinear, repeat addressing (the same arithmetic as DisneyMaterial::bilinear)
 DEV float sample_image1(const DeviceBvh& bvh, uint32_t index, float u, float v) {
@@ -74,8 +76,17 @@ DEV float sample_image1(const DeviceBvh& bvh, uint32_t index, float u, float v) 
   const int w = (int)im.w, h = (int)im.h;
   const int ix = (int)x0, iy = (int)y0;
   const int xa = ((ix % w) + w) % w, xb = (((ix + 1) % w) + w) % w, ya = ((iy % h) + h) % h, yb = (((iy + 1) % h) + h) % h;
-  const float* t = bvh.image1_texels + im.offset;
-  const float a = lerp1(t[(size_t)ya * w + xa], t[(size_t)ya * w + xb], fx), b = lerp1(t[(size_t)yb * w + xa], t[(size_t)yb * w + xb], fx);
+  float t00, t10, t01, t11;
+  if (im.format) {  // STHIP_IMAGE_FORMAT_R8_UNORM: bytes, decoded as (float)b / 255.0f (sthip.h)
+    const uint8_t* t = bvh.image1_texels8 + im.offset;
+    t00 = (float)t[(size_t)ya * w + xa] / 255.0f, t10 = (float)t[(size_t)ya * w + xb] / 255.0f;
+    t01 = (float)t[(size_t)yb * w + xa] / 255.0f, t11 = (float)t[(size_t)yb * w + xb] / 255.0f;
+  } else {
+    const float* t = bvh.image1_texels + im.offset;
+    t00 = t[(size_t)ya * w + xa], t10 = t[(size_t)ya * w + xb];
+    t01 = t[(size_t)yb * w + xa], t11 = t[(size_t)yb * w + xb];
+  }
+  const float a = lerp1(t00, t10, fx), b = lerp1(t01, t11, fx);
   return lerp1(a, b, fy);
 }
 

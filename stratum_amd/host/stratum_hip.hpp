@@ -44,6 +44,9 @@
 #pragma weak sthip_scene_set_rigs
 #pragma weak sthip_scene_animate
 #pragma weak sthip_scene_read_vertices
+// ... and one without 8-bit resident textures lacks these: Scene::update then converts such images to float on the host
+#pragma weak sthip_scene_upload_formats
+#pragma weak sthip_scene_read_image
 // ... and one without the post block lacks these: Denoiser::denoise then throws
 #pragma weak sthip_accumulate
 #pragma weak sthip_denoise_filter
@@ -378,15 +381,22 @@ inline TransformData node_to_world(const Node& node) {
 // ------------------------------------------------------------------------------------------------
 // scene components: Material.hpp:13-38, Scene.hpp:15-37
 // ------------------------------------------------------------------------------------------------
-// an RGBA32F texture (what the reference holds as an Image::View of a Texture2D<float4>)
+// an RGBA32F texture (what the reference holds as an Image::View of a Texture2D<float4>), or an RGBA8_UNORM one
+// (R8G8B8A8Unorm, Scene.cpp:178,229) when `bytes` is filled instead of `pixels`: it then goes up and stays resident as bytes
 struct Image {
   uint32_t width = 0, height = 0;
-  std::vector<float> pixels;  // width * height * 4, row 0 first
+  std::vector<float> pixels;   // width * height * 4, row 0 first
+  std::vector<uint8_t> bytes;  // width * height * 4, row 0 first: a byte b is the texel (float)b / 255.0f (sthip.h)
+  bool is_8bit() const { return !bytes.empty(); }
+  float channel(size_t i) const { return is_8bit() ? (float)bytes[i] / 255.0f : pixels[i]; }
 };
-// a one-channel float texture (Texture2D<float>): what Material::alpha_mask holds (R8Unorm coverage upstream, Scene.cpp:182)
+// a one-channel texture (Texture2D<float>): what Material::alpha_mask holds (R8Unorm coverage upstream, Scene.cpp:182), as floats
+// or, when `bytes` is filled instead of `pixels`, as R8_UNORM
 struct Image1 {
   uint32_t width = 0, height = 0;
-  std::vector<float> pixels;  // width * height, row 0 first
+  std::vector<float> pixels;   // width * height, row 0 first
+  std::vector<uint8_t> bytes;  // width * height, row 0 first
+  bool is_8bit() const { return !bytes.empty(); }
 };
 // MaterialResources, image_value.h:34-66: images get their gImages / gImage1s index the first time a material stores them
 struct MaterialResources {
@@ -600,7 +610,8 @@ inline void build_distributions(const Image& img, std::vector<float>& pdf_margin
   cdf_rows.assign((size_t)(W + 1) * H, 0.f);
   const float invHeight = 1 / (float)H;
   auto f = [&](uint32_t x, uint32_t y) -> double {
-    const float* c = &img.pixels[4 * ((size_t)y * W + x)];
+    const size_t at = 4 * ((size_t)y * W + x);
+    const float c[3] = {img.channel(at), img.channel(at + 1), img.channel(at + 2)};
     const float lum = (c[0] * 0.2126f + c[1] * 0.7152f) + c[2] * 0.0722f;
     return lum * std::sin(M_PI * (y + 0.5f) * invHeight);
   };
@@ -727,6 +738,17 @@ class Scene {
     std::vector<Node*> mInstanceNodes;
     MaterialResources mResources;
     std::vector<sthip_image_desc> mImageDescs, mImage1Descs;
+    // sthip_image_format per image: 1 where the descriptor points at the bytes of an 8-bit image. With a library that lacks
+    // sthip_scene_upload_formats all are 0 and the 8-bit images are converted to floats here (mConvertedImages)
+    std::vector<uint8_t> mImageFormats, mImage1Formats;
+    std::vector<std::vector<float>> mConvertedImages;
+    // the scene to a context, with the formats where some image is 8-bit
+    int upload(sthip_ctx* ctx) const {
+      const sthip_scene_desc d = desc();
+      const auto any = [](const std::vector<uint8_t>& f) { return std::find_if(f.begin(), f.end(), [](uint8_t v) { return v != 0; }) != f.end(); };
+      if (!any(mImageFormats) && !any(mImage1Formats)) return sthip_scene_upload(ctx, &d);
+      return sthip_scene_upload_formats(ctx, &d, mImageFormats.empty() ? nullptr : mImageFormats.data(), mImage1Formats.empty() ? nullptr : mImage1Formats.data());
+    }
     std::vector<sthip_volume_desc> mVolumeDescs;                          // gVolumes
     std::vector<std::pair<const Medium*, uint32_t>> mMediumInstances;     // Medium component -> its volume instance (mInstanceTransformMap)
     std::vector<float> mDistributionData;  // gDistributions, Scene.cpp:670-683
@@ -946,8 +968,24 @@ class Scene {
         environment->store(sd->mMaterialData, sd->mResources);
       }
     });
-    for (const Image* im : sd->mResources.image4s) sd->mImageDescs.push_back(sthip_image_desc{im->pixels.data(), im->width, im->height});
-    for (const Image1* im : sd->mResources.image1s) sd->mImage1Descs.push_back(sthip_image_desc{im->pixels.data(), im->width, im->height});
+    // an 8-bit image goes over as its bytes (sthip_scene_upload_formats); a library without the call gets the decoded floats
+    const auto describe = [&](const std::vector<float>& pixels, const std::vector<uint8_t>& bytes, uint32_t width, uint32_t height, std::vector<sthip_image_desc>& descs, std::vector<uint8_t>& formats) {
+      if (bytes.empty()) {
+        descs.push_back(sthip_image_desc{pixels.data(), width, height});
+        formats.push_back(0);
+      } else if (sthip_scene_upload_formats) {
+        descs.push_back(sthip_image_desc{reinterpret_cast<const float*>(bytes.data()), width, height});
+        formats.push_back(1);
+      } else {
+        sd->mConvertedImages.emplace_back(bytes.size());
+        std::vector<float>& f = sd->mConvertedImages.back();  // (its heap block stays where it is when the outer vector grows)
+        for (size_t i = 0; i < bytes.size(); i++) f[i] = (float)bytes[i] / 255.0f;
+        descs.push_back(sthip_image_desc{f.data(), width, height});
+        formats.push_back(0);
+      }
+    };
+    for (const Image* im : sd->mResources.image4s) describe(im->pixels, im->bytes, im->width, im->height, sd->mImageDescs, sd->mImageFormats);
+    for (const Image1* im : sd->mResources.image1s) describe(im->pixels, im->bytes, im->width, im->height, sd->mImage1Descs, sd->mImage1Formats);
     sd->mDistributionData.resize(sd->mResources.distribution_data_size);
     for (const auto& e : sd->mResources.distribution_data_map) std::copy(e.first->begin(), e.first->end(), sd->mDistributionData.begin() + e.second);  // Scene.cpp:679-680
     mSceneData = sd;
@@ -1256,7 +1294,7 @@ class BDPT {
       }
     }
     mLastUpdateWasTransformsOnly = updated;
-    if (!updated && sthip_scene_upload(mCtx, &d) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_upload: ") + sthip_last_error(mCtx));
+    if (!updated && sd.upload(mCtx) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_upload: ") + sthip_last_error(mCtx));
     if (!updated) {  // the upload dropped the rigs: they go up once, over the rest poses that just went up, and take their pose
       mRigsResident = false;
       if (rigs) {

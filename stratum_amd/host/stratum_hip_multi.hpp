@@ -236,13 +236,13 @@ class MultiDeviceBDPT : public BDPT {
         took_update[r] = 1;
         return;
       }
-      if (sthip_scene_upload(mRanks[r].ctx, &d) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_upload (rank ") + std::to_string(r) + "): " + sthip_last_error(mRanks[r].ctx));
+      if (scene->data()->upload(mRanks[r].ctx) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_upload (rank ") + std::to_string(r) + "): " + sthip_last_error(mRanks[r].ctx));
     });
     if (transforms_only)  // a rank that had to fall back to the full upload (cannot happen with identical histories) makes everyone do so
       for (size_t r = 1; r < mRanks.size(); r++)
         if (!took_update[r]) {
           mThreads->run(0, [&](size_t q) {
-            if (sthip_scene_upload(mRanks[q].ctx, &d) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_upload (rank ") + std::to_string(q) + "): " + sthip_last_error(mRanks[q].ctx));
+            if (scene->data()->upload(mRanks[q].ctx) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_upload (rank ") + std::to_string(q) + "): " + sthip_last_error(mRanks[q].ctx));
           });
           break;
         }

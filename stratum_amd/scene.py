@@ -94,8 +94,8 @@ class SceneData:
         self.motion_transforms = motion_xf
         self.materials = materials
         self.lights = lights
-        self.images = []  # RGBA32F arrays (H, W, 4): Texture2D<float4> gImages[]
-        self.images1 = []  # float32 arrays (H, W): Texture2D<float> gImage1s[] (alpha masks)
+        self.images = []  # float32 (RGBA32F) or uint8 (RGBA8_UNORM) arrays (H, W, 4): Texture2D<float4> gImages[]
+        self.images1 = []  # float32 or uint8 (R8_UNORM) arrays (H, W): Texture2D<float> gImage1s[] (alpha masks)
         self.distributions = np.zeros(0, np.float32)  # StructuredBuffer<float> gDistributions
         self.environment_address = 0xFFFFFFFF  # SceneData::mEnvironmentMaterialAddress, Scene.cpp:631-640
         self.volumes = []  # uint8 arrays: ByteAddressBuffer gVolumes[] (NanoVDB float grids)
@@ -157,6 +157,17 @@ class SceneData:
                     out[v] = i
         return out
 
+    def formats(self):
+        """(image_formats, image1_formats) for sthip_scene_upload_formats: per image 1 where the array is uint8 (uploaded and
+        kept resident as 8-bit texels), 0 where it is float32 (as sthip_scene_upload takes it)."""
+        for im in list(self.images) + list(self.images1):
+            if im.dtype not in (np.uint8, np.float32) or not im.flags["C_CONTIGUOUS"]:
+                raise ValueError("an image must be a C-contiguous float32 or uint8 array, not %s" % (im.dtype,))
+        return (
+            np.array([wire.IMAGE_FORMAT_RGBA8_UNORM if im.dtype == np.uint8 else wire.IMAGE_FORMAT_RGBA32F for im in self.images], np.uint8),
+            np.array([wire.IMAGE_FORMAT_R8_UNORM if im.dtype == np.uint8 else wire.IMAGE_FORMAT_R32F for im in self.images1], np.uint8),
+        )
+
     def desc(self):
         d = wire.SceneDesc()
         d.gVertices = wire.ptr(self.vertices)
@@ -211,8 +222,8 @@ class SceneBuilder:
         self._meshes = []  # (first_vertex, indices_byte_offset, prim_count, stride)
         self._materials = []  # MaterialRecord entries
         self._instances = []  # (mesh, material index, 4x4 transform)
-        self._images = []  # RGBA32F (H, W, 4)
-        self._images1 = []  # float32 (H, W): one-channel images (alpha masks)
+        self._images = []  # RGBA32F (H, W, 4), or uint8 (H, W, 4): RGBA8_UNORM
+        self._images1 = []  # float32 (H, W), or uint8 (H, W): one-channel images (alpha masks)
         self._spheres = []  # (material index, 4x4 node transform, radius): SpherePrimitive, Scene.hpp:34-37
         self._environment = None  # (value rgb, image handle or None): Environment, environment.h
 
@@ -242,15 +253,17 @@ class SceneBuilder:
         return len(self._materials) - 1  # a handle; byte addresses are assigned in build() in order of first use
 
     def add_image(self, rgba):
-        """Registers a Texture2D<float4> (float32 array H x W x 4, row 0 first); returns its index in gImages."""
-        im = np.ascontiguousarray(rgba, dtype=np.float32)
+        """Registers a Texture2D<float4> (float32 array H x W x 4, row 0 first); returns its index in gImages.
+        A uint8 array stays uint8: it is uploaded and kept resident as RGBA8_UNORM (a byte b is the texel b / 255)."""
+        im = np.ascontiguousarray(rgba, dtype=np.uint8 if np.asarray(rgba).dtype == np.uint8 else np.float32)
         assert im.ndim == 3 and im.shape[2] == 4
         self._images.append(im)
         return len(self._images) - 1
 
     def add_image1(self, gray):
-        """Registers a Texture2D<float> (float32 array H x W, row 0 first); returns its handle (gImage1s index by first use)."""
-        im = np.ascontiguousarray(gray, dtype=np.float32)
+        """Registers a Texture2D<float> (float32 array H x W, row 0 first); returns its handle (gImage1s index by first use).
+        A uint8 array stays uint8: it is uploaded and kept resident as R8_UNORM."""
+        im = np.ascontiguousarray(gray, dtype=np.uint8 if np.asarray(gray).dtype == np.uint8 else np.float32)
         assert im.ndim == 2
         self._images1.append(im)
         return len(self._images1) - 1
@@ -459,7 +472,8 @@ class SceneBuilder:
             rec[3] = image_index(0xFFFFFFFF if image is None else image)
             parts = [rec]
             if image is not None:  # Environment::store, environment.h:17-22: offsets into gDistributions in get_index order
-                tables = build_distributions(self._images[int(image)])  # marginal_pdf, row_pdf, marginal_cdf, row_cdf
+                env = self._images[int(image)]  # (an 8-bit environment is refused at render; its tables are those of the decoded bytes)
+                tables = build_distributions(env.astype(np.float32) / np.float32(255) if env.dtype == np.uint8 else env)  # marginal_pdf, row_pdf, marginal_cdf, row_cdf
                 offs, off = [], 0
                 for t in tables:
                     offs.append(off)

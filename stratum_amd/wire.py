@@ -171,6 +171,14 @@ class ImageDesc(C.Structure):
     _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
+# sthip_image_format (include/sthip.h): the resident texel format of an image, per image (sthip_scene_upload_formats)
+IMAGE_FORMAT_RGBA32F = 0
+IMAGE_FORMAT_RGBA8_UNORM = 1  # gImages: width * height * 4 bytes; a byte b decodes to float32(b) / float32(255)
+IMAGE_FORMAT_R32F = 0
+IMAGE_FORMAT_R8_UNORM = 1  # gImage1s: width * height bytes
+MAX_MIPS = 16  # levels of a mip chain at most (STHIP_MAX_MIPS)
+
+
 class FrameDesc(C.Structure):
     _fields_ = [
         ("gViews", C.c_void_p),
