@@ -214,7 +214,13 @@ int sthip_set_stream(sthip_ctx* ctx, void* hip_stream);
 /* ---- scene: replaces BLAS/TLAS build + descriptor writes (Scene.cpp:429-509,614-629; BDPT.cpp:341-421) ----
  * Both scene calls first wait for the work already enqueued on the context's stream (frames of the previous scene that
  * were rendered with device output pointers), then replace the resident arrays: a caller never has to synchronise
- * before re-uploading. */
+ * before re-uploading.
+ * The arguments are checked first, everything that can be decided without building the acceleration structure: a call
+ * refused there (STHIP_ERR_INVALID_ARGUMENT: a NULL array, an index or address out of range, a bad image, a format that is
+ * none; STHIP_ERR_UNSUPPORTED: 8-bit texels beyond 32-bit offsets) changes nothing but sthip_last_error — the previous scene
+ * stays resident and renderable, with its rigs and everything kept for it. A failure after that (the builder refuses the
+ * meshes, a HIP error) leaves NO scene resident. A scene wrong in one way gets the code and message it always got; of two
+ * mistakes at once, one found by these checks is reported before one only the builder finds. */
 int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* scene);
 
 /* sthip_scene_upload with a resident format per image (sthip_image_format above): image_formats has scene->image_count

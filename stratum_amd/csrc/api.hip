@@ -26,6 +26,7 @@
 #include "kernel_instances.h"  // kernels.h + the instantiations that live in shade_*.hip / trace_kernels.hip
 #include "mips.h"
 #include "post.h"
+#include "scene_prepare.h"
 #include "ceilings.h"
 
 STHIP_DECLARE_KERNEL_INSTANCES
@@ -154,6 +155,12 @@ struct KeptScene {
       volumes[i] = sthip_volume_desc{volume_bytes[i].data(), s.gVolumes[i].bytes};
     }
     valid = true;
+  }
+  void set_transforms(const sthip_TransformData* new_xf, const sthip_TransformData* new_inv, const sthip_TransformData* new_motion, uint32_t n) {  // (motion NULL: identity)
+    xf.assign(new_xf, new_xf + n);
+    inv.assign(new_inv, new_inv + n);
+    motion.clear();
+    if (new_motion) motion.assign(new_motion, new_motion + n);
   }
   sthip_scene_desc desc() const {
     sthip_scene_desc d{};
@@ -835,30 +842,26 @@ static hipError_t upload_nodes(sthip_ctx* ctx, size_t first, const BvhNode* node
   return hipMemcpy(ctx->nodes.p + first, slots.data(), count * sizeof(BvhNodeSlot), hipMemcpyHostToDevice);
 }
 
-// EmitterBounds from the exact box of an emitter's vertices: widened by 2^-15 of its coordinates' magnitude, as the packed nodes
-// of the tree are, and the sphere that sizes the per-ray padding. false: not finite (the table cannot be used).
-static bool pad_emitter_bounds(EmitterBounds& b) {
-  double diag = 0;
-  for (int a = 0; a < 3; a++) {
-    const float mag = std::max(fabsf(b.lo[a]), fabsf(b.hi[a])) * (1.0f / 32768.0f) + 1e-30f;
-    b.lo[a] -= mag;
-    b.hi[a] += mag;
-    b.sphere[a] = 0.5f * b.lo[a] + 0.5f * b.hi[a];
-    diag += ((double)b.hi[a] - b.lo[a]) * ((double)b.hi[a] - b.lo[a]);
-  }
-  b.sphere[3] = (float)sqrt(diag);  // (twice the box's own radius: the padding only has to be large enough)
-  return std::isfinite(b.sphere[3]);
+static void clear_wide(sthip_ctx* ctx) {  // no 4-wide form: k_trace walks the binary tree (or the 8-wide form)
+  ctx->bvh.wide_nodes = nullptr;
+  ctx->bvh.wide_entries = nullptr;
+  ctx->bvh.wide_root_ref = BVH_INVALID_REF;
+  ctx->bvh.wide_stack_depth = 0;
+  ctx->wide_node_count = 0;
+}
+static void clear_wide8(sthip_ctx* ctx) {  // no 8-wide form (ctx->wide8_host stays: a new top level is made behind its bottom levels)
+  ctx->bvh.wide8_nodes = nullptr;
+  ctx->bvh.wide8_entries = nullptr;
+  ctx->bvh.wide8_root = BVH_INVALID_REF;
+  ctx->bvh.wide8_stack_depth = 0;
+  ctx->wide8_node_count = 0;
 }
 
 // The 4-wide form of the tree that is resident now (ctx->nodes / ctx->entries / ctx->bvh.root_ref), made on the device
 // (wide.hip): after a GPU build and after a transforms-only update. On failure the binary walk stays (STHIP_OK): a tree whose
 // boxes do not fit the wide nodes' grid is still a tree.
 static int collapse_resident_tree(sthip_ctx* ctx) {
-  ctx->bvh.wide_nodes = nullptr;
-  ctx->bvh.wide_entries = nullptr;
-  ctx->bvh.wide_root_ref = BVH_INVALID_REF;
-  ctx->bvh.wide_stack_depth = 0;
-  ctx->wide_node_count = 0;
+  clear_wide(ctx);
   const size_t count = (size_t)ctx->bvh_nodes;
   if (count == 0 || ctx->bvh.root_ref == BVH_INVALID_REF || (ctx->bvh.root_ref & BVH_LEAF_BIT) || count * sizeof(WideNode) > 0xFFFFFFFFull) return STHIP_OK;
   if (!ctx->wide_scratch) ctx->wide_scratch = sthip::device_wide_scratch_create();
@@ -963,21 +966,30 @@ static int upload_kept_scene(sthip_ctx* ctx) {
 int sthip_scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s) { return scene_upload(ctx, s, nullptr, nullptr); }
 int sthip_scene_upload_formats(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats) { return scene_upload(ctx, s, image_formats, image1_formats); }
 
-static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats) {
-  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
-  if (!s || !s->gInstances || !s->gInstanceTransforms || !s->gInstanceInverseTransforms || !s->gMaterialData || s->instance_count == 0)
-    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: a required array is NULL or there are no instances");
-  if ((s->vertex_count && !s->gVertices) || (s->indices_bytes && !s->gIndices))  // a scene of sphere instances alone has neither
-    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: vertex_count / indices_bytes > 0 but the array is NULL");
-  if (s->instance_count > 0xFFFF) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: more than 65535 instances (16-bit instance index, scene.h:23)");
-  if (s->light_count && !s->gLightInstances) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: light_count > 0 but gLightInstances is NULL");
-  for (uint32_t i = 0; image_formats && s->gImages && i < s->image_count; i++)
-    if (image_formats[i] > STHIP_IMAGE_FORMAT_RGBA8_UNORM) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: image_formats[" + std::to_string(i) + "] = " + std::to_string(image_formats[i]) + " is not a format of gImages");
-  for (uint32_t i = 0; image1_formats && s->gImage1s && i < s->image1_count; i++)
-    if (image1_formats[i] > STHIP_IMAGE_FORMAT_R8_UNORM) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: image1_formats[" + std::to_string(i) + "] = " + std::to_string(image1_formats[i]) + " is not a format of gImage1s");
+// ---- the phases of an upload, in the order scene_upload runs them ----
+// What scene_prepare.cpp makes of a checked scene on the host, before anything of the context changes
+struct PreparedScene {
+  sthip::MaterialAnalysis materials;
+  sthip::ImageLayout images;
+  sthip::MaskLayout masks;
+  std::vector<uint32_t> volume_first_words;
+  size_t volume_words = 0;
+};
+static int prepare_scene(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats, PreparedScene& prep) {
+  prep.materials = sthip::analyse_materials(*s, image_formats);
+  prep.images = sthip::layout_images(*s, image_formats);
+  if (prep.images.error) return fail(ctx, STHIP_ERR_UNSUPPORTED, prep.images.error);
+  prep.masks = sthip::layout_alpha_masks(*s, image1_formats);
+  if (prep.masks.error) return fail(ctx, STHIP_ERR_UNSUPPORTED, prep.masks.error);
+  prep.volume_words = sthip::volume_first_words(*s, prep.volume_first_words);
+  return STHIP_OK;
+}
+
+// The previous scene goes away: from here on no scene is resident until the call has succeeded
+static int retire_scene(sthip_ctx* ctx, const sthip_scene_desc* s) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // frames of the previous scene may still be in flight on the caller's stream (device output pointers: sthip_render only
-  // enqueues), and the copies below go through the null stream, which a non-blocking stream does not wait for
+  // enqueues), and the copies of the upload go through the null stream, which a non-blocking stream does not wait for
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, drain_in_flight(ctx));  // ... and the copy stream of sthip_render_async still reads the staging sets of its frames
   ctx->has_scene = false;
@@ -989,126 +1001,29 @@ static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t
     drop_rigs(ctx);
     ctx->kept_stale.clear();
   }
-  for (uint32_t i = 0; i < s->light_count; i++)
-    if (s->gLightInstances[i] >= s->instance_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: gLightInstances entry out of range");
-  bool any_specular = false, any_image = false, any_alpha = false;
-  if (s->image_count && !s->gImages) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: image_count > 0 but gImages is NULL");
-  // Per-channel extremes of an image (level 0; every mip level is an average of it, and bilinear / trilinear taps are
-  // convex combinations, so a sampled value lies between them). Scanned on first use: the device multiplies the
-  // constant by the texel (image_value.h:194-198), so whether a material can be specular depends on the texels.
-  std::vector<int> scanned(s->image_count, 0);
-  std::vector<float> tex_min((size_t)s->image_count * 4, 0.0f), tex_max((size_t)s->image_count * 4, 0.0f);
-  auto image_range = [&](uint32_t index, int channel, float& lo, float& hi) {
-    if (!scanned[index]) {
-      const float* px = s->gImages[index].pixels;
-      const uint8_t* px8 = image_formats && image_formats[index] ? reinterpret_cast<const uint8_t*>(px) : nullptr;  // RGBA8: the decoded bytes
-      const size_t count = (size_t)s->gImages[index].width * s->gImages[index].height;
-      for (int c = 0; c < 4; c++) {
-        float a = __builtin_inff(), b = -__builtin_inff();
-        bool nan = false;
-        for (size_t k = 0; px && k < count; k++) {
-          const float t = px8 ? (float)px8[4 * k + c] / 255.0f : px[4 * k + c];
-          if (t != t) nan = true;
-          a = std::min(a, t);
-          b = std::max(b, t);
-        }
-        if (nan || !px || !count) a = -__builtin_inff(), b = __builtin_inff();  // unknown: everything is possible
-        tex_min[(size_t)index * 4 + c] = a;
-        tex_max[(size_t)index * 4 + c] = b;
-      }
-      scanned[index] = 1;
-    }
-    lo = tex_min[(size_t)index * 4 + channel];
-    hi = tex_max[(size_t)index * 4 + channel];
-  };
-  // bounds of one component of an image value: constant, or constant * texel (zero when no component of the constant is positive)
-  auto value_range = [&](const sthip_MaterialRecord& rec, int k, int channel, float& lo, float& hi) {
-    const float c = rec.values[k].value[channel];
-    lo = hi = c;
-    const uint32_t index = rec.values[k].image_index;
-    if (index >= STHIP_IMAGE_COUNT || index >= s->image_count) return;
-    const float* v = rec.values[k].value;
-    if (!(v[0] > 0 || v[1] > 0 || v[2] > 0 || v[3] > 0)) {
-      lo = hi = 0.0f;
-      return;
-    }
-    float a, b;
-    image_range(index, channel, a, b);
-    lo = std::min(c * a, c * b);
-    hi = std::max(c * a, c * b);
-    if (lo != lo || hi != hi) lo = -__builtin_inff(), hi = __builtin_inff();
-  };
-  // materials: constant values or image values over gImages (image_value.h:183-207)
-  std::vector<uint8_t> inst_flags(std::max<uint32_t>(1, s->instance_count), (uint8_t)INST_FLAG_KEEP);  // k_cull_terminal's table (kernels.h)
-  for (uint32_t i = 0; i < s->instance_count; i++) {
-    const uint32_t addr = s->gInstances[i].packed[0] >> 4;
-    if ((s->gInstances[i].packed[0] & 0xF) == STHIP_INSTANCE_TYPE_VOLUME) {  // a Medium record (Material.hpp:80-87), 40 bytes
-      if ((size_t)addr + 40 > s->material_bytes || (addr & 3)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: medium material_address out of range");
-      uint32_t vol[2];
-      memcpy(vol, (const uint8_t*)s->gMaterialData + addr + 32, 8);
-      if (vol[0] >= s->volume_count || (vol[1] != 0xFFFFFFFFu && vol[1] >= s->volume_count)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: a medium refers to a volume that is not in gVolumes");
-      float anisotropy;
-      memcpy(&anisotropy, (const uint8_t*)s->gMaterialData + addr + 12, 4);
-      if (!(fabsf(anisotropy) <= 0.999f)) any_specular = true;  // Medium::is_specular (medium.hlsli:22): its vertices are not diffuse vertices
-      continue;
-    }
-    if ((size_t)addr + sizeof(sthip_MaterialRecord) > s->material_bytes) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: material_address out of range");
-    sthip_MaterialRecord rec;
-    memcpy(&rec, (const uint8_t*)s->gMaterialData + addr, sizeof(rec));
-    for (int k = 0; k < 3; k++)
-      if (rec.values[k].image_index < STHIP_IMAGE_COUNT) {
-        if (rec.values[k].image_index >= s->image_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: a material refers to an image that is not in gImages");
-        any_image = true;
-      }
-    if (rec.bump_index < STHIP_IMAGE_COUNT) {
-      if (rec.bump_index >= s->image_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: a bump map refers to an image that is not in gImages");
-      any_image = true;
-    }
-    if (rec.alpha_mask_index < STHIP_IMAGE_COUNT && (s->gInstances[i].packed[0] & 0xF) == STHIP_INSTANCE_TYPE_TRIANGLES) {
-      if (rec.alpha_mask_index >= s->image1_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: a material refers to an alpha mask that is not in gImage1s");
-      any_alpha = true;
-    }
-    // DisneyMaterial::is_specular (disney_material.hlsli:125) is evaluated per hit on value * texel, so the host test is
-    // over what the product can reach: conservative (a "maybe" only costs bounce rounds that find empty queues)
-    float lo, metallic_hi, roughness_lo, transmission_hi;
-    value_range(rec, 1, 0, lo, metallic_hi);
-    value_range(rec, 1, 1, roughness_lo, lo);
-    value_range(rec, 2, 2, lo, transmission_hi);
-    if ((metallic_hi > 0.999f || transmission_hi > 0.999f) && roughness_lo <= 1e-2f) any_specular = true;
-    if ((s->gInstances[i].packed[0] & 0xF) == STHIP_INSTANCE_TYPE_TRIANGLES || (s->gInstances[i].packed[0] & 0xF) == STHIP_INSTANCE_TYPE_SPHERE) {
-      // what DisneyMaterial::load reads of an untextured record (shading.h), with the device's arithmetic: Le = base_color *
-      // emission, can_eval, is_specular (only the untextured k_shade instantiations, i.e. a scene without images, consult this)
-      float f[14];
-      memcpy(f, (const uint8_t*)s->gMaterialData + addr, sizeof(f));
-      const float le[3] = {f[0] * f[3], f[1] * f[3], f[2] * f[3]};
-      const bool emits = le[0] > 0 || le[1] > 0 || le[2] > 0;
-      const bool can_eval = f[3] <= 0 && (f[0] > 0 || f[1] > 0 || f[2] > 0);
-      const bool specular = (f[5] > 0.999f || f[12] > 0.999f) && f[6] <= 1e-2f;
-      inst_flags[i] = (uint8_t)((emits ? INST_FLAG_EMITS : 0) | (can_eval ? INST_FLAG_CAN_EVAL : 0) | (specular ? INST_FLAG_SPECULAR : 0));
-    }
-  }
-  ctx->inst_flags_host = inst_flags;
-  HIP_TRY(ctx, ctx->inst_flags.ensure(inst_flags.size()));
-  HIP_TRY(ctx, hipMemcpy(ctx->inst_flags.p, inst_flags.data(), inst_flags.size(), hipMemcpyHostToDevice));
-  ctx->has_specular = any_specular;
-  ctx->textured = any_image;
-  if (s->image_count && !s->gImages) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: image_count > 0 but gImages is NULL");
-  if (s->image1_count && !s->gImage1s) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: image1_count > 0 but gImage1s is NULL");
-  if (s->volume_count && !s->gVolumes) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: volume_count > 0 but gVolumes is NULL");
-  sthip::BuiltBvh built;
+  return STHIP_OK;
+}
+
+static int upload_vertices_and_indices(sthip_ctx* ctx, const sthip_scene_desc* s) {
+  HIP_TRY(ctx, ctx->vertices.ensure(std::max(1u, s->vertex_count)));
+  HIP_TRY(ctx, ctx->indices.ensure((size_t)s->indices_bytes + 8));
+  if (s->vertex_count) HIP_TRY(ctx, hipMemcpy(ctx->vertices.p, s->gVertices, (size_t)s->vertex_count * sizeof(sthip_PackedVertexData), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemset(ctx->indices.p + s->indices_bytes, 0, 8));
+  if (s->indices_bytes) HIP_TRY(ctx, hipMemcpy(ctx->indices.p, s->gIndices, s->indices_bytes, hipMemcpyHostToDevice));
+  ctx->vertex_count = s->vertex_count;
+  ctx->indices_bytes = s->indices_bytes;
+  return STHIP_OK;
+}
+
+static int build_tree(sthip_ctx* ctx, const sthip_scene_desc* s, sthip::BuiltBvh& built) {
   std::string err;
-  const uint32_t n = s->instance_count;
   // The GPU builder works on the device-resident scene: vertices and indices go up BEFORE the build, and the bottom levels
-  // are written in place (lbvh.hip: lbvh_build_device). From here on the previous scene is gone, also when the call fails.
+  // are written in place (lbvh.hip: lbvh_build_device).
   const bool device_build = ctx->bvh_builder == sthip::BVH_BUILDER_LBVH_GPU;
   sthip::DeviceBuildTarget target;
   if (device_build) {
-    ctx->has_scene = false;
-    HIP_TRY(ctx, ctx->vertices.ensure(std::max(1u, s->vertex_count)));
-    HIP_TRY(ctx, ctx->indices.ensure((size_t)s->indices_bytes + 8));
-    if (s->vertex_count) HIP_TRY(ctx, hipMemcpy(ctx->vertices.p, s->gVertices, (size_t)s->vertex_count * sizeof(sthip_PackedVertexData), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemset(ctx->indices.p + s->indices_bytes, 0, 8));
-    if (s->indices_bytes) HIP_TRY(ctx, hipMemcpy(ctx->indices.p, s->gIndices, s->indices_bytes, hipMemcpyHostToDevice));
+    const int rc = upload_vertices_and_indices(ctx, s);
+    if (rc != STHIP_OK) return rc;
     target.vertices = ctx->vertices.p;
     target.vertex_count = s->vertex_count;
     target.indices = ctx->indices.p;
@@ -1135,61 +1050,107 @@ static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t
   if (built.stack_depth > STHIP_MAX_STACK_DEPTH) return fail(ctx, STHIP_ERR_UNSUPPORTED, "scene: the acceleration structure is too deep for the traversal stack (use the SAH builder)");
   ctx->stats.bvh_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
   ctx->stats.bvh_build_gpu_ms = built.gpu_build_ms;
-  {
-    // The bounds of the emissive triangle instances (kernels.h: EmitterBounds), from the validated scene arrays: the box of the
-    // vertices an instance's triangles refer to, widened by 2^-15 of its coordinates' magnitude as the packed nodes of the
-    // tree are, in world space for an instance with identity transforms (that is where its triangles are tested, whether the
-    // builder merged it or not: the identity's fmaf chain returns the world-space ray) and in object space otherwise.
-    std::vector<EmitterBounds> bounds;
-    bool usable = true;
-    for (uint32_t i = 0; i < s->instance_count && usable; i++) {
-      // (sphere lights, environments: scenes of the extended k_shade instantiation, which does not answer last rays)
-      if ((s->gInstances[i].packed[0] & 0xF) != STHIP_INSTANCE_TYPE_TRIANGLES || !(ctx->inst_flags_host[i] & INST_FLAG_EMITS)) continue;
-      if (bounds.size() == STHIP_MAX_EMITTER_BOUNDS) {
-        usable = false;
-        break;
-      }
-      const uint32_t prims = (s->gInstances[i].packed[1] >> 12) & 0xFFFFu, stride = s->gInstances[i].packed[1] >> 28;
-      const uint32_t first_vertex = s->gInstances[i].packed[2];
-      const uint8_t* ib = (const uint8_t*)s->gIndices + s->gInstances[i].packed[3];
-      EmitterBounds b{};
-      for (int a = 0; a < 3; a++) b.lo[a] = __builtin_inff(), b.hi[a] = -__builtin_inff();
-      for (uint32_t k = 0; k < 3 * prims; k++) {
-        uint32_t index;
-        if (stride == 2) {
-          uint16_t w;
-          memcpy(&w, ib + 2 * (size_t)k, 2);
-          index = w;
-        } else {
-          memcpy(&index, ib + 4 * (size_t)k, 4);
-        }
-        if ((size_t)first_vertex + index >= s->vertex_count) {  // (the builders have refused such a scene already)
-          usable = false;
-          break;
-        }
-        const float* pos = s->gVertices[first_vertex + index].position;
-        for (int a = 0; a < 3; a++) {
-          b.lo[a] = std::min(b.lo[a], pos[a]);
-          b.hi[a] = std::max(b.hi[a], pos[a]);
-        }
-      }
-      if (!prims || !(b.lo[0] <= b.hi[0])) continue;  // (no triangle: nothing to hit)
-      if (!pad_emitter_bounds(b)) usable = false;
-      b.instance = i;
-      static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-      b.identity = (!memcmp(&s->gInstanceTransforms[i], ident, 48) && !memcmp(&s->gInstanceInverseTransforms[i], ident, 48)) ? 1u : 0u;
-      bounds.push_back(b);
-    }
-    ctx->emitter_count = usable ? (uint32_t)bounds.size() : 0u;
-    ctx->emitters_host = usable ? bounds : std::vector<EmitterBounds>();
-    if (ctx->emitter_count) {
-      HIP_TRY(ctx, ctx->emitters.ensure(bounds.size()));
-      HIP_TRY(ctx, hipMemcpy(ctx->emitters.p, bounds.data(), bounds.size() * sizeof(EmitterBounds), hipMemcpyHostToDevice));
-    }
+  return STHIP_OK;
+}
+
+static int upload_motion_or_identity(sthip_ctx* ctx, const sthip_TransformData* motion, uint32_t n) {
+  if (motion) {
+    HIP_TRY(ctx, hipMemcpy(ctx->motion_xf.p, motion, (size_t)n * 48, hipMemcpyHostToDevice));
+  } else {
+    std::vector<sthip_TransformData> I(n);
+    memset(I.data(), 0, (size_t)n * 48);
+    for (auto& t : I) t.m[0][0] = t.m[1][1] = t.m[2][2] = 1;
+    HIP_TRY(ctx, hipMemcpy(ctx->motion_xf.p, I.data(), (size_t)n * 48, hipMemcpyHostToDevice));
   }
-  if (!device_build) {
-    HIP_TRY(ctx, ctx->vertices.ensure(std::max(1u, s->vertex_count)));
-    HIP_TRY(ctx, ctx->indices.ensure((size_t)s->indices_bytes + 8));
+  return STHIP_OK;
+}
+
+// gImages: the table and the float texels as scene_prepare.cpp laid them out; an RGBA8 image's level 0 goes up as it is, each
+// further level is one launch over the level before it, in stream order (mips.hip)
+static int install_images(sthip_ctx* ctx, const sthip_scene_desc* s, sthip::ImageLayout& images) {
+  const std::vector<DeviceImage>& table = images.table;
+  ctx->image_dims.clear();
+  for (uint32_t i = 0; i < s->image_count; i++) ctx->image_dims.emplace_back(s->gImages[i].width, s->gImages[i].height);
+  HIP_TRY(ctx, ctx->images.ensure(std::max<size_t>(1, table.size())));
+  HIP_TRY(ctx, ctx->image_texels.ensure(std::max<size_t>(1, images.texels.size() / 4)));
+  if (!table.empty()) HIP_TRY(ctx, hipMemcpy(ctx->images.p, table.data(), table.size() * sizeof(DeviceImage), hipMemcpyHostToDevice));
+  if (!images.texels.empty()) HIP_TRY(ctx, hipMemcpy(ctx->image_texels.p, images.texels.data(), images.texels.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, ctx->image_texels8.ensure(std::max<size_t>(1, images.texels8)));
+  std::string err;
+  for (uint32_t i = 0; i < s->image_count; i++) {
+    const DeviceImage& im = table[i];
+    if (im.format != STHIP_IMAGE_FORMAT_RGBA8_UNORM) continue;
+    HIP_TRY(ctx, hipMemcpy(ctx->image_texels8.p + im.offset[0], s->gImages[i].pixels, (size_t)im.w[0] * im.h[0] * 4, hipMemcpyHostToDevice));
+    for (uint32_t level = 0; level + 1 < im.levels; level++)
+      if (!sthip::mip_rgba8_launch(ctx->image_texels8.p + im.offset[level], im.w[level], im.h[level], ctx->image_texels8.p + im.offset[level + 1], ctx->cu_count, ctx->stream, err)) return fail(ctx, STHIP_ERR_HIP, "scene: " + err);
+  }
+  if (images.texels8) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->image_count = s->image_count;
+  ctx->images_host = std::move(images.table);
+  return STHIP_OK;
+}
+
+// alpha masks: one-channel images and the per-instance mask index the traversal looks up (the per-triangle uvs it
+// interpolates are filled with the shading records, once the triangles are resident)
+static int install_alpha_masks(sthip_ctx* ctx, const sthip::MaskLayout& masks, bool any_alpha, const sthip::BuiltBvh& built) {
+  HIP_TRY(ctx, ctx->images1.ensure(std::max<size_t>(1, masks.table.size())));
+  HIP_TRY(ctx, ctx->image1_texels.ensure(std::max<size_t>(1, masks.texels.size())));
+  HIP_TRY(ctx, ctx->tri_uvs.ensure(1));
+  if (!masks.table.empty()) HIP_TRY(ctx, hipMemcpy(ctx->images1.p, masks.table.data(), masks.table.size() * sizeof(DeviceImage1), hipMemcpyHostToDevice));
+  if (!masks.texels.empty()) HIP_TRY(ctx, hipMemcpy(ctx->image1_texels.p, masks.texels.data(), masks.texels.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, ctx->image1_texels8.ensure(std::max<size_t>(1, masks.texels8.size())));
+  if (!masks.texels8.empty()) HIP_TRY(ctx, hipMemcpy(ctx->image1_texels8.p, masks.texels8.data(), masks.texels8.size(), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, ctx->inst_alpha.ensure(std::max<size_t>(1, built.inst_alpha.size())));
+  if (!built.inst_alpha.empty()) HIP_TRY(ctx, hipMemcpy(ctx->inst_alpha.p, built.inst_alpha.data(), built.inst_alpha.size() * 4, hipMemcpyHostToDevice));
+  ctx->bvh.inst_alpha = ctx->inst_alpha.p;
+  ctx->has_alpha = any_alpha && built.any_alpha;
+  ctx->bvh.tri_uv = reinterpret_cast<const float2*>(ctx->tri_uvs.p);
+  ctx->bvh.images1 = ctx->images1.p;
+  ctx->bvh.image1_texels = ctx->image1_texels.p;
+  ctx->bvh.image1_texels8 = ctx->image1_texels8.p;
+  ctx->bvh.alpha_test = 0;
+  ctx->bvh.flip_uvs = 0;
+  return STHIP_OK;
+}
+
+// gVolumes: the grids back to back as 32-bit words, and their parsed headers
+static int install_volumes(sthip_ctx* ctx, const sthip_scene_desc* s, const std::vector<uint32_t>& first_words, size_t words, sthip::BuiltBvh& built) {
+  for (uint32_t i = 0; i < s->volume_count; i++) built.volumes[i].first_word = first_words[i];
+  HIP_TRY(ctx, ctx->volume_words.ensure(std::max<size_t>(1, words)));
+  HIP_TRY(ctx, ctx->volumes.ensure(std::max<size_t>(1, built.volumes.size())));
+  for (uint32_t i = 0; i < s->volume_count; i++)
+    HIP_TRY(ctx, hipMemcpy(ctx->volume_words.p + built.volumes[i].first_word, s->gVolumes[i].data, (size_t)s->gVolumes[i].bytes, hipMemcpyHostToDevice));
+  if (!built.volumes.empty()) HIP_TRY(ctx, hipMemcpy(ctx->volumes.p, built.volumes.data(), built.volumes.size() * sizeof(DeviceVolume), hipMemcpyHostToDevice));
+  ctx->volume_count = s->volume_count;
+  ctx->bvh.volumes = ctx->volumes.p;
+  return STHIP_OK;
+}
+
+// The scene's arrays and what the host derived from them, into HBM and into the context
+static int install_scene_arrays(sthip_ctx* ctx, const sthip_scene_desc* s, PreparedScene& prep, sthip::BuiltBvh& built) {
+  const uint32_t n = s->instance_count;
+  sthip::MaterialAnalysis& m = prep.materials;
+  HIP_TRY(ctx, ctx->inst_flags.ensure(m.inst_flags.size()));
+  HIP_TRY(ctx, hipMemcpy(ctx->inst_flags.p, m.inst_flags.data(), m.inst_flags.size(), hipMemcpyHostToDevice));
+  // after build_scene_bvh has succeeded: emitter_bounds reads gIndices at offsets only the builder has validated
+  std::vector<EmitterBounds> bounds;
+  sthip::emitter_bounds(*s, m.inst_flags, bounds);
+  ctx->emitter_count = (uint32_t)bounds.size();
+  if (ctx->emitter_count) {
+    HIP_TRY(ctx, ctx->emitters.ensure(bounds.size()));
+    HIP_TRY(ctx, hipMemcpy(ctx->emitters.p, bounds.data(), bounds.size() * sizeof(EmitterBounds), hipMemcpyHostToDevice));
+  }
+  ctx->emitters_host = std::move(bounds);
+  ctx->inst_flags_host = std::move(m.inst_flags);
+  ctx->has_specular = m.has_specular;
+  ctx->textured = m.textured;
+  ctx->has_spheres = m.has_spheres;
+  ctx->has_volumes = m.has_volumes;
+  ctx->volume_instances = m.volume_instances;
+  ctx->instance_is_volume = std::move(m.instance_is_volume);
+  if (ctx->bvh_builder != sthip::BVH_BUILDER_LBVH_GPU) {  // (the GPU builder has them already)
+    const int rc = upload_vertices_and_indices(ctx, s);
+    if (rc != STHIP_OK) return rc;
   }
   HIP_TRY(ctx, ctx->instances.ensure(n));
   HIP_TRY(ctx, ctx->xf.ensure(n));
@@ -1197,113 +1158,46 @@ static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t
   HIP_TRY(ctx, ctx->motion_xf.ensure(n));
   HIP_TRY(ctx, ctx->materials.ensure(s->material_bytes));
   HIP_TRY(ctx, ctx->lights.ensure(std::max(1u, s->light_count)));
-  if (!device_build) {
-    if (s->vertex_count) HIP_TRY(ctx, hipMemcpy(ctx->vertices.p, s->gVertices, (size_t)s->vertex_count * sizeof(sthip_PackedVertexData), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemset(ctx->indices.p, 0, (size_t)s->indices_bytes + 8));
-    if (s->indices_bytes) HIP_TRY(ctx, hipMemcpy(ctx->indices.p, s->gIndices, s->indices_bytes, hipMemcpyHostToDevice));
-  }
   HIP_TRY(ctx, hipMemcpy(ctx->instances.p, s->gInstances, (size_t)n * 16, hipMemcpyHostToDevice));
   HIP_TRY(ctx, hipMemcpy(ctx->xf.p, s->gInstanceTransforms, (size_t)n * 48, hipMemcpyHostToDevice));
   HIP_TRY(ctx, hipMemcpy(ctx->inv_xf.p, s->gInstanceInverseTransforms, (size_t)n * 48, hipMemcpyHostToDevice));
-  if (s->gInstanceMotionTransforms) {
-    HIP_TRY(ctx, hipMemcpy(ctx->motion_xf.p, s->gInstanceMotionTransforms, (size_t)n * 48, hipMemcpyHostToDevice));
-  } else {
-    std::vector<sthip_TransformData> I(n);
-    memset(I.data(), 0, (size_t)n * 48);
-    for (auto& t : I) t.m[0][0] = t.m[1][1] = t.m[2][2] = 1;
-    HIP_TRY(ctx, hipMemcpy(ctx->motion_xf.p, I.data(), (size_t)n * 48, hipMemcpyHostToDevice));
-  }
+  int rc = upload_motion_or_identity(ctx, s->gInstanceMotionTransforms, n);
+  if (rc != STHIP_OK) return rc;
   HIP_TRY(ctx, hipMemcpy(ctx->materials.p, s->gMaterialData, s->material_bytes, hipMemcpyHostToDevice));
   if (s->light_count) HIP_TRY(ctx, hipMemcpy(ctx->lights.p, s->gLightInstances, (size_t)s->light_count * 4, hipMemcpyHostToDevice));
   ctx->instance_count = n;
   ctx->light_count = s->light_count;
   ctx->materials_host.assign((const uint8_t*)s->gMaterialData, (const uint8_t*)s->gMaterialData + s->material_bytes);
-  ctx->has_spheres = false;
-  for (uint32_t i = 0; i < n; i++)
-    if ((s->gInstances[i].packed[0] & 0xF) == STHIP_INSTANCE_TYPE_SPHERE) ctx->has_spheres = true;
-  if (s->distribution_count && !s->gDistributions) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: distribution_count > 0 but gDistributions is NULL");
   HIP_TRY(ctx, ctx->distributions.ensure(std::max<size_t>(1, s->distribution_count)));
   if (s->distribution_count) HIP_TRY(ctx, hipMemcpy(ctx->distributions.p, s->gDistributions, (size_t)s->distribution_count * 4, hipMemcpyHostToDevice));
   ctx->distribution_count = s->distribution_count;
-  ctx->image_dims.clear();
-  for (uint32_t i = 0; i < s->image_count; i++) ctx->image_dims.emplace_back(s->gImages[i].width, s->gImages[i].height);
-  // images: mip chain by 2x2 box filter, level k+1 = max(1, floor(dim / 2)), ((a + b) + (c + d)) * 0.25
-  // (RGBA8 images, sthip_scene_upload_formats: the same shape in an array of their own, (a + b + c + d + 2) >> 2 per channel,
-  // made on the device from level 0 — mips.hip)
-  {
-    std::vector<DeviceImage> table(s->image_count);
-    std::vector<float> texels;
-    size_t texels8 = 0;  // words of image_texels8
-    for (uint32_t i = 0; i < s->image_count; i++) {
-      uint32_t w = s->gImages[i].width, h = s->gImages[i].height;
-      if (!s->gImages[i].pixels || w == 0 || h == 0 || w > 0xFFFF || h > 0xFFFF) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: bad image");
-      DeviceImage& im = table[i];
-      memset(&im, 0, sizeof(im));
-      if (image_formats && image_formats[i] == STHIP_IMAGE_FORMAT_RGBA8_UNORM) {  // the layout only: the texels go up below
-        im.format = STHIP_IMAGE_FORMAT_RGBA8_UNORM;
-        for (uint32_t level = 0;; level++) {
-          im.offset[level] = (uint32_t)texels8;
-          im.w[level] = (uint16_t)w;
-          im.h[level] = (uint16_t)h;
-          im.levels = level + 1;
-          texels8 += (size_t)w * h;
-          if ((w == 1 && h == 1) || level + 1 == STHIP_MAX_MIPS) break;
-          w = std::max(1u, w / 2);
-          h = std::max(1u, h / 2);
-        }
-        if (texels8 > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_UNSUPPORTED, "scene: the RGBA8 images exceed 2^32 texels (32-bit texel offsets)");
-        continue;
-      }
-      size_t level_start = texels.size();
-      texels.insert(texels.end(), s->gImages[i].pixels, s->gImages[i].pixels + (size_t)w * h * 4);
-      for (uint32_t level = 0;; level++) {
-        im.offset[level] = (uint32_t)(level_start / 4);
-        im.w[level] = (uint16_t)w;
-        im.h[level] = (uint16_t)h;
-        im.levels = level + 1;
-        if ((w == 1 && h == 1) || level + 1 == STHIP_MAX_MIPS) break;
-        const uint32_t nw = std::max(1u, w / 2), nh = std::max(1u, h / 2);
-        const size_t next_start = texels.size();
-        texels.resize(next_start + (size_t)nw * nh * 4);
-        const float* prev = texels.data() + level_start;
-        float* next = texels.data() + next_start;
-        for (uint32_t y = 0; y < nh; y++)
-          for (uint32_t x = 0; x < nw; x++) {
-            const uint32_t x0 = std::min(2 * x, w - 1), x1 = std::min(2 * x + 1, w - 1), y0 = std::min(2 * y, h - 1), y1 = std::min(2 * y + 1, h - 1);
-            for (int k = 0; k < 4; k++) {
-              const float a = prev[4 * ((size_t)y0 * w + x0) + k], b = prev[4 * ((size_t)y0 * w + x1) + k];
-              const float c = prev[4 * ((size_t)y1 * w + x0) + k], e = prev[4 * ((size_t)y1 * w + x1) + k];
-              next[4 * ((size_t)y * nw + x) + k] = ((a + b) + (c + e)) * 0.25f;
-            }
-          }
-        level_start = next_start;
-        w = nw;
-        h = nh;
-      }
-    }
-    HIP_TRY(ctx, ctx->images.ensure(std::max<size_t>(1, table.size())));
-    HIP_TRY(ctx, ctx->image_texels.ensure(std::max<size_t>(1, texels.size() / 4)));
-    if (!table.empty()) HIP_TRY(ctx, hipMemcpy(ctx->images.p, table.data(), table.size() * sizeof(DeviceImage), hipMemcpyHostToDevice));
-    if (!texels.empty()) HIP_TRY(ctx, hipMemcpy(ctx->image_texels.p, texels.data(), texels.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, ctx->image_texels8.ensure(std::max<size_t>(1, texels8)));
-    for (uint32_t i = 0; i < s->image_count; i++) {  // RGBA8: level 0 goes up as it is, each further level is one launch over the level before it, in stream order
-      const DeviceImage& im = table[i];
-      if (im.format != STHIP_IMAGE_FORMAT_RGBA8_UNORM) continue;
-      HIP_TRY(ctx, hipMemcpy(ctx->image_texels8.p + im.offset[0], s->gImages[i].pixels, (size_t)im.w[0] * im.h[0] * 4, hipMemcpyHostToDevice));
-      for (uint32_t level = 0; level + 1 < im.levels; level++)
-        if (!sthip::mip_rgba8_launch(ctx->image_texels8.p + im.offset[level], im.w[level], im.h[level], ctx->image_texels8.p + im.offset[level + 1], ctx->cu_count, ctx->stream, err)) return fail(ctx, STHIP_ERR_HIP, "scene: " + err);
-    }
-    if (texels8) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->image_count = s->image_count;
-    ctx->images_host = std::move(table);
-  }
+  if ((rc = install_images(ctx, s, prep.images)) != STHIP_OK) return rc;
+  if ((rc = install_alpha_masks(ctx, prep.masks, m.any_alpha, built)) != STHIP_OK) return rc;
+  return install_volumes(ctx, s, prep.volume_first_words, prep.volume_words, built);
+}
 
+// The 8-wide form becomes the one k_trace walks: nodes [first, ...) of ctx->wide8_host (the ones before are resident) and
+// the entry table go up; the device arrays are large enough
+static int install_wide8(sthip_ctx* ctx, size_t first, const std::vector<TlasEntry>& entries, uint32_t root, uint32_t stack_depth) {
+  if (ctx->wide8_host.size() > first)
+    HIP_TRY(ctx, hipMemcpy(ctx->wide8_nodes.p + first, ctx->wide8_host.data() + first, (ctx->wide8_host.size() - first) * sizeof(Wide8Node), hipMemcpyHostToDevice));
+  if (!entries.empty()) HIP_TRY(ctx, hipMemcpy(ctx->wide8_entries.p, entries.data(), entries.size() * sizeof(TlasEntry), hipMemcpyHostToDevice));
+  ctx->bvh.wide8_nodes = reinterpret_cast<const uint4*>(ctx->wide8_nodes.p);
+  ctx->bvh.wide8_entries = ctx->wide8_entries.p;
+  ctx->bvh.wide8_root = root;
+  ctx->bvh.wide8_stack_depth = stack_depth;
+  ctx->wide8_node_count = ctx->wide8_host.size();
+  return STHIP_OK;
+}
+
+// The tree: nodes (or embedded units), triangles and entries, the wide form k_trace walks, and ctx->bvh
+static int install_tree(sthip_ctx* ctx, sthip::BuiltBvh& built) {
   // the 8-wide form permutes the leaf triangles (bvh_build.h): made before anything of the tree is uploaded
   if (ctx->use_wide == 3 && !ctx->use_treetop && !built.embedded && built.dev_nodes == 0) sthip::build_wide8_bvh(built);
   // headroom: a transforms-only update may build a top level with more inner nodes than this one (at most 2 per entry)
   const size_t nodes_total = (size_t)built.dev_nodes + built.nodes.size(), tris_total = (size_t)built.dev_tris + built.tris.size();
   const size_t nodes_needed = std::max<size_t>(1, built.top.blas_nodes + 2 * built.entries.size() + 2);
-  if (device_build && built.dev_nodes) {  // the device region is already in place: growing the arrays now would lose it
+  if (built.dev_nodes) {  // the device region is already in place: growing the arrays now would lose it
     if (ctx->nodes.n < std::max(nodes_needed, nodes_total) || ctx->tris.n < std::max<size_t>(1, tris_total)) return fail(ctx, STHIP_ERR_HIP, "scene: the reserved device arrays are too small");
   } else {
     HIP_TRY(ctx, ctx->nodes.ensure(std::max(nodes_needed, nodes_total)));
@@ -1322,30 +1216,17 @@ static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t
     if (!built.tris.empty()) HIP_TRY(ctx, hipMemcpy(ctx->tris.p + built.dev_tris, built.tris.data(), built.tris.size() * sizeof(BvhTri), hipMemcpyHostToDevice));
   }
   if (!built.entries.empty()) HIP_TRY(ctx, hipMemcpy(ctx->entries.p, built.entries.data(), built.entries.size() * sizeof(TlasEntry), hipMemcpyHostToDevice));
-  ctx->bvh.wide_nodes = nullptr;
-  ctx->bvh.wide_entries = nullptr;
-  ctx->bvh.wide_root_ref = BVH_INVALID_REF;
-  ctx->bvh.wide_stack_depth = 0;
-  ctx->wide_node_count = 0;
-  ctx->bvh.wide8_nodes = nullptr;
-  ctx->bvh.wide8_entries = nullptr;
-  ctx->bvh.wide8_root = BVH_INVALID_REF;
-  ctx->bvh.wide8_stack_depth = 0;
+  clear_wide(ctx);
+  clear_wide8(ctx);
   ctx->bvh.wide8_tri_min = ctx->tri_min_lanes;
-  ctx->wide8_node_count = 0;
   ctx->wide8_host.clear();
   if (!built.wide8_nodes.empty()) {
     // (room for a rebuilt top level: at most one node per entry and per two entries above them, and a copy of the merged mesh's root)
     HIP_TRY(ctx, ctx->wide8_nodes.ensure(built.top.wide8_blas_nodes + 2 * built.entries.size() + 4));
     HIP_TRY(ctx, ctx->wide8_entries.ensure(std::max<size_t>(1, built.entries.size())));
-    HIP_TRY(ctx, hipMemcpy(ctx->wide8_nodes.p, built.wide8_nodes.data(), built.wide8_nodes.size() * sizeof(Wide8Node), hipMemcpyHostToDevice));
-    if (!built.wide8_entries.empty()) HIP_TRY(ctx, hipMemcpy(ctx->wide8_entries.p, built.wide8_entries.data(), built.wide8_entries.size() * sizeof(TlasEntry), hipMemcpyHostToDevice));
-    ctx->bvh.wide8_nodes = reinterpret_cast<const uint4*>(ctx->wide8_nodes.p);
-    ctx->bvh.wide8_entries = ctx->wide8_entries.p;
-    ctx->bvh.wide8_root = built.wide8_root;
-    ctx->bvh.wide8_stack_depth = built.wide8_stack_depth;
-    ctx->wide8_node_count = built.wide8_nodes.size();
     ctx->wide8_host = std::move(built.wide8_nodes);
+    const int rc = install_wide8(ctx, 0, built.wide8_entries, built.wide8_root, built.wide8_stack_depth);
+    if (rc != STHIP_OK) return rc;
   }
   ctx->want_wide = (ctx->use_wide == 1 || (ctx->use_wide == 3 && !ctx->bvh.wide8_nodes) || (ctx->use_wide == 2 && nodes_total * sizeof(BvhNodePacked) > ((size_t)4 << 20))) && !ctx->use_treetop && !built.embedded;
   if (ctx->want_wide && built.dev_nodes == 0) {  // a host-built tree: collapsed on the host from its exact boxes (a device build: below, from the nodes in HBM)
@@ -1362,69 +1243,6 @@ static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t
       ctx->wide_node_count = built.wide_nodes.size();
     }
   }
-  {  // alpha masks: one-channel images and the per-triangle uvs the traversal interpolates
-    std::vector<DeviceImage1> table(s->image1_count);
-    std::vector<float> texels;
-    std::vector<uint8_t> texels8;  // the R8 masks (sthip_scene_upload_formats), in an array of their own
-    for (uint32_t i = 0; i < s->image1_count; i++) {
-      const sthip_image_desc& im = s->gImage1s[i];
-      if (!im.pixels || im.width == 0 || im.height == 0 || im.width > 0xFFFF || im.height > 0xFFFF) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: bad alpha-mask image");
-      table[i].w = im.width;
-      table[i].h = im.height;
-      if (image1_formats && image1_formats[i] == STHIP_IMAGE_FORMAT_R8_UNORM) {
-        const uint8_t* bytes = reinterpret_cast<const uint8_t*>(im.pixels);
-        table[i].offset = (uint32_t)texels8.size();
-        table[i].format = STHIP_IMAGE_FORMAT_R8_UNORM;
-        texels8.insert(texels8.end(), bytes, bytes + (size_t)im.width * im.height);
-        if (texels8.size() > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_UNSUPPORTED, "scene: the R8 alpha masks exceed 2^32 texels (32-bit texel offsets)");
-        continue;
-      }
-      table[i].offset = (uint32_t)texels.size();
-      table[i].format = STHIP_IMAGE_FORMAT_R32F;
-      texels.insert(texels.end(), im.pixels, im.pixels + (size_t)im.width * im.height);
-    }
-    HIP_TRY(ctx, ctx->images1.ensure(std::max<size_t>(1, table.size())));
-    HIP_TRY(ctx, ctx->image1_texels.ensure(std::max<size_t>(1, texels.size())));
-    HIP_TRY(ctx, ctx->tri_uvs.ensure(1));  // (sized and filled with the shading records further down, once the triangles are resident)
-    if (!table.empty()) HIP_TRY(ctx, hipMemcpy(ctx->images1.p, table.data(), table.size() * sizeof(DeviceImage1), hipMemcpyHostToDevice));
-    if (!texels.empty()) HIP_TRY(ctx, hipMemcpy(ctx->image1_texels.p, texels.data(), texels.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, ctx->image1_texels8.ensure(std::max<size_t>(1, texels8.size())));
-    if (!texels8.empty()) HIP_TRY(ctx, hipMemcpy(ctx->image1_texels8.p, texels8.data(), texels8.size(), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, ctx->inst_alpha.ensure(std::max<size_t>(1, built.inst_alpha.size())));
-    if (!built.inst_alpha.empty()) HIP_TRY(ctx, hipMemcpy(ctx->inst_alpha.p, built.inst_alpha.data(), built.inst_alpha.size() * 4, hipMemcpyHostToDevice));
-    ctx->bvh.inst_alpha = ctx->inst_alpha.p;
-    ctx->has_alpha = any_alpha && built.any_alpha;
-    ctx->bvh.tri_uv = reinterpret_cast<const float2*>(ctx->tri_uvs.p);
-    ctx->bvh.images1 = ctx->images1.p;
-    ctx->bvh.image1_texels = ctx->image1_texels.p;
-    ctx->bvh.image1_texels8 = ctx->image1_texels8.p;
-    ctx->bvh.alpha_test = 0;
-    ctx->bvh.flip_uvs = 0;
-  }
-  {  // gVolumes: the grids back to back as 32-bit words, and their parsed headers
-    size_t words = 0;
-    for (uint32_t i = 0; i < s->volume_count; i++) {
-      built.volumes[i].first_word = (uint32_t)words;
-      words += (size_t)(s->gVolumes[i].bytes / 4);
-    }
-    if (words > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "scene: gVolumes exceed 16 GiB");
-    HIP_TRY(ctx, ctx->volume_words.ensure(std::max<size_t>(1, words)));
-    HIP_TRY(ctx, ctx->volumes.ensure(std::max<size_t>(1, built.volumes.size())));
-    for (uint32_t i = 0; i < s->volume_count; i++)
-      HIP_TRY(ctx, hipMemcpy(ctx->volume_words.p + built.volumes[i].first_word, s->gVolumes[i].data, (size_t)s->gVolumes[i].bytes, hipMemcpyHostToDevice));
-    if (!built.volumes.empty()) HIP_TRY(ctx, hipMemcpy(ctx->volumes.p, built.volumes.data(), built.volumes.size() * sizeof(DeviceVolume), hipMemcpyHostToDevice));
-    ctx->volume_count = s->volume_count;
-    ctx->has_volumes = false;
-    ctx->volume_instances = 0;
-    ctx->instance_is_volume.assign(n, 0);
-    for (uint32_t i = 0; i < n; i++)
-      if ((s->gInstances[i].packed[0] & 0xF) == STHIP_INSTANCE_TYPE_VOLUME) {
-        ctx->has_volumes = true;
-        ctx->volume_instances++;
-        ctx->instance_is_volume[i] = 1;
-      }
-    ctx->bvh.volumes = ctx->volumes.p;
-  }
   ctx->bvh.nodes = reinterpret_cast<const float4*>(ctx->nodes.p);
   ctx->bvh.tris = built.embedded ? reinterpret_cast<const float4*>(ctx->nodes.p) : reinterpret_cast<const float4*>(ctx->tris.p);
   ctx->bvh.entries = ctx->entries.p;
@@ -1437,8 +1255,6 @@ static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t
   ctx->bvh.scene_radius = built.scene_radius;
   ctx->bvh_nodes = nodes_total;
   ctx->bvh_tris = tris_total;
-  ctx->vertex_count = s->vertex_count;
-  ctx->indices_bytes = s->indices_bytes;
   ctx->embedded_resident = built.embedded;
   ctx->top = std::move(built.top);
   if (ctx->want_wide && built.dev_nodes != 0) {  // the GPU builder's tree: its wide form is made where the nodes are
@@ -1454,31 +1270,56 @@ static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t
     if (!built.nodes.empty()) memcpy(ctx->nodes_host.p + built.dev_nodes, built.nodes.data(), built.nodes.size() * sizeof(BvhNode));
     ctx->nodes_host.n = nodes_total;
   }
-  {  // the shading records beside the leaf triangles (bvh.h: BvhTriShade), from the triangles as they lie in HBM now
-    const size_t units = built.embedded ? nodes_total : tris_total;  // (embedded leaves: a triangle is a unit of the node array; the units that are nodes get a record nobody reads)
-    HIP_TRY(ctx, ctx->tri_shade.ensure(std::max<size_t>(1, units)));
-    if (ctx->has_alpha) {  // the uvs the traversal's alpha test interpolates (gAlphaTest, intersection.hlsli:117-131), in the same order
-      HIP_TRY(ctx, ctx->tri_uvs.ensure(std::max<size_t>(1, units)));
-      ctx->bvh.tri_uv = reinterpret_cast<const float2*>(ctx->tri_uvs.p);
-    }
-    if (units && s->vertex_count) {
-      DevBuf<uint8_t> is_tri;  // embedded leaves: which units are triangles
-      if (built.embedded) {
-        std::vector<uint8_t> flags(units, 0);
-        for (size_t u = 0; u < built.unit_tri.size() && u < units; u++) flags[u] = built.unit_tri[u] != 0xFFFFFFFFu;
-        HIP_TRY(ctx, is_tri.ensure(units));
-        HIP_TRY(ctx, hipMemcpy(is_tri.p, flags.data(), units, hipMemcpyHostToDevice));
-      }
-      hipLaunchKernelGGL(k_fill_tri_shade, dim3(grid_for(ctx, units)), dim3(STHIP_BLOCK), 0, ctx->stream, reinterpret_cast<const BvhTri*>(ctx->bvh.tris), (uint32_t)units, is_tri.p, ctx->vertices.p, s->vertex_count,
-                         ctx->indices.p, (uint64_t)s->indices_bytes, ctx->tri_shade.p, ctx->has_alpha ? ctx->tri_uvs.p : nullptr);
-      HIP_TRY(ctx, hipGetLastError());
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (`is_tri` goes out of scope)
-    }
+  return STHIP_OK;
+}
+
+// k_fill_tri_shade over the first `units` resident leaf triangles (`is_tri`: which units are triangles, NULL = all)
+static int launch_fill_tri_shade(sthip_ctx* ctx, size_t units, const uint8_t* is_tri) {
+  hipLaunchKernelGGL(k_fill_tri_shade, dim3(grid_for(ctx, units)), dim3(STHIP_BLOCK), 0, ctx->stream, reinterpret_cast<const BvhTri*>(ctx->bvh.tris), (uint32_t)units, is_tri, ctx->vertices.p, ctx->vertex_count,
+                     ctx->indices.p, ctx->indices_bytes, ctx->tri_shade.p, ctx->has_alpha ? ctx->tri_uvs.p : nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  return STHIP_OK;
+}
+
+// the shading records beside the leaf triangles (bvh.h: BvhTriShade), from the triangles as they lie in HBM now
+static int derive_leaf_records(sthip_ctx* ctx, const sthip::BuiltBvh& built) {
+  const size_t units = built.embedded ? ctx->bvh_nodes : ctx->bvh_tris;  // (embedded leaves: a triangle is a unit of the node array; the units that are nodes get a record nobody reads)
+  HIP_TRY(ctx, ctx->tri_shade.ensure(std::max<size_t>(1, units)));
+  if (ctx->has_alpha) {  // the uvs the traversal's alpha test interpolates (gAlphaTest, intersection.hlsli:117-131), in the same order
+    HIP_TRY(ctx, ctx->tri_uvs.ensure(std::max<size_t>(1, units)));
+    ctx->bvh.tri_uv = reinterpret_cast<const float2*>(ctx->tri_uvs.p);
   }
-  {
-    const int rc = configure_stack(ctx);
+  if (units && ctx->vertex_count) {
+    DevBuf<uint8_t> is_tri;  // embedded leaves: which units are triangles
+    if (built.embedded) {
+      std::vector<uint8_t> flags(units, 0);
+      for (size_t u = 0; u < built.unit_tri.size() && u < units; u++) flags[u] = built.unit_tri[u] != 0xFFFFFFFFu;
+      HIP_TRY(ctx, is_tri.ensure(units));
+      HIP_TRY(ctx, hipMemcpy(is_tri.p, flags.data(), units, hipMemcpyHostToDevice));
+    }
+    const int rc = launch_fill_tri_shade(ctx, units, is_tri.p);
     if (rc != STHIP_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (`is_tri` goes out of scope)
   }
+  return STHIP_OK;
+}
+
+// sthip.h. check -> prepare -> retire the previous scene -> build -> install -> derive -> keep: a call refused by the check or
+// the preparation leaves the context as it was; a failure from the build onward leaves no scene resident.
+static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  int rc = STHIP_OK;
+  std::string why;
+  if (!sthip::check_scene(s, image_formats, image1_formats, rc, why)) return fail(ctx, rc, why);
+  PreparedScene prep;
+  sthip::BuiltBvh built;
+  if ((rc = prepare_scene(ctx, s, image_formats, image1_formats, prep)) != STHIP_OK) return rc;
+  if ((rc = retire_scene(ctx, s)) != STHIP_OK) return rc;
+  if ((rc = build_tree(ctx, s, built)) != STHIP_OK) return rc;
+  if ((rc = install_scene_arrays(ctx, s, prep, built)) != STHIP_OK) return rc;
+  if ((rc = install_tree(ctx, built)) != STHIP_OK) return rc;
+  if ((rc = derive_leaf_records(ctx, built)) != STHIP_OK) return rc;
+  if ((rc = configure_stack(ctx)) != STHIP_OK) return rc;
   ctx->has_scene = true;
   ctx->reuse_grids_valid = false;  // (stored samples name materials and lights of the scene they were taken in)
   if (ctx->keep_scene) {
@@ -1486,13 +1327,10 @@ static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t
   } else {
     ctx->kept = KeptScene();
   }
-  if (getenv("STHIP_VERBOSE")) {
-    int per_cu = 0;
-    per_cu = trace_occupancy(ctx, trace_lds_bytes(ctx));
+  if (getenv("STHIP_VERBOSE"))
     fprintf(stderr, "[sthip] bvh (%s): %zu nodes, %zu tris, %zu top-level entries, stack depth %u (%zu B LDS / block%s, treetop %u nodes), %d trace blocks / CU, build %.1f ms (GPU kernels %.2f ms)\n",
-            ctx->bvh_builder ? "lbvh/gpu" : "sah/host", (size_t)ctx->bvh_nodes, (size_t)ctx->bvh_tris, built.entries.size(), built.stack_depth, stack_bytes(ctx), ctx->bvh.spill ? ", bounded" : "", ctx->bvh.top_count, per_cu, ctx->stats.bvh_build_ms,
-            ctx->stats.bvh_build_gpu_ms);
-  }
+            ctx->bvh_builder ? "lbvh/gpu" : "sah/host", (size_t)ctx->bvh_nodes, (size_t)ctx->bvh_tris, built.entries.size(), built.stack_depth, stack_bytes(ctx), ctx->bvh.spill ? ", bounded" : "", ctx->bvh.top_count,
+            trace_occupancy(ctx, trace_lds_bytes(ctx)), ctx->stats.bvh_build_ms, ctx->stats.bvh_build_gpu_ms);
   return STHIP_OK;
 }
 
@@ -1641,23 +1479,15 @@ static int install_top_level(sthip_ctx* ctx, sthip::TopLevelState& next, const s
   ctx->top = std::move(next);
   // the wide form was made from the old top level: made again from the nodes in HBM (the bottom levels come out as before,
   // the top level new), so a moved scene keeps the walk it was uploaded with
-  ctx->bvh.wide_nodes = nullptr;
-  ctx->bvh.wide_entries = nullptr;
+  clear_wide(ctx);
   if (ctx->bvh.wide8_nodes) {  // the 8-wide form: its top level again, on the host (a node per few entries), behind the bottom levels' nodes
     std::vector<TlasEntry> entries8;
     uint32_t root8 = BVH_INVALID_REF, depth8 = 0;
-    ctx->bvh.wide8_nodes = nullptr;
+    clear_wide8(ctx);
     if (sthip::build_wide8_top(ctx->top, tlas.data(), ctx->top.blas_nodes, root_ref, top_is_world != 0, ctx->wide8_host, entries8, root8, depth8) && ctx->wide8_host.size() <= ctx->wide8_nodes.n &&
         entries8.size() <= ctx->wide8_entries.n) {
-      const size_t first = ctx->top.wide8_blas_nodes;
-      if (ctx->wide8_host.size() > first)
-        HIP_TRY(ctx, hipMemcpy(ctx->wide8_nodes.p + first, ctx->wide8_host.data() + first, (ctx->wide8_host.size() - first) * sizeof(Wide8Node), hipMemcpyHostToDevice));
-      if (!entries8.empty()) HIP_TRY(ctx, hipMemcpy(ctx->wide8_entries.p, entries8.data(), entries8.size() * sizeof(TlasEntry), hipMemcpyHostToDevice));
-      ctx->bvh.wide8_nodes = reinterpret_cast<const uint4*>(ctx->wide8_nodes.p);
-      ctx->bvh.wide8_entries = ctx->wide8_entries.p;
-      ctx->bvh.wide8_root = root8;
-      ctx->bvh.wide8_stack_depth = depth8;
-      ctx->wide8_node_count = ctx->wide8_host.size();
+      const int rc = install_wide8(ctx, ctx->top.wide8_blas_nodes, entries8, root8, depth8);
+      if (rc != STHIP_OK) return rc;
     } else {  // (a top level that cannot take the form: the 4-wide one from here on)
       ctx->want_wide = !ctx->use_treetop;
     }
@@ -1695,12 +1525,7 @@ int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf,
         const int rc = sync_kept_vertices(ctx);
         if (rc != STHIP_OK) return rc;
       }
-      ctx->kept.xf.assign(xf, xf + instance_count);
-      ctx->kept.inv.assign(inv, inv + instance_count);
-      if (motion)
-        ctx->kept.motion.assign(motion, motion + instance_count);
-      else
-        ctx->kept.motion.clear();
+      ctx->kept.set_transforms(xf, inv, motion, instance_count);
       ctx->stats.full_rebuilds++;
       return upload_kept_scene(ctx);
     }
@@ -1713,24 +1538,13 @@ int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf,
   const uint32_t n = instance_count;
   HIP_TRY(ctx, hipMemcpy(ctx->xf.p, xf, (size_t)n * 48, hipMemcpyHostToDevice));
   HIP_TRY(ctx, hipMemcpy(ctx->inv_xf.p, inv, (size_t)n * 48, hipMemcpyHostToDevice));
-  if (motion) {
-    HIP_TRY(ctx, hipMemcpy(ctx->motion_xf.p, motion, (size_t)n * 48, hipMemcpyHostToDevice));
-  } else {
-    std::vector<sthip_TransformData> I(n);
-    memset(I.data(), 0, (size_t)n * 48);
-    for (auto& t : I) t.m[0][0] = t.m[1][1] = t.m[2][2] = 1;
-    HIP_TRY(ctx, hipMemcpy(ctx->motion_xf.p, I.data(), (size_t)n * 48, hipMemcpyHostToDevice));
+  {
+    const int rc = upload_motion_or_identity(ctx, motion, n);
+    if (rc != STHIP_OK) return rc;
   }
   // the kept scene follows: a later rebuild from it (sthip_scene_update_vertices on a layout it does not refit) must find the
   // instances where they are now, and the refit takes the transforms of its top level from here instead of from the device
-  if (ctx->kept.valid && ctx->kept.instances.size() == n) {
-    ctx->kept.xf.assign(xf, xf + n);
-    ctx->kept.inv.assign(inv, inv + n);
-    if (motion)
-      ctx->kept.motion.assign(motion, motion + n);
-    else
-      ctx->kept.motion.clear();
-  }
+  if (ctx->kept.valid && ctx->kept.instances.size() == n) ctx->kept.set_transforms(xf, inv, motion, n);
   return install_top_level(ctx, next, tlas, root_ref, top_is_world, stack_depth, center, radius);
 }
 
@@ -1766,9 +1580,8 @@ static int refit_resident_scene(sthip_ctx* ctx, const VertexSource& src, bool ke
   if (!sthip::refit_gather(ctx->refit, ctx->tris.p, (uint32_t)ctx->bvh_tris, ctx->vertices.p, ctx->vertex_count, ctx->indices.p, ctx->indices_bytes, ctx->stream, err))
     return fail(ctx, STHIP_ERR_HIP, call + err);
   if (ctx->bvh_tris && ctx->vertex_count) {
-    hipLaunchKernelGGL(k_fill_tri_shade, dim3(grid_for(ctx, (size_t)ctx->bvh_tris)), dim3(STHIP_BLOCK), 0, ctx->stream, reinterpret_cast<const BvhTri*>(ctx->bvh.tris), (uint32_t)ctx->bvh_tris,
-                       (const uint8_t*)nullptr, ctx->vertices.p, ctx->vertex_count, ctx->indices.p, ctx->indices_bytes, ctx->tri_shade.p, ctx->has_alpha ? ctx->tri_uvs.p : nullptr);
-    HIP_TRY(ctx, hipGetLastError());
+    const int rc = launch_fill_tri_shade(ctx, (size_t)ctx->bvh_tris, nullptr);
+    if (rc != STHIP_OK) return rc;
   }
   std::vector<uint32_t> emitter_instances;
   for (uint32_t k = 0; k < ctx->emitter_count && k < ctx->emitters_host.size(); k++) emitter_instances.push_back(ctx->emitters_host[k].instance);
@@ -1799,7 +1612,7 @@ static int refit_resident_scene(sthip_ctx* ctx, const VertexSource& src, bool ke
       EmitterBounds& b = ctx->emitters_host[k];
       memcpy(b.lo, &res.emitter_boxes[8 * k], 12);
       memcpy(b.hi, &res.emitter_boxes[8 * k + 4], 12);
-      if (!(b.lo[0] <= b.hi[0]) || !pad_emitter_bounds(b)) usable = false;
+      if (!(b.lo[0] <= b.hi[0]) || !sthip::pad_emitter_bounds(b)) usable = false;
     }
     if (usable) {
       HIP_TRY(ctx, hipMemcpy(ctx->emitters.p, ctx->emitters_host.data(), emitter_instances.size() * sizeof(EmitterBounds), hipMemcpyHostToDevice));

@@ -143,6 +143,41 @@ struct DeviceVolume {
   float pad2[3];
 };
 
+// ---- what the upload lays out on the host (scene_prepare.cpp) and the kernels read as it is ----
+// gImages (shading.h samples them): the mip chain of one image in image_texels / image_texels8
+#ifndef STHIP_MAX_MIPS
+#define STHIP_MAX_MIPS 16
+#endif
+struct DeviceImage {
+  uint32_t offset[STHIP_MAX_MIPS];  // first texel of each level in image_texels (format 0) or in image_texels8 (format 1)
+  uint16_t w[STHIP_MAX_MIPS], h[STHIP_MAX_MIPS];
+  uint32_t levels;
+  uint32_t format;  // sthip_image_format: STHIP_IMAGE_FORMAT_RGBA32F / STHIP_IMAGE_FORMAT_RGBA8_UNORM, uniform per image
+  uint32_t pad[2];
+};
+// gImage1s, the alpha masks (traverse.h samples them): level 0 only
+struct DeviceImage1 {
+  uint32_t offset, w, h;  // offset: first texel in image1_texels (format 0) or in image1_texels8 (format 1)
+  uint32_t format;        // sthip_image_format: STHIP_IMAGE_FORMAT_R32F / STHIP_IMAGE_FORMAT_R8_UNORM
+};
+// One emissive triangle instance: the box of its vertices in the space the traversal tests its triangles in (world space for an
+// instance with identity transforms, the instance's object space otherwise) and a sphere around it that sizes the per-ray
+// padding of the slab test exactly as the traversal's own boxes are padded (setup_space).
+struct EmitterBounds {
+  float lo[3];
+  uint32_t instance;
+  float hi[3];
+  uint32_t identity;
+  float sphere[4];
+};
+#define STHIP_MAX_EMITTER_BOUNDS 16u
+// DisneyMaterial::Le() > 0 somewhere / can_eval() / is_specular() of an instance's untextured material, evaluated on the host with
+// the device's arithmetic at upload (scene_prepare.cpp); KEEP: not a triangle instance, no statement made
+#define INST_FLAG_EMITS 1u
+#define INST_FLAG_CAN_EVAL 2u
+#define INST_FLAG_SPECULAR 4u
+#define INST_FLAG_KEEP 0x80u
+
 #ifdef __cplusplus
 static_assert(sizeof(BvhNode) == 64, "BvhNode");
 static_assert(sizeof(BvhNodePacked) == 48, "BvhNodePacked");

@@ -300,7 +300,7 @@ struct InstView {
 };
 inline InstView view(const sthip_InstanceData& d) {
   InstView v;
-  v.type = d.packed[0] & 0xF;
+  v.type = instance_type(d);
   v.material_address = d.packed[0] >> 4;
   v.prim_count = (d.packed[1] >> 12) & 0xFFFF;
   v.stride = d.packed[1] >> 28;

@@ -18,6 +18,8 @@
 
 namespace sthip {
 
+inline uint32_t instance_type(const sthip_InstanceData& inst) { return inst.packed[0] & 0xFu; }  // STHIP_INSTANCE_TYPE_* (scene.h:29-47)
+
 // What a transforms-only update needs from the last full build (kept by the uploader): the bottom levels stay as they
 // are in HBM, the top level is rebuilt over new world boxes. The analogue of the reference's BLAS cache (Scene.cpp:435-459).
 struct TopLevelState {

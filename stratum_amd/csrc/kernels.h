@@ -182,24 +182,6 @@ DEV void store_color(void* img, size_t i, float4 v, uint32_t half) {
   else
     store_px(reinterpret_cast<float4*>(img), i, v);
 }
-// One emissive triangle instance: the box of its vertices in the space the traversal tests its triangles in (world space for an
-// instance with identity transforms, the instance's object space otherwise) and a sphere around it that sizes the per-ray
-// padding of the slab test exactly as the traversal's own boxes are padded (setup_space).
-struct EmitterBounds {
-  float lo[3];
-  uint32_t instance;
-  float hi[3];
-  uint32_t identity;
-  float sphere[4];
-};
-#define STHIP_MAX_EMITTER_BOUNDS 16u
-// DisneyMaterial::Le() > 0 somewhere / can_eval() / is_specular() of an instance's untextured material, evaluated on the host with
-// the device's arithmetic at upload (api.hip); KEEP: not a triangle instance, no statement made
-#define INST_FLAG_EMITS 1u
-#define INST_FLAG_CAN_EVAL 2u
-#define INST_FLAG_SPECULAR 4u
-#define INST_FLAG_KEEP 0x80u
-
 DEV bool flag(const FrameParams& p, int bit) { return (p.sampling_flags >> bit) & 1u; }
 
 // one global atomic per wave (and none when the wave's sum is zero): per-thread atomics on one

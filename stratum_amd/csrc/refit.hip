@@ -290,7 +290,7 @@ __global__ void k_refit_roots(const float4* box, const uint32_t* roots, uint32_t
   out[2 * r] = box[2 * (size_t)roots[r]];
   out[2 * r + 1] = box[2 * (size_t)roots[r] + 1];
 }
-// The box of the vertices an emissive instance's triangles refer to (kernels.h: EmitterBounds before its padding): one block
+// The box of the vertices an emissive instance's triangles refer to (bvh.h: EmitterBounds before its padding): one block
 // per instance, minima and maxima are exact whatever the order.
 __global__ void __launch_bounds__(REFIT_BLOCK) k_refit_emitter_boxes(const sthip_InstanceData* instances, const uint32_t* emitter_instance, const float4* vertices, uint32_t vertex_count, const uint8_t* indices,
                                                                      uint64_t indices_bytes, float4* out) {

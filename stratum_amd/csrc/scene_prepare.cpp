@@ -1,0 +1,305 @@
+// scene_prepare.cpp — see scene_prepare.h. Everything here is arithmetic over the caller's arrays; api.hip copies the results.
+#include "scene_prepare.h"
+
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+
+namespace sthip {
+
+bool check_scene(const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats, int& code, std::string& message) {
+  auto bad = [&](const std::string& m) {
+    code = STHIP_ERR_INVALID_ARGUMENT;
+    message = m;
+    return false;
+  };
+  auto bad_image = [](const sthip_image_desc& im) { return !im.pixels || im.width == 0 || im.height == 0 || im.width > 0xFFFF || im.height > 0xFFFF; };
+  if (!s || !s->gInstances || !s->gInstanceTransforms || !s->gInstanceInverseTransforms || !s->gMaterialData || s->instance_count == 0)
+    return bad("scene: a required array is NULL or there are no instances");
+  if ((s->vertex_count && !s->gVertices) || (s->indices_bytes && !s->gIndices))  // a scene of sphere instances alone has neither
+    return bad("scene: vertex_count / indices_bytes > 0 but the array is NULL");
+  if (s->instance_count > 0xFFFF) return bad("scene: more than 65535 instances (16-bit instance index, scene.h:23)");
+  if (s->light_count && !s->gLightInstances) return bad("scene: light_count > 0 but gLightInstances is NULL");
+  for (uint32_t i = 0; image_formats && s->gImages && i < s->image_count; i++)
+    if (image_formats[i] > STHIP_IMAGE_FORMAT_RGBA8_UNORM) return bad("scene: image_formats[" + std::to_string(i) + "] = " + std::to_string(image_formats[i]) + " is not a format of gImages");
+  for (uint32_t i = 0; image1_formats && s->gImage1s && i < s->image1_count; i++)
+    if (image1_formats[i] > STHIP_IMAGE_FORMAT_R8_UNORM) return bad("scene: image1_formats[" + std::to_string(i) + "] = " + std::to_string(image1_formats[i]) + " is not a format of gImage1s");
+  for (uint32_t i = 0; i < s->light_count; i++)
+    if (s->gLightInstances[i] >= s->instance_count) return bad("scene: gLightInstances entry out of range");
+  if (s->image_count && !s->gImages) return bad("scene: image_count > 0 but gImages is NULL");
+  // materials: constant values or image values over gImages (image_value.h:183-207)
+  for (uint32_t i = 0; i < s->instance_count; i++) {
+    const uint32_t addr = s->gInstances[i].packed[0] >> 4;
+    if (instance_type(s->gInstances[i]) == STHIP_INSTANCE_TYPE_VOLUME) {  // a Medium record (Material.hpp:80-87), 40 bytes
+      if ((size_t)addr + 40 > s->material_bytes || (addr & 3)) return bad("scene: medium material_address out of range");
+      uint32_t vol[2];
+      memcpy(vol, (const uint8_t*)s->gMaterialData + addr + 32, 8);
+      if (vol[0] >= s->volume_count || (vol[1] != 0xFFFFFFFFu && vol[1] >= s->volume_count)) return bad("scene: a medium refers to a volume that is not in gVolumes");
+      continue;
+    }
+    if ((size_t)addr + sizeof(sthip_MaterialRecord) > s->material_bytes) return bad("scene: material_address out of range");
+    sthip_MaterialRecord rec;
+    memcpy(&rec, (const uint8_t*)s->gMaterialData + addr, sizeof(rec));
+    for (int k = 0; k < 3; k++)
+      if (rec.values[k].image_index < STHIP_IMAGE_COUNT && rec.values[k].image_index >= s->image_count) return bad("scene: a material refers to an image that is not in gImages");
+    if (rec.bump_index < STHIP_IMAGE_COUNT && rec.bump_index >= s->image_count) return bad("scene: a bump map refers to an image that is not in gImages");
+    if (rec.alpha_mask_index < STHIP_IMAGE_COUNT && instance_type(s->gInstances[i]) == STHIP_INSTANCE_TYPE_TRIANGLES && rec.alpha_mask_index >= s->image1_count)
+      return bad("scene: a material refers to an alpha mask that is not in gImage1s");
+  }
+  if (s->image1_count && !s->gImage1s) return bad("scene: image1_count > 0 but gImage1s is NULL");
+  if (s->volume_count && !s->gVolumes) return bad("scene: volume_count > 0 but gVolumes is NULL");
+  if (s->distribution_count && !s->gDistributions) return bad("scene: distribution_count > 0 but gDistributions is NULL");
+  for (uint32_t i = 0; i < s->image_count; i++)
+    if (bad_image(s->gImages[i])) return bad("scene: bad image");
+  for (uint32_t i = 0; i < s->image1_count; i++)
+    if (bad_image(s->gImage1s[i])) return bad("scene: bad alpha-mask image");
+  std::vector<uint32_t> first_words;
+  if (volume_first_words(*s, first_words) > 0xFFFFFFFFull) return bad("scene: gVolumes exceed 16 GiB");
+  return true;
+}
+
+MaterialAnalysis analyse_materials(const sthip_scene_desc& s, const uint8_t* image_formats) {
+  MaterialAnalysis m;
+  // Per-channel extremes of an image (level 0; every mip level is an average of it, and bilinear / trilinear taps are
+  // convex combinations, so a sampled value lies between them). Scanned on first use: the device multiplies the
+  // constant by the texel (image_value.h:194-198), so whether a material can be specular depends on the texels.
+  std::vector<int> scanned(s.image_count, 0);
+  std::vector<float> tex_min((size_t)s.image_count * 4, 0.0f), tex_max((size_t)s.image_count * 4, 0.0f);
+  auto image_range = [&](uint32_t index, int channel, float& lo, float& hi) {
+    if (!scanned[index]) {
+      const float* px = s.gImages[index].pixels;
+      const uint8_t* px8 = image_formats && image_formats[index] ? reinterpret_cast<const uint8_t*>(px) : nullptr;  // RGBA8: the decoded bytes
+      const size_t count = (size_t)s.gImages[index].width * s.gImages[index].height;
+      for (int c = 0; c < 4; c++) {
+        float a = __builtin_inff(), b = -__builtin_inff();
+        bool nan = false;
+        for (size_t k = 0; px && k < count; k++) {
+          const float t = px8 ? (float)px8[4 * k + c] / 255.0f : px[4 * k + c];
+          if (t != t) nan = true;
+          a = std::min(a, t);
+          b = std::max(b, t);
+        }
+        if (nan || !px || !count) a = -__builtin_inff(), b = __builtin_inff();  // unknown: everything is possible
+        tex_min[(size_t)index * 4 + c] = a;
+        tex_max[(size_t)index * 4 + c] = b;
+      }
+      scanned[index] = 1;
+    }
+    lo = tex_min[(size_t)index * 4 + channel];
+    hi = tex_max[(size_t)index * 4 + channel];
+  };
+  // bounds of one component of an image value: constant, or constant * texel (zero when no component of the constant is positive)
+  auto value_range = [&](const sthip_MaterialRecord& rec, int k, int channel, float& lo, float& hi) {
+    const float c = rec.values[k].value[channel];
+    lo = hi = c;
+    const uint32_t index = rec.values[k].image_index;
+    if (index >= STHIP_IMAGE_COUNT || index >= s.image_count) return;
+    const float* v = rec.values[k].value;
+    if (!(v[0] > 0 || v[1] > 0 || v[2] > 0 || v[3] > 0)) {
+      lo = hi = 0.0f;
+      return;
+    }
+    float a, b;
+    image_range(index, channel, a, b);
+    lo = std::min(c * a, c * b);
+    hi = std::max(c * a, c * b);
+    if (lo != lo || hi != hi) lo = -__builtin_inff(), hi = __builtin_inff();
+  };
+  m.inst_flags.assign(std::max<uint32_t>(1, s.instance_count), (uint8_t)INST_FLAG_KEEP);  // k_cull_terminal's table (kernels.h)
+  m.instance_is_volume.assign(s.instance_count, 0);
+  for (uint32_t i = 0; i < s.instance_count; i++) {
+    const uint32_t addr = s.gInstances[i].packed[0] >> 4, type = instance_type(s.gInstances[i]);
+    if (type == STHIP_INSTANCE_TYPE_SPHERE) m.has_spheres = true;
+    if (type == STHIP_INSTANCE_TYPE_VOLUME) {  // a Medium record (Material.hpp:80-87), 40 bytes
+      m.has_volumes = true;
+      m.volume_instances++;
+      m.instance_is_volume[i] = 1;
+      float anisotropy;
+      memcpy(&anisotropy, (const uint8_t*)s.gMaterialData + addr + 12, 4);
+      if (!(fabsf(anisotropy) <= 0.999f)) m.has_specular = true;  // Medium::is_specular (medium.hlsli:22): its vertices are not diffuse vertices
+      continue;
+    }
+    sthip_MaterialRecord rec;
+    memcpy(&rec, (const uint8_t*)s.gMaterialData + addr, sizeof(rec));
+    for (int k = 0; k < 3; k++)
+      if (rec.values[k].image_index < STHIP_IMAGE_COUNT) m.textured = true;
+    if (rec.bump_index < STHIP_IMAGE_COUNT) m.textured = true;
+    if (rec.alpha_mask_index < STHIP_IMAGE_COUNT && type == STHIP_INSTANCE_TYPE_TRIANGLES) m.any_alpha = true;
+    // DisneyMaterial::is_specular (disney_material.hlsli:125) is evaluated per hit on value * texel, so the host test is
+    // over what the product can reach: conservative (a "maybe" only costs bounce rounds that find empty queues)
+    float lo, metallic_hi, roughness_lo, transmission_hi;
+    value_range(rec, 1, 0, lo, metallic_hi);
+    value_range(rec, 1, 1, roughness_lo, lo);
+    value_range(rec, 2, 2, lo, transmission_hi);
+    if ((metallic_hi > 0.999f || transmission_hi > 0.999f) && roughness_lo <= 1e-2f) m.has_specular = true;
+    if (type == STHIP_INSTANCE_TYPE_TRIANGLES || type == STHIP_INSTANCE_TYPE_SPHERE) {
+      // what DisneyMaterial::load reads of an untextured record (shading.h), with the device's arithmetic: Le = base_color *
+      // emission, can_eval, is_specular (only the untextured k_shade instantiations, i.e. a scene without images, consult this)
+      float f[14];
+      memcpy(f, (const uint8_t*)s.gMaterialData + addr, sizeof(f));
+      const float le[3] = {f[0] * f[3], f[1] * f[3], f[2] * f[3]};
+      const bool emits = le[0] > 0 || le[1] > 0 || le[2] > 0;
+      const bool can_eval = f[3] <= 0 && (f[0] > 0 || f[1] > 0 || f[2] > 0);
+      const bool specular = (f[5] > 0.999f || f[12] > 0.999f) && f[6] <= 1e-2f;
+      m.inst_flags[i] = (uint8_t)((emits ? INST_FLAG_EMITS : 0) | (can_eval ? INST_FLAG_CAN_EVAL : 0) | (specular ? INST_FLAG_SPECULAR : 0));
+    }
+  }
+  return m;
+}
+
+bool pad_emitter_bounds(EmitterBounds& b) {
+  double diag = 0;
+  for (int a = 0; a < 3; a++) {
+    const float mag = std::max(fabsf(b.lo[a]), fabsf(b.hi[a])) * (1.0f / 32768.0f) + 1e-30f;
+    b.lo[a] -= mag;
+    b.hi[a] += mag;
+    b.sphere[a] = 0.5f * b.lo[a] + 0.5f * b.hi[a];
+    diag += ((double)b.hi[a] - b.lo[a]) * ((double)b.hi[a] - b.lo[a]);
+  }
+  b.sphere[3] = (float)sqrt(diag);  // (twice the box's own radius: the padding only has to be large enough)
+  return std::isfinite(b.sphere[3]);
+}
+
+void emitter_bounds(const sthip_scene_desc& s, const std::vector<uint8_t>& inst_flags, std::vector<EmitterBounds>& out) {
+  out.clear();
+  bool usable = true;
+  for (uint32_t i = 0; i < s.instance_count && usable; i++) {
+    // (sphere lights, environments: scenes of the extended k_shade instantiation, which does not answer last rays)
+    if (instance_type(s.gInstances[i]) != STHIP_INSTANCE_TYPE_TRIANGLES || !(inst_flags[i] & INST_FLAG_EMITS)) continue;
+    if (out.size() == STHIP_MAX_EMITTER_BOUNDS) {
+      usable = false;
+      break;
+    }
+    const uint32_t prims = (s.gInstances[i].packed[1] >> 12) & 0xFFFFu, stride = s.gInstances[i].packed[1] >> 28;
+    const uint32_t first_vertex = s.gInstances[i].packed[2];
+    const uint8_t* ib = (const uint8_t*)s.gIndices + s.gInstances[i].packed[3];
+    EmitterBounds b{};
+    for (int a = 0; a < 3; a++) b.lo[a] = __builtin_inff(), b.hi[a] = -__builtin_inff();
+    for (uint32_t k = 0; k < 3 * prims; k++) {
+      uint32_t index;
+      if (stride == 2) {
+        uint16_t w;
+        memcpy(&w, ib + 2 * (size_t)k, 2);
+        index = w;
+      } else {
+        memcpy(&index, ib + 4 * (size_t)k, 4);
+      }
+      if ((size_t)first_vertex + index >= s.vertex_count) {  // (the builders have refused such a scene already)
+        usable = false;
+        break;
+      }
+      const float* pos = s.gVertices[first_vertex + index].position;
+      for (int a = 0; a < 3; a++) {
+        b.lo[a] = std::min(b.lo[a], pos[a]);
+        b.hi[a] = std::max(b.hi[a], pos[a]);
+      }
+    }
+    if (!prims || !(b.lo[0] <= b.hi[0])) continue;  // (no triangle: nothing to hit)
+    if (!pad_emitter_bounds(b)) usable = false;
+    b.instance = i;
+    static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    b.identity = (!memcmp(&s.gInstanceTransforms[i], ident, 48) && !memcmp(&s.gInstanceInverseTransforms[i], ident, 48)) ? 1u : 0u;
+    out.push_back(b);
+  }
+  if (!usable) out.clear();
+}
+
+// images: mip chain by 2x2 box filter, level k+1 = max(1, floor(dim / 2)), ((a + b) + (c + d)) * 0.25
+// (RGBA8 images, sthip_scene_upload_formats: the same shape in an array of their own, (a + b + c + d + 2) >> 2 per channel,
+// made on the device from level 0 — mips.hip)
+ImageLayout layout_images(const sthip_scene_desc& s, const uint8_t* image_formats) {
+  ImageLayout out;
+  std::vector<DeviceImage>& table = out.table;
+  std::vector<float>& texels = out.texels;
+  size_t& texels8 = out.texels8;  // words of image_texels8
+  table.resize(s.image_count);
+  for (uint32_t i = 0; i < s.image_count; i++) {
+    uint32_t w = s.gImages[i].width, h = s.gImages[i].height;
+    DeviceImage& im = table[i];
+    memset(&im, 0, sizeof(im));
+    if (image_formats && image_formats[i] == STHIP_IMAGE_FORMAT_RGBA8_UNORM) {  // the layout only: the texels go up from the caller's array
+      im.format = STHIP_IMAGE_FORMAT_RGBA8_UNORM;
+      for (uint32_t level = 0;; level++) {
+        im.offset[level] = (uint32_t)texels8;
+        im.w[level] = (uint16_t)w;
+        im.h[level] = (uint16_t)h;
+        im.levels = level + 1;
+        texels8 += (size_t)w * h;
+        if ((w == 1 && h == 1) || level + 1 == STHIP_MAX_MIPS) break;
+        w = std::max(1u, w / 2);
+        h = std::max(1u, h / 2);
+      }
+      if (texels8 > 0xFFFFFFFFull) {
+        out.error = "scene: the RGBA8 images exceed 2^32 texels (32-bit texel offsets)";
+        return out;
+      }
+      continue;
+    }
+    size_t level_start = texels.size();
+    texels.insert(texels.end(), s.gImages[i].pixels, s.gImages[i].pixels + (size_t)w * h * 4);
+    for (uint32_t level = 0;; level++) {
+      im.offset[level] = (uint32_t)(level_start / 4);
+      im.w[level] = (uint16_t)w;
+      im.h[level] = (uint16_t)h;
+      im.levels = level + 1;
+      if ((w == 1 && h == 1) || level + 1 == STHIP_MAX_MIPS) break;
+      const uint32_t nw = std::max(1u, w / 2), nh = std::max(1u, h / 2);
+      const size_t next_start = texels.size();
+      texels.resize(next_start + (size_t)nw * nh * 4);
+      const float* prev = texels.data() + level_start;
+      float* next = texels.data() + next_start;
+      for (uint32_t y = 0; y < nh; y++)
+        for (uint32_t x = 0; x < nw; x++) {
+          const uint32_t x0 = std::min(2 * x, w - 1), x1 = std::min(2 * x + 1, w - 1), y0 = std::min(2 * y, h - 1), y1 = std::min(2 * y + 1, h - 1);
+          for (int k = 0; k < 4; k++) {
+            const float a = prev[4 * ((size_t)y0 * w + x0) + k], b = prev[4 * ((size_t)y0 * w + x1) + k];
+            const float c = prev[4 * ((size_t)y1 * w + x0) + k], e = prev[4 * ((size_t)y1 * w + x1) + k];
+            next[4 * ((size_t)y * nw + x) + k] = ((a + b) + (c + e)) * 0.25f;
+          }
+        }
+      level_start = next_start;
+      w = nw;
+      h = nh;
+    }
+  }
+  return out;
+}
+
+MaskLayout layout_alpha_masks(const sthip_scene_desc& s, const uint8_t* image1_formats) {
+  MaskLayout out;
+  out.table.resize(s.image1_count);
+  for (uint32_t i = 0; i < s.image1_count; i++) {
+    const sthip_image_desc& im = s.gImage1s[i];
+    out.table[i].w = im.width;
+    out.table[i].h = im.height;
+    if (image1_formats && image1_formats[i] == STHIP_IMAGE_FORMAT_R8_UNORM) {
+      const uint8_t* bytes = reinterpret_cast<const uint8_t*>(im.pixels);
+      out.table[i].offset = (uint32_t)out.texels8.size();
+      out.table[i].format = STHIP_IMAGE_FORMAT_R8_UNORM;
+      out.texels8.insert(out.texels8.end(), bytes, bytes + (size_t)im.width * im.height);
+      if (out.texels8.size() > 0xFFFFFFFFull) {
+        out.error = "scene: the R8 alpha masks exceed 2^32 texels (32-bit texel offsets)";
+        return out;
+      }
+      continue;
+    }
+    out.table[i].offset = (uint32_t)out.texels.size();
+    out.table[i].format = STHIP_IMAGE_FORMAT_R32F;
+    out.texels.insert(out.texels.end(), im.pixels, im.pixels + (size_t)im.width * im.height);
+  }
+  return out;
+}
+
+size_t volume_first_words(const sthip_scene_desc& s, std::vector<uint32_t>& out) {
+  out.resize(s.volume_count);
+  size_t words = 0;
+  for (uint32_t i = 0; i < s.volume_count; i++) {
+    out[i] = (uint32_t)words;
+    words += (size_t)(s.gVolumes[i].bytes / 4);
+  }
+  return words;
+}
+
+}  // namespace sthip

@@ -1,0 +1,68 @@
+// scene_prepare.h — the host part of sthip_scene_upload that needs neither the built tree nor the device: the argument checks,
+// the scan of the materials, and the tables the upload copies to HBM as they are (bvh.h holds their layouts). No HIP, like
+// bvh_build.cpp: tests/cpp/scene_prepare_check.cpp runs it on the CPU under ASan / UBSan.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/sthip.h"
+#include "../../include/sthip_wire.h"
+#include "bvh.h"
+#include "bvh_build.h"
+
+namespace sthip {
+
+// Every refusal of an upload that can be decided from the arguments alone, in the order the checks have always had. false:
+// `code` (sthip_status) and `message` say why, and the caller changes nothing of its context. The image_formats /
+// image1_formats arrays are those of sthip_scene_upload_formats (NULL: all 0).
+bool check_scene(const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats, int& code, std::string& message);
+
+// What the materials of a checked scene say about the kernels it needs, and k_cull_terminal's per-instance table
+struct MaterialAnalysis {
+  bool has_specular = false;  // some material can satisfy DisneyMaterial::is_specular (or a medium Medium::is_specular)
+  bool textured = false;      // some material binds an image of gImages
+  bool any_alpha = false;     // some triangle instance's material has an alpha mask
+  bool has_spheres = false, has_volumes = false;
+  uint32_t volume_instances = 0;
+  std::vector<uint8_t> instance_is_volume;  // per instance
+  std::vector<uint8_t> inst_flags;          // per instance (at least one entry): INST_FLAG_*
+};
+MaterialAnalysis analyse_materials(const sthip_scene_desc& s, const uint8_t* image_formats);
+
+// EmitterBounds from the exact box of an emitter's vertices: widened by 2^-15 of its coordinates' magnitude, as the packed nodes
+// of the tree are, and the sphere that sizes the per-ray padding. false: not finite (the table cannot be used).
+bool pad_emitter_bounds(EmitterBounds& b);
+// The bounds of the emissive triangle instances (bvh.h: EmitterBounds), from the validated scene arrays: the box of the
+// vertices an instance's triangles refer to, widened by 2^-15 of its coordinates' magnitude as the packed nodes of the
+// tree are, in world space for an instance with identity transforms (that is where its triangles are tested, whether the
+// builder merged it or not: the identity's fmaf chain returns the world-space ray) and in object space otherwise. `out` stays
+// empty when the table cannot be used (more than STHIP_MAX_EMITTER_BOUNDS emitters, a box that is not finite). It reads
+// gIndices at offsets only build_scene_bvh validates: call it after that has succeeded on the same arrays.
+void emitter_bounds(const sthip_scene_desc& s, const std::vector<uint8_t>& inst_flags, std::vector<EmitterBounds>& out);
+
+// gImages as they lie in HBM: the table, the float images' texels with their mip chains (2x2 box filter), and the size of the
+// RGBA8 images' array in words (their layout only: level 0 goes up as it is and mips.hip makes the rest)
+struct ImageLayout {
+  std::vector<DeviceImage> table;
+  std::vector<float> texels;
+  size_t texels8 = 0;
+  const char* error = nullptr;  // set: the RGBA8 images exceed the 32-bit texel offsets (STHIP_ERR_UNSUPPORTED); the rest is not filled
+};
+ImageLayout layout_images(const sthip_scene_desc& s, const uint8_t* image_formats);
+
+// gImage1s (alpha masks: level 0 only): the table, the R32F texels and the R8 bytes, each array back to back
+struct MaskLayout {
+  std::vector<DeviceImage1> table;
+  std::vector<float> texels;
+  std::vector<uint8_t> texels8;
+  const char* error = nullptr;  // as ImageLayout::error, for the R8 masks
+};
+MaskLayout layout_alpha_masks(const sthip_scene_desc& s, const uint8_t* image1_formats);
+
+// gVolumes back to back as 32-bit words: the first word of each grid; returns the words in all
+size_t volume_first_words(const sthip_scene_desc& s, std::vector<uint32_t>& out);
+
+}  // namespace sthip

@@ -35,16 +35,6 @@ struct DeviceScene {
   const float4* leaf_shade;
 };
 
-#ifndef STHIP_MAX_MIPS
-#define STHIP_MAX_MIPS 16
-#endif
-struct DeviceImage {
-  uint32_t offset[STHIP_MAX_MIPS];  // first texel of each level in image_texels (format 0) or in image_texels8 (format 1)
-  uint16_t w[STHIP_MAX_MIPS], h[STHIP_MAX_MIPS];
-  uint32_t levels;
-  uint32_t format;  // sthip_image_format: STHIP_IMAGE_FORMAT_RGBA32F / STHIP_IMAGE_FORMAT_RGBA8_UNORM, uniform per image
-  uint32_t pad[2];
-};
 // an RGBA8 texel decoded: each byte b is the correctly rounded quotient (float)b / 255.0f (sthip.h; IEEE division)
 DEV float4 decode_rgba8(uint32_t t) {
   return make_float4((float)(t & 0xFFu) / 255.0f, (float)((t >> 8) & 0xFFu) / 255.0f, (float)((t >> 16) & 0xFFu) / 255.0f, (float)(t >> 24) / 255.0f);

@@ -63,10 +63,6 @@ struct DeviceBvh {
   uint32_t wide8_stack_depth;
   uint32_t wide8_tri_min;  // the leaf phase of the 8-wide walk goes on while at least this many lanes of the wave hold a triangle ("tri_min_lanes")
 };
-struct DeviceImage1 {
-  uint32_t offset, w, h;  // offset: first texel in image1_texels (format 0) or in image1_texels8 (format 1)
-  uint32_t format;        // sthip_image_format: STHIP_IMAGE_FORMAT_R32F / STHIP_IMAGE_FORMAT_R8_UNORM
-};
 // level-0 lookup of a one-channel image: bilinear, repeat addressing (the same arithmetic as DisneyMaterial::bilinear)
 DEV float sample_image1(const DeviceBvh& bvh, uint32_t index, float u, float v) {
   const DeviceImage1 im = bvh.images1[index];

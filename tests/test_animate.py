@@ -333,6 +333,33 @@ def test_a_rig_on_an_emissive_mesh_moves_the_emitter_bounds(built):
 
 
 @pytest.mark.gpu
+def test_rigs_survive_an_upload_refused_by_its_check(built):
+    """An upload that check_scene refuses leaves the context as it was: the rigs set before it still pose the resident scene, and
+    the frame is the one the same pose gives without the refused call in between."""
+    from stratum_amd._lib import StratumHipError
+
+    sc, cam = scenes.cornell_box()
+    frame = camera.Frame(32, 32, cam["fovy"], cam["eye"], cam["target"])
+    rigs = _scene_rigs(sc, [(0, 2, 0)])  # the floor
+    frames = []
+    for refused in (False, True):
+        r = make_renderer()
+        try:
+            r.update(sc)
+            r.set_rigs([rig for rig, _, _ in rigs])
+            if refused:
+                bad, _ = scenes.cornell_box()
+                bad.lights[0] = bad.instances.shape[0]
+                with pytest.raises(StratumHipError, match="gLightInstances entry out of range"):
+                    r.update(bad)
+            assert r.animate([pose for _, pose, _ in rigs])["rebuilt"] == 0
+            frames.append({k: v.copy() for k, v in r.render(frame, 0, 1).items()})
+        finally:
+            r.close()
+    same_frame(frames[1], frames[0], "the pose without the refused upload")
+
+
+@pytest.mark.gpu
 def test_chain_of_three_poses_is_the_last_pose_alone(built):
     """A pose is a function of the rest pose, not of the poses before it."""
     sc, cam = scenes.cornell_box()

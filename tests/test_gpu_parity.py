@@ -2116,3 +2116,40 @@ def test_reuse_grids_persist_between_calls():
             assert np.array_equal(r.render(frame, 6, 1, aovs=False)["radiance"], alone[2]["radiance"]), flags
         finally:
             r.close()
+
+
+def test_an_upload_refused_by_its_check_leaves_the_resident_scene():
+    """A call refused by check_scene changes nothing but sthip_last_error: the previous scene still renders the same frame with
+    the same rays, from the first hits kept before the refused call (no primary packet is traced again). A failure from the
+    build onward leaves no scene, as it always has."""
+    import re
+
+    from stratum_amd._lib import StratumHipError
+    from stratum_amd.bdpt import BDPT
+
+    sc, cam = scenes.cornell_box()
+    frame = camera.Frame(32, 32, cam["fovy"], cam["eye"], cam["target"])
+    r = BDPT(device=0)
+    try:
+        r.update(sc)
+        first = {k: v.copy() for k, v in r.render(frame, 0, 1).items()}
+        assert r.stats()["rays_primary_packets"] > 0
+        bad, _ = scenes.cornell_box()
+        bad.lights[0] = bad.instances.shape[0]
+        with pytest.raises(StratumHipError, match=re.escape("sthip_scene_upload failed (-1): scene: gLightInstances entry out of range")):
+            r.update(bad)
+        again = r.render(frame, 0, 1)
+        for k in first:
+            assert again[k].tobytes() == first[k].tobytes(), k
+        assert r.stats()["rays_primary_packets"] == 0
+        # the builder refuses an index past vertex_count: that is found after the previous scene was retired
+        bad, _ = scenes.cornell_box()
+        stride = int(bad.instances["packed"][0, 1] >> 28)
+        at = int(bad.instances["packed"][0, 3])
+        bad.indices[at : at + stride] = np.frombuffer((0xFFFF if stride == 2 else 0x7FFFFFFF).to_bytes(stride, "little"), dtype=np.uint8)
+        with pytest.raises(StratumHipError, match=re.escape("sthip_scene_upload failed (-1): scene: vertex index exceeds gVertices")):
+            r.update(bad)
+        with pytest.raises(StratumHipError, match=r"sthip_render\w* failed \(-5\)"):
+            r.render(frame, 0, 1)
+    finally:
+        r.close()

@@ -363,3 +363,407 @@ def test_host_bvh_builder_under_sanitizers(tmp_path, sanitizer):
         env = dict(os.environ, STHIP_BUILD_THREADS="6", ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1", TSAN_OPTIONS="halt_on_error=1")
         out = subprocess.run([exe, str(d)], capture_output=True, text=True, env=env)
         assert out.returncode == 0 and "BVH HOST OK" in out.stdout, name + ": " + out.stdout + out.stderr[-3000:]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The host part of the upload (stratum_amd/csrc/scene_prepare.cpp) under ASan + UBSan: tests/cpp/scene_prepare_check.cpp
+# ---------------------------------------------------------------------------------------------------------------------------
+F32 = np.float32
+DEVICE_IMAGE = np.dtype([("offset", "<u4", (16,)), ("w", "<u2", (16,)), ("h", "<u2", (16,)), ("levels", "<u4"), ("format", "<u4"), ("pad", "<u4", (2,))])
+DEVICE_IMAGE1 = np.dtype([("offset", "<u4"), ("w", "<u4"), ("h", "<u4"), ("format", "<u4")])
+EMITTER_BOUNDS = np.dtype([("lo", "<f4", (3,)), ("instance", "<u4"), ("hi", "<f4", (3,)), ("identity", "<u4"), ("sphere", "<f4", (4,))])
+INVALID = -1  # STHIP_ERR_INVALID_ARGUMENT
+
+
+@pytest.fixture(scope="module")
+def scene_prepare_check(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("scene_prepare") / "scene_prepare_check")
+    csrc = os.path.join(ROOT, "stratum_amd", "csrc")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
+                           os.path.join(ROOT, "tests", "cpp", "scene_prepare_check.cpp"), os.path.join(csrc, "scene_prepare.cpp"), os.path.join(csrc, "bvh_build.cpp"), "-lpthread"])
+    return exe
+
+
+def _image_entries(images):
+    """(width, height, format, payload) per image as scene_prepare_check reads them: uint8 arrays are the 8-bit formats"""
+    return [(im.shape[1], im.shape[0], 1 if im.dtype == np.uint8 else 0, im) for im in images]
+
+
+def _dump_arrays(d, sc, images=None, masks=None, volumes=None):
+    """The scene arrays of `sc` into directory `d`; images / masks / volumes override what the scene holds with explicit
+    entries (so that a descriptor can state what no array could hold: a width of 65536, 16 GiB of grids)"""
+    d.mkdir()
+    for arr, fn in ((sc.vertices, "vertices"), (sc.indices, "indices"), (sc.instances, "instances"), (sc.transforms, "xf"), (sc.inverse_transforms, "inv_xf"), (sc.materials, "materials"),
+                    (sc.lights.astype(np.uint32), "lights"), (sc.distributions.astype(F32), "distributions")):
+        np.ascontiguousarray(arr).tofile(str(d / (fn + ".bin")))
+    for fn, entries in (("images", _image_entries(sc.images) if images is None else images), ("masks", _image_entries(sc.images1) if masks is None else masks)):
+        with open(str(d / (fn + ".bin")), "wb") as f:
+            f.write(np.uint32(len(entries)).tobytes())
+            for w, h, fmt, payload in entries:
+                data = b"" if payload is None else np.ascontiguousarray(payload).tobytes()
+                f.write(np.array([w, h, fmt], np.uint32).tobytes() + np.uint64(len(data)).tobytes() + data)
+    with open(str(d / "volumes.bin"), "wb") as f:
+        entries = [(g.nbytes, g) for g in sc.volumes] if volumes is None else volumes
+        f.write(np.uint32(len(entries)).tobytes())
+        for stated, payload in entries:
+            data = np.ascontiguousarray(payload).tobytes()
+            f.write(np.array([stated, len(data)], np.uint64).tobytes() + data)
+    return str(d)
+
+
+def _run_prepare(exe, *args):
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
+    out = subprocess.run([exe] + list(args), capture_output=True, text=True, env=env)
+    assert out.returncode == 0, out.stdout + out.stderr[-3000:]
+    return out.stdout
+
+
+def _sphere_and_quad():
+    b = SceneBuilder("sphere_and_quad")
+    quad = b.add_mesh(*scenes._quad((-1, 0, 1), (1, 0, 1), (1, 0, -1), (-1, 0, -1), (0, 1, 0)))
+    b.add_instance(quad, b.add_material((0.7, 0.7, 0.7), roughness=0.3))
+    b.add_sphere(b.add_material((0.2, 0.5, 0.9), roughness=0.4), 0.5, translate((0, 1, 0)))
+    return b.build()
+
+
+def _record(sc, instance):
+    """the material record of an instance, as a writable view into the scene's material bytes"""
+    address = int(sc.instances["packed"][instance, 0]) >> 4
+    return sc.materials[address : address + wire.MaterialRecord.itemsize].view(wire.MaterialRecord)[0]
+
+
+def _rejections():
+    """(name, make scene, defect(sc) -> dump overrides or None, arguments, message): a valid scene with exactly one defect. The
+    messages are those of the upload before its checks moved into check_scene, copied here."""
+    cornell = lambda: scenes.cornell_box()[0]
+    textured = lambda: scenes.textured_box()[0]
+    foliage = lambda: scenes.foliage()[0]
+    foggy = lambda: foggy_cornell()[0]
+    env = lambda: scenes.environment_scene()[0]
+    cases = []
+    add = lambda name, make, defect, args, message: cases.append((name, make, defect, args, message))
+    required = "scene: a required array is NULL or there are no instances"
+    for a in ("scene", "gInstances", "gInstanceTransforms", "gInstanceInverseTransforms", "gMaterialData"):
+        add("null_" + a, cornell, None, ["null:" + a], required)
+
+    def no_instances(sc):
+        sc.instances = sc.instances[:0]
+
+    add("no_instances", cornell, no_instances, [], required)
+    for a in ("gVertices", "gIndices"):
+        add("null_" + a, cornell, None, ["null:" + a], "scene: vertex_count / indices_bytes > 0 but the array is NULL")
+
+    def many_instances(sc):
+        reps = 65536 // sc.instances.shape[0] + 1
+        sc.instances, sc.transforms, sc.inverse_transforms = (np.tile(a, reps)[:65536] for a in (sc.instances, sc.transforms, sc.inverse_transforms))
+
+    add("65536_instances", cornell, many_instances, [], "scene: more than 65535 instances (16-bit instance index, scene.h:23)")
+    add("null_gLightInstances", cornell, None, ["null:gLightInstances"], "scene: light_count > 0 but gLightInstances is NULL")
+
+    def image_format_2(sc):
+        e = _image_entries(sc.images)
+        e[0] = e[0][:2] + (2,) + e[0][3:]
+        return {"images": e}
+
+    def mask_format_2(sc):
+        e = _image_entries(sc.images1)
+        e[0] = e[0][:2] + (2,) + e[0][3:]
+        return {"masks": e}
+
+    add("image_format_2", textured, image_format_2, [], "scene: image_formats[0] = 2 is not a format of gImages")
+    add("mask_format_2", foliage, mask_format_2, [], "scene: image1_formats[0] = 2 is not a format of gImage1s")
+
+    def light_out_of_range(sc):
+        sc.lights[0] = sc.instances.shape[0]
+
+    add("light_out_of_range", cornell, light_out_of_range, [], "scene: gLightInstances entry out of range")
+    add("null_gImages", textured, None, ["null:gImages"], "scene: image_count > 0 but gImages is NULL")
+
+    def medium_of(sc):
+        return int(np.nonzero((sc.instances["packed"][:, 0] & 0xF) == wire.INSTANCE_TYPE_VOLUME)[0][0])
+
+    def medium_address(sc):
+        sc.instances["packed"][medium_of(sc), 0] = ((sc.materials.size - 36) << 4) | wire.INSTANCE_TYPE_VOLUME
+
+    def medium_misaligned(sc):
+        sc.instances["packed"][medium_of(sc), 0] += 2 << 4
+        sc.materials = np.concatenate([sc.materials, np.zeros(4, np.uint8)])
+
+    def medium_volume(sc):
+        address = int(sc.instances["packed"][medium_of(sc), 0]) >> 4
+        sc.materials[address + 32 : address + 36] = np.array([len(sc.volumes)], np.uint32).view(np.uint8)
+
+    add("medium_address", foggy, medium_address, [], "scene: medium material_address out of range")
+    add("medium_misaligned", foggy, medium_misaligned, [], "scene: medium material_address out of range")
+    add("medium_volume", foggy, medium_volume, [], "scene: a medium refers to a volume that is not in gVolumes")
+
+    def material_address(sc):
+        sc.instances["packed"][0, 0] = (sc.materials.size - wire.MaterialRecord.itemsize + 4) << 4
+
+    add("material_address", cornell, material_address, [], "scene: material_address out of range")
+    for k in range(3):
+        def image_index(sc, k=k):
+            _record(sc, 0)["values"]["image_index"][k] = len(sc.images)
+
+        add("image_index_%d" % k, textured, image_index, [], "scene: a material refers to an image that is not in gImages")
+
+    def bump_index(sc):
+        _record(sc, 0)["bump_index"] = len(sc.images)
+
+    add("bump_index", textured, bump_index, [], "scene: a bump map refers to an image that is not in gImages")
+
+    def alpha_index(instance):
+        def defect(sc):
+            _record(sc, instance)["alpha_mask_index"] = len(sc.images1)
+
+        return defect
+
+    add("alpha_index_foliage", foliage, lambda sc: alpha_index(int(np.nonzero([_record(sc, i)["alpha_mask_index"] < 4096 for i in range(sc.instances.shape[0])])[0][0]))(sc), [],
+        "scene: a material refers to an alpha mask that is not in gImage1s")
+    add("alpha_index_triangles", _sphere_and_quad, alpha_index(0), [], "scene: a material refers to an alpha mask that is not in gImage1s")
+    add("alpha_index_sphere", _sphere_and_quad, alpha_index(1), [], None)  # (a sphere has no uv to test a mask at: accepted)
+    add("null_gImage1s", foliage, None, ["null:gImage1s"], "scene: image1_count > 0 but gImage1s is NULL")
+    add("null_gVolumes", foggy, None, ["null:gVolumes"], "scene: volume_count > 0 but gVolumes is NULL")
+    add("null_gDistributions", env, None, ["null:gDistributions"], "scene: distribution_count > 0 but gDistributions is NULL")
+
+    def bad_image(which, w=None, h=None, pixels=True):
+        def defect(sc):
+            e = _image_entries(sc.images if which == "images" else sc.images1)
+            texel = np.zeros(4, F32)  # (the check looks at the descriptor only)
+            e[0] = (e[0][0] if w is None else w, e[0][1] if h is None else h, 0, texel if pixels else None)
+            return {which: e}
+
+        return defect
+
+    add("image_0_wide", textured, bad_image("images", w=0), [], "scene: bad image")
+    add("image_0_high", textured, bad_image("images", h=0), [], "scene: bad image")
+    add("image_65536_wide", textured, bad_image("images", w=65536), [], "scene: bad image")
+    add("image_65536_high", textured, bad_image("images", h=65536), [], "scene: bad image")
+    add("image_no_pixels", textured, bad_image("images", pixels=False), [], "scene: bad image")
+    add("mask_0_wide", foliage, bad_image("masks", w=0), [], "scene: bad alpha-mask image")
+    add("mask_65536_high", foliage, bad_image("masks", h=65536), [], "scene: bad alpha-mask image")
+    add("mask_no_pixels", foliage, bad_image("masks", pixels=False), [], "scene: bad alpha-mask image")
+    add("volumes_16_gib", foggy, lambda sc: {"volumes": [(1 << 34, g) for g in sc.volumes]}, [], "scene: gVolumes exceed 16 GiB")
+    add("valid_cornell", cornell, None, [], None)
+    add("valid_foggy", foggy, None, [], None)
+    return cases
+
+
+def test_check_scene_refuses_what_the_upload_refused(scene_prepare_check, tmp_path):
+    """Every refusal that moved from scene_upload into check_scene: a small valid scene with exactly that defect gets the code
+    and the message, byte for byte, that the upload gave it before the move."""
+    for name, make, defect, args, message in _rejections():
+        sc = make()
+        overrides = (defect(sc) if defect else None) or {}
+        out = _run_prepare(scene_prepare_check, "check", _dump_arrays(tmp_path / name, sc, **overrides), *args)
+        assert out == ("ACCEPTED\n" if message is None else "REFUSED %d\n%s\n" % (INVALID, message)), name + ": " + out
+
+
+# ---- the numpy restatement of scene_prepare.cpp's arithmetic: float32, the same operations in the same order ----
+def _texel_range(image, channel):
+    t = image[..., channel].reshape(-1)
+    t = t.astype(F32) / F32(255) if image.dtype == np.uint8 else t
+    if t.size == 0 or np.isnan(t).any():
+        return F32(-np.inf), F32(np.inf)
+    return t.min(), t.max()
+
+
+def _value_range(sc, rec, k, channel):
+    c = F32(rec["values"]["value"][k][channel])
+    index = int(rec["values"]["image_index"][k])
+    if index >= 4096 or index >= len(sc.images):
+        return c, c
+    if not np.any(rec["values"]["value"][k] > 0):
+        return F32(0), F32(0)
+    a, b = _texel_range(sc.images[index], channel)
+    with np.errstate(invalid="ignore"):
+        pa, pb = F32(c * a), F32(c * b)
+    lo, hi = (pb if pb < pa else pa), (pb if pa < pb else pa)  # std::min / std::max
+    if np.isnan(lo) or np.isnan(hi):
+        return F32(-np.inf), F32(np.inf)
+    return lo, hi
+
+
+def _analyse(sc):
+    n = sc.instances.shape[0]
+    flags = np.full(max(1, n), 0x80, np.uint8)
+    is_volume = np.zeros(n, np.uint8)
+    specular = textured = alpha = spheres = False
+    for i in range(n):
+        kind, address = int(sc.instances["packed"][i, 0]) & 0xF, int(sc.instances["packed"][i, 0]) >> 4
+        spheres |= kind == wire.INSTANCE_TYPE_SPHERE
+        if kind == wire.INSTANCE_TYPE_VOLUME:
+            is_volume[i] = 1
+            specular |= not (abs(sc.materials[address + 12 : address + 16].view(F32)[0]) <= F32(0.999))
+            continue
+        rec = sc.materials[address : address + wire.MaterialRecord.itemsize].view(wire.MaterialRecord)[0]
+        textured |= bool(np.any(rec["values"]["image_index"] < 4096)) or rec["bump_index"] < 4096
+        alpha |= rec["alpha_mask_index"] < 4096 and kind == wire.INSTANCE_TYPE_TRIANGLES
+        metallic_hi, roughness_lo, transmission_hi = _value_range(sc, rec, 1, 0)[1], _value_range(sc, rec, 1, 1)[0], _value_range(sc, rec, 2, 2)[1]
+        specular |= bool((metallic_hi > F32(0.999) or transmission_hi > F32(0.999)) and roughness_lo <= F32(1e-2))
+        f = sc.materials[address : address + 56].view(F32)
+        le = [F32(f[k] * f[3]) for k in range(3)]
+        emits, can_eval = any(v > 0 for v in le), f[3] <= 0 and any(f[k] > 0 for k in range(3))
+        flags[i] = (1 if emits else 0) | (2 if can_eval else 0) | (4 if (f[5] > F32(0.999) or f[12] > F32(0.999)) and f[6] <= F32(1e-2) else 0)
+    return np.array([specular, textured, alpha, spheres, bool(is_volume.any())], np.uint8), flags, is_volume
+
+
+def _layout_images(images):
+    table, texels, words8 = np.zeros(len(images), DEVICE_IMAGE), [], 0
+    floats = 0  # float4 texels so far
+    for i, im in enumerate(images):
+        h, w = im.shape[:2]
+        level = im
+        for k in range(16):
+            table[i]["offset"][k], table[i]["w"][k], table[i]["h"][k], table[i]["levels"] = (words8 if im.dtype == np.uint8 else floats), w, h, k + 1
+            if im.dtype == np.uint8:
+                table[i]["format"] = 1
+                words8 += w * h
+            else:
+                texels.append(level.reshape(-1))
+                floats += w * h
+            if (w == 1 and h == 1) or k == 15:
+                break
+            nw, nh = max(1, w // 2), max(1, h // 2)
+            if im.dtype != np.uint8:
+                x0, x1 = np.minimum(2 * np.arange(nw), w - 1), np.minimum(2 * np.arange(nw) + 1, w - 1)
+                y0, y1 = np.minimum(2 * np.arange(nh), h - 1), np.minimum(2 * np.arange(nh) + 1, h - 1)
+                a, b, c, e = level[y0][:, x0], level[y0][:, x1], level[y1][:, x0], level[y1][:, x1]
+                level = (((a + b) + (c + e)) * F32(0.25)).astype(F32)
+            w, h = nw, nh
+    return table, (np.concatenate(texels) if texels else np.zeros(0, F32)), np.uint64(words8)
+
+
+def _layout_masks(masks):
+    table, texels, texels8 = np.zeros(len(masks), DEVICE_IMAGE1), [np.zeros(0, F32)], [np.zeros(0, np.uint8)]
+    for i, im in enumerate(masks):
+        own = texels8 if im.dtype == np.uint8 else texels
+        table[i] = (sum(t.size for t in own), im.shape[1], im.shape[0], 1 if im.dtype == np.uint8 else 0)
+        own.append(im.reshape(-1))
+    return table, np.concatenate(texels), np.concatenate(texels8)
+
+
+def _emitters(sc, flags):
+    out = []
+    ident = np.eye(4, dtype=F32)[:3]
+    for i in range(sc.instances.shape[0]):
+        p = [int(v) for v in sc.instances["packed"][i]]
+        if (p[0] & 0xF) != wire.INSTANCE_TYPE_TRIANGLES or not (flags[i] & 1):
+            continue
+        if len(out) == 16:
+            return np.zeros(0, EMITTER_BOUNDS)
+        prims, stride = (p[1] >> 12) & 0xFFFF, p[1] >> 28
+        index = sc.indices[p[3] : p[3] + 3 * prims * stride].view("<u2" if stride == 2 else "<u4").astype(np.int64)
+        pos = sc.vertices["position"][p[2] + index]
+        b = np.zeros((), EMITTER_BOUNDS)
+        lo, hi = pos.min(axis=0), pos.max(axis=0)
+        mag = (np.maximum(np.abs(lo), np.abs(hi)) * (F32(1.0) / F32(32768.0)) + F32(1e-30)).astype(F32)
+        lo, hi = (lo - mag).astype(F32), (hi + mag).astype(F32)
+        b["lo"], b["hi"], b["instance"] = lo, hi, i
+        b["sphere"][:3] = F32(0.5) * lo + F32(0.5) * hi
+        b["sphere"][3] = F32(np.sqrt(np.sum((hi.astype(np.float64) - lo.astype(np.float64)) ** 2)))
+        b["identity"] = np.array_equal(sc.transforms["m"][i], ident) and np.array_equal(sc.inverse_transforms["m"][i], ident)
+        out.append(b)
+    return np.array(out, EMITTER_BOUNDS) if out else np.zeros(0, EMITTER_BOUNDS)
+
+
+def _expect(d, sc, what=("analysis", "images", "masks", "emitters", "volumes")):
+    """writes the restatement's results for `sc` beside the dumped arrays; the program compares bytes"""
+    flags5, inst_flags, is_volume = _analyse(sc)
+    results = {}
+    if "analysis" in what:
+        results.update(scene_flags=flags5, inst_flags=inst_flags, instance_is_volume=is_volume, volume_instances=np.uint32(is_volume.sum()))
+    if "images" in what:
+        results["image_table"], results["image_texels"], results["image_words8"] = _layout_images(sc.images)
+    if "masks" in what:
+        results["mask_table"], results["mask_texels"], results["mask_texels8"] = _layout_masks(sc.images1)
+    if "emitters" in what:
+        results["emitters"] = _emitters(sc, inst_flags)
+        results["emitter_count"] = np.uint32(results["emitters"].shape[0])
+    if "volumes" in what:
+        words = [g.nbytes // 4 for g in sc.volumes]
+        results["volume_first_words"], results["volume_words"] = np.cumsum([0] + words)[:-1].astype(np.uint32), np.uint64(sum(words))
+    for name, value in results.items():
+        np.ascontiguousarray(value).tofile(os.path.join(d, "expect_%s.bin" % name))
+    return results
+
+
+def _one_quad(material):
+    """a scene of one quad whose material `material(builder)` makes"""
+    b = SceneBuilder("one_quad")
+    b.add_instance(b.add_mesh(*scenes._quad((-1, 0, 1), (1, 0, 1), (1, 0, -1), (-1, 0, -1), (0, 1, 0))), material(b))
+    return b.build()
+
+
+def _params_material(texture, metallic=1.0, roughness=0.005):
+    def make(b):
+        m = b.add_material((0.8, 0.8, 0.8), metallic=metallic, roughness=roughness)
+        b.set_material_images(m, params_image=b.add_image(texture))
+        return m
+
+    return make
+
+
+def _prepared_scenes():
+    """(name, scene, has_specular the case is there to show or None)"""
+    out = [(make.__name__, make()[0], None) for make in (scenes.cornell_box, scenes.textured_box, scenes.spheres_room, scenes.environment_scene, scenes.foliage, foggy_cornell, shared_mesh_scene)]
+    out.append(("textured_box_mirror_map", scenes.textured_box(mirror_map=True)[0], 1))
+    # has_specular: what constant * texel can reach over the image's texels
+    rough0, rough1 = np.ones((2, 3, 4), F32), np.ones((2, 3, 4), F32)
+    rough0[1, 2, 1] = 0
+    nan = rough1.copy()
+    nan[0, 1, 1] = np.nan
+    out.append(("metal_roughness_texel_0", _one_quad(_params_material(rough0)), 1))
+    out.append(("metal_roughness_texel_1", _one_quad(_params_material(rough1)), 1))  # (0.005 * 1 is still <= 0.01)
+    out.append(("metal_rough_texel_0", _one_quad(_params_material(rough0, roughness=0.5)), 1))
+    out.append(("metal_rough_texel_1", _one_quad(_params_material(rough1, roughness=0.5)), 0))
+    out.append(("metal_rough_nan_texel", _one_quad(_params_material(nan, roughness=0.5)), 1))
+    out.append(("no_positive_component", _one_quad(_params_material(rough0, metallic=0.0, roughness=0.0)), 0))
+    out.append(("metal_rough_byte_0", _one_quad(_params_material((rough0 * 255).astype(np.uint8), roughness=0.5)), 1))
+    out.append(("metal_rough_byte_255", _one_quad(_params_material((rough1 * 255).astype(np.uint8), roughness=0.5)), 0))
+    # the mip chains: odd sizes (the min(2x + 1, w - 1) clamp), 65535 x 1 (16 levels: the STHIP_MAX_MIPS stop and the 1 x 1 stop
+    # coincide), float and RGBA8 images interleaved (two offset counters)
+    rng = np.random.default_rng(7)
+    sc = scenes.cornell_box()[0]
+    sc.images = []
+    for k, (w, h) in enumerate([(1, 1), (2, 2), (3, 5), (5, 3), (1, 7), (7, 1), (65535, 1)]):
+        sc.images.append(rng.random((h, w, 4), dtype=F32) * F32(4))
+        if k % 2 == 0:
+            sc.images.append(rng.integers(0, 256, (min(w, 8) + 1, h + 2, 4), dtype=np.uint8))
+    sc.images1 = [rng.random((2, 3), dtype=F32), rng.integers(0, 256, (3, 5), dtype=np.uint8), rng.random((1, 1), dtype=F32), rng.integers(0, 256, (2, 2), dtype=np.uint8)]
+    out.append(("mip_chains_and_masks", sc, None))
+    # 17 emitters: one more than the table holds, so there is no table
+    b = SceneBuilder("emitters17")
+    quad = b.add_mesh(*scenes._quad((-1, 0, 1), (1, 0, 1), (1, 0, -1), (-1, 0, -1), (0, 1, 0)))
+    light = b.add_emitter((5.0, 5.0, 5.0))
+    for k in range(17):
+        b.add_instance(quad, light, translate((3.0 * k, 0, 0)))
+    out.append(("emitters17", b.build(), None))
+    # two grids back to back
+    sc = foggy_cornell()[0]
+    sc.volumes = [sc.volumes[0], sc.volumes[0].copy()]
+    out.append(("two_grids", sc, None))
+    return out
+
+
+def test_scene_prepare_matches_its_numpy_restatement(scene_prepare_check, tmp_path):
+    """analyse_materials, layout_images, layout_alpha_masks, emitter_bounds and volume_first_words against the float32
+    restatement above, byte for byte, under ASan + UBSan."""
+    for name, sc, has_specular in _prepared_scenes():
+        d = _dump_arrays(tmp_path / name, sc)
+        results = _expect(d, sc)
+        if has_specular is not None:
+            assert results["scene_flags"][0] == has_specular, name
+        if name == "mip_chains_and_masks":
+            assert results["image_table"]["levels"][9] == 16 and results["image_table"]["w"][9][15] == 1  # 65535 x 1
+            assert [int(t["levels"]) for t in results["image_table"][[0, 2, 3]]] == [1, 2, 3]  # 1x1, 2x2, 3x5
+        if name == "emitters17":
+            assert results["emitter_count"] == 0
+        if name == "cornell_box":
+            assert results["emitter_count"] == 1 and results["emitters"]["identity"][0] == 1
+        if name == "shared_mesh_scene":
+            assert results["emitter_count"] == 1 and results["emitters"]["identity"][0] == 0
+        if name == "two_grids":
+            assert list(results["volume_first_words"]) == [0, sc.volumes[0].nbytes // 4]
+        out = _run_prepare(scene_prepare_check, "results", d)
+        assert "SCENE PREPARE OK" in out and out.count("bytes agree") == len(results), name + ": " + out

@@ -126,7 +126,7 @@ def test_header_loader_and_wire_agree_on_the_new_symbols(built):
     assert values == {"STHIP_IMAGE_FORMAT_RGBA32F": 0, "STHIP_IMAGE_FORMAT_RGBA8_UNORM": 1, "STHIP_IMAGE_FORMAT_R32F": 0, "STHIP_IMAGE_FORMAT_R8_UNORM": 1}
     for name, v in values.items():
         assert getattr(wire, name[len("STHIP_") :]) == v
-    shading = open(os.path.join(ROOT, "stratum_amd", "csrc", "shading.h")).read()
+    shading = open(os.path.join(ROOT, "stratum_amd", "csrc", "bvh.h")).read()  # (DeviceImage and its level count live there)
     assert int(re.search(r"#define\s+STHIP_MAX_MIPS\s+(\d+)", shading).group(1)) == wire.MAX_MIPS
     L = _lib.lib()
     for name in ("sthip_scene_upload_formats", "sthip_scene_read_image"):
