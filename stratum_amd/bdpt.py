@@ -67,12 +67,17 @@ class BDPT:
             raise StratumHipError("sthip_create(%d) failed (%d): %s" % (device, rc, self._lib.sthip_last_error(None).decode()))
         self._h = h
         self.device = device
-        self.mSamplingFlags = wire.DEFAULT_SAMPLING_FLAGS
-        self.mPushConstants = wire.default_push_constants(0, 0, 0)
-        self.mPushConstants.gLightPathCount = 64  # BDPT.cpp:70: the size of the light vertex cache unless --lightPathCount says otherwise (without eLVC: one path per pixel, :469-470)
         self._scene = None
         self._prev_result = None
         self.half_color_precision = False  # BDPT.hpp mHalfColorPrecision: colour images RGBA16F (set_half_color_precision)
+        self.set_args(args)
+
+    def set_args(self, args=None):
+        """The renderer arguments of the constructor, from the defaults (BDPT.cpp:55-127): what `args` does not name goes back to
+        its default. A living renderer may call it again; the scene, the options and the colour precision stay."""
+        self.mSamplingFlags = wire.DEFAULT_SAMPLING_FLAGS
+        self.mPushConstants = wire.default_push_constants(0, 0, 0)
+        self.mPushConstants.gLightPathCount = 64  # BDPT.cpp:70: the size of the light vertex cache unless --lightPathCount says otherwise (without eLVC: one path per pixel, :469-470)
         args = args or {}
         for key, field in (
             ("minPathVertices", "gMinPathVertices"),

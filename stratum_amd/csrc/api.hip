@@ -2563,8 +2563,9 @@ static void shade_view_round(const RenderRun& run, FrameParams& p, uint32_t dept
     launch_kernel(r.k_probe, r.grid, r.probe_lds, st, probe, depth);
   };
   const unsigned reduce_grid = (unsigned)((p.path_count + STHIP_BLOCK - 1) / STHIP_BLOCK);
+  const bool any_paths = p.path_count != 0;  // a shard that owns no tile of a small frame has no path: nothing to probe or reduce (and no grid of 0 blocks)
   p.rr = nullptr;
-  if (r.coherent_rr && depth + 2 >= r.pc.gMinPathVertices && depth + 2 < r.pc.gMaxPathVertices && (ctx->has_specular || depth + 1 <= r.pc.gMaxDiffuseVertices)) {
+  if (any_paths && r.coherent_rr && depth + 2 >= r.pc.gMinPathVertices && depth + 2 < r.pc.gMaxPathVertices && (ctx->has_specular || depth + 1 <= r.pc.gMaxDiffuseVertices)) {
     p.rr = ctx->rr.p;
     (void)hipMemsetAsync(ctx->rr.p, 0, (size_t)p.path_count * 16, st);
     launch_probe(1);
@@ -2574,13 +2575,13 @@ static void shade_view_round(const RenderRun& run, FrameParams& p, uint32_t dept
   // known: how many numbers a path draws in between depends on the candidates it looked at)
   p.cs_nee = nullptr;
   p.cs_lvc = nullptr;
-  if (r.coherent_nee) {
+  if (any_paths && r.coherent_nee) {
     p.cs_nee = ctx->cs_nee.p;
     (void)hipMemsetAsync(ctx->cs_nee.p, 0, (size_t)p.path_count * 8, st);
     launch_probe(2);
     hipLaunchKernelGGL(k_cs_reduce, dim3(reduce_grid), dim3(STHIP_BLOCK), 0, st, p.cs_nee, p.path_count);
   }
-  if (r.coherent_lvc) {
+  if (any_paths && r.coherent_lvc) {
     p.cs_lvc = ctx->cs_lvc.p;
     (void)hipMemsetAsync(ctx->cs_lvc.p, 0, (size_t)p.path_count * 8, st);
     launch_probe(3);

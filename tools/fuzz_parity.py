@@ -38,6 +38,69 @@ class _Dry:
     def close(self): pass
 
 
+def compare_frames(got, ref, W, H, shard_r=0, shard_n=1, connects=False, debug_mode=0, debug_start=None):
+    """One frame of the HIP path against the oracle's, bit for bit: radiance, albedo, prev-uv, the visibility ids and packed
+    normals, the three depth fields, the ray counts and, with a debug mode, the debug image. On a shard (16 x 8 tiles): its
+    own pixels against the frame's, zeros elsewhere (the debug image: as it was), the ray counts the shard's own; `ref` is
+    overwritten there with what cannot be compared. `connects`: eConnectToViews / eConnectToLightPaths is on (every shard
+    traces all light paths). Shared by fuzz_parity.py and fuzz_sequences.py."""
+    ok = True
+    if shard_n > 1:  # a shard renders its own tiles and writes zeros elsewhere; ray counts are the shard's own
+        from stratum_amd import shard as shard_mod
+
+        own = shard_mod.owner_map(W, H, shard_n, 16, 8) == shard_r
+        ok &= np.array_equal(got["radiance"].view(np.uint32)[own], ref["radiance"].view(np.uint32)[own]) and not got["radiance"][~own].any()
+        if connects:
+            ref["ray_count"] = got["ray_count"]  # every shard traces all light paths
+        else:
+            ref["ray_count"] = got["ray_count"] if own.sum() < W * H else ref["ray_count"]
+        for k in ("albedo", "prev_uv"):
+            ref[k] = got[k]
+        for k in ("visibility", "depth"):
+            ref[k] = got[k]
+        ref["radiance"] = got["radiance"]
+        if debug_mode:  # (a shard leaves the pixels of the others as they were; light tracing's splats land on its own pixels only)
+            ok &= np.array_equal(got["debug"].view(np.uint32)[own], ref["debug"].view(np.uint32)[own]) and np.array_equal(got["debug"][~own], debug_start[~own])
+            ref["debug"] = got["debug"]
+    if debug_mode: ok &= np.array_equal(got["debug"].view(np.uint32), ref["debug"].view(np.uint32))
+    for k in ("radiance", "albedo", "prev_uv"):
+        ok &= np.array_equal(got[k].view(np.uint32), ref[k].view(np.uint32))
+    ok &= np.array_equal(got["visibility"]["instance_primitive_index"], ref["visibility"]["instance_primitive_index"])
+    ok &= np.array_equal(got["visibility"]["packed_normal"], ref["visibility"]["packed_normal"])
+    for f in ("z", "prev_z", "dz_dxy"):
+        ok &= np.array_equal(got["depth"][f].view(np.uint32), ref["depth"][f].view(np.uint32))
+    ok &= np.array_equal(got["ray_count"], ref["ray_count"])
+    return bool(ok)
+
+
+def canon16(a):
+    """A float16 array with every NaN as the one quiet NaN 0x7E00 (a copy): NaN payloads are not part of the contract."""
+    a = np.array(a, dtype=np.float16, copy=True)
+    a.view(np.uint16)[np.isnan(a)] = 0x7E00
+    return a
+
+
+def half_of(a32):
+    """What half colour precision makes of a binary32 image: every value rounded to nearest even, NaN where it is NaN."""
+    with np.errstate(over="ignore"):
+        return canon16(np.asarray(a32, np.float32).astype(np.float16))
+
+
+def same_half(got16, want32):
+    """A float16 image against the RTNE of a binary32 one, bit for bit. The one statement of the rule, for both tools."""
+    return got16.dtype == np.float16 and np.array_equal(canon16(got16).view(np.uint16), half_of(want32).view(np.uint16))
+
+
+def compare_half(gh, got, debug=False):
+    """A frame rendered with half colour precision against its binary32 frame `got`: radiance / albedo (and the debug image) =
+    RTNE of the binary32 ones, NaN where they are NaN; the rest identical. Returns the names that differ."""
+    wrong = [k for k in ("radiance", "albedo") + (("debug",) if debug else ()) if not same_half(gh[k], got[k])]
+    for k in ("prev_uv", "visibility", "depth", "ray_count"):
+        if not np.array_equal(gh[k].view(np.uint8), got[k].view(np.uint8)):
+            wrong.append(k)
+    return wrong
+
+
 def run(cases=60, seed=1):
     rng = np.random.default_rng(seed)
     fog_params = {}
@@ -180,49 +243,19 @@ def run(cases=60, seed=1):
                 print("MISMATCH (oracle rejects, GPU accepts): %s %s %s: %s" % (kind, flags, args, e))
                 bad += 1
                 continue
-            ok = True
             ref0_debug = ref["debug"].copy() if debug_mode else None
             ref0_rad = ref["radiance"].copy()
-            if shard_n > 1:  # a shard renders its own tiles and writes zeros elsewhere; ray counts are the shard's own
-                from stratum_amd import shard as shard_mod
-
-                own = shard_mod.owner_map(W, H, shard_n, 16, 8) == shard_r
-                ok &= np.array_equal(got["radiance"].view(np.uint32)[own], ref["radiance"].view(np.uint32)[own]) and not got["radiance"][~own].any()
-                if "connecttoviews" in flags or "connecttolightpaths" in flags:
-                    ref["ray_count"] = got["ray_count"]  # every shard traces all light paths
-                else:
-                    ref["ray_count"] = got["ray_count"] if own.sum() < W * H else ref["ray_count"]
-                for k in ("albedo", "prev_uv"):
-                    ref[k] = got[k]
-                for k in ("visibility", "depth"):
-                    ref[k] = got[k]
-                ref["radiance"] = got["radiance"]
-                if debug_mode:  # (a shard leaves the pixels of the others as they were; light tracing's splats land on its own pixels only)
-                    ok &= np.array_equal(got["debug"].view(np.uint32)[own], ref["debug"].view(np.uint32)[own]) and np.array_equal(got["debug"][~own], debug_start[~own])
-                    ref["debug"] = got["debug"]
-            if debug_mode: ok &= np.array_equal(got["debug"].view(np.uint32), ref["debug"].view(np.uint32))
-            for k in ("radiance", "albedo", "prev_uv"):
-                ok &= np.array_equal(got[k].view(np.uint32), ref[k].view(np.uint32))
-            ok &= np.array_equal(got["visibility"]["instance_primitive_index"], ref["visibility"]["instance_primitive_index"])
-            ok &= np.array_equal(got["visibility"]["packed_normal"], ref["visibility"]["packed_normal"])
-            for f in ("z", "prev_z", "dz_dxy"):
-                ok &= np.array_equal(got["depth"][f].view(np.uint32), ref["depth"][f].view(np.uint32))
-            ok &= np.array_equal(got["ray_count"], ref["ray_count"])
+            ok = compare_frames(got, ref, W, H, shard_r, shard_n, "connecttoviews" in flags or "connecttolightpaths" in flags, debug_mode, debug_start)
             if HALF:  # the case again with half colour precision: radiance / albedo = RTNE of this binary32 frame, the rest identical
                 r.set_half_color_precision(True)
                 try:
                     gh = r.render(fr, seed0, seeds, debug_mode=debug_mode, debug_image=debug_start)
                 finally:
                     r.set_half_color_precision(False)
-                for k in ("radiance", "albedo"):
-                    with np.errstate(over="ignore"):
-                        want = got[k].astype(np.float16)
-                    nan = np.isnan(want)
-                    ok_h = gh[k].dtype == np.float16 and np.array_equal(np.isnan(gh[k]), nan) and np.array_equal(gh[k].view(np.uint16)[~nan], want.view(np.uint16)[~nan])
-                    if not ok_h: print("MISMATCH (half %s) %s %s %s" % (k, kind, flags, args))
-                    ok &= ok_h
-                for k in ("prev_uv", "visibility", "depth", "ray_count"):
-                    ok &= np.array_equal(gh[k].view(np.uint8), got[k].view(np.uint8))
+                wrong = compare_half(gh, got)
+                for k in wrong:
+                    if k in ("radiance", "albedo"): print("MISMATCH (half %s) %s %s %s" % (k, kind, flags, args))
+                ok &= not wrong
             done += 1
             if not ok:
                 bad += 1
@@ -253,6 +286,34 @@ def run(cases=60, seed=1):
 
 
 
+def awkward_rays(rng, sc, n):
+    """(rays, the style of each, the scene's bounds): axis-aligned and zero direction components, unnormalised and tiny / huge
+    directions, origins on vertices and far away, tmin > 0, tmin >= tmax, finite tmax."""
+    from stratum_amd import wire
+
+    lo = np.minimum.reduce([v for v in sc.vertices["position"]]) if sc.vertices.shape[0] else np.array([-2.0, -2, -2])
+    hi = np.maximum.reduce([v for v in sc.vertices["position"]]) if sc.vertices.shape[0] else np.array([2.0, 2, 2])
+    rays = np.zeros(n, wire.Ray)
+    o = rng.uniform(lo - 0.3 * (hi - lo), hi + 0.3 * (hi - lo), (n, 3))
+    d = rng.normal(size=(n, 3))
+    style = rng.integers(0, 8, n)
+    d[style == 1, int(rng.integers(3))] = 0.0                      # one zero component
+    z = style == 2
+    d[z] = 0.0
+    d[z, rng.integers(0, 3, z.sum())] = rng.choice([-1.0, 1.0], z.sum())  # axis-aligned
+    d[style == 3] *= 1e-6                                          # tiny, unnormalised
+    d[style == 4] *= 1e5                                           # huge
+    d[style == 5] = 0.0                                            # no direction at all
+    o[style == 6] *= 50.0                                          # far away
+    if sc.vertices.shape[0]:                                        # origins exactly on vertices
+        on = style == 7
+        o[on] = sc.vertices["position"][rng.integers(0, sc.vertices.shape[0], on.sum())]
+    rays["origin"], rays["direction"] = o.astype(np.float32), d.astype(np.float32)
+    rays["tmin"] = np.where(rng.integers(0, 4, n) == 0, rng.uniform(0, 1, n), 0).astype(np.float32)
+    rays["tmax"] = np.where(rng.integers(0, 3, n) == 0, rng.uniform(0, 3, n), np.inf).astype(np.float32)
+    return rays, style, lo, hi
+
+
 def run_rays(cases=40, seed=1, n=20000):
     """The traversal contract on awkward rays: axis-aligned and zero direction components, unnormalised and tiny / huge
     directions, origins on surfaces and far away, tmin > 0, tmin >= tmax, finite tmax; closest hit and any hit against
@@ -269,26 +330,7 @@ def run_rays(cases=40, seed=1, n=20000):
         elif kind == "foliage": sc, _ = scenes.foliage()
         elif kind == "textured": sc, _ = scenes.textured_box()
         else: sc, _ = scenes.cornell_box()
-        lo = np.minimum.reduce([v for v in sc.vertices["position"]]) if sc.vertices.shape[0] else np.array([-2.0, -2, -2])
-        hi = np.maximum.reduce([v for v in sc.vertices["position"]]) if sc.vertices.shape[0] else np.array([2.0, 2, 2])
-        rays = np.zeros(n, wire.Ray)
-        o = rng.uniform(lo - 0.3 * (hi - lo), hi + 0.3 * (hi - lo), (n, 3))
-        d = rng.normal(size=(n, 3))
-        style = rng.integers(0, 8, n)
-        d[style == 1, int(rng.integers(3))] = 0.0                      # one zero component
-        z = style == 2
-        d[z] = 0.0
-        d[z, rng.integers(0, 3, z.sum())] = rng.choice([-1.0, 1.0], z.sum())  # axis-aligned
-        d[style == 3] *= 1e-6                                          # tiny, unnormalised
-        d[style == 4] *= 1e5                                           # huge
-        d[style == 5] = 0.0                                            # no direction at all
-        o[style == 6] *= 50.0                                          # far away
-        if sc.vertices.shape[0]:                                        # origins exactly on vertices
-            on = style == 7
-            o[on] = sc.vertices["position"][rng.integers(0, sc.vertices.shape[0], on.sum())]
-        rays["origin"], rays["direction"] = o.astype(np.float32), d.astype(np.float32)
-        rays["tmin"] = np.where(rng.integers(0, 4, n) == 0, rng.uniform(0, 1, n), 0).astype(np.float32)
-        rays["tmax"] = np.where(rng.integers(0, 3, n) == 0, rng.uniform(0, 3, n), np.inf).astype(np.float32)
+        rays, style, lo, hi = awkward_rays(rng, sc, n)
         alpha = bool(rng.integers(2)) and kind == "foliage"
         r = BDPT(0)
         try:
