@@ -348,6 +348,81 @@ int sthip_scene_set_rigs(sthip_ctx* ctx, const sthip_rig_desc* rigs, uint32_t ri
 int sthip_scene_animate(sthip_ctx* ctx, const sthip_rig_pose* poses, uint32_t pose_count, sthip_refit_info* info);
 int sthip_scene_read_vertices(sthip_ctx* ctx, uint32_t first_vertex, uint32_t vertex_count, sthip_PackedVertexData* out);
 
+/* ---- material conversion: where the images of a material come from (Scene.cpp:123-256 -> kernels/material_convert.hlsl) ----
+ * The library renders from three R8G8B8A8Unorm images per material (DisneyMaterialData, disney_data.h) and one R8Unorm alpha
+ * mask. Upstream makes them on the device from what an asset holds: Scene::make_metallic_roughness_material (glTF: base colour
+ * + metallic/roughness) dispatches from_gltf_pbr (hlsl:46-76), Scene::make_diffuse_specular_material (Mitsuba / OBJ: diffuse +
+ * specular + shininess) from_diffuse_specular (:78-108), Scene::alpha_to_roughness and Scene::shininess_to_roughness the two
+ * one-channel kernels (:28-35, :37-44). sthip_convert_material is those four kernels; `kind` chooses one.
+ *
+ * Images are linear arrays of width * height texels, row 0 first. Sources: gDiffuse, gSpecular, gTransmittance — four
+ * channels, STHIP_IMAGE_FORMAT_RGBA32F or _RGBA8_UNORM, a format byte each; gRoughness (DIFFUSE_SPECULAR) and gInput (the two
+ * roughness kinds) — one channel, _R32F or _R8_UNORM. A NULL source is upstream's gUseX = false. A byte decodes as
+ * (float)b / 255.0f. Outputs: gOutput[3], the three DisneyMaterialData vectors per texel (data[0] = base colour rgb, emission;
+ * data[1] = metallic, roughness, anisotropic, subsurface; data[2] = clearcoat, clearcoat gloss, transmission, eta);
+ * gOutputAlphaMask, one channel, written only when gDiffuse is given; gOutputMinAlpha, one uint32_t, set to 0xFFFFFFFF by the
+ * call itself and then reduced; gRoughnessRW (one channel) for the roughness kinds. output_format 1: bytes (RGBA8 / R8, what
+ * upstream stores), 0: the unquantised binary32 values (RGBA32F / R32F).
+ * device_ptrs as in the calls after the path: host form — the sources are staged, the outputs copied back, and the call
+ * returns synchronised; device form — the clear of gOutputMinAlpha and one kernel are only enqueued on the context's stream,
+ * nothing is allocated or waited for, and gOutputMinAlpha is a device pointer too. Device images are naturally aligned (an
+ * RGBA8 image to 4 bytes, RGBA32F to 16, R32F to 4); all-8-bit images aligned to 16 bytes (one-channel ones to 4) take the
+ * wide path: four texels per lane.
+ *
+ * THE ARITHMETIC CONTRACT. Binary32, unfused, in the source order of the shader; only IEEE + - * / and sqrtf, all correctly
+ * rounded, so no det_* function is involved.
+ *   luminance(c) = (c.x * 0.2126f + c.y * 0.7152f) + c.z * 0.0722f
+ *   saturate(a)  = a > 0 ? (a < 1 ? a : 1) : 0, so a NaN gives 0.
+ *   GLTF_PBR          base = gDiffuse.rgb, or 1 without gDiffuse; metallic = gSpecular.b, roughness = gSpecular.g, both 1 without
+ *                     gSpecular; transmission = saturate(luminance(gTransmittance.rgb) / (l > 0 ? l : 1)) with l = luminance(base),
+ *                     0 without gTransmittance. Every other channel (emission, anisotropic, subsurface, clearcoat, clearcoat
+ *                     gloss, eta) is 1, as upstream's m.data[i] = 1.
+ *   DIFFUSE_SPECULAR  d, s, t = the rgb of gDiffuse, gSpecular, gTransmittance, 0 where absent; ld, ls, lt their luminances;
+ *                     den = (ls + ld) + lt; base = ((d * ld + s * ls) + t * lt) / den per channel; metallic = saturate(ls / den)
+ *                     only with gSpecular, roughness = gRoughness only with gRoughness, transmission = saturate(lt / den) only
+ *                     with gTransmittance; otherwise those channels stay 1, as all the others. 0 / 0 is a NaN and is kept in
+ *                     the float form.
+ *   ALPHA_TO_ROUGHNESS     saturate(sqrtf(x));  SHININESS_TO_ROUGHNESS  saturate(sqrtf(2 / (x + 2)))
+ *   quantisation (output_format 1)  byte = (uint32_t)(saturate(v) * 255.0f + 0.5f): two operations and a truncation; a NaN
+ *                     gives 0. Consequence: a byte that only passes through — GLTF base colour, metallic, roughness,
+ *                     gRoughness, the alpha mask — comes out as the byte that went in (it holds for all 256 bytes).
+ *   alpha             the mask receives gDiffuse.a, quantised as above or as it is. For texels with a < 1 (false for a NaN)
+ *                     min_alpha = min(min_alpha, (uint32_t)(saturate(a) * 4294967296.0f)): upstream's 0xFFFFFFFF becomes 2^32
+ *                     as a float, and the scaling is exact. The payload and sign of a NaN are not part of the contract.
+ * Differences from upstream, stated: all given sources must have the extent width x height (upstream reads the others at the
+ * first image's coordinates and relies on robust buffer access); the roughness result has output_format, not the input's.
+ * Refused with STHIP_ERR_INVALID_ARGUMENT, the message naming the field: an unknown kind; an empty extent or one of more than
+ * 2^30 texels; an output_format or the format byte of a given source that is none; no source at all for the two material
+ * kinds; a NULL gInput / gRoughnessRW for the roughness kinds; a NULL gOutput[k] or gOutputMinAlpha; a NULL gOutputAlphaMask
+ * although gDiffuse is given; with device_ptrs an image that is not naturally aligned. Fields a kind does not use are ignored.
+ * A library without the feature lacks the symbol. */
+enum {
+  STHIP_CONVERT_GLTF_PBR = 0,
+  STHIP_CONVERT_DIFFUSE_SPECULAR = 1,
+  STHIP_CONVERT_ALPHA_TO_ROUGHNESS = 2,
+  STHIP_CONVERT_SHININESS_TO_ROUGHNESS = 3,
+  STHIP_CONVERT_KIND_COUNT
+};
+typedef struct sthip_convert_material_desc {
+  uint32_t kind; /* STHIP_CONVERT_* */
+  uint32_t width, height;
+  uint32_t device_ptrs;
+  uint32_t output_format; /* sthip_image_format of every output */
+  uint8_t diffuse_format, specular_format, transmittance_format, roughness_format; /* sthip_image_format per source */
+  uint8_t input_format;
+  uint8_t pad_[7];
+  const void* gDiffuse; /* also the base colour; rgba */
+  const void* gSpecular; /* GLTF_PBR: the metallic/roughness image (b, g) */
+  const void* gTransmittance;
+  const void* gRoughness; /* one channel; DIFFUSE_SPECULAR */
+  const void* gInput;     /* one channel; the roughness kinds */
+  void* gOutput[3];
+  void* gOutputAlphaMask;    /* one channel */
+  uint32_t* gOutputMinAlpha; /* one word */
+  void* gRoughnessRW;        /* one channel; the roughness kinds */
+} sthip_convert_material_desc;
+int sthip_convert_material(sthip_ctx* ctx, const sthip_convert_material_desc* desc);
+
 /* ---- frame: replaces the dispatch sequence of BDPT::render (BDPT.cpp:607-720) ----
  * Renders seeds seed_begin .. seed_begin+seed_count-1 (gRandomSeed = seed, BDPT.cpp:480), one
  * sample per pixel centre per seed (bdpt.hlsl:167), and averages them with the running mean of

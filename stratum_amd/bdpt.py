@@ -234,6 +234,50 @@ class BDPT:
         self._check(self._lib.sthip_scene_read_image(self._h, int(index), int(level), wire.ptr(out), out.nbytes), "sthip_scene_read_image")
         return out
 
+    def convert_material(self, kind, diffuse=None, specular=None, transmittance=None, roughness=None, input=None, output_format=1):
+        """sthip_convert_material in its host form (kernels/material_convert.hlsl). `kind`: a name of wire.CONVERT or its
+        number. Sources are C-contiguous uint8 or float32 arrays, (H, W, 4) or, for `roughness` / `input`, (H, W); None =
+        absent. Returns a dict: "output" (three (H, W, 4) arrays), "alpha_mask" ((H, W), or None without `diffuse`) and
+        "min_alpha" (int) for the two material kinds, "roughness" ((H, W)) for the two roughness kinds; uint8 with
+        output_format 1, float32 with 0."""
+        kind = wire.CONVERT[kind] if isinstance(kind, str) else int(kind)
+        sources = {"gDiffuse": diffuse, "gSpecular": specular, "gTransmittance": transmittance, "gRoughness": roughness, "gInput": input}
+        formats = {"gDiffuse": "diffuse_format", "gSpecular": "specular_format", "gTransmittance": "transmittance_format", "gRoughness": "roughness_format", "gInput": "input_format"}
+        d = wire.ConvertMaterialDesc()
+        d.kind, d.device_ptrs, d.output_format = kind, 0, int(output_format)
+        extent = None
+        for name, a in sources.items():
+            if a is None:
+                continue
+            channels = 1 if name in ("gRoughness", "gInput") else 4
+            if a.dtype not in (np.uint8, np.float32) or not a.flags["C_CONTIGUOUS"] or a.ndim != (2 if channels == 1 else 3) or (channels == 4 and a.shape[2] != 4):
+                raise ValueError("%s must be a C-contiguous uint8 or float32 array of %d channel(s)" % (name, channels))
+            if extent is None:
+                extent = a.shape[:2]
+            elif a.shape[:2] != extent:
+                raise ValueError("%s has the extent %s, the first image %s: all sources must have one extent" % (name, a.shape[:2], extent))
+            setattr(d, name, a.ctypes.data)
+            setattr(d, formats[name], 1 if a.dtype == np.uint8 else 0)
+        if extent is None:
+            raise ValueError("convert_material: no source image")
+        H, W = extent
+        d.width, d.height = W, H
+        out_dtype = np.uint8 if output_format else np.float32
+        if kind in (wire.CONVERT["GltfPbr"], wire.CONVERT["DiffuseSpecular"]):
+            out = [np.zeros((H, W, 4), out_dtype) for _ in range(3)]
+            mask = np.zeros((H, W), out_dtype) if diffuse is not None else None
+            min_alpha = np.zeros(1, np.uint32)
+            for k in range(3):
+                d.gOutput[k] = out[k].ctypes.data
+            d.gOutputAlphaMask = mask.ctypes.data if mask is not None else None
+            d.gOutputMinAlpha = min_alpha.ctypes.data
+            self._check(self._lib.sthip_convert_material(self._h, C.byref(d)), "sthip_convert_material")
+            return {"output": out, "alpha_mask": mask, "min_alpha": int(min_alpha[0])}
+        rough = np.zeros((H, W), out_dtype)
+        d.gRoughnessRW = rough.ctypes.data
+        self._check(self._lib.sthip_convert_material(self._h, C.byref(d)), "sthip_convert_material")
+        return {"roughness": rough}
+
     def set_stream(self, stream_handle):
         self._check(self._lib.sthip_set_stream(self._h, C.c_void_p(stream_handle)), "sthip_set_stream")
 

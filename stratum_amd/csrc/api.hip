@@ -23,6 +23,7 @@
 #include "denoise.h"
 #include "bvh_build.h"
 #include "first_hits.h"
+#include "material_convert.h"
 #include "kernel_instances.h"  // kernels.h + the instantiations that live in shade_*.hip / trace_kernels.hip
 #include "mips.h"
 #include "post.h"
@@ -3282,6 +3283,105 @@ int sthip_denoise_filter(sthip_ctx* ctx, const sthip_denoise_desc* d) {
   release();
   if (!ok && e == hipSuccess) return fail(ctx, STHIP_ERR_HIP, "sthip_denoise_filter: " + err);
   if (e != hipSuccess || es != hipSuccess) return fail(ctx, STHIP_ERR_HIP, std::string("sthip_denoise_filter: ") + hipGetErrorString(e != hipSuccess ? e : es));
+  return STHIP_OK;
+}
+
+int sthip_convert_material(sthip_ctx* ctx, const sthip_convert_material_desc* d) {
+  if (!ctx || !d) return STHIP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const char* field, const char* why) { return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, std::string("sthip_convert_material: ") + field + " " + why); };
+  if (d->kind >= STHIP_CONVERT_KIND_COUNT) return refuse("kind", "must be below 4 (STHIP_CONVERT_*)");
+  if (!d->width) return refuse("width", "is 0");
+  if (!d->height) return refuse("height", "is 0");
+  if ((uint64_t)d->width * d->height > (1ull << 30)) return refuse("width x height", "is too large (more than 2^30 texels)");
+  if (d->output_format > 1) return refuse("output_format", "is no sthip_image_format");
+  const bool material = d->kind == STHIP_CONVERT_GLTF_PBR || d->kind == STHIP_CONVERT_DIFFUSE_SPECULAR;
+  const bool with_roughness = d->kind == STHIP_CONVERT_DIFFUSE_SPECULAR;
+  const size_t n = (size_t)d->width * d->height, out4 = d->output_format ? 4 : 16, out1 = d->output_format ? 1 : 4;
+  struct Image {  // one image of the descriptor: the bytes of a texel and what a device pointer must be aligned to
+    const char* name;
+    const void* p;
+    size_t texel, align;
+    bool source;
+  };
+  std::vector<Image> images;
+  int i_diffuse = -1, i_specular = -1, i_transmittance = -1, i_roughness = -1, i_input = -1, i_out[3] = {-1, -1, -1}, i_mask = -1, i_min = -1, i_rw = -1;
+  auto add = [&](const char* name, const void* p, size_t texel, size_t align, bool source) {
+    images.push_back({name, p, texel, align, source});
+    return (int)images.size() - 1;
+  };
+  if (material) {
+    if (!d->gDiffuse && !d->gSpecular && !d->gTransmittance && !(with_roughness && d->gRoughness))
+      return refuse(with_roughness ? "gDiffuse / gSpecular / gTransmittance / gRoughness" : "gDiffuse / gSpecular / gTransmittance", "are all NULL: no source");
+    if (d->gDiffuse && d->diffuse_format > 1) return refuse("diffuse_format", "is no sthip_image_format");
+    if (d->gSpecular && d->specular_format > 1) return refuse("specular_format", "is no sthip_image_format");
+    if (d->gTransmittance && d->transmittance_format > 1) return refuse("transmittance_format", "is no sthip_image_format");
+    if (with_roughness && d->gRoughness && d->roughness_format > 1) return refuse("roughness_format", "is no sthip_image_format");
+    if (!d->gOutput[0]) return refuse("gOutput[0]", "is NULL");
+    if (!d->gOutput[1]) return refuse("gOutput[1]", "is NULL");
+    if (!d->gOutput[2]) return refuse("gOutput[2]", "is NULL");
+    if (!d->gOutputMinAlpha) return refuse("gOutputMinAlpha", "is NULL");
+    if (d->gDiffuse && !d->gOutputAlphaMask) return refuse("gOutputAlphaMask", "is NULL although gDiffuse is given");
+    if (d->gDiffuse) i_diffuse = add("gDiffuse", d->gDiffuse, d->diffuse_format ? 4 : 16, d->diffuse_format ? 4 : 16, true);
+    if (d->gSpecular) i_specular = add("gSpecular", d->gSpecular, d->specular_format ? 4 : 16, d->specular_format ? 4 : 16, true);
+    if (d->gTransmittance) i_transmittance = add("gTransmittance", d->gTransmittance, d->transmittance_format ? 4 : 16, d->transmittance_format ? 4 : 16, true);
+    if (with_roughness && d->gRoughness) i_roughness = add("gRoughness", d->gRoughness, d->roughness_format ? 1 : 4, d->roughness_format ? 1 : 4, true);
+    i_out[0] = add("gOutput[0]", d->gOutput[0], out4, out4, false);
+    i_out[1] = add("gOutput[1]", d->gOutput[1], out4, out4, false);
+    i_out[2] = add("gOutput[2]", d->gOutput[2], out4, out4, false);
+    if (d->gDiffuse) i_mask = add("gOutputAlphaMask", d->gOutputAlphaMask, out1, out1, false);
+    i_min = add("gOutputMinAlpha", d->gOutputMinAlpha, 0, 4, false);  // (one word, whatever the extent)
+  } else {
+    if (!d->gInput) return refuse("gInput", "is NULL");
+    if (!d->gRoughnessRW) return refuse("gRoughnessRW", "is NULL");
+    if (d->input_format > 1) return refuse("input_format", "is no sthip_image_format");
+    i_input = add("gInput", d->gInput, d->input_format ? 1 : 4, d->input_format ? 1 : 4, true);
+    i_rw = add("gRoughnessRW", d->gRoughnessRW, out1, out1, false);
+  }
+  if (d->device_ptrs)
+    for (const Image& im : images)
+      if ((uintptr_t)im.p & (im.align - 1)) return refuse(im.name, "is not naturally aligned");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // host form: one device buffer per image (DevBuf: freed on return; poisoned under STHIP_POISON_ALLOC), sources copied up
+  std::vector<DevBuf<uint8_t>> staged(d->device_ptrs ? 0 : images.size());
+  std::vector<void*> dev(images.size());
+  for (size_t k = 0; k < images.size(); k++) {
+    const size_t bytes = images[k].texel ? n * images[k].texel : 4;
+    if (d->device_ptrs) {
+      dev[k] = const_cast<void*>(images[k].p);
+      continue;
+    }
+    HIP_TRY(ctx, staged[k].ensure(bytes));
+    dev[k] = staged[k].p;
+    if (images[k].source) HIP_TRY(ctx, hipMemcpyAsync(dev[k], images[k].p, bytes, hipMemcpyHostToDevice, st));
+  }
+  auto device_of = [&](int k) -> void* { return k < 0 ? nullptr : dev[k]; };
+  sthip::MaterialConvertParams p{};
+  p.kind = d->kind;
+  p.texels = n;
+  p.output_format = d->output_format;
+  p.diffuse = device_of(i_diffuse);
+  p.specular = device_of(i_specular);
+  p.transmittance = device_of(i_transmittance);
+  p.roughness = device_of(i_roughness);
+  p.input = device_of(i_input);
+  p.diffuse_format = d->diffuse_format, p.specular_format = d->specular_format, p.transmittance_format = d->transmittance_format, p.roughness_format = d->roughness_format;
+  p.input_format = d->input_format;
+  for (int k = 0; k < 3; k++) p.out[k] = device_of(i_out[k]);
+  p.alpha_mask = device_of(i_mask);
+  p.min_alpha = (uint32_t*)device_of(i_min);
+  p.roughness_rw = device_of(i_rw);
+  std::string err;
+  const bool ok = sthip::material_convert_launch(p, st, err);
+  hipError_t e = hipSuccess;
+  if (!d->device_ptrs) {  // the staged buffers must outlive the kernel: always synchronise
+    for (size_t k = 0; ok && e == hipSuccess && k < images.size(); k++)
+      if (!images[k].source) e = hipMemcpyAsync(const_cast<void*>(images[k].p), dev[k], images[k].texel ? n * images[k].texel : 4, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+  }
+  if (!ok) return fail(ctx, STHIP_ERR_HIP, "sthip_convert_material: " + err);
+  if (e != hipSuccess) return fail(ctx, STHIP_ERR_HIP, std::string("sthip_convert_material: ") + hipGetErrorString(e));
   return STHIP_OK;
 }
 

@@ -48,6 +48,8 @@
 #pragma weak sthip_scene_upload_formats
 #pragma weak sthip_scene_read_image
 // ... and one without the post block lacks these: Denoiser::denoise then throws
+// ... and one without the material conversions lacks this: Scene::make_*_material then throw for a material with images
+#pragma weak sthip_convert_material
 #pragma weak sthip_accumulate
 #pragma weak sthip_denoise_filter
 #include "../../include/sthip_detmath.h"  // det_f16tof32: export_hdr of a half frame
@@ -439,11 +441,25 @@ struct ImageValue4 {
   float value[4] = {0, 0, 0, 0};
   component_ptr<Image> image;  // null: constant value
 };
+// ImageValue1 / ImageValue3 (image_value.h): what the material conversions of Scene take (Scene.cpp:123-256). The image of an
+// ImageValue3 is an rgba Image, as upstream's is a Texture2D<float4>
+struct ImageValue1 {
+  float value = 0;
+  component_ptr<Image1> image;
+};
+struct ImageValue3 {
+  float value[3] = {0, 0, 0};
+  component_ptr<Image> image;
+};
 struct Material {
   ImageValue4 values[3];
   component_ptr<Image1> alpha_mask;  // Material.hpp:14
   component_ptr<Image> bump_image;
   float bump_strength = 1;
+  // Material.hpp:15,19: the reduced minimum of the base colour's alpha, which only a converted material has
+  bool has_min_alpha = false;
+  uint32_t min_alpha = 0xFFFFFFFFu;
+  bool alpha_test() const { return has_min_alpha && min_alpha < 0xFFFFFFFFu / 2; }
   float* base_color() { return values[0].value; }
   float& emission() { return values[0].value[3]; }
   float& metallic() { return values[1].value[0]; }
@@ -705,6 +721,7 @@ struct Camera {
 // the HIP stream stands in for the Vulkan command buffer the reference threads through update()/render()
 struct CommandBuffer {
   void* hip_stream = nullptr;
+  sthip_ctx* ctx = nullptr;  // the device the material conversions of Scene run on (upstream: commandBuffer.mDevice); BDPT::context()
 };
 
 // Application.hpp:11-29: only the two events the renderer hooks
@@ -809,6 +826,45 @@ class Scene {
     on = on && sthip_scene_set_rigs && sthip_scene_animate;
     if (on != mPoseOnDevice) mDirty = true;
     mPoseOnDevice = on;
+  }
+
+  // ---- the material conversions, Scene.cpp:123-256 -> kernels/material_convert.hlsl (sthip_convert_material) ----
+  // The scalar part in binary32 as upstream writes it; with an image present the kernels run on cb.ctx (host form), and the
+  // results become 8-bit Image / Image1 components on child nodes of this Scene's node. All given images must have one extent.
+  static float luminance(const float c[3]) { return (c[0] * 0.2126f + c[1] * 0.7152f) + c[2] * 0.0722f; }
+  ImageValue1 alpha_to_roughness(CommandBuffer& cb, const ImageValue1& alpha) { return to_roughness(cb, alpha, STHIP_CONVERT_ALPHA_TO_ROUGHNESS); }              // Scene.cpp:123-138
+  ImageValue1 shininess_to_roughness(CommandBuffer& cb, const ImageValue1& shininess) { return to_roughness(cb, shininess, STHIP_CONVERT_SHININESS_TO_ROUGHNESS); }  // :139-154
+  Material make_metallic_roughness_material(CommandBuffer& cb, const ImageValue3& base_color, const ImageValue4& metallic_roughness, const ImageValue3& transmission, float eta,
+                                            const ImageValue3& emission) {  // Scene.cpp:156-203
+    Material dst;
+    if (emissive(emission, dst)) return dst;
+    for (int k = 0; k < 3; k++) dst.base_color()[k] = base_color.value[k];
+    dst.emission() = 0;
+    dst.metallic() = metallic_roughness.value[2];
+    dst.roughness() = metallic_roughness.value[1];
+    dst.anisotropic() = dst.subsurface() = dst.clearcoat() = 0;
+    dst.clearcoat_gloss() = 1;
+    dst.transmission() = luminance(transmission.value);
+    dst.eta() = eta;
+    convert(cb, STHIP_CONVERT_GLTF_PBR, base_color.image.get(), metallic_roughness.image.get(), transmission.image.get(), nullptr, dst);
+    return dst;
+  }
+  Material make_diffuse_specular_material(CommandBuffer& cb, const ImageValue3& diffuse, const ImageValue3& specular, const ImageValue1& roughness, const ImageValue3& transmission, float eta,
+                                          const ImageValue3& emission) {  // Scene.cpp:204-256
+    Material dst;
+    if (emissive(emission, dst)) return dst;
+    const float ld = luminance(diffuse.value), ls = luminance(specular.value), lt = luminance(transmission.value);
+    const float den = (ld + ls) + lt;
+    for (int k = 0; k < 3; k++) dst.base_color()[k] = ((diffuse.value[k] * ld + specular.value[k] * ls) + transmission.value[k] * lt) / den;
+    dst.emission() = 0;
+    dst.metallic() = ls / den;
+    dst.roughness() = roughness.value;
+    dst.anisotropic() = dst.subsurface() = dst.clearcoat() = 0;
+    dst.clearcoat_gloss() = 1;
+    dst.transmission() = lt / den;
+    dst.eta() = eta;
+    convert(cb, STHIP_CONVERT_DIFFUSE_SPECULAR, diffuse.image.get(), specular.image.get(), transmission.image.get(), roughness.image.get(), dst);
+    return dst;
   }
 
   // Scene.cpp:299-684 for MeshPrimitive instances: same traversal order (breadth-first), same packing
@@ -993,6 +1049,75 @@ class Scene {
   }
 
  private:
+  // the early return of both material functions, Scene.cpp:158-164,206-212
+  static bool emissive(const ImageValue3& emission, Material& dst) {
+    if (!(emission.value[0] > 0 || emission.value[1] > 0 || emission.value[2] > 0)) return false;
+    const float l = luminance(emission.value);
+    dst.values[0].image = emission.image;
+    for (int k = 0; k < 3; k++) dst.base_color()[k] = emission.value[k] / l;
+    dst.emission() = l;
+    dst.eta() = 0;
+    return true;
+  }
+  static sthip_ctx* convert_context(CommandBuffer& cb) {
+    if (!sthip_convert_material) throw std::runtime_error("this libstratum_hip.so has no sthip_convert_material");
+    if (!cb.ctx) throw std::invalid_argument("converting an image needs CommandBuffer::ctx (BDPT::context()): the kernels run on the device");
+    return cb.ctx;
+  }
+  template <typename I>
+  static void source(const I* im, uint32_t& width, uint32_t& height, const void*& p, uint8_t& format) {
+    if (!im) return;
+    if (!width) width = im->width, height = im->height;  // (upstream's order: the extent is the first present image's)
+    if (im->width != width || im->height != height) throw std::invalid_argument("material conversion: all source images must have the extent of the first one");
+    p = im->is_8bit() ? (const void*)im->bytes.data() : (const void*)im->pixels.data();
+    format = im->is_8bit() ? 1 : 0;
+  }
+  ImageValue1 to_roughness(CommandBuffer& cb, const ImageValue1& x, uint32_t kind) {
+    ImageValue1 roughness;
+    roughness.value = kind == STHIP_CONVERT_ALPHA_TO_ROUGHNESS ? std::sqrt(x.value) : std::sqrt(2.0f / (x.value + 2.0f));
+    if (!x.image) return roughness;
+    sthip_ctx* ctx = convert_context(cb);
+    sthip_convert_material_desc d{};
+    d.kind = kind;
+    d.output_format = 1;
+    source(x.image.get(), d.width, d.height, d.gInput, d.input_format);
+    roughness.image = mNode.make_child("roughness").make_component<Image1>();
+    roughness.image->width = d.width, roughness.image->height = d.height;
+    roughness.image->bytes.resize((size_t)d.width * d.height);
+    d.gRoughnessRW = roughness.image->bytes.data();
+    if (sthip_convert_material(ctx, &d) != STHIP_OK) throw std::runtime_error(std::string("sthip_convert_material: ") + sthip_last_error(ctx));
+    return roughness;
+  }
+  void convert(CommandBuffer& cb, uint32_t kind, const Image* diffuse, const Image* specular, const Image* transmittance, const Image1* roughness, Material& dst) {
+    if (!diffuse && !specular && !transmittance && !roughness) return;
+    sthip_ctx* ctx = convert_context(cb);
+    sthip_convert_material_desc d{};
+    d.kind = kind;
+    d.output_format = 1;
+    source(diffuse, d.width, d.height, d.gDiffuse, d.diffuse_format);
+    source(specular, d.width, d.height, d.gSpecular, d.specular_format);
+    source(transmittance, d.width, d.height, d.gTransmittance, d.transmittance_format);
+    source(roughness, d.width, d.height, d.gRoughness, d.roughness_format);
+    const size_t n = (size_t)d.width * d.height;
+    for (int k = 0; k < 3; k++) {
+      dst.values[k].image = mNode.make_child("material data").make_component<Image>();
+      dst.values[k].image->width = d.width, dst.values[k].image->height = d.height;
+      dst.values[k].image->bytes.resize(n * 4);
+      d.gOutput[k] = dst.values[k].image->bytes.data();
+    }
+    std::vector<uint8_t> mask(diffuse ? n : 0);
+    if (diffuse) d.gOutputAlphaMask = mask.data();
+    dst.min_alpha = 0xFFFFFFFFu;
+    d.gOutputMinAlpha = &dst.min_alpha;
+    if (sthip_convert_material(ctx, &d) != STHIP_OK) throw std::runtime_error(std::string("sthip_convert_material: ") + sthip_last_error(ctx));
+    dst.has_min_alpha = true;
+    // upstream marks the geometry of a material whose alpha_test() is false opaque: its mask is never read, so it gets none
+    if (diffuse && dst.alpha_test()) {
+      dst.alpha_mask = mNode.make_child("alpha mask").make_component<Image1>();
+      dst.alpha_mask->width = d.width, dst.alpha_mask->height = d.height;
+      dst.alpha_mask->bytes = std::move(mask);
+    }
+  }
   Node& mNode;
   std::shared_ptr<SceneData> mSceneData;
   bool mDirty = true;
@@ -1144,6 +1269,7 @@ class BDPT {
     sthip_destroy(mCtx);
   }
   BDPT(const BDPT&) = delete;
+  sthip_ctx* context() const { return mCtx; }  // for CommandBuffer::ctx
 
   // the instance arguments BDPT's constructor reads (BDPT.cpp:78-127): `minPathVertices`, `maxPathVertices`,
   // `maxDiffuseVertices`, `maxNullCollisions`, `environmentSampleProbability`, `lightPresampleTileSize`,

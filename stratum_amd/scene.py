@@ -212,6 +212,29 @@ class SceneData:
         return d
 
 
+class ImageValue:
+    """ImageValue1 / ImageValue3 / ImageValue4 (image_value.h): a constant `value` (1, 3 or 4 floats) and an optional image, a
+    C-contiguous uint8 or float32 array, (H, W) for one channel and (H, W, 4) otherwise. What the material conversions of
+    SceneBuilder take; a plain number or sequence stands for a value without an image."""
+
+    def __init__(self, value, image=None):
+        self.value = np.atleast_1d(np.asarray(value, dtype=np.float32))
+        self.image = image
+
+    @staticmethod
+    def of(x, n):
+        v = x if isinstance(x, ImageValue) else ImageValue(x)
+        if v.value.shape != (n,):
+            raise ValueError("an ImageValue%d needs %d value(s), not %s" % (n, n, v.value.shape))
+        return v
+
+
+def _luminance(c):
+    """luminance (common.h) in binary32, added left to right."""
+    c = np.asarray(c, np.float32)
+    return np.float32(np.float32(c[0] * np.float32(0.2126) + c[1] * np.float32(0.7152)) + c[2] * np.float32(0.0722))
+
+
 class SceneBuilder:
     def __init__(self, name=""):
         self.name = name
@@ -226,6 +249,7 @@ class SceneBuilder:
         self._images1 = []  # float32 (H, W), or uint8 (H, W): one-channel images (alpha masks)
         self._spheres = []  # (material index, 4x4 node transform, radius): SpherePrimitive, Scene.hpp:34-37
         self._environment = None  # (value rgb, image handle or None): Environment, environment.h
+        self._min_alpha = {}  # material handle -> Material::min_alpha of a converted material (Material.hpp:15)
 
     # -- Material::store, Material.hpp:32-38; conventions of load_mitsuba.cpp:330-343,454-489 --
     def add_material(
@@ -281,6 +305,93 @@ class SceneBuilder:
         if bump_image is not None:
             rec["bump_index"] = bump_image
             rec["bump_strength"] = bump_strength
+
+    # -- the material conversions, Scene.cpp:123-256 -> kernels/material_convert.hlsl (sthip_convert_material) --
+    def min_alpha(self, material):
+        """Material::min_alpha (Material.hpp:15): the reduced minimum of the base colour's alpha of a converted material, in
+        units of 2^-32; None for a material that never had one."""
+        return self._min_alpha.get(material)
+
+    def alpha_test(self, material):
+        """Material::alpha_test (Material.hpp:19): min_alpha < 0xFFFFFFFF / 2; false without a min_alpha."""
+        m = self._min_alpha.get(material)
+        return m is not None and m < 0xFFFFFFFF // 2
+
+    def _roughness(self, kind, x, context):
+        x = ImageValue.of(x, 1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            v = x.value[0]
+            value = np.sqrt(v) if kind == "AlphaToRoughness" else np.sqrt(np.float32(2) / np.float32(v + np.float32(2)))
+        if x.image is None:
+            return ImageValue(value)
+        if context is None:
+            raise ValueError("converting an image needs a context (a BDPT): the kernels run on the device")
+        return ImageValue(value, context.convert_material(kind, input=x.image)["roughness"])
+
+    def alpha_to_roughness(self, alpha, context=None):
+        """Scene::alpha_to_roughness (Scene.cpp:123-138): value sqrt(alpha); the image, if any, through the device kernel
+        (saturate(sqrt(x)), stored as R8). Returns an ImageValue."""
+        return self._roughness("AlphaToRoughness", alpha, context)
+
+    def shininess_to_roughness(self, shininess, context=None):
+        """Scene::shininess_to_roughness (Scene.cpp:139-154): sqrt(2 / (shininess + 2)), value and image."""
+        return self._roughness("ShininessToRoughness", shininess, context)
+
+    def _emissive(self, emission):
+        # the early return of both functions, Scene.cpp:158-164,206-212: the emission image becomes the base colour image
+        lum = _luminance(emission.value)
+        m = self.add_material(emission.value / lum, emission=float(lum), eta=0.0)
+        if emission.image is not None:
+            self.set_material_images(m, base_color_image=self.add_image(emission.image))
+        return m
+
+    def _converted(self, material, kind, sources, context):
+        images = [a for a in sources.values() if a is not None]  # (upstream's order: the extent is the first present image's)
+        if not images:
+            return material
+        if context is None:
+            raise ValueError("converting images needs a context (a BDPT): the kernels run on the device")
+        for a in images:
+            if a.shape[:2] != images[0].shape[:2]:
+                raise ValueError("all source images must have the extent of the first one")
+        r = context.convert_material(kind, output_format=1, **sources)
+        handles = [self.add_image(im) for im in r["output"]]
+        self.set_material_images(material, base_color_image=handles[0], params_image=handles[1], lobes_image=handles[2])
+        self._min_alpha[material] = r["min_alpha"]
+        # upstream marks the geometry of a material whose alpha_test() is false opaque: its mask is never read, so it gets none
+        if r["alpha_mask"] is not None and self.alpha_test(material):
+            self.set_material_alpha_mask(material, self.add_image1(r["alpha_mask"]))
+        return material
+
+    def make_metallic_roughness_material(self, base_color, metallic_roughness=(1.0, 1.0, 1.0, 1.0), transmission=(0.0, 0.0, 0.0), eta=1.5, emission=(0.0, 0.0, 0.0), context=None):
+        """Scene::make_metallic_roughness_material (Scene.cpp:156-203), the glTF form: base_color (ImageValue3; its image is
+        rgba), metallic_roughness (ImageValue4: metallic in b, roughness in g), transmission and emission (ImageValue3). The
+        scalar part is computed here in binary32; with an image present the three material images, the alpha mask and its
+        minimum come from from_gltf_pbr on the device (`context`: a BDPT) and are registered as 8-bit images. Returns the
+        material's handle."""
+        base_color, metallic_roughness = ImageValue.of(base_color, 3), ImageValue.of(metallic_roughness, 4)
+        transmission, emission = ImageValue.of(transmission, 3), ImageValue.of(emission, 3)
+        if (emission.value > 0).any():
+            return self._emissive(emission)
+        m = self.add_material(base_color.value, emission=0.0, metallic=metallic_roughness.value[2], roughness=metallic_roughness.value[1], anisotropic=0.0, subsurface=0.0, clearcoat=0.0,
+                              clearcoat_gloss=1.0, transmission=_luminance(transmission.value), eta=eta)
+        return self._converted(m, "GltfPbr", {"diffuse": base_color.image, "specular": metallic_roughness.image, "transmittance": transmission.image}, context)
+
+    def make_diffuse_specular_material(self, diffuse, specular=(0.0, 0.0, 0.0), roughness=1.0, transmission=(0.0, 0.0, 0.0), eta=1.5, emission=(0.0, 0.0, 0.0), context=None):
+        """Scene::make_diffuse_specular_material (Scene.cpp:204-256), the Mitsuba / OBJ form: diffuse, specular, transmission
+        and emission are ImageValue3 (the diffuse image is rgba), roughness an ImageValue1. Values in binary32 as upstream
+        writes them; images through from_diffuse_specular on the device. Returns the material's handle."""
+        diffuse, specular, roughness = ImageValue.of(diffuse, 3), ImageValue.of(specular, 3), ImageValue.of(roughness, 1)
+        transmission, emission = ImageValue.of(transmission, 3), ImageValue.of(emission, 3)
+        if (emission.value > 0).any():
+            return self._emissive(emission)
+        ld, ls, lt = _luminance(diffuse.value), _luminance(specular.value), _luminance(transmission.value)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            den = np.float32(np.float32(ld + ls) + lt)
+            base = ((diffuse.value * ld + specular.value * ls) + transmission.value * lt) / den
+            m = self.add_material(base, emission=0.0, metallic=ls / den, roughness=roughness.value[0], anisotropic=0.0, subsurface=0.0, clearcoat=0.0, clearcoat_gloss=1.0,
+                                  transmission=lt / den, eta=eta)
+        return self._converted(m, "DiffuseSpecular", {"diffuse": diffuse.image, "specular": specular.image, "transmittance": transmission.image, "roughness": roughness.image}, context)
 
     def add_emitter(self, radiance):
         """Mitsuba area emitter: base_color = L / lum(L), emission = lum(L), eta = 0 (load_mitsuba.cpp:480-489)."""

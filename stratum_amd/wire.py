@@ -410,3 +410,33 @@ class DenoiseDesc(C.Structure):
         ("gFilterImages", C.c_void_p * 2),
         ("pass_ms", C.c_void_p),
     ]
+
+
+# sthip_convert_material (include/sthip.h): the four kernels of kernels/material_convert.hlsl
+CONVERT_KINDS = ["GltfPbr", "DiffuseSpecular", "AlphaToRoughness", "ShininessToRoughness"]  # STHIP_CONVERT_*
+CONVERT = {n: i for i, n in enumerate(CONVERT_KINDS)}
+
+
+class ConvertMaterialDesc(C.Structure):
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("device_ptrs", C.c_uint32),
+        ("output_format", C.c_uint32),
+        ("diffuse_format", C.c_uint8),
+        ("specular_format", C.c_uint8),
+        ("transmittance_format", C.c_uint8),
+        ("roughness_format", C.c_uint8),
+        ("input_format", C.c_uint8),
+        ("pad_", C.c_uint8 * 7),
+        ("gDiffuse", C.c_void_p),
+        ("gSpecular", C.c_void_p),
+        ("gTransmittance", C.c_void_p),
+        ("gRoughness", C.c_void_p),
+        ("gInput", C.c_void_p),
+        ("gOutput", C.c_void_p * 3),
+        ("gOutputAlphaMask", C.c_void_p),
+        ("gOutputMinAlpha", C.c_void_p),
+        ("gRoughnessRW", C.c_void_p),
+    ]
