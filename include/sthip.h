@@ -423,6 +423,92 @@ typedef struct sthip_convert_material_desc {
 } sthip_convert_material_desc;
 int sthip_convert_material(sthip_ctx* ctx, const sthip_convert_material_desc* desc);
 
+/* ---- the environment of a resident scene (environment.h:8-25,96-150; dist2.h:80-154) ----
+ * An image environment is three things in HBM: the RGBA32F image of gImages with its mip chain (Environment::sample_texel
+ * descends it under eSampleEnvironmentMapDirectly), the four dist2d tables in gDistributions — marginal_pdf[H], row_pdf[H*W],
+ * marginal_cdf[H+1], row_cdf[H*(W+1)] — and the Environment record in gMaterialData: ImageValue3 {value[3], image index} and,
+ * with an image, the four table offsets. sthip_scene_set_environment replaces the value and / or the texels of the resident
+ * environment and makes the mip chain and the tables again ON THE DEVICE (environment.hip); nothing else of the scene is
+ * copied, rebuilt or analysed again.
+ *   pixels != NULL: level 0 of the record's image is replaced (width x height must be the resident extent), every further
+ *     level is made again, and the four tables are made again at the offsets the record names.
+ *   pixels == NULL and value == NULL: the tables are made from the texels that are resident ("build the tables of what is
+ *     resident": a host that uploaded zero-filled tables calls this once).
+ *   value != NULL: the three floats of the record are rewritten, in gMaterialData on the device, in the context's host copy
+ *     of it and in the kept scene. Alone it touches neither texels nor tables.
+ * The trees, emitter tables and the material analysis stay as they are. The call does not count as a scene change for
+ * "reuse_first_hits" (no triangle, instance or alpha mask moves: kept first hits stay valid); kept reservoir grids
+ * ("reuse_grids_persist") are dropped, as at an upload. It waits for the stream and completes the frames in flight first, as
+ * the other scene calls do, and returns when its own work on the stream has finished.
+ *
+ * The arithmetic is part of the contract; the results are the bits the host statements give (layout_images of
+ * scene_prepare.cpp; build_distributions of scene.py and of stratum_hip.hpp).
+ *   mip chain, all binary32: level k+1 has the extent max(1, w/2) x max(1, h/2); each channel of a texel is
+ *     ((a + b) + (c + e)) * 0.25f over the texels (x0, y0), (x1, y0), (x0, y1), (x1, y1) of level k with
+ *     x0 = min(2x, w-1), x1 = min(2x+1, w-1), y0 = min(2y, h-1), y1 = min(2y+1, h-1).
+ *   tables, for the W x H texels of level 0:
+ *     lum = (r*0.2126f + g*0.7152f) + b*0.0722f, binary32, unfused;
+ *     s[y] = sin(M_PI * (y + 0.5f) * (1/(float)H)): y + 0.5f and 1/(float)H are binary32, the products and the sine binary64.
+ *       The host part of the call computes the H values with libm and sends them up (no device sine equals libm's bits);
+ *     f(x,y) = (double)lum * s[y];
+ *     row[0] = 0; row[x+1] = (float)((double)row[x] + f(x,y)) for x = 0 .. W-1 in this order; integral = row[W];
+ *     integral > 0: row[x] = row[x] / integral for x < W (a binary32 division), row_pdf[x] = (float)(f(x,y) / (double)integral);
+ *     otherwise (zero, negative or NaN): row_pdf[x] = 1.0f / (float)W, row[x] = (float)x / (float)W, row[W] = 1;
+ *     marginal: m[0] = 0; m[y+1] = m[y] + row_y[W] in y order, binary32 (a fallback row weighs 1); total = m[H];
+ *     total > 0: marginal_cdf[y] = m[y] / total for y < H, marginal_pdf[y] = row_y[W] / total;
+ *     otherwise: marginal_pdf[y] = 1.0f / (float)H, marginal_cdf[y] = (float)y / (float)H; in both cases marginal_cdf[H] = 1;
+ *     last, row_y[W] = 1 for every row.
+ *   Denormals are kept. Where a NaN stands is part of the contract; its sign and payload are not.
+ * Only the x order of a row and the y order of the marginal are serial; the device runs one chain per lane for the rows
+ * (k_env_rows), one lane for the marginal (k_env_marginal) and everything else elementwise (k_env_normalise, k_mip_rgba32f).
+ *
+ * Refusals are all decided before anything resident is touched; a refused call changes nothing.
+ * STHIP_ERR_INVALID_ARGUMENT: no scene; a wrong struct_size; a material_address that is not a multiple of 4 or whose record
+ * does not lie inside gMaterialData; an image index that is not in gImages; `pixels` for a record without an image; a width or
+ * height that differs from the resident extent; a table that lies outside gDistributions (the check sthip_render makes) or
+ * two tables of the record that overlap; a `value` of three zeros (upstream stores no record for a zero environment,
+ * Scene.cpp:631-640). STHIP_ERR_UNSUPPORTED: the image is resident as RGBA8_UNORM (sthip_render refuses such an environment
+ * too); `pixels` for an image that a material record of gMaterialData also names (the material analysis of the upload scanned
+ * its texels: other texels could need other kernels).
+ *
+ * The kept scene ("keep_scene" = 1): a host `pixels` array and a `value` go into the kept copy at once. Pixels from a device
+ * pointer and tables built on the device are NOT copied back per call: the kept image and the kept tables are marked stale and
+ * fetched from the device immediately before anything is built again from the kept scene (a moved instance of the merged
+ * mesh, a layout the refit does not serve, the failure fallback) — the rule the rigs follow. With "keep_scene" = 0 nothing is
+ * kept and nothing needs doing.
+ *
+ * Cost, measured on an MI355X (profiles/r10/environment.json, tools/environment_times.py, medians of 9 calls, a small scene
+ * under a 4096 x 2048 sky: 128 MB of texels, 64 MB of tables): 7.29 ms for the call with `pixels` in pageable host memory
+ * (7.25 ms of it on the stream: the copy), 0.38 ms from a device pointer, 0.27 ms for the tables alone; the alternative
+ * without this call is 38.9 ms for the host's build_distributions (one thread) plus 94.5 ms for sthip_scene_upload of the same
+ * scene in the same process. Under a 2048 x 1024 sky: 1.86, 0.19 and 0.14 ms against 7.5 + 25.1 ms. The row pass is
+ * latency-bound (0.18 ms, 0.18 of the triad rate, with 16 rows per wave, the default of "env_rows_per_wave"; 0.49 ms with 64).
+ *
+ * Measurement only: with the environment variable STHIP_ENVIRONMENT_TIMES=<file> (read once per process) every call that
+ * builds tables appends one JSON line to the file with the HIP-event time of each stage: copy_ms, mips_ms, sines_ms,
+ * k_env_rows_ms, k_env_marginal_ms, k_env_normalise_ms and the rows_per_wave in force (tools/environment_times.py reads them).
+ * Without the variable the call makes no extra event and touches no file.
+ *
+ * sthip_scene_read_distributions: the resident gDistributions[first, first + count) copied to host memory after the work on
+ * the stream has finished (tests; a host that wants device-built tables back). STHIP_ERR_INVALID_ARGUMENT: no scene, a range
+ * past distribution_count, a NULL `out` with count > 0.
+ * A library without the feature lacks the two symbols. */
+typedef struct sthip_environment_desc {
+  uint32_t struct_size;      /* sizeof(sthip_environment_desc) */
+  uint32_t material_address; /* byte address of the Environment record in gMaterialData (what a render passes as gEnvironmentMaterialAddress) */
+  const float* value;        /* 3 floats: new ImageValue3::value; NULL = keep */
+  const void* pixels;        /* RGBA32F, width x height, tightly packed; NULL = keep the resident texels */
+  uint32_t width, height;    /* with pixels: must equal the resident extent of the record's image */
+  uint32_t device_ptr;       /* 1: pixels is device memory, readable in the order of the context's stream */
+  uint32_t pad;
+} sthip_environment_desc;
+typedef struct sthip_environment_info { /* optional out-parameter, may be NULL */
+  float device_ms;                      /* stream time of the copies and kernels of the call (HIP events) */
+  float total_ms;                       /* wall time of the call */
+} sthip_environment_info;
+int sthip_scene_set_environment(sthip_ctx* ctx, const sthip_environment_desc* desc, sthip_environment_info* info);
+int sthip_scene_read_distributions(sthip_ctx* ctx, uint32_t first, uint32_t count, float* out);
+
 /* ---- frame: replaces the dispatch sequence of BDPT::render (BDPT.cpp:607-720) ----
  * Renders seeds seed_begin .. seed_begin+seed_count-1 (gRandomSeed = seed, BDPT.cpp:480), one
  * sample per pixel centre per seed (bdpt.hlsl:167), and averages them with the running mean of
@@ -673,7 +759,9 @@ int sthip_measure_ceiling(sthip_ctx* ctx, uint32_t kind, double* gbytes_per_s);
  * with it.
  * "output_ring" (1..8, default 2): see sthip_render_async.
  * "denoise_block" (0 = default, 1): the lanes of a block of sthip_denoise_filter's kernels cover 32x8 or 16x16 pixels; never
- * changes results. */
+ * changes results.
+ * "env_rows_per_wave" (16 = default, or 64; anything else is refused): the rows a wave of k_env_rows owns in
+ * sthip_scene_set_environment; never changes results. */
 int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value);
 
 /* ---- after the path: display transform, image metric, HDR export ---- */

@@ -30,6 +30,8 @@ EXPORTS = [
     "sthip_scene_animate",
     "sthip_scene_read_vertices",
     "sthip_convert_material",
+    "sthip_scene_set_environment",
+    "sthip_scene_read_distributions",
     "sthip_render",
     "sthip_host_alloc",
     "sthip_host_free",
@@ -121,6 +123,11 @@ def lib():
     if hasattr(L, "sthip_convert_material"):  # (an older build named by STHIP_LIB lacks it: calling it raises)
         L.sthip_convert_material.restype = C.c_int
         L.sthip_convert_material.argtypes = [C.c_void_p, C.POINTER(wire.ConvertMaterialDesc)]
+    if hasattr(L, "sthip_scene_set_environment"):  # (an older build named by STHIP_LIB lacks the two: calling them raises)
+        L.sthip_scene_set_environment.restype = C.c_int
+        L.sthip_scene_set_environment.argtypes = [C.c_void_p, C.POINTER(wire.EnvironmentDesc), C.POINTER(wire.EnvironmentInfo)]
+        L.sthip_scene_read_distributions.restype = C.c_int
+        L.sthip_scene_read_distributions.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.sthip_render.restype = C.c_int
     L.sthip_render.argtypes = [
         C.c_void_p,

@@ -146,6 +146,8 @@ class BDPT:
             self._check(self._lib.sthip_scene_upload(self._h, C.byref(d)), "sthip_scene_upload")
         scene.dirty_vertices = None  # (the whole vertex array went up)
         self._scene = scene
+        if getattr(scene, "environment_tables", "host") == "device":  # SceneBuilder.build(environment_tables="device"): zero-filled tables went up
+            self.set_environment()
 
     def update_transforms(self, scene):
         """Only instance transforms changed since update(scene) (SceneData.set_instance_transform): the top level of the
@@ -232,6 +234,52 @@ class BDPT:
         h, w = max(1, im.shape[0] >> int(level)), max(1, im.shape[1] >> int(level))
         out = np.zeros((h, w, 4), im.dtype)
         self._check(self._lib.sthip_scene_read_image(self._h, int(index), int(level), wire.ptr(out), out.nbytes), "sthip_scene_read_image")
+        return out
+
+    def set_environment(self, value=None, image=None, device_ptr=False):
+        """Replace the environment of the resident scene (sthip_scene_set_environment): `value` = three floats, the new
+        ImageValue3::value; `image` = the new texels of the environment's image, a C-contiguous float32 array (H, W, 4) of the
+        resident extent, or with device_ptr=True anything with data_ptr() and shape (a torch tensor on this device: float32,
+        contiguous, (H, W, 4)). The mip chain and the four dist2d tables are made again on the device. With neither, the tables
+        are built from the resident texels. The scene object handed to update() follows (value, host image; with a device
+        image and for the tables, read_image / read_distributions say what is resident). After a host image the scene object's
+        `distributions` no longer belong to its image: it is marked environment_tables = "device", so that a later update(scene)
+        has the device build them again behind the upload. Returns sthip_environment_info as a dict."""
+        scene = self._scene
+        d = wire.EnvironmentDesc()
+        d.struct_size = C.sizeof(wire.EnvironmentDesc)
+        d.material_address = (scene.environment_address if scene is not None else 0) & 0xFFFFFFFF
+        keep = []
+        if value is not None:
+            v = np.ascontiguousarray(np.asarray(value, dtype=np.float32).reshape(3))
+            keep.append(v)
+            d.value = v.ctypes.data
+        if image is not None:
+            if device_ptr:
+                if tuple(image.shape[2:]) != (4,) or "float32" not in str(image.dtype) or not image.is_contiguous():
+                    raise ValueError("set_environment: a device image must be a contiguous float32 tensor (H, W, 4)")
+                d.pixels, d.device_ptr = int(image.data_ptr()), 1
+            else:
+                if image.dtype != np.float32 or not image.flags["C_CONTIGUOUS"] or image.ndim != 3 or image.shape[2] != 4:
+                    raise ValueError("set_environment: the image must be a C-contiguous float32 array (H, W, 4)")
+                d.pixels = image.ctypes.data
+            d.height, d.width = int(image.shape[0]), int(image.shape[1])
+        info = wire.EnvironmentInfo()
+        self._check(self._lib.sthip_scene_set_environment(self._h, C.byref(d), C.byref(info)), "sthip_scene_set_environment")
+        if value is not None:  # the arrays a later update() would send hold what is resident
+            a = scene.environment_address
+            scene.materials[a : a + 12] = keep[0].view(np.uint8)
+        if image is not None and not device_ptr:
+            index = int(scene.materials[scene.environment_address + 12 : scene.environment_address + 16].view(np.uint32)[0])
+            scene.images[index] = image
+            scene.environment_tables = "device"  # (scene.distributions are the tables of the image before)
+        return {"device_ms": info.device_ms, "total_ms": info.total_ms}
+
+    def read_distributions(self, first=0, count=None):
+        """The resident gDistributions[first, first + count) as a float32 array (sthip_scene_read_distributions); all by default."""
+        n = int((self._scene.distributions.size - first if self._scene is not None else 0) if count is None else count)  # (no scene: the library says so)
+        out = np.zeros(n, np.float32)
+        self._check(self._lib.sthip_scene_read_distributions(self._h, int(first), n, wire.ptr(out) if n else None), "sthip_scene_read_distributions")
         return out
 
     def convert_material(self, kind, diffuse=None, specular=None, transmittance=None, roughness=None, input=None, output_format=1):

@@ -21,6 +21,7 @@
 #include "../../include/sthip.h"
 #include "animate.h"
 #include "denoise.h"
+#include "environment.h"
 #include "bvh_build.h"
 #include "first_hits.h"
 #include "material_convert.h"
@@ -313,10 +314,19 @@ struct sthip_ctx {
   DevBuf<sthip_TransformData> rig_bones;
   std::vector<sthip_TransformData> rig_bones_host;
   std::vector<std::array<float, 4>> rig_factors;  // of the animate call in progress
-  hipEvent_t rig_ev[2] = {nullptr, nullptr};      // around the k_animate launches of a call (sthip_refit_info::device_ms)
+  hipEvent_t rig_ev[2] = {nullptr, nullptr};      // around the k_animate launches of a call (sthip_refit_info::device_ms); around the work of sthip_scene_set_environment
   // ranges [first, end) of the kept scene's vertices that an animate call left behind the device's: read back before anything
   // is built from the kept scene (sync_kept_vertices)
   std::vector<std::pair<uint32_t, uint32_t>> kept_stale;
+  // sthip_scene_set_environment (environment.hip): which images of gImages a material record names (their texels decided the
+  // kernels: the call does not replace them), the s[y] of the rows and the rows' integrals between the passes, and what of the
+  // kept scene the call left behind the device's (fetched before anything is built from the kept scene: sync_kept_environment)
+  std::vector<uint8_t> image_in_material;
+  DevBuf<double> env_sines;
+  DevBuf<float> env_integrals;
+  uint32_t env_rows_per_wave = sthip::ENV_ROWS_PER_WAVE_DEFAULT;  // "env_rows_per_wave": 16 or 64 (environment.h)
+  bool kept_env_image_stale = false, kept_env_tables_stale = false;
+  uint32_t kept_env_image = 0;  // the image the stale texels belong to
   bool embedded_resident = false;  // the leaf triangles lie in the node array (BuiltBvh::embedded)
   bool want_wide = false;                            // the current scene is walked in its 4-wide form (decided at upload)
   bool lds_materials = true;  // k_shade stages gMaterialData in LDS when it fits 32 KB
@@ -803,6 +813,9 @@ int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value) {
   } else if (!strcmp(name, "denoise_block")) {
     if (value != 0 && value != 1) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "denoise_block: 0 (32x8) or 1 (16x16)");
     ctx->denoise_block = (uint32_t)value;
+  } else if (!strcmp(name, "env_rows_per_wave")) {  // rows a wave of k_env_rows owns (environment.h)
+    if (value != 16 && value != 64) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "env_rows_per_wave: 16 or 64");
+    ctx->env_rows_per_wave = (uint32_t)value;
   } else if (!strcmp(name, "inner_min_lanes"))
     ctx->inner_min_lanes = (uint32_t)std::min<int64_t>(64, std::max<int64_t>(1, value));
   else
@@ -957,9 +970,32 @@ static int pose_rigs(sthip_ctx* ctx, const char* call) {
   return STHIP_OK;
 }
 
+// The kept scene's environment is current again: texels that came from a device pointer and tables that were built on the
+// device (sthip_scene_set_environment) come back to the host. Called immediately before anything is built from the kept scene.
+static int sync_kept_environment(sthip_ctx* ctx) {
+  if (!ctx->kept_env_image_stale && !ctx->kept_env_tables_stale) return STHIP_OK;
+  if (ctx->kept.valid && ctx->has_scene) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const uint32_t i = ctx->kept_env_image;
+    if (ctx->kept_env_image_stale && i < ctx->images_host.size() && i < ctx->kept.image_pixels.size() && ctx->images_host[i].format == STHIP_IMAGE_FORMAT_RGBA32F) {
+      const DeviceImage& im = ctx->images_host[i];
+      const size_t floats = (size_t)im.w[0] * im.h[0] * 4;
+      if (ctx->kept.image_pixels[i].size() == floats) HIP_TRY(ctx, hipMemcpy(ctx->kept.image_pixels[i].data(), ctx->image_texels.p + im.offset[0], floats * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    if (ctx->kept_env_tables_stale && ctx->kept.distributions.size() == ctx->distribution_count && ctx->distribution_count)
+      HIP_TRY(ctx, hipMemcpy(ctx->kept.distributions.data(), ctx->distributions.p, (size_t)ctx->distribution_count * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  ctx->kept_env_image_stale = ctx->kept_env_tables_stale = false;
+  return STHIP_OK;
+}
+
 // What the kept copy is built again from: the kept arrays with the formats their images were uploaded in.
 static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats);
 static int upload_kept_scene(sthip_ctx* ctx) {
+  {  // (an environment a device pointer or the device's table build left newer than the kept copy: the rebuild must see it)
+    const int rc = sync_kept_environment(ctx);
+    if (rc != STHIP_OK) return rc;
+  }
   const sthip_scene_desc d = ctx->kept.desc();
   return scene_upload(ctx, &d, ctx->kept.image_formats.empty() ? nullptr : ctx->kept.image_formats.data(), ctx->kept.image1_formats.empty() ? nullptr : ctx->kept.image1_formats.data());
 }
@@ -1149,6 +1185,7 @@ static int install_scene_arrays(sthip_ctx* ctx, const sthip_scene_desc* s, Prepa
   ctx->has_volumes = m.has_volumes;
   ctx->volume_instances = m.volume_instances;
   ctx->instance_is_volume = std::move(m.instance_is_volume);
+  ctx->image_in_material = std::move(m.image_in_material);
   if (ctx->bvh_builder != sthip::BVH_BUILDER_LBVH_GPU) {  // (the GPU builder has them already)
     const int rc = upload_vertices_and_indices(ctx, s);
     if (rc != STHIP_OK) return rc;
@@ -1328,6 +1365,7 @@ static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t
   } else {
     ctx->kept = KeptScene();
   }
+  ctx->kept_env_image_stale = ctx->kept_env_tables_stale = false;  // (what is kept now is what is resident)
   if (getenv("STHIP_VERBOSE"))
     fprintf(stderr, "[sthip] bvh (%s): %zu nodes, %zu tris, %zu top-level entries, stack depth %u (%zu B LDS / block%s, treetop %u nodes), %d trace blocks / CU, build %.1f ms (GPU kernels %.2f ms)\n",
             ctx->bvh_builder ? "lbvh/gpu" : "sah/host", (size_t)ctx->bvh_nodes, (size_t)ctx->bvh_tris, built.entries.size(), built.stack_depth, stack_bytes(ctx), ctx->bvh.spill ? ", bounded" : "", ctx->bvh.top_count,
@@ -1857,6 +1895,149 @@ int sthip_scene_read_image(sthip_ctx* ctx, uint32_t image_index, uint32_t level,
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   const void* src = bytes ? (const void*)(ctx->image_texels8.p + im.offset[level]) : (const void*)(ctx->image_texels.p + im.offset[level]);
   HIP_TRY(ctx, hipMemcpy(out, src, (size_t)want, hipMemcpyDeviceToHost));
+  return STHIP_OK;
+}
+
+int sthip_scene_read_distributions(sthip_ctx* ctx, uint32_t first, uint32_t count, float* out) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_distributions before sthip_scene_upload");
+  if ((uint64_t)first + count > ctx->distribution_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_distributions: the range ends past the distribution_count of the uploaded scene");
+  if (!count) return STHIP_OK;
+  if (!out) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_distributions: out is NULL");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(out, ctx->distributions.p + first, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+  return STHIP_OK;
+}
+
+// sthip.h. check (scene_prepare.cpp: nothing resident is touched before it has passed) -> reserve -> wait -> value, texels,
+// mip chain, tables on the stream -> the kept scene follows
+int sthip_scene_set_environment(sthip_ctx* ctx, const sthip_environment_desc* d, sthip_environment_info* info) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  const auto t0 = std::chrono::steady_clock::now();
+  sthip::ResidentEnvironmentScene resident;
+  resident.has_scene = ctx->has_scene;
+  resident.materials = ctx->materials_host.data();
+  resident.material_bytes = ctx->materials_host.size();
+  resident.images = ctx->images_host.data();
+  resident.image_count = (uint32_t)std::min<size_t>(ctx->image_count, ctx->images_host.size());
+  resident.image_in_material = ctx->image_in_material.size() >= resident.image_count ? ctx->image_in_material.data() : nullptr;
+  resident.distribution_count = ctx->distribution_count;
+  sthip::EnvironmentPlan plan;
+  int rc = STHIP_OK;
+  std::string why;
+  if (!sthip::check_environment(resident, d, plan, rc, why)) return fail(ctx, rc, why);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // everything that can run out of memory, before anything resident changes
+  std::vector<double> sines;
+  if (plan.build_tables) {
+    sthip::environment_row_sines(plan.height, sines);
+    HIP_TRY(ctx, ctx->env_sines.ensure(plan.height));
+    HIP_TRY(ctx, ctx->env_integrals.ensure(plan.height));
+  }
+  for (int k = 0; k < 2; k++)
+    if (!ctx->rig_ev[k]) HIP_TRY(ctx, hipEventCreate(&ctx->rig_ev[k]));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old environment
+  HIP_TRY(ctx, drain_in_flight(ctx));               // (sthip_render_async: their copies too, so that their tickets are complete)
+  ctx->reuse_grids_valid = false;                   // (stored samples carry radiance of the environment they were taken in)
+  hipStream_t st = ctx->stream;
+  const size_t addr = d->material_address;
+  // measurement (sthip.h, tools/environment_times.py): STHIP_ENVIRONMENT_TIMES=<file> gets one line per table-building call
+  // with the HIP-event time of each stage. The variable is read once per process; without it no event is made here.
+  static const char* const times_path = [] {
+    const char* v = getenv("STHIP_ENVIRONMENT_TIMES");
+    return v && *v ? v : nullptr;
+  }();
+  enum Stage { STAGE_BEGIN, STAGE_COPY, STAGE_MIPS, STAGE_SINES, STAGE_ROWS, STAGE_MARGINAL, STAGE_NORMALISE, STAGE_COUNT };
+  struct StageEvents {  // ev[k]: recorded when stage k is enqueued (a stage the call skips is recorded where it would stand: 0 ms)
+    hipEvent_t ev[STAGE_COUNT] = {};
+    bool on = false;
+    ~StageEvents() {
+      for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    }
+  } stages;
+  if (times_path && plan.build_tables) {  // (a failure to make one only loses the measurement)
+    stages.on = true;
+    for (hipEvent_t& e : stages.ev) stages.on = stages.on && hipEventCreate(&e) == hipSuccess;
+  }
+  auto stage_done = [&](Stage k) {
+    if (stages.on) (void)hipEventRecord(stages.ev[k], st);
+  };
+  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[0], st));
+  stage_done(STAGE_BEGIN);
+  if (plan.set_value) {
+    memcpy(ctx->materials_host.data() + addr, d->value, 12);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->materials.p + addr, ctx->materials_host.data() + addr, 12, hipMemcpyHostToDevice, st));
+    if (ctx->kept.valid && ctx->kept.materials.size() == ctx->materials_host.size()) memcpy(ctx->kept.materials.data() + addr, d->value, 12);
+  }
+  std::string err;
+  if (plan.replace_pixels) {
+    const DeviceImage& im = ctx->images_host[plan.image_index];
+    const size_t bytes = (size_t)plan.width * plan.height * 16;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->image_texels.p + im.offset[0], d->pixels, bytes, d->device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    stage_done(STAGE_COPY);
+    for (uint32_t level = 0; level + 1 < im.levels; level++)
+      if (!sthip::mip_rgba32f_launch(ctx->image_texels.p + im.offset[level], im.w[level], im.h[level], ctx->image_texels.p + im.offset[level + 1], ctx->cu_count, st, err))
+        return fail(ctx, STHIP_ERR_HIP, "sthip_scene_set_environment: " + err);
+    stage_done(STAGE_MIPS);
+    if (ctx->kept.valid && plan.image_index < ctx->kept.image_pixels.size() && ctx->kept.image_pixels[plan.image_index].size() == bytes / 4) {
+      if (d->device_ptr) {
+        ctx->kept_env_image_stale = true;
+        ctx->kept_env_image = plan.image_index;
+      } else {
+        memcpy(ctx->kept.image_pixels[plan.image_index].data(), d->pixels, bytes);
+        if (ctx->kept_env_image == plan.image_index) ctx->kept_env_image_stale = false;
+      }
+    }
+  }
+  if (plan.build_tables) {
+    const DeviceImage& im = ctx->images_host[plan.image_index];
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->env_sines.p, sines.data(), sines.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    sthip::EnvironmentTables t;
+    t.texels = ctx->image_texels.p + im.offset[0];
+    t.width = plan.width;
+    t.height = plan.height;
+    t.sines = ctx->env_sines.p;
+    t.integrals = ctx->env_integrals.p;
+    t.marginal_pdf = ctx->distributions.p + plan.table[0];
+    t.row_pdf = ctx->distributions.p + plan.table[1];
+    t.marginal_cdf = ctx->distributions.p + plan.table[2];
+    t.row_cdf = ctx->distributions.p + plan.table[3];
+    if (!plan.replace_pixels) {
+      stage_done(STAGE_COPY);
+      stage_done(STAGE_MIPS);
+    }
+    stage_done(STAGE_SINES);
+    bool ok = sthip::env_rows_launch(t, ctx->env_rows_per_wave, st, err);
+    stage_done(STAGE_ROWS);
+    ok = ok && sthip::env_marginal_launch(t, st, err);
+    stage_done(STAGE_MARGINAL);
+    ok = ok && sthip::env_normalise_launch(t, st, err);
+    stage_done(STAGE_NORMALISE);
+    if (!ok) return fail(ctx, STHIP_ERR_HIP, "sthip_scene_set_environment: " + err);
+    if (ctx->kept.valid && ctx->kept.distributions.size() == ctx->distribution_count) ctx->kept_env_tables_stale = true;
+  }
+  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[1], st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));  // (`sines` and a pageable `pixels` array are the caller's again from here on)
+  if (stages.on) {
+    static const char* names[STAGE_COUNT - 1] = {"copy_ms", "mips_ms", "sines_ms", "k_env_rows_ms", "k_env_marginal_ms", "k_env_normalise_ms"};
+    if (FILE* f = fopen(times_path, "a")) {
+      fprintf(f, "{\"rows_per_wave\": %u", ctx->env_rows_per_wave);
+      for (int k = 0; k + 1 < STAGE_COUNT; k++) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, stages.ev[k], stages.ev[k + 1]);
+        fprintf(f, ", \"%s\": %.5f", names[k], ms);
+      }
+      fprintf(f, "}\n");
+      fclose(f);
+    }
+  }
+  if (info) {
+    info->device_ms = 0;
+    (void)hipEventElapsedTime(&info->device_ms, ctx->rig_ev[0], ctx->rig_ev[1]);
+    info->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
   return STHIP_OK;
 }
 

@@ -109,6 +109,7 @@ MaterialAnalysis analyse_materials(const sthip_scene_desc& s, const uint8_t* ima
   };
   m.inst_flags.assign(std::max<uint32_t>(1, s.instance_count), (uint8_t)INST_FLAG_KEEP);  // k_cull_terminal's table (kernels.h)
   m.instance_is_volume.assign(s.instance_count, 0);
+  m.image_in_material.assign(s.image_count, 0);
   for (uint32_t i = 0; i < s.instance_count; i++) {
     const uint32_t addr = s.gInstances[i].packed[0] >> 4, type = instance_type(s.gInstances[i]);
     if (type == STHIP_INSTANCE_TYPE_SPHERE) m.has_spheres = true;
@@ -126,6 +127,10 @@ MaterialAnalysis analyse_materials(const sthip_scene_desc& s, const uint8_t* ima
     for (int k = 0; k < 3; k++)
       if (rec.values[k].image_index < STHIP_IMAGE_COUNT) m.textured = true;
     if (rec.bump_index < STHIP_IMAGE_COUNT) m.textured = true;
+    for (int k = 0; k < 4; k++) {
+      const uint32_t index = k < 3 ? rec.values[k].image_index : rec.bump_index;
+      if (index < s.image_count) m.image_in_material[index] = 1;
+    }
     if (rec.alpha_mask_index < STHIP_IMAGE_COUNT && type == STHIP_INSTANCE_TYPE_TRIANGLES) m.any_alpha = true;
     // DisneyMaterial::is_specular (disney_material.hlsli:125) is evaluated per hit on value * texel, so the host test is
     // over what the product can reach: conservative (a "maybe" only costs bounce rounds that find empty queues)
@@ -147,6 +152,62 @@ MaterialAnalysis analyse_materials(const sthip_scene_desc& s, const uint8_t* ima
     }
   }
   return m;
+}
+
+bool check_environment(const ResidentEnvironmentScene& scene, const sthip_environment_desc* d, EnvironmentPlan& plan, int& code, std::string& message) {
+  auto refuse = [&](int c, const std::string& m) {
+    code = c;
+    message = "sthip_scene_set_environment: " + m;
+    return false;
+  };
+  auto bad = [&](const std::string& m) { return refuse(STHIP_ERR_INVALID_ARGUMENT, m); };
+  plan = EnvironmentPlan();
+  if (!d) return bad("the description is NULL");
+  if (d->struct_size != sizeof(sthip_environment_desc)) return bad("struct_size is " + std::to_string(d->struct_size) + ", not sizeof(sthip_environment_desc) = " + std::to_string(sizeof(sthip_environment_desc)));
+  if (!scene.has_scene || !scene.materials) return bad("no scene is resident (before sthip_scene_upload)");
+  const size_t addr = d->material_address;
+  if ((addr & 3) || addr + 16 > scene.material_bytes) return bad("material_address is unaligned or outside gMaterialData");
+  uint32_t rec[8] = {0};
+  memcpy(rec, scene.materials + addr, 16);
+  plan.has_image = rec[3] < STHIP_IMAGE_COUNT;
+  plan.set_value = d->value != nullptr;
+  plan.replace_pixels = d->pixels != nullptr;
+  plan.build_tables = plan.replace_pixels || !plan.set_value;
+  if (plan.set_value && d->value[0] == 0 && d->value[1] == 0 && d->value[2] == 0) return bad("value is zero: upstream stores no record for a zero environment (upload the scene without one)");
+  if (!plan.has_image) {
+    if (plan.replace_pixels) return bad("pixels for an environment record without an image");
+    plan.build_tables = false;  // (a constant environment has no tables: nothing to build)
+    return true;
+  }
+  if (rec[3] >= scene.image_count || addr + 32 > scene.material_bytes) return bad("the record refers to an image that is not in gImages, or its table offsets lie outside gMaterialData");
+  memcpy(rec, scene.materials + addr, 32);
+  const DeviceImage& im = scene.images[rec[3]];
+  plan.image_index = rec[3];
+  plan.width = im.w[0];
+  plan.height = im.h[0];
+  if (plan.replace_pixels && (d->width != plan.width || d->height != plan.height))
+    return bad("the extent " + std::to_string(d->width) + " x " + std::to_string(d->height) + " differs from the resident image's " + std::to_string(plan.width) + " x " + std::to_string(plan.height) +
+               " (a change of extent is an upload)");
+  const size_t w = plan.width, h = plan.height;
+  const size_t need[4] = {h, w * h, h + 1, (w + 1) * h};  // marginal_pdf, row_pdf, marginal_cdf, row_cdf (dist2.h)
+  for (int k = 0; k < 4; k++) {
+    plan.table[k] = rec[4 + k];
+    if ((size_t)rec[4 + k] + need[k] > scene.distribution_count) return bad("an environment distribution table lies outside gDistributions");
+  }
+  for (int k = 0; k < 4; k++)
+    for (int j = k + 1; j < 4; j++)
+      if ((size_t)rec[4 + k] < (size_t)rec[4 + j] + need[j] && (size_t)rec[4 + j] < (size_t)rec[4 + k] + need[k]) return bad("two distribution tables of the record overlap");
+  if (im.format != STHIP_IMAGE_FORMAT_RGBA32F)
+    return refuse(STHIP_ERR_UNSUPPORTED, "the environment map is an 8-bit image (gImages[" + std::to_string(rec[3]) + "] is RGBA8_UNORM): upload it as RGBA32F");
+  if (plan.replace_pixels && scene.image_in_material && scene.image_in_material[rec[3]])
+    return refuse(STHIP_ERR_UNSUPPORTED, "gImages[" + std::to_string(rec[3]) + "] is also named by a material record: its texels decided the kernels of the scene (upload the scene again)");
+  return true;
+}
+
+void environment_row_sines(uint32_t height, std::vector<double>& out) {
+  out.resize(height);
+  const float inv_height = 1 / (float)height;
+  for (uint32_t y = 0; y < height; y++) out[y] = std::sin(M_PI * (y + 0.5f) * inv_height);
 }
 
 bool pad_emitter_bounds(EmitterBounds& b) {

@@ -29,12 +29,39 @@ struct MaterialAnalysis {
   uint32_t volume_instances = 0;
   std::vector<uint8_t> instance_is_volume;  // per instance
   std::vector<uint8_t> inst_flags;          // per instance (at least one entry): INST_FLAG_*
+  std::vector<uint8_t> image_in_material;   // per image of gImages: 1 = some instance's material record names it (its texels were scanned above)
 };
 MaterialAnalysis analyse_materials(const sthip_scene_desc& s, const uint8_t* image_formats);
 
 // EmitterBounds from the exact box of an emitter's vertices: widened by 2^-15 of its coordinates' magnitude, as the packed nodes
 // of the tree are, and the sphere that sizes the per-ray padding. false: not finite (the table cannot be used).
 bool pad_emitter_bounds(EmitterBounds& b);
+// ---- sthip_scene_set_environment: what of it needs no device ----
+// What the context knows of the resident scene, as far as the environment call consults it
+struct ResidentEnvironmentScene {
+  bool has_scene = false;
+  const uint8_t* materials = nullptr;  // gMaterialData as uploaded
+  size_t material_bytes = 0;
+  const DeviceImage* images = nullptr;  // the image table as uploaded
+  uint32_t image_count = 0;
+  const uint8_t* image_in_material = nullptr;  // MaterialAnalysis::image_in_material (image_count entries, or NULL: none)
+  uint32_t distribution_count = 0;
+};
+// What an accepted call does
+struct EnvironmentPlan {
+  bool has_image = false;       // the record binds an image (and names four tables)
+  bool replace_pixels = false;  // level 0 from the caller, further levels again
+  bool build_tables = false;    // the four tables again
+  bool set_value = false;       // the record's three floats
+  uint32_t image_index = 0, width = 0, height = 0;
+  uint32_t table[4] = {0, 0, 0, 0};  // offsets in gDistributions: marginal_pdf, row_pdf, marginal_cdf, row_cdf
+};
+// Every refusal of sthip_scene_set_environment (sthip.h), decided from the arguments and the host-side state alone. false:
+// `code` and `message` say why and the caller changes nothing.
+bool check_environment(const ResidentEnvironmentScene& scene, const sthip_environment_desc* d, EnvironmentPlan& plan, int& code, std::string& message);
+// s[y] = sin(M_PI * (y + 0.5f) * (1 / (float)H)) for the H rows of a lat-long image, with libm (sthip.h: the device gets them as they are)
+void environment_row_sines(uint32_t height, std::vector<double>& out);
+
 // The bounds of the emissive triangle instances (bvh.h: EmitterBounds), from the validated scene arrays: the box of the
 // vertices an instance's triangles refer to, widened by 2^-15 of its coordinates' magnitude as the packed nodes of the
 // tree are, in world space for an instance with identity transforms (that is where its triangles are tested, whether the

@@ -50,6 +50,9 @@
 // ... and one without the post block lacks these: Denoiser::denoise then throws
 // ... and one without the material conversions lacks this: Scene::make_*_material then throw for a material with images
 #pragma weak sthip_convert_material
+// ... and one that cannot replace the environment of a resident scene lacks these: the host builds the tables and uploads
+#pragma weak sthip_scene_set_environment
+#pragma weak sthip_scene_read_distributions
 #pragma weak sthip_accumulate
 #pragma weak sthip_denoise_filter
 #include "../../include/sthip_detmath.h"  // det_f16tof32: export_hdr of a half frame
@@ -669,7 +672,26 @@ struct Environment {
   float value[3] = {0, 0, 0};
   component_ptr<Image> image;
   std::vector<float> marginal_pdf, row_pdf, marginal_cdf, row_cdf;
+  // true: the tables above are sized and zeroed, and the device builds them (sthip_scene_set_environment) after an upload and
+  // after mark_image_dirty(). Where that cannot be — a library without the call, Scene::set_environment_on_device(false), the
+  // multi-device driver — Scene::update has ensure_host_tables() build them here, as make_environment does without the flag.
+  bool tables_on_device = false;
+  uint32_t image_serial = 0;          // counts mark_image_dirty(): what tells the texels of one Image object apart
+  uint32_t host_tables_serial = ~0u;  // the image_serial the tables above were built for on the host (~0u: never)
   bool is_zero() const { return value[0] == 0 && value[1] == 0 && value[2] == 0; }
+  // A host that changes only these two things of a scene between frames (and marks the Scene dirty) gets
+  // sthip_scene_set_environment from BDPT::update instead of an upload.
+  void set_value(float r, float g, float b) { value[0] = r, value[1] = g, value[2] = b; }
+  // The host wrote image->pixels (same extent). The host tables are NOT built again here: Scene::update builds them when it
+  // packs for a library or a driver that cannot build them on the device, and otherwise packs them as they are and marks them
+  // for the device (SceneData::mEnvironmentTablesOnDevice), which builds them in the environment-only call or after an upload.
+  void mark_image_dirty() { image_serial++; }
+  bool host_tables_current() const { return !image || (!tables_on_device && host_tables_serial == image_serial); }
+  void ensure_host_tables() {
+    if (!image || host_tables_serial == image_serial) return;
+    build_distributions(*image, marginal_pdf, row_pdf, marginal_cdf, row_cdf);
+    host_tables_serial = image_serial;
+  }
   void store(std::vector<uint32_t>& bytes, MaterialResources& resources) const {
     for (int j = 0; j < 3; j++) {
       uint32_t u;
@@ -686,11 +708,20 @@ struct Environment {
   }
 };
 // load_environment, environment.h:99-150, for an image that is already in memory
-inline Environment make_environment(const component_ptr<Image>& image, float r = 1, float g = 1, float b = 1) {
+inline Environment make_environment(const component_ptr<Image>& image, float r = 1, float g = 1, float b = 1, bool tables_on_device = false) {
   Environment e;
   e.value[0] = r, e.value[1] = g, e.value[2] = b;
   e.image = image;
-  if (image) build_distributions(*image, e.marginal_pdf, e.row_pdf, e.marginal_cdf, e.row_cdf);
+  e.tables_on_device = tables_on_device && image;
+  if (e.tables_on_device) {
+    const size_t W = image->width, H = image->height;
+    e.marginal_pdf.assign(H, 0.f);
+    e.row_pdf.assign(W * H, 0.f);
+    e.marginal_cdf.assign(H + 1, 0.f);
+    e.row_cdf.assign((W + 1) * H, 0.f);
+  } else {
+    e.ensure_host_tables();
+  }
   return e;
 }
 struct Rect2D {
@@ -770,6 +801,11 @@ class Scene {
     std::vector<std::pair<const Medium*, uint32_t>> mMediumInstances;     // Medium component -> its volume instance (mInstanceTransformMap)
     std::vector<float> mDistributionData;  // gDistributions, Scene.cpp:670-683
     uint32_t mEnvironmentMaterialAddress = ~0u;
+    // the environment as it was packed: its image object and that image's serial (Environment::mark_image_dirty), and whether
+    // mDistributionData holds zeros where its tables go (the device builds them after the upload: BDPT::update)
+    const Image* mEnvironmentImage = nullptr;
+    uint32_t mEnvironmentImageSerial = 0;
+    bool mEnvironmentTablesOnDevice = false;
     uint32_t mMaterialCount = 0;
     uint32_t mEmissivePrimitiveCount = 0;
     // rigs posed on the device (Scene::pose_on_device()): mVertices holds their rest poses; mPoses[i] belongs to mRigs[i]
@@ -826,6 +862,16 @@ class Scene {
     on = on && sthip_scene_set_rigs && sthip_scene_animate;
     if (on != mPoseOnDevice) mDirty = true;
     mPoseOnDevice = on;
+  }
+
+  // true (the default with a library that has sthip_scene_set_environment): BDPT::update sends a change of the environment
+  // alone through that call, and an Environment with tables_on_device is packed with zeroed tables. false (what a library
+  // without the call gets, and the multi-device driver sets): the tables are built here and every change is an upload.
+  bool environment_on_device() const { return mEnvironmentOnDevice; }
+  void set_environment_on_device(bool on) {
+    on = on && sthip_scene_set_environment;
+    if (on != mEnvironmentOnDevice) mDirty = true;
+    mEnvironmentOnDevice = on;
   }
 
   // ---- the material conversions, Scene.cpp:123-256 -> kernels/material_convert.hlsl (sthip_convert_material) ----
@@ -1021,6 +1067,16 @@ class Scene {
       if (environment && !environment->is_zero() && sd->mEnvironmentMaterialAddress == ~0u) {
         sd->mEnvironmentMaterialAddress = (uint32_t)(sd->mMaterialData.size() * sizeof(uint32_t));
         sd->mMaterialCount++;
+        if (environment->image) {
+          sd->mEnvironmentImage = environment->image.get();
+          sd->mEnvironmentImageSerial = environment->image_serial;
+          // the device builds the tables where it can and the host's are not there or not current (mark_image_dirty())
+          sd->mEnvironmentTablesOnDevice = !environment->host_tables_current() && mEnvironmentOnDevice && environment->image->bytes.empty();
+          if (!sd->mEnvironmentTablesOnDevice) {
+            environment->ensure_host_tables();
+            environment->tables_on_device = false;  // (they are real tables from here on)
+          }
+        }
         environment->store(sd->mMaterialData, sd->mResources);
       }
     });
@@ -1122,6 +1178,7 @@ class Scene {
   std::shared_ptr<SceneData> mSceneData;
   bool mDirty = true;
   bool mPoseOnDevice = sthip_scene_set_rigs && sthip_scene_animate;
+  bool mEnvironmentOnDevice = sthip_scene_set_environment != nullptr;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1324,6 +1381,9 @@ class BDPT {
   const Frame& prev_result() const { return mPrevFrame; }  // BDPT.hpp:18
   bool last_update_was_transforms_only() const { return mLastUpdateWasTransformsOnly; }
   bool last_update_was_vertices_only() const { return mLastUpdateWasVerticesOnly; }  // (no transform changed with them)
+  bool last_update_was_environment_only() const { return mLastUpdateWasEnvironmentOnly; }
+  uint32_t upload_calls() const { return mUploadCalls; }                    // sthip_scene_upload(_formats) calls of update() so far
+  uint32_t environment_calls() const { return mEnvironmentCalls; }          // sthip_scene_set_environment calls of update() so far
   // tone-map state the reference keeps on its pipeline objects (BDPT.cpp:44-54,190-193,304-309)
   uint32_t& tonemap_mode() { return mTonemapMode; }
   float& exposure() { return mExposure; }
@@ -1364,8 +1424,21 @@ class BDPT {
     // are still right, as the reference's cached BLASes are (Scene.cpp:435-459); rebuild the top level only.
     bool updated = false;
     mLastUpdateWasVerticesOnly = false;
+    mLastUpdateWasEnvironmentOnly = false;
     const Scene::SceneData& sd = *scene->data();
     const bool rigs = !sd.mRigs.empty();  // (packed only with a library that has the calls: Scene::pose_on_device())
+    if (scene->environment_on_device() && mBoundData && environment_only_changed(*mBoundData, sd)) {
+      // Only the environment's value and / or the texels of its image changed: the value, the texels, the mip chain and the
+      // tables are replaced in the resident scene. A call the library refuses as unsupported (an image a material shares): upload.
+      const int rc = set_environment(*mBoundData, sd);
+      if (rc == STHIP_OK) {
+        mLastUpdateWasEnvironmentOnly = true;
+        mLastUpdateWasTransformsOnly = false;
+        mBound = scene->data().get();
+        mBoundData = scene->data();
+        return;
+      }
+    }
     if (rigs && mRigsResident && mBoundData && same_geometry(*mBoundData, sd) && !same_poses(*mBoundData, sd)) {
       // Only poses changed (and perhaps transforms): the rigs are resident, the bones and factors go to the device and the
       // meshes are posed and the tree refitted there. A layout the library cannot serve without a kept scene answers UNSUPPORTED: upload.
@@ -1421,6 +1494,14 @@ class BDPT {
     }
     mLastUpdateWasTransformsOnly = updated;
     if (!updated && sd.upload(mCtx) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_upload: ") + sthip_last_error(mCtx));
+    if (!updated) mUploadCalls++;
+    if (!updated && sd.mEnvironmentTablesOnDevice) {  // zeroed tables went up: the device builds them from the resident texels
+      sthip_environment_desc e{};
+      e.struct_size = sizeof(e);
+      e.material_address = sd.mEnvironmentMaterialAddress;
+      mEnvironmentCalls++;
+      if (sthip_scene_set_environment(mCtx, &e, nullptr) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_set_environment: ") + sthip_last_error(mCtx));
+    }
     if (!updated) {  // the upload dropped the rigs: they go up once, over the rest poses that just went up, and take their pose
       mRigsResident = false;
       if (rigs) {
@@ -1728,7 +1809,7 @@ class BDPT {
   sthip_ctx* mCtx = nullptr;
   const void* mBound = nullptr;
   std::shared_ptr<Scene::SceneData> mBoundData;
-  bool mLastUpdateWasTransformsOnly = false, mLastUpdateWasVerticesOnly = false;
+  bool mLastUpdateWasTransformsOnly = false, mLastUpdateWasVerticesOnly = false, mLastUpdateWasEnvironmentOnly = false;
   // false: a deformed mesh is uploaded like any other change. The multi-device driver clears it: its ranks must all walk the
   // same tree form, and it sends them uploads or transforms-only updates, nothing else (stratum_hip_multi.hpp).
   bool mRefitDeformedMeshes = true;
@@ -1737,6 +1818,42 @@ class BDPT {
     return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
   }
   bool mRigsResident = false;  // the rigs of mBoundData are on the device (sthip_scene_set_rigs after the last upload)
+  uint32_t mUploadCalls = 0, mEnvironmentCalls = 0;
+  // Everything of `b` is what `a` is except the value of the environment record, the texels of its image (the same object,
+  // another serial) and the tables that follow from them: the comparison same_poses is for the rigs.
+  static bool environment_only_changed(const Scene::SceneData& a, const Scene::SceneData& b) {
+    const uint32_t addr = b.mEnvironmentMaterialAddress;
+    if (addr == ~0u || a.mEnvironmentMaterialAddress != addr || a.mEnvironmentImage != b.mEnvironmentImage) return false;
+    if (a.mMaterialData.size() != b.mMaterialData.size() || (size_t)addr / 4 + 4 > b.mMaterialData.size()) return false;
+    const size_t at = addr / 4;
+    const bool value_changed = std::memcmp(&a.mMaterialData[at], &b.mMaterialData[at], 12) != 0;
+    const bool image_changed = b.mEnvironmentImage && a.mEnvironmentImageSerial != b.mEnvironmentImageSerial;
+    if (!value_changed && !image_changed) return false;
+    if (image_changed && !b.mEnvironmentImage->bytes.empty()) return false;  // (an 8-bit environment: nothing the call serves)
+    if (std::memcmp(a.mMaterialData.data(), b.mMaterialData.data(), at * 4) || std::memcmp(&a.mMaterialData[at + 3], &b.mMaterialData[at + 3], (b.mMaterialData.size() - at - 3) * 4)) return false;
+    if (!image_changed && !same_bytes(a.mDistributionData, b.mDistributionData)) return false;
+    if (a.mDistributionData.size() != b.mDistributionData.size()) return false;
+    if (!same_rigs(a, b) || !same_poses(a, b) || !same_bytes(a.mVertices, b.mVertices) || !same_bytes(a.mIndices, b.mIndices) || !same_bytes(a.mInstances, b.mInstances) ||
+        !same_bytes(a.mLightInstanceMap, b.mLightInstanceMap) || !same_bytes(a.mInstanceTransforms, b.mInstanceTransforms) || !same_bytes(a.mInstanceInverseTransforms, b.mInstanceInverseTransforms) ||
+        !same_bytes(a.mInstanceMotionTransforms, b.mInstanceMotionTransforms))
+      return false;
+    return a.mResources.image4s == b.mResources.image4s && a.mResources.image1s == b.mResources.image1s && a.mResources.volumes == b.mResources.volumes;  // the same objects
+  }
+  int set_environment(const Scene::SceneData& a, const Scene::SceneData& b) {
+    const size_t at = b.mEnvironmentMaterialAddress / 4;
+    sthip_environment_desc e{};
+    e.struct_size = sizeof(e);
+    e.material_address = b.mEnvironmentMaterialAddress;
+    if (std::memcmp(&a.mMaterialData[at], &b.mMaterialData[at], 12)) e.value = reinterpret_cast<const float*>(&b.mMaterialData[at]);
+    if (b.mEnvironmentImage && a.mEnvironmentImageSerial != b.mEnvironmentImageSerial) {
+      e.pixels = b.mEnvironmentImage->pixels.data();
+      e.width = b.mEnvironmentImage->width, e.height = b.mEnvironmentImage->height;
+    }
+    mEnvironmentCalls++;
+    const int rc = sthip_scene_set_environment(mCtx, &e, nullptr);
+    if (rc != STHIP_OK && rc != STHIP_ERR_UNSUPPORTED) throw std::runtime_error(std::string("sthip_scene_set_environment: ") + sthip_last_error(mCtx));
+    return rc;
+  }
   // sthip_scene_animate with the poses of `sd`. The call poses every rig; one whose mesh never got a pose is sent zero factors
   // and identity bones (its positions stay the rest pose's; its normals are normalised again if it has blend targets).
   int animate(const Scene::SceneData& sd) {
@@ -1783,7 +1900,10 @@ class BDPT {
         !same_bytes(a.mLightInstanceMap, b.mLightInstanceMap) || !same_bytes(a.mDistributionData, b.mDistributionData))
       return false;
     if (a.mResources.image4s != b.mResources.image4s || a.mResources.image1s != b.mResources.image1s || a.mResources.volumes != b.mResources.volumes) return false;  // the same objects
-    return a.mEnvironmentMaterialAddress == b.mEnvironmentMaterialAddress;
+    // (an environment whose tables the device builds packs the same bytes before and after Environment::mark_image_dirty():
+    // the image's serial is what tells the texels apart, and a partial update must not pass over a changed sky)
+    return a.mEnvironmentMaterialAddress == b.mEnvironmentMaterialAddress && a.mEnvironmentImage == b.mEnvironmentImage && a.mEnvironmentImageSerial == b.mEnvironmentImageSerial &&
+           a.mEnvironmentTablesOnDevice == b.mEnvironmentTablesOnDevice;
   }
   uint32_t mSamplingFlags = 0;
   BDPTPushConstants mPushConstants;

@@ -224,6 +224,10 @@ class MultiDeviceBDPT : public BDPT {
       scene->set_pose_on_device(false);
       scene->update(cb, dt);
     }
+    if (scene && scene->environment_on_device()) {  // sthip_scene_set_environment is not driven here: the host builds the tables and every rank uploads
+      scene->set_environment_on_device(false);
+      scene->update(cb, dt);
+    }
     if (!scene || !scene->data() || scene->data().get() == mBound) return;
     flush();
     BDPT::update(cb, dt);  // rank 0, and the bookkeeping (mBound, light count, environment)

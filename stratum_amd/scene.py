@@ -98,6 +98,7 @@ class SceneData:
         self.images1 = []  # float32 or uint8 (R8_UNORM) arrays (H, W): Texture2D<float> gImage1s[] (alpha masks)
         self.distributions = np.zeros(0, np.float32)  # StructuredBuffer<float> gDistributions
         self.environment_address = 0xFFFFFFFF  # SceneData::mEnvironmentMaterialAddress, Scene.cpp:631-640
+        self.environment_tables = "host"  # "device": `distributions` holds zeros and BDPT.update has the device build the tables
         self.volumes = []  # uint8 arrays: ByteAddressBuffer gVolumes[] (NanoVDB float grids)
         self.dirty_vertices = None  # (begin, end) of the vertex records set_vertices changed and no update has sent yet
 
@@ -460,7 +461,12 @@ class SceneBuilder:
         """Environment component: constant radiance `value`, or `value` times a lat-long image (environment.h)."""
         self._environment = (np.asarray(value, dtype=np.float32).reshape(3), image)
 
-    def build(self):
+    def build(self, environment_tables="host"):
+        """environment_tables: "host" (default) = the dist2d tables of an image environment are built here (build_distributions);
+        "device" = they are left zero-filled, at the same offsets and with the same distribution_count, and BDPT.update() has
+        the device build them after the upload (one table-only sthip_scene_set_environment)."""
+        if environment_tables not in ("host", "device"):
+            raise ValueError("environment_tables must be 'host' or 'device', not %r" % (environment_tables,))
         media = getattr(self, "_medium_instances", [])
         n = len(self._instances) + len(self._spheres) + len(media)
         inst = np.zeros(n, dtype=wire.InstanceData)
@@ -584,7 +590,11 @@ class SceneBuilder:
             parts = [rec]
             if image is not None:  # Environment::store, environment.h:17-22: offsets into gDistributions in get_index order
                 env = self._images[int(image)]  # (an 8-bit environment is refused at render; its tables are those of the decoded bytes)
-                tables = build_distributions(env.astype(np.float32) / np.float32(255) if env.dtype == np.uint8 else env)  # marginal_pdf, row_pdf, marginal_cdf, row_cdf
+                if environment_tables == "device":
+                    eh, ew = env.shape[0], env.shape[1]
+                    tables = [np.zeros(n, np.float32) for n in (eh, eh * ew, eh + 1, eh * (ew + 1))]
+                else:
+                    tables = build_distributions(env.astype(np.float32) / np.float32(255) if env.dtype == np.uint8 else env)  # marginal_pdf, row_pdf, marginal_cdf, row_cdf
                 offs, off = [], 0
                 for t in tables:
                     offs.append(off)
@@ -608,6 +618,7 @@ class SceneBuilder:
         sd.images1 = [self._images1[h] for h in image1_order]
         sd.distributions = dist
         sd.environment_address = env_address
+        sd.environment_tables = "device" if (environment_tables == "device" and dist.size) else "host"
         sd.volumes = [self._volumes[h] for h in volume_order]
         return sd
 

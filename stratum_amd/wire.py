@@ -417,6 +417,27 @@ CONVERT_KINDS = ["GltfPbr", "DiffuseSpecular", "AlphaToRoughness", "ShininessToR
 CONVERT = {n: i for i, n in enumerate(CONVERT_KINDS)}
 
 
+class EnvironmentDesc(C.Structure):  # sthip_environment_desc
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("material_address", C.c_uint32),
+        ("value", C.c_void_p),
+        ("pixels", C.c_void_p),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("device_ptr", C.c_uint32),
+        ("pad", C.c_uint32),
+    ]
+
+
+class EnvironmentInfo(C.Structure):  # sthip_environment_info
+    _fields_ = [("device_ms", C.c_float), ("total_ms", C.c_float)]
+
+
+ENVIRONMENT_DESC_BYTES = 40  # sizeof(sthip_environment_desc), include/sthip.h
+assert C.sizeof(EnvironmentDesc) == ENVIRONMENT_DESC_BYTES
+
+
 class ConvertMaterialDesc(C.Structure):
     _fields_ = [
         ("kind", C.c_uint32),
