@@ -509,6 +509,111 @@ typedef struct sthip_environment_info { /* optional out-parameter, may be NULL *
 int sthip_scene_set_environment(sthip_ctx* ctx, const sthip_environment_desc* desc, sthip_environment_info* info);
 int sthip_scene_read_distributions(sthip_ctx* ctx, uint32_t first, uint32_t count, float* out);
 
+/* ---- the materials of a resident scene: texels and records ----
+ * What a material looks like is two things in HBM: its record in gMaterialData (constants, and which images they bind) and the
+ * texels of those images. sthip_scene_set_images replaces texels, sthip_scene_set_material_data replaces record bytes; neither
+ * rebuilds a tree. Both follow the rules and the phase order of sthip_scene_set_environment: check (every refusal is decided on
+ * the host before anything resident is touched, and a refused call changes nothing but sthip_last_error), reserve, wait for the
+ * stream and complete the frames in flight, do the work on the stream, update the kept scene; they return when their work on
+ * the stream has finished.
+ *
+ * Texels are not only data. The material analysis of the upload scans level 0 of the images that material records name for
+ * their per-channel extremes, and decides from them whether some material of the scene can be specular. That decision caps
+ * the bounce and shadow rounds of a render and lets k_shade end paths at gMaxDiffuseVertices, so texels replaced under a stale
+ * analysis give wrong frames (a rough metal repainted as a mirror would lose every path beyond the diffuse budget). Both calls
+ * therefore make the analysis again; for texels the scan is made again ON THE DEVICE (image_range.hip), wherever they came from.
+ *
+ * Image ranges (k_image_range), the contract — the bits of the upload's host scan but for the sign of a zero:
+ *   lo[c] / hi[c] = the minimum / maximum of channel c over the texels of level 0 that are not NaN;
+ *   an RGBA8_UNORM texel decodes as (float)b / 255.0f, which is monotone: the bytes are reduced and the result decoded once;
+ *   bit c of nan_mask is set when some texel of channel c is a NaN; such a channel is unknown: lo[c] = -inf, hi[c] = +inf
+ *     (a channel of nothing but NaNs included);
+ *   infinities and denormals are kept as they are;
+ *   the sign of a zero result is NOT part of the contract (-0 and +0 compare equal, and the analysis only compares ranges
+ *     against 0.999f, 1e-2f and 0).
+ * The device reduces with no floating-point atomics and no flags or spins inside a launch: one 16-byte load per lane per trip
+ * of a grid-stride loop (one RGBA32F texel or four RGBA8 texels), running values in registers, cross-lane operations within a
+ * wave, one LDS step per block, per-block partials with plain stores, and a second small launch that folds them; the kernel
+ * boundary is the ordering. The results of all images of a call are read back once. The grid is sized from the device's CU count;
+ * the option "image_range_blocks" forces the block count (tests) and never changes results.
+ *
+ * sthip_scene_set_images: `n` entries, applied together (the three images of one material change together). Each replaces
+ * level 0 of gImages[index] (which = 0) or gImage1s[index] (which = 1) with `pixels`, width x height texels, tightly packed, in
+ * the image's RESIDENT format (RGBA32F or RGBA8_UNORM; R32F or R8_UNORM) and at its resident extent: a change of extent or
+ * format is an upload. device_ptr = 1: `pixels` is device memory, readable in the order of the context's stream (the outputs of
+ * sthip_convert_material in its device form, for one). The mip chain of an image of gImages is made again on the device by the
+ * rules of the upload (RGBA32F: ((a + b) + (c + e)) * 0.25f; RGBA8: (a + b + c + e + 2) >> 2); alpha masks have level 0 only.
+ * Then every replaced image of gImages that a material record names is scanned, the analysis runs again on the host over the
+ * resident records, and its has_specular is installed (nothing else of it can change through texels).
+ *   Kept state: kept reservoir grids ("reuse_grids_persist") are dropped — stored samples carry the old materials' radiance.
+ *   Kept first hits ("reuse_first_hits") stay when only images of gImages changed (no triangle or mask moved) and are dropped
+ *   when an alpha mask changed (the alpha test decides first hits).
+ *   An image that is also an environment's image: the library does not know that at this call. The dist2d tables stay as they
+ *   were; the host follows with the tables-only form of sthip_scene_set_environment. (sthip_scene_set_environment itself still
+ *   refuses texels for an image a material names.)
+ *   The kept scene ("keep_scene" = 1): host pixels go into the kept copy at once; pixels from a device pointer mark the kept
+ *   image stale, and it is fetched immediately before anything is built from the kept scene, as the environment's.
+ *   Refused with STHIP_ERR_INVALID_ARGUMENT: no scene; a struct_size that is not sizeof(sthip_image_update); NULL `entries` with
+ *   n > 0; a `which` above 1; an index out of range; NULL pixels; a width or height that differs from the resident extent; the
+ *   same image named twice in one call; with device_ptr, a pointer that is not naturally aligned (16 bytes for RGBA32F, 4 for
+ *   the other three formats).
+ *
+ * sthip_scene_set_material_data: the bytes [offset, offset + bytes) of gMaterialData are replaced by `data` (host memory);
+ * offset and bytes are multiples of 4 and the range lies inside the resident buffer. For constants (base colour, emission
+ * strength, metallic, roughness ...), for which image a value binds, and for medium parameters. The range goes into the
+ * context's host copy, into the device buffer on the stream and into the kept scene; the analysis runs again and has_specular,
+ * textured (which k_shade runs), the per-instance flags of k_cull_terminal and the set of images that materials name are
+ * installed. An image that a record names for the first time is scanned on the device from its resident texels.
+ * Kept reservoir grids are dropped; kept first hits stay.
+ *   STHIP_ERR_INVALID_ARGUMENT: no scene, NULL data, a misaligned or outlying range; or, over the buffer as it would be after
+ *   the edit, an instance's record that fails a material check of the upload (an image, bump map or alpha mask index that is
+ *   out of range, a medium's volume index that is not in gVolumes).
+ *   STHIP_ERR_UNSUPPORTED, because these entered the trees and tables at upload (upload the scene again): a triangle instance
+ *   whose alpha_mask_index changes; a medium whose volume indices change; a triangle or sphere instance whose emission
+ *   (base_color * emission > 0 in some channel) appears or disappears — the light list and the emitter bounds are the upload's.
+ *
+ * A range is the range of the texels that are resident: whatever replaces level 0 of an image of gImages (this call,
+ * sthip_scene_set_environment) forgets the range the context held for it, also for an image that no record names at that moment;
+ * the image is scanned again when a record names it.
+ *   After the checks have passed, a failure of the device (STHIP_ERR_HIP: a copy, a launch, the read-back) can leave the texels
+ *   or bytes of the call partly resident, with the material analysis and the ranges of the scene before the call and the kept
+ *   reservoir grids dropped: the state is then not one any call describes, and the host uploads the scene again. The same holds
+ *   for sthip_scene_set_material_data.
+ *
+ * sthip_scene_read_image_range: the range the context holds for gImages[image_index] (tests see the kernel's result through
+ * it). STHIP_ERR_INVALID_ARGUMENT: no scene, an index out of range, or an image whose range nobody needed: one that no material
+ * record names (any more), or names only under constants without a positive component (the upload does not scan those).
+ *
+ * Cost, measured on an MI355X (profiles/r11/material_update.json, tools/material_update_times.py, medians of 9 calls, a small
+ * scene with one 4096 x 4096 parameter image): resident as RGBA8_UNORM (64 MB) 3.44 ms for sthip_scene_set_images with the
+ * pixels in pageable host memory, 0.24 ms from a device pointer (0.26 ms for a sthip_convert_material and the call chained
+ * behind it on the stream), against 0.14 + 36.4 + 41.9 ms for conversion, copy back and sthip_scene_upload_formats of the same
+ * scene; resident as RGBA32F (256 MB) 13.5 ms and 0.55 ms against 0.28 + 139.6 + 218.0 ms. k_image_range alone, both launches:
+ * 0.025 ms (RGBA8, 0.51 of the triad rate measured in the same process) and 0.068 ms (RGBA32F, 0.76 of it).
+ *
+ * Measurement only: with the environment variable STHIP_MATERIAL_TIMES=<file> (read once per process) every call that scans
+ * appends one JSON line to the file with the HIP-event time of its k_image_range launches (k_image_range_ms), the images scanned
+ * and the block count. Without the variable the call makes no extra event and touches no file.
+ * A library without the feature lacks the three symbols. */
+typedef struct sthip_image_update {
+  uint32_t which;      /* 0 = gImages, 1 = gImage1s */
+  uint32_t index;
+  const void* pixels;  /* level 0 in the image's resident format, width x height, tightly packed */
+  uint32_t width, height;
+  uint32_t device_ptr; /* 1: pixels is device memory, readable in the order of the context's stream */
+  uint32_t pad;
+} sthip_image_update;
+typedef struct sthip_images_info { /* optional out-parameter, may be NULL */
+  float device_ms;                 /* stream time of the copies and kernels of the call (HIP events) */
+  float total_ms;                  /* wall time of the call */
+  uint32_t has_specular_before, has_specular_after; /* the analysis' verdict before and after the call (0 / 1) */
+  uint32_t images_scanned;         /* images k_image_range ran over */
+  uint32_t pad;
+} sthip_images_info;
+int sthip_scene_set_images(sthip_ctx* ctx, const sthip_image_update* entries, uint32_t n, uint32_t struct_size, sthip_images_info* info);
+int sthip_scene_set_material_data(sthip_ctx* ctx, uint32_t offset, const void* data, uint32_t bytes, sthip_images_info* info);
+int sthip_scene_read_image_range(sthip_ctx* ctx, uint32_t image_index, float lo[4], float hi[4], uint32_t* nan_mask);
+
 /* ---- frame: replaces the dispatch sequence of BDPT::render (BDPT.cpp:607-720) ----
  * Renders seeds seed_begin .. seed_begin+seed_count-1 (gRandomSeed = seed, BDPT.cpp:480), one
  * sample per pixel centre per seed (bdpt.hlsl:167), and averages them with the running mean of
@@ -761,7 +866,9 @@ int sthip_measure_ceiling(sthip_ctx* ctx, uint32_t kind, double* gbytes_per_s);
  * "denoise_block" (0 = default, 1): the lanes of a block of sthip_denoise_filter's kernels cover 32x8 or 16x16 pixels; never
  * changes results.
  * "env_rows_per_wave" (16 = default, or 64; anything else is refused): the rows a wave of k_env_rows owns in
- * sthip_scene_set_environment; never changes results. */
+ * sthip_scene_set_environment; never changes results.
+ * "image_range_blocks" (0 = default: sized from the device's CU count; 1 .. 65535 force it; anything else is refused): the
+ * blocks of k_image_range in sthip_scene_set_images / sthip_scene_set_material_data; never changes results. */
 int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value);
 
 /* ---- after the path: display transform, image metric, HDR export ---- */

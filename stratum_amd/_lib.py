@@ -32,6 +32,9 @@ EXPORTS = [
     "sthip_convert_material",
     "sthip_scene_set_environment",
     "sthip_scene_read_distributions",
+    "sthip_scene_set_images",
+    "sthip_scene_set_material_data",
+    "sthip_scene_read_image_range",
     "sthip_render",
     "sthip_host_alloc",
     "sthip_host_free",
@@ -128,6 +131,13 @@ def lib():
         L.sthip_scene_set_environment.argtypes = [C.c_void_p, C.POINTER(wire.EnvironmentDesc), C.POINTER(wire.EnvironmentInfo)]
         L.sthip_scene_read_distributions.restype = C.c_int
         L.sthip_scene_read_distributions.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    if hasattr(L, "sthip_scene_set_images"):  # (an older build named by STHIP_LIB lacks the three: calling them raises)
+        L.sthip_scene_set_images.restype = C.c_int
+        L.sthip_scene_set_images.argtypes = [C.c_void_p, C.POINTER(wire.ImageUpdate), C.c_uint32, C.c_uint32, C.POINTER(wire.ImagesInfo)]
+        L.sthip_scene_set_material_data.restype = C.c_int
+        L.sthip_scene_set_material_data.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(wire.ImagesInfo)]
+        L.sthip_scene_read_image_range.restype = C.c_int
+        L.sthip_scene_read_image_range.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     L.sthip_render.restype = C.c_int
     L.sthip_render.argtypes = [
         C.c_void_p,

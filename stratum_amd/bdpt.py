@@ -68,6 +68,7 @@ class BDPT:
         self._h = h
         self.device = device
         self._scene = None
+        self._device_images = set()  # indices of gImages whose texels set_images took from a device pointer: the scene object's are older
         self._prev_result = None
         self.half_color_precision = False  # BDPT.hpp mHalfColorPrecision: colour images RGBA16F (set_half_color_precision)
         self.set_args(args)
@@ -137,6 +138,10 @@ class BDPT:
 
     # ---- BDPT::update: (re)bind the scene ----
     def update(self, scene):
+        if scene is self._scene and self._device_images:  # the same object goes up again: its arrays first take what is resident
+            for index in sorted(self._device_images):
+                scene.images[index] = self.read_image(index, 0)
+        self._device_images = set()
         d = scene.desc()
         formats, formats1 = scene.formats()
         if formats.any() or formats1.any():  # some image is a uint8 array: it goes up, and stays resident, as 8-bit texels
@@ -281,6 +286,68 @@ class BDPT:
         out = np.zeros(n, np.float32)
         self._check(self._lib.sthip_scene_read_distributions(self._h, int(first), n, wire.ptr(out) if n else None), "sthip_scene_read_distributions")
         return out
+
+    def set_images(self, images=None, masks=None, device_ptr=False):
+        """Replace level 0 of resident images (sthip_scene_set_images). `images`: {index: texels} for gImages, `masks`: {index:
+        texels} for gImage1s — or a list of (index, texels) pairs. Texels are C-contiguous numpy arrays in the image's resident
+        format and extent: (H, W, 4) float32 or uint8 for gImages, (H, W) for gImage1s (the arrays convert_material returns go
+        in as they are); with device_ptr=True anything with data_ptr() and shape (a contiguous torch tensor on this device) of
+        that layout. All entries of one call are applied together; the mip chains, the scan of the images materials name and
+        the material analysis are made again. The scene object handed to update() follows host texels at once. Texels of
+        gImages that came from a device pointer are fetched into it (read_image) if the same object is handed to update()
+        again; until then, and for alpha masks from a device pointer (there is no read call for them: keep your own copy),
+        the scene object holds the texels before. Returns sthip_images_info as a dict."""
+        if self._scene is None:
+            raise StratumHipError("set_images: no scene is bound (update() has not run)")
+        entries = []
+        for which, group in ((0, images), (1, masks)):
+            for index, a in (group.items() if isinstance(group, dict) else (group or ())):
+                entries.append((which, int(index), a))
+        arr = (wire.ImageUpdate * max(1, len(entries)))()
+        for e, (which, index, a) in zip(arr, entries):
+            shape = tuple(a.shape)
+            if len(shape) != (2 if which else 3) or (not which and shape[2] != 4):
+                raise ValueError("set_images: %s[%d] takes texels of shape %s" % ("gImage1s" if which else "gImages", index, "(H, W)" if which else "(H, W, 4)"))
+            if device_ptr:
+                if not a.is_contiguous():
+                    raise ValueError("set_images: a device image must be contiguous")
+                e.pixels, e.device_ptr = int(a.data_ptr()), 1
+            else:
+                if a.dtype not in (np.float32, np.uint8) or not a.flags["C_CONTIGUOUS"]:
+                    raise ValueError("set_images: texels must be a C-contiguous float32 or uint8 array")
+                e.pixels = a.ctypes.data
+            resident = self._scene.images1 if which else self._scene.images
+            if index < len(resident) and str(resident[index].dtype) not in str(a.dtype):
+                raise ValueError("set_images: %s[%d] is resident as %s (a change of format is an upload)" % ("gImage1s" if which else "gImages", index, resident[index].dtype))
+            e.which, e.index, e.height, e.width = which, index, int(shape[0]), int(shape[1])
+        info = wire.ImagesInfo()
+        self._check(self._lib.sthip_scene_set_images(self._h, arr, len(entries), C.sizeof(wire.ImageUpdate), C.byref(info)), "sthip_scene_set_images")
+        for which, index, a in entries:
+            if not device_ptr:  # the arrays a later update() would send hold what is resident
+                (self._scene.images1 if which else self._scene.images)[index] = a
+                if not which:
+                    self._device_images.discard(index)
+            elif not which:
+                self._device_images.add(index)
+        return {f: getattr(info, f) for f, _ in wire.ImagesInfo._fields_ if f != "pad"}
+
+    def set_material_data(self, offset, data):
+        """Replace bytes of the resident gMaterialData (sthip_scene_set_material_data): `data` is anything numpy views as bytes
+        (a float32 array of constants, a uint32 image index, a wire.MaterialRecord ...); offset and size are multiples of 4.
+        The material analysis runs again. The scene object handed to update() follows. Returns sthip_images_info as a dict."""
+        if self._scene is None:
+            raise StratumHipError("set_material_data: no scene is bound (update() has not run)")
+        b = np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+        info = wire.ImagesInfo()
+        self._check(self._lib.sthip_scene_set_material_data(self._h, int(offset), wire.ptr(b) if b.size else None, b.size, C.byref(info)), "sthip_scene_set_material_data")
+        self._scene.materials[int(offset) : int(offset) + b.size] = b
+        return {f: getattr(info, f) for f, _ in wire.ImagesInfo._fields_ if f != "pad"}
+
+    def read_image_range(self, index):
+        """(lo, hi, nan_mask) the context holds for gImages[index]: two float32 arrays of 4 and an int (sthip_scene_read_image_range)."""
+        lo, hi, mask = np.zeros(4, np.float32), np.zeros(4, np.float32), C.c_uint32(0)
+        self._check(self._lib.sthip_scene_read_image_range(self._h, int(index), wire.ptr(lo), wire.ptr(hi), C.byref(mask)), "sthip_scene_read_image_range")
+        return lo, hi, int(mask.value)
 
     def convert_material(self, kind, diffuse=None, specular=None, transmittance=None, roughness=None, input=None, output_format=1):
         """sthip_convert_material in its host form (kernels/material_convert.hlsl). `kind`: a name of wire.CONVERT or its

@@ -14,6 +14,7 @@
 #include <chrono>
 #include <cmath>
 #include <map>
+#include <set>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -24,6 +25,7 @@
 #include "environment.h"
 #include "bvh_build.h"
 #include "first_hits.h"
+#include "image_range.h"
 #include "material_convert.h"
 #include "kernel_instances.h"  // kernels.h + the instantiations that live in shade_*.hip / trace_kernels.hip
 #include "mips.h"
@@ -325,8 +327,18 @@ struct sthip_ctx {
   DevBuf<double> env_sines;
   DevBuf<float> env_integrals;
   uint32_t env_rows_per_wave = sthip::ENV_ROWS_PER_WAVE_DEFAULT;  // "env_rows_per_wave": 16 or 64 (environment.h)
-  bool kept_env_image_stale = false, kept_env_tables_stale = false;
-  uint32_t kept_env_image = 0;  // the image the stale texels belong to
+  bool kept_env_tables_stale = false;
+  // the images of the kept scene (gImages / gImage1s, in either format) whose texels came from a device pointer and are
+  // newer on the device than in the kept copy (sthip_scene_set_environment, sthip_scene_set_images)
+  std::set<uint32_t> kept_images_stale, kept_images1_stale;
+  // sthip_scene_set_images / sthip_scene_set_material_data (image_range.hip): what the material analysis needs to run again
+  // without the scene's arrays — per instance its material address and type (whatever "keep_scene" says), per image of gImages
+  // the range of its level 0 as far as somebody scanned it — the alpha masks' table as uploaded, and the scan's buffers
+  std::vector<sthip::MaterialInstance> material_instances;
+  std::vector<sthip::ImageRange> image_ranges;
+  std::vector<DeviceImage1> images1_host;
+  DevBuf<uint32_t> range_partials, range_results;
+  uint32_t image_range_blocks = 0;  // "image_range_blocks": 0 = from cu_count
   bool embedded_resident = false;  // the leaf triangles lie in the node array (BuiltBvh::embedded)
   bool want_wide = false;                            // the current scene is walked in its 4-wide form (decided at upload)
   bool lds_materials = true;  // k_shade stages gMaterialData in LDS when it fits 32 KB
@@ -816,6 +828,9 @@ int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value) {
   } else if (!strcmp(name, "env_rows_per_wave")) {  // rows a wave of k_env_rows owns (environment.h)
     if (value != 16 && value != 64) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "env_rows_per_wave: 16 or 64");
     ctx->env_rows_per_wave = (uint32_t)value;
+  } else if (!strcmp(name, "image_range_blocks")) {  // blocks of k_image_range (image_range.h); 0 = sized from the CU count
+    if (value < 0 || value > (int64_t)sthip::IMAGE_RANGE_MAX_BLOCKS) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "image_range_blocks: 0 (default) or 1 .. 65535");
+    ctx->image_range_blocks = (uint32_t)value;
   } else if (!strcmp(name, "inner_min_lanes"))
     ctx->inner_min_lanes = (uint32_t)std::min<int64_t>(64, std::max<int64_t>(1, value));
   else
@@ -970,22 +985,39 @@ static int pose_rigs(sthip_ctx* ctx, const char* call) {
   return STHIP_OK;
 }
 
-// The kept scene's environment is current again: texels that came from a device pointer and tables that were built on the
-// device (sthip_scene_set_environment) come back to the host. Called immediately before anything is built from the kept scene.
+// The kept scene's images and tables are current again: texels that came from a device pointer (sthip_scene_set_environment,
+// sthip_scene_set_images) and tables that were built on the device come back to the host. Called immediately before anything is
+// built from the kept scene.
 static int sync_kept_environment(sthip_ctx* ctx) {
-  if (!ctx->kept_env_image_stale && !ctx->kept_env_tables_stale) return STHIP_OK;
+  if (ctx->kept_images_stale.empty() && ctx->kept_images1_stale.empty() && !ctx->kept_env_tables_stale) return STHIP_OK;
   if (ctx->kept.valid && ctx->has_scene) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const uint32_t i = ctx->kept_env_image;
-    if (ctx->kept_env_image_stale && i < ctx->images_host.size() && i < ctx->kept.image_pixels.size() && ctx->images_host[i].format == STHIP_IMAGE_FORMAT_RGBA32F) {
+    for (const uint32_t i : ctx->kept_images_stale) {  // level 0, in the format the image is resident and kept in
+      if (i >= ctx->images_host.size() || i >= ctx->kept.image_pixels.size()) continue;
       const DeviceImage& im = ctx->images_host[i];
-      const size_t floats = (size_t)im.w[0] * im.h[0] * 4;
-      if (ctx->kept.image_pixels[i].size() == floats) HIP_TRY(ctx, hipMemcpy(ctx->kept.image_pixels[i].data(), ctx->image_texels.p + im.offset[0], floats * sizeof(float), hipMemcpyDeviceToHost));
+      const size_t texels = (size_t)im.w[0] * im.h[0];
+      if (im.format == STHIP_IMAGE_FORMAT_RGBA8_UNORM) {
+        if (ctx->kept.image_bytes[i].size() == texels * 4) HIP_TRY(ctx, hipMemcpy(ctx->kept.image_bytes[i].data(), ctx->image_texels8.p + im.offset[0], texels * 4, hipMemcpyDeviceToHost));
+      } else if (ctx->kept.image_pixels[i].size() == texels * 4) {
+        HIP_TRY(ctx, hipMemcpy(ctx->kept.image_pixels[i].data(), ctx->image_texels.p + im.offset[0], texels * 16, hipMemcpyDeviceToHost));
+      }
+    }
+    for (const uint32_t i : ctx->kept_images1_stale) {
+      if (i >= ctx->images1_host.size() || i >= ctx->kept.image1_pixels.size()) continue;
+      const DeviceImage1& im = ctx->images1_host[i];
+      const size_t texels = (size_t)im.w * im.h;
+      if (im.format == STHIP_IMAGE_FORMAT_R8_UNORM) {
+        if (ctx->kept.image1_bytes[i].size() == texels) HIP_TRY(ctx, hipMemcpy(ctx->kept.image1_bytes[i].data(), ctx->image1_texels8.p + im.offset, texels, hipMemcpyDeviceToHost));
+      } else if (ctx->kept.image1_pixels[i].size() == texels) {
+        HIP_TRY(ctx, hipMemcpy(ctx->kept.image1_pixels[i].data(), ctx->image1_texels.p + im.offset, texels * 4, hipMemcpyDeviceToHost));
+      }
     }
     if (ctx->kept_env_tables_stale && ctx->kept.distributions.size() == ctx->distribution_count && ctx->distribution_count)
       HIP_TRY(ctx, hipMemcpy(ctx->kept.distributions.data(), ctx->distributions.p, (size_t)ctx->distribution_count * sizeof(float), hipMemcpyDeviceToHost));
   }
-  ctx->kept_env_image_stale = ctx->kept_env_tables_stale = false;
+  ctx->kept_images_stale.clear();
+  ctx->kept_images1_stale.clear();
+  ctx->kept_env_tables_stale = false;
   return STHIP_OK;
 }
 
@@ -1139,6 +1171,7 @@ static int install_alpha_masks(sthip_ctx* ctx, const sthip::MaskLayout& masks, b
   if (!masks.texels8.empty()) HIP_TRY(ctx, hipMemcpy(ctx->image1_texels8.p, masks.texels8.data(), masks.texels8.size(), hipMemcpyHostToDevice));
   HIP_TRY(ctx, ctx->inst_alpha.ensure(std::max<size_t>(1, built.inst_alpha.size())));
   if (!built.inst_alpha.empty()) HIP_TRY(ctx, hipMemcpy(ctx->inst_alpha.p, built.inst_alpha.data(), built.inst_alpha.size() * 4, hipMemcpyHostToDevice));
+  ctx->images1_host = masks.table;
   ctx->bvh.inst_alpha = ctx->inst_alpha.p;
   ctx->has_alpha = any_alpha && built.any_alpha;
   ctx->bvh.tri_uv = reinterpret_cast<const float2*>(ctx->tri_uvs.p);
@@ -1186,6 +1219,9 @@ static int install_scene_arrays(sthip_ctx* ctx, const sthip_scene_desc* s, Prepa
   ctx->volume_instances = m.volume_instances;
   ctx->instance_is_volume = std::move(m.instance_is_volume);
   ctx->image_in_material = std::move(m.image_in_material);
+  ctx->image_ranges = std::move(m.image_ranges);
+  ctx->material_instances.resize(n);
+  for (uint32_t i = 0; i < n; i++) ctx->material_instances[i] = sthip::MaterialInstance{s->gInstances[i].packed[0] >> 4, sthip::instance_type(s->gInstances[i])};
   if (ctx->bvh_builder != sthip::BVH_BUILDER_LBVH_GPU) {  // (the GPU builder has them already)
     const int rc = upload_vertices_and_indices(ctx, s);
     if (rc != STHIP_OK) return rc;
@@ -1365,7 +1401,9 @@ static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t
   } else {
     ctx->kept = KeptScene();
   }
-  ctx->kept_env_image_stale = ctx->kept_env_tables_stale = false;  // (what is kept now is what is resident)
+  ctx->kept_images_stale.clear();  // (what is kept now is what is resident)
+  ctx->kept_images1_stale.clear();
+  ctx->kept_env_tables_stale = false;
   if (getenv("STHIP_VERBOSE"))
     fprintf(stderr, "[sthip] bvh (%s): %zu nodes, %zu tris, %zu top-level entries, stack depth %u (%zu B LDS / block%s, treetop %u nodes), %d trace blocks / CU, build %.1f ms (GPU kernels %.2f ms)\n",
             ctx->bvh_builder ? "lbvh/gpu" : "sah/host", (size_t)ctx->bvh_nodes, (size_t)ctx->bvh_tris, built.entries.size(), built.stack_depth, stack_bytes(ctx), ctx->bvh.spill ? ", bounded" : "", ctx->bvh.top_count,
@@ -1975,6 +2013,9 @@ int sthip_scene_set_environment(sthip_ctx* ctx, const sthip_environment_desc* d,
   if (plan.replace_pixels) {
     const DeviceImage& im = ctx->images_host[plan.image_index];
     const size_t bytes = (size_t)plan.width * plan.height * 16;
+    // (no record names the image now, but one may have and may again: a range kept from the old texels is forgotten, so that
+    // sthip_scene_set_material_data scans the new ones when a record binds the image)
+    if (plan.image_index < ctx->image_ranges.size()) ctx->image_ranges[plan.image_index] = sthip::ImageRange();
     HIP_TRY(ctx, hipMemcpyAsync(ctx->image_texels.p + im.offset[0], d->pixels, bytes, d->device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     stage_done(STAGE_COPY);
     for (uint32_t level = 0; level + 1 < im.levels; level++)
@@ -1983,11 +2024,10 @@ int sthip_scene_set_environment(sthip_ctx* ctx, const sthip_environment_desc* d,
     stage_done(STAGE_MIPS);
     if (ctx->kept.valid && plan.image_index < ctx->kept.image_pixels.size() && ctx->kept.image_pixels[plan.image_index].size() == bytes / 4) {
       if (d->device_ptr) {
-        ctx->kept_env_image_stale = true;
-        ctx->kept_env_image = plan.image_index;
+        ctx->kept_images_stale.insert(plan.image_index);
       } else {
         memcpy(ctx->kept.image_pixels[plan.image_index].data(), d->pixels, bytes);
-        if (ctx->kept_env_image == plan.image_index) ctx->kept_env_image_stale = false;
+        ctx->kept_images_stale.erase(plan.image_index);
       }
     }
   }
@@ -2038,6 +2078,263 @@ int sthip_scene_set_environment(sthip_ctx* ctx, const sthip_environment_desc* d,
     (void)hipEventElapsedTime(&info->device_ms, ctx->rig_ev[0], ctx->rig_ev[1]);
     info->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
+  return STHIP_OK;
+}
+
+// ---- sthip_scene_set_images / sthip_scene_set_material_data / sthip_scene_read_image_range (sthip.h) ----
+// Room for the scan of `count` images by at most `blocks` blocks each: everything of it that can run out of memory
+static int reserve_image_ranges(sthip_ctx* ctx, size_t count, uint32_t blocks) {
+  if (!count) return STHIP_OK;
+  HIP_TRY(ctx, ctx->range_partials.ensure((size_t)blocks * sthip::IMAGE_RANGE_PARTIAL_WORDS));
+  HIP_TRY(ctx, ctx->range_results.ensure(count * sthip::IMAGE_RANGE_RESULT_WORDS));
+  return STHIP_OK;
+}
+static uint32_t image_range_blocks_for(const sthip_ctx* ctx, const DeviceImage& im) {
+  return sthip::image_range_blocks((uint64_t)im.w[0] * im.h[0], im.format == STHIP_IMAGE_FORMAT_RGBA8_UNORM, ctx->cu_count, ctx->image_range_blocks);
+}
+// k_image_range over level 0 of the images `scan` names, as they are resident in stream order; the partials are one buffer
+// (the launches of one stream run one after the other), the results one 12-word record per image
+static int enqueue_image_ranges(sthip_ctx* ctx, const std::vector<uint32_t>& scan, hipStream_t st, const char* call) {
+  std::string err;
+  for (size_t k = 0; k < scan.size(); k++) {
+    const DeviceImage& im = ctx->images_host[scan[k]];
+    const bool rgba8 = im.format == STHIP_IMAGE_FORMAT_RGBA8_UNORM;
+    const void* src = rgba8 ? (const void*)(ctx->image_texels8.p + im.offset[0]) : (const void*)(ctx->image_texels.p + im.offset[0]);
+    if (!sthip::image_range_launch(src, (uint64_t)im.w[0] * im.h[0], rgba8, image_range_blocks_for(ctx, im), ctx->range_partials.p, ctx->range_results.p + k * sthip::IMAGE_RANGE_RESULT_WORDS, st, err))
+      return fail(ctx, STHIP_ERR_HIP, std::string(call) + ": " + err);
+  }
+  return STHIP_OK;
+}
+// The one read-back of a call (it waits for the stream), into the ranges the context keeps
+static int fetch_image_ranges(sthip_ctx* ctx, const std::vector<uint32_t>& scan, hipStream_t st) {
+  std::vector<uint32_t> words(scan.size() * sthip::IMAGE_RANGE_RESULT_WORDS);
+  if (!scan.empty()) HIP_TRY(ctx, hipMemcpyAsync(words.data(), ctx->range_results.p, words.size() * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  for (size_t k = 0; k < scan.size(); k++) {
+    sthip::ImageRange& r = ctx->image_ranges[scan[k]];
+    const uint32_t* w = words.data() + k * sthip::IMAGE_RANGE_RESULT_WORDS;
+    memcpy(r.lo, w, 16);
+    memcpy(r.hi, w + 4, 16);
+    r.nan_mask = w[8];
+    r.known = 1;
+  }
+  return STHIP_OK;
+}
+// Measurement only (sthip.h, tools/material_update_times.py): with STHIP_MATERIAL_TIMES=<file> (read once per process) every call
+// that scans appends one JSON line with the HIP-event time of its k_image_range launches alone. Without the variable no event
+// is made here and no file touched.
+struct RangeTimes {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool on = false;
+  static const char* path() {
+    static const char* const p = [] {
+      const char* v = getenv("STHIP_MATERIAL_TIMES");
+      return v && *v ? v : nullptr;
+    }();
+    return p;
+  }
+  explicit RangeTimes(bool scans) {
+    if (!scans || !path()) return;
+    on = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;  // (a failure to make one only loses the measurement)
+  }
+  ~RangeTimes() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  void mark(int k, hipStream_t st) {
+    if (on) (void)hipEventRecord(ev[k], st);
+  }
+  void write(const char* call, size_t images, uint32_t blocks) {  // after the stream has been waited for
+    if (!on) return;
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+    if (FILE* f = fopen(path(), "a")) {
+      fprintf(f, "{\"call\": \"%s\", \"images\": %zu, \"blocks\": %u, \"k_image_range_ms\": %.5f}\n", call, images, blocks, ms);
+      fclose(f);
+    }
+  }
+};
+static sthip::MaterialAnalysis analyse_resident_materials(const sthip_ctx* ctx) {
+  return sthip::analyse_materials(ctx->material_instances.data(), (uint32_t)ctx->material_instances.size(), ctx->materials_host.data(), (uint32_t)ctx->image_ranges.size(), ctx->image_ranges.data());
+}
+static void fill_images_info(sthip_ctx* ctx, sthip_images_info* info, bool before, size_t scanned, std::chrono::steady_clock::time_point t0) {
+  if (!info) return;
+  info->device_ms = 0;
+  (void)hipEventElapsedTime(&info->device_ms, ctx->rig_ev[0], ctx->rig_ev[1]);
+  info->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  info->has_specular_before = before ? 1u : 0u;
+  info->has_specular_after = ctx->has_specular ? 1u : 0u;
+  info->images_scanned = (uint32_t)scanned;
+  info->pad = 0;
+}
+
+// check (scene_prepare.cpp) -> reserve -> wait -> texels, mip chains, scans on the stream -> one read-back -> the analysis again
+// -> the kept scene follows
+int sthip_scene_set_images(sthip_ctx* ctx, const sthip_image_update* entries, uint32_t n, uint32_t struct_size, sthip_images_info* info) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  const auto t0 = std::chrono::steady_clock::now();
+  sthip::ResidentImages resident;
+  resident.has_scene = ctx->has_scene;
+  resident.images = ctx->images_host.data();
+  resident.image_count = (uint32_t)std::min<size_t>(ctx->image_count, ctx->images_host.size());
+  resident.images1 = ctx->images1_host.data();
+  resident.image1_count = (uint32_t)ctx->images1_host.size();
+  int rc = STHIP_OK;
+  std::string why;
+  if (!sthip::check_images(resident, entries, n, struct_size, rc, why)) return fail(ctx, rc, why);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<uint32_t> scan;  // the replaced images a material record names
+  uint32_t blocks = 1;
+  bool mask_changed = false;
+  for (uint32_t k = 0; k < n; k++) {
+    const sthip_image_update& e = entries[k];
+    if (e.which) {
+      mask_changed = true;
+    } else if (e.index < ctx->image_in_material.size() && ctx->image_in_material[e.index] && e.index < ctx->image_ranges.size()) {
+      scan.push_back(e.index);
+      blocks = std::max(blocks, image_range_blocks_for(ctx, ctx->images_host[e.index]));
+    }
+  }
+  if ((rc = reserve_image_ranges(ctx, scan.size(), blocks)) != STHIP_OK) return rc;
+  for (int k = 0; k < 2; k++)
+    if (!ctx->rig_ev[k]) HIP_TRY(ctx, hipEventCreate(&ctx->rig_ev[k]));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old texels
+  HIP_TRY(ctx, drain_in_flight(ctx));
+  ctx->reuse_grids_valid = false;         // (stored samples carry the old materials' radiance)
+  if (mask_changed) ctx->scene_serial++;  // (first_hits.h: the alpha test decides first hits; images of gImages alone move none)
+  // the range the context holds for a replaced image is the old texels': forgotten here, and made again below for the images
+  // a record names. An image nobody names stays unscanned until a record binds it (sthip_scene_set_material_data scans it then).
+  for (uint32_t k = 0; k < n; k++)
+    if (!entries[k].which && entries[k].index < ctx->image_ranges.size()) ctx->image_ranges[entries[k].index] = sthip::ImageRange();
+  hipStream_t st = ctx->stream;
+  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[0], st));
+  std::string err;
+  for (uint32_t k = 0; k < n; k++) {
+    const sthip_image_update& e = entries[k];
+    const hipMemcpyKind kind = e.device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (e.which) {
+      const DeviceImage1& im = ctx->images1_host[e.index];
+      const size_t texels = (size_t)im.w * im.h;
+      if (im.format == STHIP_IMAGE_FORMAT_R8_UNORM)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->image1_texels8.p + im.offset, e.pixels, texels, kind, st));
+      else
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->image1_texels.p + im.offset, e.pixels, texels * 4, kind, st));
+      continue;
+    }
+    const DeviceImage& im = ctx->images_host[e.index];
+    const size_t texels = (size_t)im.w[0] * im.h[0];
+    const bool rgba8 = im.format == STHIP_IMAGE_FORMAT_RGBA8_UNORM;
+    if (rgba8)
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->image_texels8.p + im.offset[0], e.pixels, texels * 4, kind, st));
+    else
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->image_texels.p + im.offset[0], e.pixels, texels * 16, kind, st));
+    for (uint32_t level = 0; level + 1 < im.levels; level++) {
+      const bool ok = rgba8 ? sthip::mip_rgba8_launch(ctx->image_texels8.p + im.offset[level], im.w[level], im.h[level], ctx->image_texels8.p + im.offset[level + 1], ctx->cu_count, st, err)
+                            : sthip::mip_rgba32f_launch(ctx->image_texels.p + im.offset[level], im.w[level], im.h[level], ctx->image_texels.p + im.offset[level + 1], ctx->cu_count, st, err);
+      if (!ok) return fail(ctx, STHIP_ERR_HIP, "sthip_scene_set_images: " + err);
+    }
+  }
+  RangeTimes times(!scan.empty());
+  times.mark(0, st);
+  if ((rc = enqueue_image_ranges(ctx, scan, st, "sthip_scene_set_images")) != STHIP_OK) return rc;
+  times.mark(1, st);
+  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[1], st));
+  if ((rc = fetch_image_ranges(ctx, scan, st)) != STHIP_OK) return rc;  // (a pageable `pixels` array is the caller's again from here on)
+  times.write("sthip_scene_set_images", scan.size(), blocks);
+  const bool before = ctx->has_specular;
+  if (!scan.empty()) ctx->has_specular = analyse_resident_materials(ctx).has_specular;  // (nothing else of the analysis depends on texels)
+  if (ctx->kept.valid) {
+    for (uint32_t k = 0; k < n; k++) {
+      const sthip_image_update& e = entries[k];
+      std::vector<std::vector<float>>& floats = e.which ? ctx->kept.image1_pixels : ctx->kept.image_pixels;
+      std::vector<std::vector<uint8_t>>& bytes = e.which ? ctx->kept.image1_bytes : ctx->kept.image_bytes;
+      std::set<uint32_t>& stale = e.which ? ctx->kept_images1_stale : ctx->kept_images_stale;
+      if (e.index >= floats.size() || e.index >= bytes.size()) continue;
+      if (e.device_ptr) {
+        stale.insert(e.index);
+        continue;
+      }
+      const size_t channels = e.which ? 1 : 4, values = (size_t)e.width * e.height * channels;
+      if (bytes[e.index].size() == values) memcpy(bytes[e.index].data(), e.pixels, values);
+      if (floats[e.index].size() == values) memcpy(floats[e.index].data(), e.pixels, values * 4);
+      stale.erase(e.index);
+    }
+  }
+  fill_images_info(ctx, info, before, scan.size(), t0);
+  return STHIP_OK;
+}
+
+// check (scene_prepare.cpp) -> reserve -> wait -> the bytes, the scans of images the analysis newly reads -> the analysis again
+int sthip_scene_set_material_data(sthip_ctx* ctx, uint32_t offset, const void* data, uint32_t bytes, sthip_images_info* info) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  const auto t0 = std::chrono::steady_clock::now();
+  sthip::ResidentMaterials resident;
+  resident.has_scene = ctx->has_scene;
+  resident.materials = ctx->materials_host.data();
+  resident.material_bytes = ctx->materials_host.size();
+  resident.instances = ctx->material_instances.data();
+  resident.instance_count = (uint32_t)ctx->material_instances.size();
+  resident.image_count = (uint32_t)std::min<size_t>(ctx->image_count, ctx->images_host.size());
+  resident.image1_count = (uint32_t)ctx->images1_host.size();
+  resident.volume_count = ctx->volume_count;
+  int rc = STHIP_OK;
+  std::string why;
+  std::vector<uint8_t> edited;
+  if (!sthip::check_material_data(resident, offset, data, bytes, edited, rc, why)) return fail(ctx, rc, why);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // an image whose range the analysis reads now and nobody has scanned (a record names it for the first time, or under a
+  // constant that has become positive): scanned from the resident texels
+  std::vector<uint8_t> named, range_read;
+  sthip::material_images(resident.instances, resident.instance_count, edited.data(), (uint32_t)ctx->image_ranges.size(), named, range_read);
+  std::vector<uint32_t> scan;
+  uint32_t blocks = 1;
+  for (uint32_t i = 0; i < range_read.size() && i < resident.image_count; i++)
+    if (range_read[i] && !ctx->image_ranges[i].known) {
+      scan.push_back(i);
+      blocks = std::max(blocks, image_range_blocks_for(ctx, ctx->images_host[i]));
+    }
+  if ((rc = reserve_image_ranges(ctx, scan.size(), blocks)) != STHIP_OK) return rc;
+  for (int k = 0; k < 2; k++)
+    if (!ctx->rig_ev[k]) HIP_TRY(ctx, hipEventCreate(&ctx->rig_ev[k]));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old records
+  HIP_TRY(ctx, drain_in_flight(ctx));
+  ctx->reuse_grids_valid = false;  // (stored samples carry the old materials' radiance)
+  hipStream_t st = ctx->stream;
+  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[0], st));
+  if (bytes) {
+    memcpy(ctx->materials_host.data() + offset, data, bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->materials.p + offset, ctx->materials_host.data() + offset, bytes, hipMemcpyHostToDevice, st));
+    if (ctx->kept.valid && ctx->kept.materials.size() == ctx->materials_host.size()) memcpy(ctx->kept.materials.data() + offset, data, bytes);
+  }
+  RangeTimes times(!scan.empty());
+  times.mark(0, st);
+  if ((rc = enqueue_image_ranges(ctx, scan, st, "sthip_scene_set_material_data")) != STHIP_OK) return rc;
+  times.mark(1, st);
+  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[1], st));
+  if ((rc = fetch_image_ranges(ctx, scan, st)) != STHIP_OK) return rc;
+  times.write("sthip_scene_set_material_data", scan.size(), blocks);
+  const bool before = ctx->has_specular;
+  sthip::MaterialAnalysis m = analyse_resident_materials(ctx);
+  if (m.inst_flags.size() == ctx->inst_flags_host.size() && m.inst_flags != ctx->inst_flags_host)
+    HIP_TRY(ctx, hipMemcpy(ctx->inst_flags.p, m.inst_flags.data(), m.inst_flags.size(), hipMemcpyHostToDevice));
+  ctx->inst_flags_host = std::move(m.inst_flags);
+  ctx->has_specular = m.has_specular;
+  ctx->textured = m.textured;
+  ctx->image_in_material = std::move(m.image_in_material);
+  fill_images_info(ctx, info, before, scan.size(), t0);
+  return STHIP_OK;
+}
+
+int sthip_scene_read_image_range(sthip_ctx* ctx, uint32_t image_index, float lo[4], float hi[4], uint32_t* nan_mask) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_image_range before sthip_scene_upload");
+  if (image_index >= ctx->image_count || image_index >= ctx->image_ranges.size()) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_image_range: image_index is not in gImages");
+  const sthip::ImageRange& r = ctx->image_ranges[image_index];
+  if (!r.known || image_index >= ctx->image_in_material.size() || !ctx->image_in_material[image_index])
+    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_image_range: the context holds no range for gImages[" + std::to_string(image_index) + "] (no material record names it under a constant with a positive component)");
+  if (lo) memcpy(lo, r.lo, 16);
+  if (hi) memcpy(hi, r.hi, 16);
+  if (nan_mask) *nan_mask = r.nan_mask;
   return STHIP_OK;
 }
 

@@ -60,42 +60,80 @@ bool check_scene(const sthip_scene_desc* s, const uint8_t* image_formats, const 
   return true;
 }
 
-MaterialAnalysis analyse_materials(const sthip_scene_desc& s, const uint8_t* image_formats) {
-  MaterialAnalysis m;
+ImageRange scan_image_range(const void* pixels, size_t count, bool rgba8) {
   // Per-channel extremes of an image (level 0; every mip level is an average of it, and bilinear / trilinear taps are
-  // convex combinations, so a sampled value lies between them). Scanned on first use: the device multiplies the
-  // constant by the texel (image_value.h:194-198), so whether a material can be specular depends on the texels.
-  std::vector<int> scanned(s.image_count, 0);
-  std::vector<float> tex_min((size_t)s.image_count * 4, 0.0f), tex_max((size_t)s.image_count * 4, 0.0f);
-  auto image_range = [&](uint32_t index, int channel, float& lo, float& hi) {
-    if (!scanned[index]) {
-      const float* px = s.gImages[index].pixels;
-      const uint8_t* px8 = image_formats && image_formats[index] ? reinterpret_cast<const uint8_t*>(px) : nullptr;  // RGBA8: the decoded bytes
-      const size_t count = (size_t)s.gImages[index].width * s.gImages[index].height;
-      for (int c = 0; c < 4; c++) {
-        float a = __builtin_inff(), b = -__builtin_inff();
-        bool nan = false;
-        for (size_t k = 0; px && k < count; k++) {
-          const float t = px8 ? (float)px8[4 * k + c] / 255.0f : px[4 * k + c];
-          if (t != t) nan = true;
-          a = std::min(a, t);
-          b = std::max(b, t);
-        }
-        if (nan || !px || !count) a = -__builtin_inff(), b = __builtin_inff();  // unknown: everything is possible
-        tex_min[(size_t)index * 4 + c] = a;
-        tex_max[(size_t)index * 4 + c] = b;
-      }
-      scanned[index] = 1;
+  // convex combinations, so a sampled value lies between them): the device multiplies the constant by the texel
+  // (image_value.h:194-198), so whether a material can be specular depends on the texels.
+  ImageRange r;
+  const float* px = rgba8 ? nullptr : static_cast<const float*>(pixels);
+  const uint8_t* px8 = rgba8 ? static_cast<const uint8_t*>(pixels) : nullptr;  // RGBA8: the decoded bytes
+  for (int c = 0; c < 4; c++) {
+    float a = __builtin_inff(), b = -__builtin_inff();
+    bool nan = false;
+    for (size_t k = 0; pixels && k < count; k++) {
+      const float t = px8 ? (float)px8[4 * k + c] / 255.0f : px[4 * k + c];
+      if (t != t) nan = true;
+      a = std::min(a, t);
+      b = std::max(b, t);
     }
-    lo = tex_min[(size_t)index * 4 + channel];
-    hi = tex_max[(size_t)index * 4 + channel];
+    if (nan) r.nan_mask |= 1u << c;
+    if (nan || !pixels || !count) a = -__builtin_inff(), b = __builtin_inff();  // unknown: everything is possible
+    r.lo[c] = a;
+    r.hi[c] = b;
+  }
+  r.known = 1;
+  return r;
+}
+
+// the images whose range value_range below reads: metallic and roughness (values[1]), transmission (values[2])
+static bool reads_range(const sthip_MaterialRecord& rec, int k, uint32_t image_count) {
+  const uint32_t index = rec.values[k].image_index;
+  if (index >= STHIP_IMAGE_COUNT || index >= image_count) return false;
+  const float* v = rec.values[k].value;
+  return v[0] > 0 || v[1] > 0 || v[2] > 0 || v[3] > 0;
+}
+
+void material_images(const MaterialInstance* instances, uint32_t instance_count, const uint8_t* materials, uint32_t image_count, std::vector<uint8_t>& named, std::vector<uint8_t>& range_read) {
+  named.assign(image_count, 0);
+  range_read.assign(image_count, 0);
+  for (uint32_t i = 0; i < instance_count; i++) {
+    if (instances[i].type == STHIP_INSTANCE_TYPE_VOLUME) continue;
+    sthip_MaterialRecord rec;
+    memcpy(&rec, materials + instances[i].address, sizeof(rec));
+    for (int k = 0; k < 4; k++) {
+      const uint32_t index = k < 3 ? rec.values[k].image_index : rec.bump_index;
+      if (index < image_count) named[index] = 1;
+    }
+    for (int k = 1; k < 3; k++)
+      if (reads_range(rec, k, image_count)) range_read[rec.values[k].image_index] = 1;
+  }
+}
+
+MaterialAnalysis analyse_materials(const sthip_scene_desc& s, const uint8_t* image_formats) {
+  std::vector<MaterialInstance> instances(s.instance_count);
+  for (uint32_t i = 0; i < s.instance_count; i++) instances[i] = MaterialInstance{s.gInstances[i].packed[0] >> 4, instance_type(s.gInstances[i])};
+  std::vector<uint8_t> named, range_read;
+  material_images(instances.data(), s.instance_count, (const uint8_t*)s.gMaterialData, s.image_count, named, range_read);
+  std::vector<ImageRange> ranges(s.image_count);
+  for (uint32_t i = 0; i < s.image_count; i++)
+    if (range_read[i]) ranges[i] = scan_image_range(s.gImages[i].pixels, (size_t)s.gImages[i].width * s.gImages[i].height, image_formats && image_formats[i]);
+  MaterialAnalysis m = analyse_materials(instances.data(), s.instance_count, (const uint8_t*)s.gMaterialData, s.image_count, ranges.data());
+  m.image_ranges = std::move(ranges);
+  return m;
+}
+
+MaterialAnalysis analyse_materials(const MaterialInstance* instances, uint32_t instance_count, const uint8_t* materials, uint32_t image_count, const ImageRange* ranges) {
+  MaterialAnalysis m;
+  auto image_range = [&](uint32_t index, int channel, float& lo, float& hi) {
+    lo = -__builtin_inff(), hi = __builtin_inff();  // an image nobody scanned: everything is possible
+    if (ranges[index].known) lo = ranges[index].lo[channel], hi = ranges[index].hi[channel];
   };
   // bounds of one component of an image value: constant, or constant * texel (zero when no component of the constant is positive)
   auto value_range = [&](const sthip_MaterialRecord& rec, int k, int channel, float& lo, float& hi) {
     const float c = rec.values[k].value[channel];
     lo = hi = c;
     const uint32_t index = rec.values[k].image_index;
-    if (index >= STHIP_IMAGE_COUNT || index >= s.image_count) return;
+    if (index >= STHIP_IMAGE_COUNT || index >= image_count) return;
     const float* v = rec.values[k].value;
     if (!(v[0] > 0 || v[1] > 0 || v[2] > 0 || v[3] > 0)) {
       lo = hi = 0.0f;
@@ -107,29 +145,29 @@ MaterialAnalysis analyse_materials(const sthip_scene_desc& s, const uint8_t* ima
     hi = std::max(c * a, c * b);
     if (lo != lo || hi != hi) lo = -__builtin_inff(), hi = __builtin_inff();
   };
-  m.inst_flags.assign(std::max<uint32_t>(1, s.instance_count), (uint8_t)INST_FLAG_KEEP);  // k_cull_terminal's table (kernels.h)
-  m.instance_is_volume.assign(s.instance_count, 0);
-  m.image_in_material.assign(s.image_count, 0);
-  for (uint32_t i = 0; i < s.instance_count; i++) {
-    const uint32_t addr = s.gInstances[i].packed[0] >> 4, type = instance_type(s.gInstances[i]);
+  m.inst_flags.assign(std::max<uint32_t>(1, instance_count), (uint8_t)INST_FLAG_KEEP);  // k_cull_terminal's table (kernels.h)
+  m.instance_is_volume.assign(instance_count, 0);
+  m.image_in_material.assign(image_count, 0);
+  for (uint32_t i = 0; i < instance_count; i++) {
+    const uint32_t addr = instances[i].address, type = instances[i].type;
     if (type == STHIP_INSTANCE_TYPE_SPHERE) m.has_spheres = true;
     if (type == STHIP_INSTANCE_TYPE_VOLUME) {  // a Medium record (Material.hpp:80-87), 40 bytes
       m.has_volumes = true;
       m.volume_instances++;
       m.instance_is_volume[i] = 1;
       float anisotropy;
-      memcpy(&anisotropy, (const uint8_t*)s.gMaterialData + addr + 12, 4);
+      memcpy(&anisotropy, materials + addr + 12, 4);
       if (!(fabsf(anisotropy) <= 0.999f)) m.has_specular = true;  // Medium::is_specular (medium.hlsli:22): its vertices are not diffuse vertices
       continue;
     }
     sthip_MaterialRecord rec;
-    memcpy(&rec, (const uint8_t*)s.gMaterialData + addr, sizeof(rec));
+    memcpy(&rec, materials + addr, sizeof(rec));
     for (int k = 0; k < 3; k++)
       if (rec.values[k].image_index < STHIP_IMAGE_COUNT) m.textured = true;
     if (rec.bump_index < STHIP_IMAGE_COUNT) m.textured = true;
     for (int k = 0; k < 4; k++) {
       const uint32_t index = k < 3 ? rec.values[k].image_index : rec.bump_index;
-      if (index < s.image_count) m.image_in_material[index] = 1;
+      if (index < image_count) m.image_in_material[index] = 1;
     }
     if (rec.alpha_mask_index < STHIP_IMAGE_COUNT && type == STHIP_INSTANCE_TYPE_TRIANGLES) m.any_alpha = true;
     // DisneyMaterial::is_specular (disney_material.hlsli:125) is evaluated per hit on value * texel, so the host test is
@@ -143,7 +181,7 @@ MaterialAnalysis analyse_materials(const sthip_scene_desc& s, const uint8_t* ima
       // what DisneyMaterial::load reads of an untextured record (shading.h), with the device's arithmetic: Le = base_color *
       // emission, can_eval, is_specular (only the untextured k_shade instantiations, i.e. a scene without images, consult this)
       float f[14];
-      memcpy(f, (const uint8_t*)s.gMaterialData + addr, sizeof(f));
+      memcpy(f, materials + addr, sizeof(f));
       const float le[3] = {f[0] * f[3], f[1] * f[3], f[2] * f[3]};
       const bool emits = le[0] > 0 || le[1] > 0 || le[2] > 0;
       const bool can_eval = f[3] <= 0 && (f[0] > 0 || f[1] > 0 || f[2] > 0);
@@ -201,6 +239,81 @@ bool check_environment(const ResidentEnvironmentScene& scene, const sthip_enviro
     return refuse(STHIP_ERR_UNSUPPORTED, "the environment map is an 8-bit image (gImages[" + std::to_string(rec[3]) + "] is RGBA8_UNORM): upload it as RGBA32F");
   if (plan.replace_pixels && scene.image_in_material && scene.image_in_material[rec[3]])
     return refuse(STHIP_ERR_UNSUPPORTED, "gImages[" + std::to_string(rec[3]) + "] is also named by a material record: its texels decided the kernels of the scene (upload the scene again)");
+  return true;
+}
+
+bool check_images(const ResidentImages& scene, const sthip_image_update* entries, uint32_t n, uint32_t struct_size, int& code, std::string& message) {
+  auto bad = [&](const std::string& m) {
+    code = STHIP_ERR_INVALID_ARGUMENT;
+    message = "sthip_scene_set_images: " + m;
+    return false;
+  };
+  if (struct_size != sizeof(sthip_image_update)) return bad("struct_size is " + std::to_string(struct_size) + ", not sizeof(sthip_image_update) = " + std::to_string(sizeof(sthip_image_update)));
+  if (!scene.has_scene) return bad("no scene is resident (before sthip_scene_upload)");
+  if (n && !entries) return bad("entries is NULL");
+  for (uint32_t k = 0; k < n; k++) {
+    const sthip_image_update& e = entries[k];
+    const std::string at = "entries[" + std::to_string(k) + "]: ";
+    if (e.which > 1) return bad(at + "which is " + std::to_string(e.which) + " (0 = gImages, 1 = gImage1s)");
+    const uint32_t count = e.which ? scene.image1_count : scene.image_count;
+    const char* array = e.which ? "gImage1s" : "gImages";
+    if (e.index >= count) return bad(at + "index " + std::to_string(e.index) + " is not in " + array);
+    if (!e.pixels) return bad(at + "pixels is NULL");
+    const uint32_t w = e.which ? scene.images1[e.index].w : scene.images[e.index].w[0], h = e.which ? scene.images1[e.index].h : scene.images[e.index].h[0];
+    if (e.width != w || e.height != h)
+      return bad(at + "the extent " + std::to_string(e.width) + " x " + std::to_string(e.height) + " differs from the resident image's " + std::to_string(w) + " x " + std::to_string(h) + " (a change of extent is an upload)");
+    for (uint32_t j = 0; j < k; j++)
+      if (entries[j].which == e.which && entries[j].index == e.index) return bad(at + array + "[" + std::to_string(e.index) + "] is named twice in one call");
+    const bool rgba32f = !e.which && scene.images[e.index].format == STHIP_IMAGE_FORMAT_RGBA32F;
+    if (e.device_ptr && ((uintptr_t)e.pixels & (rgba32f ? 15u : 3u))) return bad(at + "the device pointer is not aligned to " + (rgba32f ? "16" : "4") + " bytes");
+  }
+  return true;
+}
+
+bool check_material_data(const ResidentMaterials& scene, uint32_t offset, const void* data, uint32_t bytes, std::vector<uint8_t>& edited, int& code, std::string& message) {
+  auto refuse = [&](int c, const std::string& m) {
+    code = c;
+    message = "sthip_scene_set_material_data: " + m;
+    return false;
+  };
+  auto bad = [&](const std::string& m) { return refuse(STHIP_ERR_INVALID_ARGUMENT, m); };
+  auto unsupported = [&](uint32_t i, const std::string& m) { return refuse(STHIP_ERR_UNSUPPORTED, "instance " + std::to_string(i) + ": " + m + " (upload the scene again)"); };
+  if (!scene.has_scene || !scene.materials) return bad("no scene is resident (before sthip_scene_upload)");
+  if (bytes && !data) return bad("data is NULL");
+  if ((offset & 3) || (bytes & 3)) return bad("offset and bytes must be multiples of 4");
+  if ((size_t)offset + bytes > scene.material_bytes) return bad("the range [" + std::to_string(offset) + ", " + std::to_string((size_t)offset + bytes) + ") ends past the " + std::to_string(scene.material_bytes) + " bytes of gMaterialData");
+  edited.assign(scene.materials, scene.materials + scene.material_bytes);
+  if (bytes) memcpy(edited.data() + offset, data, bytes);
+  auto emits = [](const uint8_t* record) {  // (analyse_materials: Le = base_color * emission of the untextured record)
+    float f[4];
+    memcpy(f, record, sizeof(f));
+    return f[0] * f[3] > 0 || f[1] * f[3] > 0 || f[2] * f[3] > 0;
+  };
+  for (uint32_t i = 0; i < scene.instance_count; i++) {
+    const uint32_t addr = scene.instances[i].address, type = scene.instances[i].type;
+    const size_t size = type == STHIP_INSTANCE_TYPE_VOLUME ? 40 : sizeof(sthip_MaterialRecord);
+    if ((size_t)addr + size <= offset || (size_t)offset + bytes <= addr) continue;  // (the record lies outside the edit)
+    if (type == STHIP_INSTANCE_TYPE_VOLUME) {
+      uint32_t vol[2], old[2];
+      memcpy(vol, edited.data() + addr + 32, 8);
+      memcpy(old, scene.materials + addr + 32, 8);
+      if (vol[0] >= scene.volume_count || (vol[1] != 0xFFFFFFFFu && vol[1] >= scene.volume_count)) return bad("a medium refers to a volume that is not in gVolumes");
+      if (vol[0] != old[0] || vol[1] != old[1]) return unsupported(i, "the volume indices of a medium change");
+      continue;
+    }
+    sthip_MaterialRecord rec, was;
+    memcpy(&rec, edited.data() + addr, sizeof(rec));
+    memcpy(&was, scene.materials + addr, sizeof(was));
+    for (int k = 0; k < 3; k++)
+      if (rec.values[k].image_index < STHIP_IMAGE_COUNT && rec.values[k].image_index >= scene.image_count) return bad("a material refers to an image that is not in gImages");
+    if (rec.bump_index < STHIP_IMAGE_COUNT && rec.bump_index >= scene.image_count) return bad("a bump map refers to an image that is not in gImages");
+    if (type == STHIP_INSTANCE_TYPE_TRIANGLES) {
+      if (rec.alpha_mask_index < STHIP_IMAGE_COUNT && rec.alpha_mask_index >= scene.image1_count) return bad("a material refers to an alpha mask that is not in gImage1s");
+      if (rec.alpha_mask_index != was.alpha_mask_index) return unsupported(i, "the alpha_mask_index of a triangle instance changes (the mask is in the tree)");
+    }
+    if ((type == STHIP_INSTANCE_TYPE_TRIANGLES || type == STHIP_INSTANCE_TYPE_SPHERE) && emits(edited.data() + addr) != emits(scene.materials + addr))
+      return unsupported(i, "its emission appears or disappears (the light list and the emitter bounds are the upload's)");
+  }
   return true;
 }
 

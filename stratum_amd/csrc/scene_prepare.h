@@ -20,6 +20,15 @@ namespace sthip {
 // image1_formats arrays are those of sthip_scene_upload_formats (NULL: all 0).
 bool check_scene(const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats, int& code, std::string& message);
 
+// The per-channel extremes of level 0 of one image of gImages (include/sthip.h, "image ranges"): lo / hi over the texels that
+// are not NaN; a channel in which a NaN was seen (bit c of nan_mask), or an image without texels, is unknown: -inf / +inf.
+// known = 0: nobody has scanned the image; the analysis treats every channel of it as unknown.
+struct ImageRange {
+  float lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
+  uint32_t nan_mask = 0;
+  uint32_t known = 0;
+};
+
 // What the materials of a checked scene say about the kernels it needs, and k_cull_terminal's per-instance table
 struct MaterialAnalysis {
   bool has_specular = false;  // some material can satisfy DisneyMaterial::is_specular (or a medium Medium::is_specular)
@@ -30,8 +39,48 @@ struct MaterialAnalysis {
   std::vector<uint8_t> instance_is_volume;  // per instance
   std::vector<uint8_t> inst_flags;          // per instance (at least one entry): INST_FLAG_*
   std::vector<uint8_t> image_in_material;   // per image of gImages: 1 = some instance's material record names it (its texels were scanned above)
+  std::vector<ImageRange> image_ranges;      // analyse_materials(s, formats) only: per image of gImages, what its scan found (known = 0: not scanned)
 };
 MaterialAnalysis analyse_materials(const sthip_scene_desc& s, const uint8_t* image_formats);
+
+// ---- the two halves of analyse_materials (sthip_scene_set_images / sthip_scene_set_material_data run them apart) ----
+// The scan on the host (ImageRange, above): `count` texels of RGBA32F, or of RGBA8_UNORM (rgba8; a byte decodes as (float)b / 255.0f)
+ImageRange scan_image_range(const void* pixels, size_t count, bool rgba8);
+// What the analysis reads of an instance: 8 bytes, kept by the context whatever "keep_scene" says
+struct MaterialInstance {
+  uint32_t address;  // InstanceData::material_address
+  uint32_t type;     // STHIP_INSTANCE_TYPE_*
+};
+// Which images of gImages the records name (MaterialAnalysis::image_in_material) and which of them the analysis reads the range
+// of (an image value whose constant has a positive component): the upload scans the latter on the host.
+void material_images(const MaterialInstance* instances, uint32_t instance_count, const uint8_t* materials, uint32_t image_count, std::vector<uint8_t>& named, std::vector<uint8_t>& range_read);
+// The rest of the analysis, with the ranges already known (`ranges`: image_count entries). analyse_materials(s, formats) is
+// material_images + scan_image_range of the images whose range is read + this.
+MaterialAnalysis analyse_materials(const MaterialInstance* instances, uint32_t instance_count, const uint8_t* materials, uint32_t image_count, const ImageRange* ranges);
+
+// ---- sthip_scene_set_images / sthip_scene_set_material_data: what of them needs no device ----
+struct ResidentImages {
+  bool has_scene = false;
+  const DeviceImage* images = nullptr;  // the tables as uploaded
+  uint32_t image_count = 0;
+  const DeviceImage1* images1 = nullptr;
+  uint32_t image1_count = 0;
+};
+// Every refusal of sthip_scene_set_images (sthip.h), from the arguments and the host-side tables alone. false: `code` and
+// `message` say why and the caller changes nothing.
+bool check_images(const ResidentImages& scene, const sthip_image_update* entries, uint32_t n, uint32_t struct_size, int& code, std::string& message);
+
+struct ResidentMaterials {
+  bool has_scene = false;
+  const uint8_t* materials = nullptr;  // gMaterialData as resident
+  size_t material_bytes = 0;
+  const MaterialInstance* instances = nullptr;
+  uint32_t instance_count = 0;
+  uint32_t image_count = 0, image1_count = 0, volume_count = 0;
+};
+// Every refusal of sthip_scene_set_material_data. true: `edited` is gMaterialData as it is after the edit (every instance's
+// record in it passes the material checks of check_scene, and nothing the trees or the light tables were built from differs).
+bool check_material_data(const ResidentMaterials& scene, uint32_t offset, const void* data, uint32_t bytes, std::vector<uint8_t>& edited, int& code, std::string& message);
 
 // EmitterBounds from the exact box of an emitter's vertices: widened by 2^-15 of its coordinates' magnitude, as the packed nodes
 // of the tree are, and the sphere that sizes the per-ray padding. false: not finite (the table cannot be used).

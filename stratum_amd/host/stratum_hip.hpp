@@ -53,6 +53,10 @@
 // ... and one that cannot replace the environment of a resident scene lacks these: the host builds the tables and uploads
 #pragma weak sthip_scene_set_environment
 #pragma weak sthip_scene_read_distributions
+// ... and one that cannot edit the materials of a resident scene lacks these: a changed colour or texture is an upload
+#pragma weak sthip_scene_set_images
+#pragma weak sthip_scene_set_material_data
+#pragma weak sthip_scene_read_image_range
 #pragma weak sthip_accumulate
 #pragma weak sthip_denoise_filter
 #include "../../include/sthip_detmath.h"  // det_f16tof32: export_hdr of a half frame
@@ -394,6 +398,10 @@ struct Image {
   std::vector<uint8_t> bytes;  // width * height * 4, row 0 first: a byte b is the texel (float)b / 255.0f (sthip.h)
   bool is_8bit() const { return !bytes.empty(); }
   float channel(size_t i) const { return is_8bit() ? (float)bytes[i] / 255.0f : pixels[i]; }
+  // counts mark_dirty(): what tells the texels of one Image object apart. A host that repaints the texels in place (same extent,
+  // same format) says so, and BDPT::update sends them to the resident scene (sthip_scene_set_images) instead of uploading.
+  uint32_t serial = 0;
+  void mark_dirty() { serial++; }
 };
 // a one-channel texture (Texture2D<float>): what Material::alpha_mask holds (R8Unorm coverage upstream, Scene.cpp:182), as floats
 // or, when `bytes` is filled instead of `pixels`, as R8_UNORM
@@ -402,6 +410,8 @@ struct Image1 {
   std::vector<float> pixels;   // width * height, row 0 first
   std::vector<uint8_t> bytes;  // width * height, row 0 first
   bool is_8bit() const { return !bytes.empty(); }
+  uint32_t serial = 0;  // as Image::serial
+  void mark_dirty() { serial++; }
 };
 // MaterialResources, image_value.h:34-66: images get their gImages / gImage1s index the first time a material stores them
 struct MaterialResources {
@@ -805,6 +815,8 @@ class Scene {
     // mDistributionData holds zeros where its tables go (the device builds them after the upload: BDPT::update)
     const Image* mEnvironmentImage = nullptr;
     uint32_t mEnvironmentImageSerial = 0;
+    // Image::serial / Image1::serial of the images as they were packed, in gImages / gImage1s order
+    std::vector<uint32_t> mImageSerials, mImage1Serials;
     bool mEnvironmentTablesOnDevice = false;
     uint32_t mMaterialCount = 0;
     uint32_t mEmissivePrimitiveCount = 0;
@@ -1098,6 +1110,8 @@ class Scene {
     };
     for (const Image* im : sd->mResources.image4s) describe(im->pixels, im->bytes, im->width, im->height, sd->mImageDescs, sd->mImageFormats);
     for (const Image1* im : sd->mResources.image1s) describe(im->pixels, im->bytes, im->width, im->height, sd->mImage1Descs, sd->mImage1Formats);
+    for (const Image* im : sd->mResources.image4s) sd->mImageSerials.push_back(im->serial);
+    for (const Image1* im : sd->mResources.image1s) sd->mImage1Serials.push_back(im->serial);
     sd->mDistributionData.resize(sd->mResources.distribution_data_size);
     for (const auto& e : sd->mResources.distribution_data_map) std::copy(e.first->begin(), e.first->end(), sd->mDistributionData.begin() + e.second);  // Scene.cpp:679-680
     mSceneData = sd;
@@ -1382,6 +1396,9 @@ class BDPT {
   bool last_update_was_transforms_only() const { return mLastUpdateWasTransformsOnly; }
   bool last_update_was_vertices_only() const { return mLastUpdateWasVerticesOnly; }  // (no transform changed with them)
   bool last_update_was_environment_only() const { return mLastUpdateWasEnvironmentOnly; }
+  bool last_update_was_materials_only() const { return mLastUpdateWasMaterialsOnly; }
+  uint32_t material_data_calls() const { return mMaterialDataCalls; }       // sthip_scene_set_material_data calls of update() so far
+  uint32_t image_calls() const { return mImageCalls; }                      // sthip_scene_set_images calls of update() so far
   uint32_t upload_calls() const { return mUploadCalls; }                    // sthip_scene_upload(_formats) calls of update() so far
   uint32_t environment_calls() const { return mEnvironmentCalls; }          // sthip_scene_set_environment calls of update() so far
   // tone-map state the reference keeps on its pipeline objects (BDPT.cpp:44-54,190-193,304-309)
@@ -1425,6 +1442,7 @@ class BDPT {
     bool updated = false;
     mLastUpdateWasVerticesOnly = false;
     mLastUpdateWasEnvironmentOnly = false;
+    mLastUpdateWasMaterialsOnly = false;
     const Scene::SceneData& sd = *scene->data();
     const bool rigs = !sd.mRigs.empty();  // (packed only with a library that has the calls: Scene::pose_on_device())
     if (scene->environment_on_device() && mBoundData && environment_only_changed(*mBoundData, sd)) {
@@ -1433,6 +1451,20 @@ class BDPT {
       const int rc = set_environment(*mBoundData, sd);
       if (rc == STHIP_OK) {
         mLastUpdateWasEnvironmentOnly = true;
+        mLastUpdateWasTransformsOnly = false;
+        mBound = scene->data().get();
+        mBoundData = scene->data();
+        return;
+      }
+    }
+    if (mMaterialsOnDevice && sthip_scene_set_images && sthip_scene_set_material_data && mBoundData && materials_only_changed(*mBoundData, sd)) {
+      // Only bytes of gMaterialData and / or the texels of images at the same extents changed (an inspector's colour, a
+      // repainted texture): the differing byte range and the differing images go to the resident scene, which makes the mip
+      // chains, the image ranges and the material analysis again. An edit the library refuses as unsupported (a light that goes
+      // out, a mask that a triangle instance gains): upload.
+      const int rc = set_materials(*mBoundData, sd);
+      if (rc == STHIP_OK) {
+        mLastUpdateWasMaterialsOnly = true;
         mLastUpdateWasTransformsOnly = false;
         mBound = scene->data().get();
         mBoundData = scene->data();
@@ -1809,7 +1841,9 @@ class BDPT {
   sthip_ctx* mCtx = nullptr;
   const void* mBound = nullptr;
   std::shared_ptr<Scene::SceneData> mBoundData;
-  bool mLastUpdateWasTransformsOnly = false, mLastUpdateWasVerticesOnly = false, mLastUpdateWasEnvironmentOnly = false;
+  bool mLastUpdateWasTransformsOnly = false, mLastUpdateWasVerticesOnly = false, mLastUpdateWasEnvironmentOnly = false, mLastUpdateWasMaterialsOnly = false;
+  // false: a changed material is uploaded like any other change. The multi-device driver clears it, as mRefitDeformedMeshes.
+  bool mMaterialsOnDevice = true;
   // false: a deformed mesh is uploaded like any other change. The multi-device driver clears it: its ranks must all walk the
   // same tree form, and it sends them uploads or transforms-only updates, nothing else (stratum_hip_multi.hpp).
   bool mRefitDeformedMeshes = true;
@@ -1818,7 +1852,56 @@ class BDPT {
     return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
   }
   bool mRigsResident = false;  // the rigs of mBoundData are on the device (sthip_scene_set_rigs after the last upload)
-  uint32_t mUploadCalls = 0, mEnvironmentCalls = 0;
+  uint32_t mUploadCalls = 0, mEnvironmentCalls = 0, mMaterialDataCalls = 0, mImageCalls = 0;
+  // Everything of `b` is what `a` is except bytes of gMaterialData outside the environment record and / or the texels of
+  // images (the same objects at the same extents and formats, another serial). An image that is also the environment's keeps
+  // the upload: its tables would have to follow.
+  static bool materials_only_changed(const Scene::SceneData& a, const Scene::SceneData& b) {
+    if (a.mMaterialData.size() != b.mMaterialData.size() || a.mImageSerials.size() != b.mImageSerials.size() || a.mImage1Serials.size() != b.mImage1Serials.size()) return false;
+    if (a.mResources.image4s != b.mResources.image4s || a.mResources.image1s != b.mResources.image1s || a.mResources.volumes != b.mResources.volumes) return false;  // the same objects
+    bool changed = !same_bytes(a.mMaterialData, b.mMaterialData);
+    for (size_t i = 0; i < b.mImageSerials.size(); i++) {
+      if (a.mImageDescs[i].width != b.mImageDescs[i].width || a.mImageDescs[i].height != b.mImageDescs[i].height || a.mImageFormats[i] != b.mImageFormats[i]) return false;
+      if (a.mImageSerials[i] == b.mImageSerials[i]) continue;
+      if (b.mResources.image4s[i] == b.mEnvironmentImage) return false;
+      changed = true;
+    }
+    for (size_t i = 0; i < b.mImage1Serials.size(); i++) {
+      if (a.mImage1Descs[i].width != b.mImage1Descs[i].width || a.mImage1Descs[i].height != b.mImage1Descs[i].height || a.mImage1Formats[i] != b.mImage1Formats[i]) return false;
+      changed = changed || a.mImage1Serials[i] != b.mImage1Serials[i];
+    }
+    if (!changed) return false;
+    if (a.mEnvironmentMaterialAddress != b.mEnvironmentMaterialAddress || a.mEnvironmentImage != b.mEnvironmentImage || a.mEnvironmentImageSerial != b.mEnvironmentImageSerial ||
+        a.mEnvironmentTablesOnDevice != b.mEnvironmentTablesOnDevice)
+      return false;
+    return same_rigs(a, b) && same_poses(a, b) && same_bytes(a.mVertices, b.mVertices) && same_bytes(a.mIndices, b.mIndices) && same_bytes(a.mInstances, b.mInstances) &&
+           same_bytes(a.mLightInstanceMap, b.mLightInstanceMap) && same_bytes(a.mInstanceTransforms, b.mInstanceTransforms) && same_bytes(a.mInstanceInverseTransforms, b.mInstanceInverseTransforms) &&
+           same_bytes(a.mInstanceMotionTransforms, b.mInstanceMotionTransforms) && same_bytes(a.mDistributionData, b.mDistributionData);
+  }
+  // The differing byte range, then the differing images in one call. STHIP_ERR_UNSUPPORTED from the bytes: nothing has changed
+  // and the caller uploads.
+  int set_materials(const Scene::SceneData& a, const Scene::SceneData& b) {
+    size_t lo = 0, hi = b.mMaterialData.size();
+    while (lo < hi && a.mMaterialData[lo] == b.mMaterialData[lo]) lo++;
+    while (hi > lo && a.mMaterialData[hi - 1] == b.mMaterialData[hi - 1]) hi--;
+    if (hi > lo) {
+      mMaterialDataCalls++;
+      const int rc = sthip_scene_set_material_data(mCtx, (uint32_t)(lo * 4), &b.mMaterialData[lo], (uint32_t)((hi - lo) * 4), nullptr);
+      if (rc == STHIP_ERR_UNSUPPORTED) return rc;
+      if (rc != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_set_material_data: ") + sthip_last_error(mCtx));
+    }
+    std::vector<sthip_image_update> entries;
+    for (size_t i = 0; i < b.mImageSerials.size(); i++)
+      if (a.mImageSerials[i] != b.mImageSerials[i]) entries.push_back(sthip_image_update{0u, (uint32_t)i, b.mImageDescs[i].pixels, b.mImageDescs[i].width, b.mImageDescs[i].height, 0u, 0u});
+    for (size_t i = 0; i < b.mImage1Serials.size(); i++)
+      if (a.mImage1Serials[i] != b.mImage1Serials[i]) entries.push_back(sthip_image_update{1u, (uint32_t)i, b.mImage1Descs[i].pixels, b.mImage1Descs[i].width, b.mImage1Descs[i].height, 0u, 0u});
+    if (!entries.empty()) {
+      mImageCalls++;
+      if (sthip_scene_set_images(mCtx, entries.data(), (uint32_t)entries.size(), (uint32_t)sizeof(sthip_image_update), nullptr) != STHIP_OK)
+        throw std::runtime_error(std::string("sthip_scene_set_images: ") + sthip_last_error(mCtx));
+    }
+    return STHIP_OK;
+  }
   // Everything of `b` is what `a` is except the value of the environment record, the texels of its image (the same object,
   // another serial) and the tables that follow from them: the comparison same_poses is for the rigs.
   static bool environment_only_changed(const Scene::SceneData& a, const Scene::SceneData& b) {
@@ -1900,6 +1983,7 @@ class BDPT {
         !same_bytes(a.mLightInstanceMap, b.mLightInstanceMap) || !same_bytes(a.mDistributionData, b.mDistributionData))
       return false;
     if (a.mResources.image4s != b.mResources.image4s || a.mResources.image1s != b.mResources.image1s || a.mResources.volumes != b.mResources.volumes) return false;  // the same objects
+    if (a.mImageSerials != b.mImageSerials || a.mImage1Serials != b.mImage1Serials) return false;  // ... with the same texels (Image::mark_dirty())
     // (an environment whose tables the device builds packs the same bytes before and after Environment::mark_image_dirty():
     // the image's serial is what tells the texels apart, and a partial update must not pass over a changed sky)
     return a.mEnvironmentMaterialAddress == b.mEnvironmentMaterialAddress && a.mEnvironmentImage == b.mEnvironmentImage && a.mEnvironmentImageSerial == b.mEnvironmentImageSerial &&

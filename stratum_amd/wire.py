@@ -438,6 +438,33 @@ ENVIRONMENT_DESC_BYTES = 40  # sizeof(sthip_environment_desc), include/sthip.h
 assert C.sizeof(EnvironmentDesc) == ENVIRONMENT_DESC_BYTES
 
 
+class ImageUpdate(C.Structure):  # sthip_image_update
+    _fields_ = [
+        ("which", C.c_uint32),
+        ("index", C.c_uint32),
+        ("pixels", C.c_void_p),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("device_ptr", C.c_uint32),
+        ("pad", C.c_uint32),
+    ]
+
+
+class ImagesInfo(C.Structure):  # sthip_images_info
+    _fields_ = [
+        ("device_ms", C.c_float),
+        ("total_ms", C.c_float),
+        ("has_specular_before", C.c_uint32),
+        ("has_specular_after", C.c_uint32),
+        ("images_scanned", C.c_uint32),
+        ("pad", C.c_uint32),
+    ]
+
+
+IMAGE_UPDATE_BYTES = 32  # sizeof(sthip_image_update), include/sthip.h
+assert C.sizeof(ImageUpdate) == IMAGE_UPDATE_BYTES and C.sizeof(ImagesInfo) == 24
+
+
 class ConvertMaterialDesc(C.Structure):
     _fields_ = [
         ("kind", C.c_uint32),
