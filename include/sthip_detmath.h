@@ -103,8 +103,19 @@ STHIP_HD float det_tanf(float x) {
   return s / c;
 }
 
-/* e^x for |x| < 87 (Cephes expf) */
+/* e^x for every x (Cephes expf).
+ *   x in [-87.3, 88.0]: the published algorithm, < 1 ulp; the clamp and the select below move no bit there.
+ *   below:  n = -126 still scales by 2^-126, so down to x ~ -87.68 the result is the (denormal) product, rounded once;
+ *           from there on, and for every x <= -88 and for -inf, the result is exactly +0 (flushed, not scaled in two
+ *           steps: e^x is below 2^-126 there and no caller tells a denormal from 0).
+ *   above:  finite and < 1 ulp up to x ~ 88.37 (n = 127); +inf from there on, although e^x stays below FLT_MAX up to
+ *           88.72; +inf for +inf.
+ *   NaN:    x itself.
+ * The result is never negative. The clamp keeps n in [-127, 128], i.e. the biased exponent written below in [0, 255]:
+ * unclamped, (n + 127) << 23 ran into the sign bit below -87.7 and past the exponent field above 88.7. */
 STHIP_HD float det_expf(float x) {
+  const float x_in = x;
+  x = fminf(fmaxf(x, -88.0f), 89.0f);
   const float n = floorf(1.44269504088896341f * x + 0.5f);
   x = x - n * 0.693359375f;
   x = x - n * -2.12194440e-4f;
@@ -117,10 +128,25 @@ STHIP_HD float det_expf(float x) {
   p = p * x + 5.0000001201e-1f;
   p = p * z + x + 1.0f;
   const int ni = (int)n;
-  return p * det_u2f((uint32_t)(ni + 127) << 23);
+  const float r = p * det_u2f((uint32_t)(ni + 127) << 23);
+  return x_in != x_in ? x_in : r;
 }
 
-/* pow(a, b) for a > 0 */
+/* 2^x for every x: the integer part of x goes into the exponent exactly, the fraction f in [-0.5, 0.5] through
+ * det_expf(f ln 2), so 2^k is exact for an integer k and the relative error does not grow with |x| (det_expf(x ln 2)
+ * carries the rounding of the product x ln 2, 3e-6 at |x| = 126). The scale is applied in two steps of at most 2^80:
+ * denormal results are the rounded product (one rounding), 0 below 2^-150, +inf from 2^128 on; NaN gives x itself. */
+STHIP_HD float det_exp2f(float x) {
+  const float xc = fminf(fmaxf(x, -160.0f), 160.0f);
+  const float k = floorf(xc + 0.5f);
+  const float m = det_expf((xc - k) * 0.693147180559945f);
+  const int ki = (int)k, k1 = ki / 2, k2 = ki - k1;
+  const float r = m * det_u2f((uint32_t)(k1 + 127) << 23) * det_u2f((uint32_t)(k2 + 127) << 23);
+  return x != x ? x : r;
+}
+
+/* pow(a, b) for a > 0, and for a == 0 with b >= 1: det_logf(0) is about -88.03 and det_expf flushes from there on, so that
+ * is +0. A result below 2^-126 may be +0; one above FLT_MAX is +inf. */
 STHIP_HD float det_powf(float a, float b) { return det_expf(b * det_logf(a)); }
 
 /* atan(x), Cephes atanf: range reduction at tan(pi/8), tan(3pi/8) */

@@ -239,6 +239,10 @@ def log(x):
     return _map("orc_log", [np.ascontiguousarray(x, np.float32)], (), np.float32)
 
 
+def exp(x):
+    return _map("orc_exp", [np.ascontiguousarray(x, np.float32)], (), np.float32)
+
+
 def atan2(y, x):
     return _map("orc_atan2", [np.ascontiguousarray(y, np.float32), np.ascontiguousarray(x, np.float32)], (), np.float32)
 

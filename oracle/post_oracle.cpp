@@ -197,7 +197,7 @@ void orc_tonemap_state(const float* input, const float* albedo, float* output, u
       exposure_state[5] = m1;
     }
   }
-  const float gain = det_expf(exposure * 0.693147180559945f);
+  const float gain = det_exp2f(exposure);
   for (size_t i = 0; i < n; i++) {  // main
     float r[3] = {input[4 * i], input[4 * i + 1], input[4 * i + 2]};
     if (modulate)

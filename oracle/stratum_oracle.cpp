@@ -4390,6 +4390,9 @@ void orc_acos(const float* x, float* out, uint32_t n) {
 void orc_asin(const float* x, float* out, uint32_t n) {
   for (uint32_t i = 0; i < n; i++) out[i] = det_asinf(x[i]);
 }
+void orc_exp(const float* x, float* out, uint32_t n) {
+  for (uint32_t i = 0; i < n; i++) out[i] = det_expf(x[i]);
+}
 void orc_pow(const float* a, const float* b, float* out, uint32_t n) {
   for (uint32_t i = 0; i < n; i++) out[i] = det_powf(a[i], b[i]);
 }

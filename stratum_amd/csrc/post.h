@@ -3,7 +3,7 @@
 //   tonemap  : src/Shaders/kernels/tonemap.hlsl (reduce_max :106-153, main :155-226), modes of tonemap.h:8-21
 //   compare  : src/Shaders/kernels/image_compare.hlsl:13-46 (what ImageComparer shows, ImageComparer.cpp:61-90)
 // Arithmetic follows the arithmetic contract (include/sthip_detmath.h): pow() is det_powf, 2^exposure is
-// det_expf(exposure * ln 2). Not restated: the exposure smoothing over frames (gExposureAlpha with gPrevMax,
+// det_exp2f(exposure) (exact for an integer exposure, total over all floats). Not restated: the exposure smoothing over frames (gExposureAlpha with gPrevMax,
 // tonemap.hlsl:170-180) — a render call here has no previous frame.
 #pragma once
 
@@ -142,7 +142,7 @@ __global__ void k_tonemap(const C* input, const C* albedo, C* output, uint32_t n
     state_out[4] = m0;
     state_out[5] = m1;
   }
-  const float scale = det_expf(exposure * 0.693147180559945f);  // pow(2, gExposure)
+  const float scale = det_exp2f(exposure);  // pow(2, gExposure)
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     f3 radiance = xyz(load_px(input, i));
     if (modulate) radiance = radiance * (F3s(1e-2f) + xyz(load_px(albedo, i)));

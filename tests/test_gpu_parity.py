@@ -1388,6 +1388,27 @@ def test_media(kwargs, flags, args):
     assert in_fog.mean() > 0.01  # first vertices inside the medium (few when the majorant is high: the first null collision ends a walk upstream)
 
 
+@pytest.mark.parametrize("density", [(300.0, 1.0, 1.0), (1.0, 300.0, 40.0), (2000.0, 2000.0, 2000.0)])
+@pytest.mark.parametrize(
+    "flags,args",
+    [
+        ([], {}),
+        (["~defershadowrays"], {}),
+        (["connecttolightpaths", "lightvertexcache"], {"maxDiffuseVertices": 3, "lightPathCount": 6000}),
+        (["neereservoirs", "neereservoirreuse"], {"maxDiffuseVertices": 3, "reservoirM": 2, "reservoirSpatialM": 3, "hashGridBucketCount": 20000}),
+    ],
+)
+def test_media_dense_and_chromatic(density, flags, args):
+    """Delta tracking draws a distance for one colour channel and evaluates exp(-majorant t) for all three: with one channel
+    300 times denser than another (or all of them very dense) the argument lies far below the domain the arithmetic
+    contract's exp once had, where it returned negative and infinite values on both sides alike. Every output equals the
+    oracle's, and no radiance is negative or infinite (tests/test_detmath_edges.py checks the oracle's exp itself)."""
+    sc, cam = scenes.cornell_box(fog=_fog(), density=density)
+    got = _compare_frame(sc, cam, flags, w=64, h=48, seeds=4, args=args)
+    rad = got["radiance"][..., :3]
+    assert np.isfinite(rad).all() and (rad >= 0).all(), float(np.nanmin(rad))
+
+
 def test_media_camera_inside_and_moved_volume(renderer):
     from stratum_amd.scene import translate
 
@@ -2015,6 +2036,7 @@ def test_debug_modes_of_the_environment():
     """eEnvironmentSampleTest / eEnvironmentSamplePDF (bdpt.hlsl:190-205): nothing is traced; eight environment samples drawn
     from the pixel's stream as spots around the view direction (added to the image), or the pdf of the view direction."""
     from stratum_amd import wire as W
+    from test_detmath_edges import check_environment_sample_test_image
 
     start = np.random.RandomState(7).rand(96, 144, 4).astype(np.float32)
     for image in (True, False):
@@ -2024,6 +2046,10 @@ def test_debug_modes_of_the_environment():
                 got = _debug_case(sc, cam, mode, flags=flags, start=start)
                 assert got["ray_count"][0] == 0 and not got["radiance"][..., :3].any()
                 assert np.array_equal(got["debug"][..., 3], start[..., 3]) and not np.array_equal(got["debug"][..., :3], start[..., :3])
+                if mode == W.DEBUG_ENVIRONMENT_SAMPLE_TEST:
+                    # the spots are 1024 pow(cos, 1024): in [0, 1024] each, the same in the three channels, small (the image
+                    # equals the oracle's bit for bit, so the same holds for that one; its own test needs no GPU)
+                    check_environment_sample_test_image(got["debug"], start)
 
 
 def test_bounded_wide8_walk_with_recycled_device_memory():

@@ -335,14 +335,18 @@ def test_pcg4d_in_python_integers():
 # ---------------------------------------------------------------------------------------------
 # one delta-tracking segment through a NanoVDB medium
 # ---------------------------------------------------------------------------------------------
-def test_delta_tracking_segment_against_a_float64_statement():
+def _delta_tracking_against_float64(density_scale, albedo_scale, unit, t_max_fractions, atol, atol_crossed, scatter_modes=(True, False), n=3000):
     """Medium::delta_track (materials/medium.hlsli:74-127), from the formulas, in float64 with Python-integer random numbers:
     majorant = density_scale * the grid's root maximum; one colour channel drawn with rng % 3; a free-flight distance
     t = unit * -log(1 - r0) / majorant[channel]; if it ends inside the segment, the local density decides between a real
     collision (r1 < sigma_t / majorant of that channel: beta *= tr * sigma_s, the position comes back in world space) and a
     null collision, which ENDS the walk upstream (beta *= tr * (majorant - sigma_t), tr = exp(-majorant t) / max(majorant));
     otherwise the segment is crossed (all three throughputs *= exp(-majorant t_max)). The grid itself (values, root maximum,
-    the index / world maps) is read by the NanoVDB reader that tests/test_oracle.py pins against the reference's own PNanoVDB.h."""
+    the index / world maps) is read by the NanoVDB reader that tests/test_oracle.py pins against the reference's own PNanoVDB.h.
+
+    Every value the walk returns must be finite and >= 0 (all n samples, the skipped ones included). Returns, per entry of
+    `scatter_modes`, how often each branch was checked and the share of samples skipped because two precisions may decide
+    them differently."""
     import os
 
     M = 1 << 32
@@ -367,7 +371,7 @@ def test_delta_tracking_segment_against_a_float64_statement():
     to_float = lambda u: float(np.array([0x3F800000 | (u >> 9)], np.uint32).view(np.float32)[0]) - 1.0  # rng_next_float, rng.hlsli:35-37
 
     grid = np.load(os.path.join(os.path.dirname(__file__), "golden", "fog_sphere.npz"))["grid"]
-    density_scale, albedo_scale, unit = np.array([3.0, 2.0, 1.5]), np.array([0.9, 0.6, 0.3]), 0.7
+    density_scale, albedo_scale = np.asarray(density_scale, np.float64), np.asarray(albedo_scale, np.float64)
     sc0, _ = scenes.furnace_box(albedo=0.5, emission=1.0)
     b = sc0.builder
     b.add_medium(b.add_volume(grid), density_scale=tuple(density_scale), albedo_scale=tuple(albedo_scale), anisotropy=0.3, attenuation_unit=unit)
@@ -377,7 +381,6 @@ def test_delta_tracking_segment_against_a_float64_statement():
     bmin, bmax, root_max, _, _ = orc.nvdb_probe(grid, np.zeros((1, 3), np.int32), np.zeros((1, 3), np.float32))
     assert root_max > 0
 
-    n = 3000
     rs = np.random.RandomState(11)
     keys = rs.randint(0, 1 << 31, (n, 4)).astype(np.uint32)
     # rays through the grid's world-space box (the sphere of fog sits in its middle), some segments short, some long
@@ -390,16 +393,20 @@ def test_delta_tracking_segment_against_a_float64_statement():
     origin = rs.uniform(wlo, whi, (n, 3)).astype(np.float32)
     direction = rs.normal(size=(n, 3))
     direction = (direction / np.linalg.norm(direction, axis=1, keepdims=True)).astype(np.float32)
-    t_max = rs.choice([0.02, 0.1, 0.5, 3.0], n).astype(np.float32) * float(np.linalg.norm(whi - wlo))
-    for can_scatter in (True, False):
+    t_max = rs.choice(t_max_fractions, n).astype(np.float32) * float(np.linalg.norm(whi - wlo))
+    results = []
+    for can_scatter in scatter_modes:
         got = o.delta_track(address, keys, origin, direction, t_max, beta=1.0, can_scatter=can_scatter)
+        for name in ("beta", "dir_pdf", "nee_pdf"):
+            bad = ~(np.isfinite(got[name]) & (got[name] >= 0))
+            assert not bad.any(), (name, int(bad.any(axis=1).sum()), float(np.nanmin(got[name])))
         _, _, _, _, maps = orc.nvdb_probe(grid, np.zeros((1, 3), np.int32), np.stack([origin, direction], 1).reshape(-1, 3))
         # (maps[m] = world_to_index of point m, world_to_index_dir of point m, ...: rows 2 k and 2 k + 1 are sample k's origin and direction)
         o_idx, d_idx = maps[0::2, 0].astype(np.float64), maps[1::2, 1].astype(np.float64)
         majorant = density_scale * float(root_max)
         checked = {"real": 0, "null": 0, "crossed": 0}
         lookups, where = [], []
-        plan = []
+        plan, skipped = [], 0
         for k in range(n):
             u = draws(keys[k], 3)
             c = u[0] % 3
@@ -408,12 +415,14 @@ def test_delta_tracking_segment_against_a_float64_statement():
             tm = float(t_max[k])
             if abs(t - tm) < 1e-4 * tm:
                 plan.append(None)  # the two precisions may disagree about which side of the segment's end t falls
+                skipped += 1
                 continue
             plan.append((c, r1, t, tm))
             if t < tm:
                 pos = o_idx[k] + d_idx[k] * t
                 if np.abs(pos - np.round(pos)).min() < 1e-3:
                     plan[-1] = None  # too close to a voxel face for the two precisions to pick the same voxel
+                    skipped += 1
                     continue
                 lookups.append(np.floor(pos).astype(np.int32))
                 where.append(k)
@@ -430,25 +439,56 @@ def test_delta_tracking_segment_against_a_float64_statement():
                 real_prob = sigma_t / majorant
                 tr = np.exp(-majorant * t) / majorant.max()
                 if abs(r1 - real_prob[c]) < 1e-5:
+                    skipped += 1
                     continue
                 if can_scatter and r1 < real_prob[c]:
                     assert got["scattered"][k]
-                    assert np.allclose(got["beta"][k], tr * sigma_s, rtol=2e-5, atol=1e-9)
-                    assert np.allclose(got["dir_pdf"][k], tr * majorant * real_prob, rtol=2e-5, atol=1e-9)
+                    assert np.allclose(got["beta"][k], tr * sigma_s, rtol=2e-5, atol=atol)
+                    assert np.allclose(got["dir_pdf"][k], tr * majorant * real_prob, rtol=2e-5, atol=atol)
                     assert np.allclose(got["nee_pdf"][k], 1.0)
                     # the position comes back in world space; the map is affine, so that is the point t along the world-space ray
                     assert np.allclose(got["position"][k], origin[k].astype(np.float64) + direction[k].astype(np.float64) * t, rtol=1e-4, atol=1e-4 * float(np.linalg.norm(whi - wlo)))
                     checked["real"] += 1
                 else:
                     assert not got["scattered"][k]
-                    assert np.allclose(got["beta"][k], tr * (majorant - sigma_t), rtol=2e-5, atol=1e-9)
-                    assert np.allclose(got["dir_pdf"][k], tr * majorant * (1 - real_prob), rtol=2e-5, atol=1e-9)
-                    assert np.allclose(got["nee_pdf"][k], tr * majorant, rtol=2e-5, atol=1e-9)
+                    assert np.allclose(got["beta"][k], tr * (majorant - sigma_t), rtol=2e-5, atol=atol)
+                    assert np.allclose(got["dir_pdf"][k], tr * majorant * (1 - real_prob), rtol=2e-5, atol=atol)
+                    assert np.allclose(got["nee_pdf"][k], tr * majorant, rtol=2e-5, atol=atol)
                     checked["null"] += 1
             else:
                 tr = np.exp(-majorant * tm)
                 assert not got["scattered"][k]
                 for name in ("beta", "dir_pdf", "nee_pdf"):
-                    assert np.allclose(got[name][k], tr, rtol=2e-5, atol=1e-12)
+                    assert np.allclose(got[name][k], tr, rtol=2e-5, atol=atol_crossed)
                 checked["crossed"] += 1
+        results.append((can_scatter, checked, skipped / n))
+    return results
+
+
+def test_delta_tracking_segment_against_a_float64_statement():
+    for can_scatter, checked, _ in _delta_tracking_against_float64((3.0, 2.0, 1.5), (0.9, 0.6, 0.3), 0.7, [0.02, 0.1, 0.5, 3.0], atol=1e-9, atol_crossed=1e-12):
         assert checked["null"] > 100 and checked["crossed"] > 100 and (checked["real"] > 100) == can_scatter, checked
+
+
+def test_delta_tracking_segment_through_dense_and_chromatic_media():
+    """The same statement where exp leaves its domain: the distance is drawn for ONE channel and exp(-majorant_k t) is
+    evaluated for all three, so with one majorant 300 times another the argument goes far below -87 (e^x below the smallest
+    normal float: the throughput is 0 or a denormal, never negative or infinite). Each value equals the float64 statement
+    to the relative tolerance of the test above plus what may be lost below the normal range, 2^-126 times the largest
+    majorant (beta = tr (majorant - sigma_t) and dir_pdf, nee_pdf = tr majorant ... with tr <= e^x / max(majorant))."""
+    import os
+
+    grid = np.load(os.path.join(os.path.dirname(__file__), "golden", "fog_sphere.npz"))["grid"]
+    _, _, root_max, _, _ = orc.nvdb_probe(grid, np.zeros((1, 3), np.int32), np.zeros((1, 3), np.float32))
+    total = {"real": 0, "null": 0, "crossed": 0}
+    for density_scale in ((300.0, 1.0, 1.0), (1.0, 300.0, 40.0), (2000.0, 2000.0, 2000.0)):
+        for unit in (1.0, 0.05):
+            atol = 2.0**-126 * max(density_scale) * float(root_max)
+            # (segments down to 1e-4 of the box's diagonal, so that dense media cross some: 295 at a majorant of 2000 with a unit
+            # of 1, still none with a unit of 0.05; the thinner cases supply the crossed branch by the hundred)
+            for _, checked, skipped in _delta_tracking_against_float64(density_scale, (0.9, 0.6, 0.3), unit, [1e-4, 1e-3, 0.02, 0.1, 0.5, 3.0], atol=atol, atol_crossed=atol, scatter_modes=(True,)):
+                print(density_scale, unit, checked, "skipped %.2f %%" % (100 * skipped))
+                assert skipped <= 0.03, (density_scale, unit, skipped)
+                for k in total:
+                    total[k] += checked[k]
+    assert min(total.values()) >= 100, total

@@ -262,6 +262,63 @@ def test_gpu_tonemap_equals_oracle(gpu_ctx, modulate, gamma, exposure):
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), "%s: %d pixels differ" % (name, (got.view(np.uint32) != want.view(np.uint32)).any(-1).sum())
 
 
+def _same_bits_or_both_nan(got, want):
+    g, w = got.view(np.uint32), want.view(np.uint32)
+    return ((g == w) | (np.isnan(got) & np.isnan(want))).all()
+
+
+@pytest.mark.gpu
+def test_gpu_tonemap_gain_is_the_hosts_over_the_whole_exposure_range(gpu_ctx):
+    """The device's evaluation of the arithmetic contract's 2^x (include/sthip_detmath.h: det_exp2f, det_expf inside it)
+    against the host's, directly: Raw without gamma correction writes input * 2^exposure. The exposures run from where the
+    gain is 0 through denormal gains and the whole normal range to +inf (tests/test_detmath_edges.py checks the host's values)."""
+    from test_detmath_edges import EXPOSURES
+
+    img = np.ones((4, 4, 4), np.float32)
+    img[..., :3] = np.array([1, 3, 0.5, 1.25, 0.75, 2, 1e-3, 1e3, 0.1, 7, 1.5, 0.999, 1e-6, 1e6, 0.3, 100], np.float32).reshape(4, 4, 1) * np.array([1, 1.0009766, 0.5], np.float32)
+    rng = np.random.default_rng(31)
+    exposures = list(EXPOSURES) + [-149.5, -149.0, -148.75, -130.25, -126.5, -125.99, -0.5, 0.5, 127.4, 127.5, 127.99] + list(rng.uniform(-120, 120, 44))
+    assert len(exposures) == 64
+    for exposure in exposures:
+        got = Tonemapper(gpu_ctx, "Raw", exposure, False)(img)
+        want, _ = oracle_py.tonemap(img, None, T["Raw"], False, False, exposure)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (exposure, got[..., 0], want[..., 0])
+        assert not np.isnan(got).any() and not np.signbit(got).any()
+
+
+@pytest.mark.gpu
+def test_gpu_log_and_exp_are_the_hosts_over_the_whole_range(gpu_ctx):
+    """The sRGB curve is pow(1.055 c, 1 / 2.4) - 0.055 = det_logf, then det_expf: one image whose channels sweep binary32
+    from the end of the curve's linear toe (0.0031308) to FLT_MAX / 1.055 (every exponent; the all-zeros and all-ones
+    mantissas and random ones) compares the device's evaluation of both with the host's bit for bit, and with float64."""
+    from test_detmath_edges import FLT_MAX, bits
+
+    lo, hi = bits(np.nextafter(np.float32(0.0031308), np.float32(1))), bits(np.float32(FLT_MAX / 1.055))
+    n = 256 * 256 * 3
+    exponents = np.arange(lo >> 23, (hi >> 23) + 1, dtype=np.uint32)
+    per = n // exponents.size
+    rng = np.random.default_rng(32)
+    mant = rng.integers(0, 1 << 23, (exponents.size, per), dtype=np.uint32)
+    mant[:, 0], mant[:, 1] = 0, 0x7FFFFF
+    u = np.clip((exponents[:, None] << 23) | mant, lo, hi).astype(np.uint32).ravel()
+    u = np.concatenate([u, np.full(n - u.size, hi, np.uint32)])
+    c = u.view(np.float32).copy()
+    c[:8] = np.array([0.0031308, np.nextafter(np.float32(0.0031308), np.float32(0)), 0.003, 1e-6, 1e-40, 0.0, np.nan, -0.25], np.float32)  # the toe, 0, a NaN
+    c[8], c[9] = np.float32(FLT_MAX / 1.055), np.nextafter(np.float32(0.0031308), np.float32(1))
+    img = np.ones((256, 256, 4), np.float32)
+    img[..., :3] = c.reshape(256, 256, 3)
+    got = Tonemapper(gpu_ctx, "Raw", 0.0, True)(img)
+    want, _ = oracle_py.tonemap(img, None, T["Raw"], False, True, 0.0)
+    assert _same_bits_or_both_nan(got, want), "%d values differ" % (got.view(np.uint32) != want.view(np.uint32)).sum()
+    x = img[..., :3].astype(np.float64)
+    curve = x > np.float64(np.float32(0.0031308))
+    ref = np.power(1.055 * x[curve], 1 / 2.4) - 0.055
+    assert curve.sum() > 190000 and np.isfinite(got[..., :3][curve]).all()
+    assert np.abs(got[..., :3][curve] / ref - 1).max() < 1.5 * 4.3e-6  # the bound of test_accuracy_inside_the_domains_against_float64
+    toe = x <= np.float64(np.float32(0.0031308))
+    assert np.array_equal(got[..., :3][toe], (img[..., :3][toe] * np.float32(12.92)))
+
+
 @pytest.mark.gpu
 def test_gpu_tonemap_of_a_rendered_frame(gpu_ctx, cornell):
     from stratum_amd import camera
