@@ -249,6 +249,81 @@ int sthip_scene_read_image(sthip_ctx* ctx, uint32_t image_index, uint32_t level,
 int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* gInstanceTransforms, const sthip_TransformData* gInstanceInverseTransforms,
                                   const sthip_TransformData* gInstanceMotionTransforms, uint32_t instance_count);
 
+/* ---- instance transforms from host or device memory; the top level built on the host or on the device (top_level.hip) ----
+ * sthip_scene_set_transforms is the descriptor form of the call above. With device_ptr = 0, top_level = 0, all three arrays
+ * given and derive_motion = 0 it IS sthip_scene_update_transforms: the same results, refusals and kept state. Beyond that:
+ *   device_ptr = 1     every non-NULL array is device memory, readable in the order of the context's stream. With the host
+ *                      builder the matrices are copied back once and today's path is taken.
+ *   inverse_transforms = NULL   the inverse is derived: the adjugate of the 3x3 block over its determinant, evaluated in
+ *                      binary64 in this order — c00 = a11*a22 - a12*a21, c01 = a12*a20 - a10*a22, c02 = a10*a21 - a11*a20,
+ *                      det = a00*c00 + a01*c01 + a02*c02; rows {c00, a02*a21 - a01*a22, a01*a12 - a02*a11} / det,
+ *                      {c01, a00*a22 - a02*a20, a02*a10 - a00*a12} / det, {c02, a01*a20 - a00*a21, a00*a11 - a01*a10} / det,
+ *                      every quotient its own IEEE division; translation 0.0 - (i0*tx + i1*ty + i2*tz) from the unrounded
+ *                      binary64 quotients; every result rounded to binary32 once, at the store; unfused arithmetic. It is
+ *                      transform_inverse of the Python host and of host/stratum_hip.hpp; an identity gives an identity.
+ *   derive_motion = 1  (motion_transforms must be NULL) motion = tmul(resident transform before the call, new inverse as
+ *                      binary32) in binary32, rows dotted left to right: ((a0*b0j + a1*b1j) + a2*b2j) (+ a3 for j = 3).
+ *                      motion_transforms = NULL with derive_motion = 0: identity, as in the call above.
+ *   top_level = 1      the top level is built on the device: entry boxes, scene centre and radius are the values the host
+ *                      builder computes for the same matrices (sphere, volume and transformed-mesh cases, the 8 corners in
+ *                      its order, rows dotted left to right and unfused, its two padding formulas, the merged mesh's kept
+ *                      box), bit for bit except for the sign of a zero. The tree is a Karras radix tree over 16-bit-per-axis
+ *                      Morton keys of the box centres with the entry index in the low 16 bits of the key (so equal codes are
+ *                      ordered by entry index), fitted bottom-up: any valid binary tree is acceptable to the walks, frames do
+ *                      not depend on its shape; same inputs give the same nodes. One entry gets a node with the leaf in both
+ *                      slots; no entries or a lone identity entry keep the walk at the merged mesh without a top level.
+ * Phase order: check, reserve, wait for the stream and the frames in flight, work beside the resident arrays, ONE small
+ * read-back (flags, scene box, height), install. Refusals leave everything as it was:
+ *   STHIP_ERR_INVALID_ARGUMENT  no desc, a struct_size that is not sizeof(sthip_transforms_desc), NULL transforms, derive_motion
+ *                      together with a motion array, top_level > 1; a derived inverse whose determinant is 0 or not finite;
+ *                      with the device builder an entry box that is not finite.
+ *   STHIP_ERR_UNSUPPORTED  an instance_count that is not the resident one; a top level that is too deep or does not fit; an
+ *                      instance of the merged mesh whose new transform or inverse is not the identity while "keep_scene" = 0.
+ *                      With a kept scene that last case builds the scene again from it (info.rebuilt = 1, full_rebuilds++).
+ * Kept first hits are dropped (the scene serial advances), as by the call above. After a device-pointer call or a derived
+ * array the host's copies of the matrices (the kept scene, the entries' inverses) are older than the device's; the library
+ * fetches them before their next reader. Layouts whose top level is made on the host from host nodes ("wide_bvh" = 3,
+ * "treetop") read the new binary nodes back once.
+ *
+ * sthip_scene_read_transforms: the resident records [first, first + count) of the three arrays (any out pointer may be NULL).
+ * sthip_scene_read_top_level: the entry boxes as the contract above defines them (6 floats per entry: lo, hi), the binary
+ * top-level nodes — planes as the packed nodes hold them, so rounded outward; a child is a node index of this array or
+ * 0x80000000 | entry — the root's index, and {centre.xyz, radius}. Without a top level node_count = 0 and root = 0xFFFFFFFF.
+ * entry_boxes / nodes may be NULL (counts only); node_capacity smaller than the node count: STHIP_ERR_INVALID_ARGUMENT.
+ * The entry boxes are not kept by either builder: when asked for them the call computes them again on the device from the
+ * resident matrices and entries (the kernel of the device builder; it uses the context's top-level staging, nothing resident
+ * changes). So they say what the contract gives for what is resident, whichever builder made the nodes.
+ * A library without the feature lacks the three symbols.
+ * Measured on an MI355X (profiles/r12/top_level.json; all instances moving, medians of 9 calls; the call above from host
+ * arrays against this call from device pointers with derived arrays and the device builder): 1 000 instances 1.17 against
+ * 0.55 ms, 8 192 instances 6.17 against 0.49 ms, 65 533 instances 21.8 against 1.55 ms (device_ms 0.45 / 0.42 / 1.47). The
+ * trade-off: the forest's 1920 x 1080 frame takes 1.662 ms under the device-built tree against 1.633 ms under the host-built
+ * one (+1.7 %, resolved); the two synthetic scenes show no difference. */
+typedef struct sthip_transforms_desc {
+  const sthip_TransformData* transforms;         /* instance_count records */
+  const sthip_TransformData* inverse_transforms; /* NULL: derived by the library */
+  const sthip_TransformData* motion_transforms;  /* NULL: identity, or derived (derive_motion) */
+  uint32_t instance_count;
+  uint32_t device_ptr;    /* 1: every non-NULL array is device memory */
+  uint32_t top_level;     /* 0: host builder (binned SAH); 1: device builder */
+  uint32_t derive_motion; /* 1 (motion_transforms must be NULL): motion = tmul(resident transform before the call, new inverse) */
+} sthip_transforms_desc;
+typedef struct sthip_transforms_info { /* optional out-parameter, may be NULL */
+  float device_ms, total_ms;
+  uint32_t top_level_nodes, top_level_depth; /* depth: an upper bound of the real height, the one the stack depth is made from */
+  uint32_t rebuilt;                          /* 1: fell back to a rebuild from the kept scene (a merged instance moved) */
+  uint32_t builder_used;                     /* 0 host, 1 device */
+} sthip_transforms_info;
+typedef struct sthip_top_node {
+  float lo[3];
+  uint32_t child0;
+  float hi[3];
+  uint32_t child1;
+} sthip_top_node; /* lo / hi: the union of the two child boxes the node holds */
+int sthip_scene_set_transforms(sthip_ctx* ctx, const sthip_transforms_desc* desc, uint32_t struct_size, sthip_transforms_info* info);
+int sthip_scene_read_transforms(sthip_ctx* ctx, uint32_t first, uint32_t count, sthip_TransformData* transforms, sthip_TransformData* inverse_transforms, sthip_TransformData* motion_transforms);
+int sthip_scene_read_top_level(sthip_ctx* ctx, float* entry_boxes, sthip_top_node* nodes, uint32_t node_capacity, uint32_t* entry_count, uint32_t* node_count, uint32_t* root, float center_radius[4]);
+
 /* A mesh deformed, nothing else changed (the reference rebuilds the BLAS of a dirty mesh, Scene.cpp:345,435-459): new
  * contents for the records [first_vertex, first_vertex + vertex_count) of gVertices — position, normal and both texture
  * coordinates; the index buffer, instances, materials and transforms are those of the last sthip_scene_upload. The range

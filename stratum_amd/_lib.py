@@ -25,6 +25,9 @@ EXPORTS = [
     "sthip_scene_upload_formats",
     "sthip_scene_read_image",
     "sthip_scene_update_transforms",
+    "sthip_scene_set_transforms",
+    "sthip_scene_read_transforms",
+    "sthip_scene_read_top_level",
     "sthip_scene_update_vertices",
     "sthip_scene_set_rigs",
     "sthip_scene_animate",
@@ -138,6 +141,13 @@ def lib():
         L.sthip_scene_set_material_data.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(wire.ImagesInfo)]
         L.sthip_scene_read_image_range.restype = C.c_int
         L.sthip_scene_read_image_range.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    if hasattr(L, "sthip_scene_set_transforms"):  # (an older build named by STHIP_LIB lacks the three: calling them raises)
+        L.sthip_scene_set_transforms.restype = C.c_int
+        L.sthip_scene_set_transforms.argtypes = [C.c_void_p, C.POINTER(wire.TransformsDesc), C.c_uint32, C.POINTER(wire.TransformsInfo)]
+        L.sthip_scene_read_transforms.restype = C.c_int
+        L.sthip_scene_read_transforms.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sthip_scene_read_top_level.restype = C.c_int
+        L.sthip_scene_read_top_level.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
     L.sthip_render.restype = C.c_int
     L.sthip_render.argtypes = [
         C.c_void_p,

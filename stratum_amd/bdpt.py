@@ -164,6 +164,72 @@ class BDPT:
         self._check(rc, "sthip_scene_update_transforms")
         self._scene = scene
 
+    def set_transforms(self, transforms, inverse=None, motion=None, derive_motion=False, top_level="host"):
+        """New instance transforms for the resident scene from host or device memory (sthip_scene_set_transforms). Each array is
+        a wire.TransformData / float32 (n, 3, 4) numpy array, or anything with data_ptr() (a contiguous float32 torch tensor
+        of n x 12 values on this device); all given arrays must be of one kind. inverse=None: the library derives the inverse
+        (scene.transform_inverse's arithmetic); motion=None: the identity, or with derive_motion=True tmul(resident transform
+        before the call, new inverse). top_level: "host" (binned SAH) or "device" (top_level.hip). The scene object handed to
+        update() does NOT follow: read_transforms() says what is resident. Returns sthip_transforms_info as a dict."""
+        if top_level not in ("host", "device"):
+            raise ValueError('set_transforms: top_level is "host" or "device"')
+        d = wire.TransformsDesc()
+        keep = []
+        device = hasattr(transforms, "data_ptr")
+
+        def pointer(a, name):
+            if a is None:
+                return None
+            if hasattr(a, "data_ptr") != device:
+                raise ValueError("set_transforms: host and device arrays cannot be mixed")
+            if device:
+                if "float32" not in str(a.dtype) or not a.is_contiguous() or a.numel() % 12:
+                    raise ValueError("set_transforms: %s must be a contiguous float32 tensor of n x 12 values" % name)
+                count = a.numel() // 12
+                ptr = int(a.data_ptr())
+            else:
+                a = np.asarray(a)
+                a = np.ascontiguousarray(a["m"] if a.dtype == wire.TransformData else a, dtype=np.float32).reshape(-1, 3, 4)
+                keep.append(a)
+                count, ptr = a.shape[0], a.ctypes.data
+            if name == "transforms":
+                d.instance_count = count
+            elif count != d.instance_count:
+                raise ValueError("set_transforms: %s has %d records, transforms %d" % (name, count, d.instance_count))
+            return ptr
+
+        d.transforms = pointer(transforms, "transforms")
+        d.inverse_transforms = pointer(inverse, "inverse")
+        d.motion_transforms = pointer(motion, "motion")
+        d.device_ptr = 1 if device else 0
+        d.top_level = 1 if top_level == "device" else 0
+        d.derive_motion = 1 if derive_motion else 0
+        info = wire.TransformsInfo()
+        self._check(self._lib.sthip_scene_set_transforms(self._h, C.byref(d), C.sizeof(d), C.byref(info)), "sthip_scene_set_transforms")
+        return {f: getattr(info, f) for f, _ in wire.TransformsInfo._fields_}
+
+    def read_transforms(self, first=0, count=None):
+        """The resident transforms, inverse transforms and motion transforms [first, first + count) as three float32 arrays
+        (count, 3, 4) (sthip_scene_read_transforms); all instances by default."""
+        n = int((self._scene.instances.shape[0] - first if self._scene is not None else 0) if count is None else count)
+        out = [np.zeros((n, 3, 4), np.float32) for _ in range(3)]
+        self._check(self._lib.sthip_scene_read_transforms(self._h, int(first), n, *[wire.ptr(a) if n else None for a in out]), "sthip_scene_read_transforms")
+        return tuple(out)
+
+    def read_top_level(self):
+        """The resident top level (sthip_scene_read_top_level): {"entry_boxes": float32 (entries, 2, 3) lo / hi, exact;
+        "nodes": a wire.TopNode array; "root": node index or 0xFFFFFFFF (no top level); "center": float32 (3,); "radius"}."""
+        ne, nn, root = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        cr = np.zeros(4, np.float32)
+        self._check(self._lib.sthip_scene_read_top_level(self._h, None, None, 0, C.byref(ne), C.byref(nn), C.byref(root), wire.ptr(cr)), "sthip_scene_read_top_level")
+        boxes = np.zeros((ne.value, 2, 3), np.float32)
+        nodes = np.zeros(nn.value, wire.TopNode)
+        rc = self._lib.sthip_scene_read_top_level(
+            self._h, wire.ptr(boxes) if ne.value else None, wire.ptr(nodes) if nn.value else None, nn.value, C.byref(ne), C.byref(nn), C.byref(root), wire.ptr(cr)
+        )
+        self._check(rc, "sthip_scene_read_top_level")
+        return {"entry_boxes": boxes, "nodes": nodes, "root": root.value, "center": cr[:3].copy(), "radius": float(cr[3])}
+
     def update_vertices(self, scene):
         """Only vertex records changed since update(scene) (SceneData.set_vertices): the dirty range goes to the device, the
         leaf triangles are gathered again and the bottom levels refitted in place (sthip_scene_update_vertices). Returns

@@ -31,6 +31,7 @@
 #include "mips.h"
 #include "post.h"
 #include "scene_prepare.h"
+#include "top_level.h"
 #include "ceilings.h"
 
 STHIP_DECLARE_KERNEL_INSTANCES
@@ -294,6 +295,12 @@ struct sthip_ctx {
   int use_wide = 1;
   size_t wide_node_count = 0;
   sthip::DeviceWideScratch* wide_scratch = nullptr;  // buffers of the device-side collapse (wide.hip), kept between calls
+  // sthip_scene_set_transforms (top_level.hip): the staging and scratch of the device path; whether its per-entry tables are
+  // those of the resident tree; whether the host's copies of the matrices (the kept scene, top.entries[k].inv) are older
+  // than the device's — a device-pointer call or a derived array left them behind (sync_kept_transforms)
+  sthip::DeviceTopLevel* top_level = nullptr;
+  bool top_level_static_valid = false;
+  bool host_transforms_stale = false;
   // sthip_scene_update_vertices (refit.hip): the schedule of the resident bottom levels and the refit's scratch; what the
   // call needs to know of the uploaded arrays; whether the resident layout is one the refit serves
   sthip::DeviceRefit* refit = nullptr;
@@ -654,6 +661,8 @@ void sthip_destroy(sthip_ctx* ctx) {
   for (void* q : ctx->host_allocs) (void)hipHostFree(q);
   sthip::device_wide_scratch_destroy(ctx->wide_scratch);
   ctx->wide_scratch = nullptr;
+  sthip::device_top_level_destroy(ctx->top_level);
+  ctx->top_level = nullptr;
   sthip::device_refit_destroy(ctx->refit);
   ctx->refit = nullptr;
   for (int k = 0; k < 2; k++)
@@ -861,6 +870,7 @@ static size_t trace_lds_bytes(const sthip_ctx* ctx);
 static int trace_occupancy(const sthip_ctx* ctx, size_t lds_bytes);
 static int configure_stack(sthip_ctx* ctx);
 static int refresh_treetop(sthip_ctx* ctx);
+static int sync_kept_transforms(sthip_ctx* ctx);
 // packs `count` nodes and writes them into the node array from slot `first` on
 static hipError_t upload_nodes(sthip_ctx* ctx, size_t first, const BvhNode* nodes, size_t count) {
   std::vector<BvhNodePacked> packed;
@@ -1024,6 +1034,10 @@ static int sync_kept_environment(sthip_ctx* ctx) {
 // What the kept copy is built again from: the kept arrays with the formats their images were uploaded in.
 static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats);
 static int upload_kept_scene(sthip_ctx* ctx) {
+  {  // (matrices a device-pointer call of sthip_scene_set_transforms left newer than the kept copy)
+    const int rc = sync_kept_transforms(ctx);
+    if (rc != STHIP_OK) return rc;
+  }
   {  // (an environment a device pointer or the device's table build left newer than the kept copy: the rebuild must see it)
     const int rc = sync_kept_environment(ctx);
     if (rc != STHIP_OK) return rc;
@@ -1292,6 +1306,8 @@ static int install_tree(sthip_ctx* ctx, sthip::BuiltBvh& built) {
   if (!built.entries.empty()) HIP_TRY(ctx, hipMemcpy(ctx->entries.p, built.entries.data(), built.entries.size() * sizeof(TlasEntry), hipMemcpyHostToDevice));
   clear_wide(ctx);
   clear_wide8(ctx);
+  ctx->top_level_static_valid = false;  // (top_level.hip: the per-entry tables belong to the tree that goes away)
+  ctx->host_transforms_stale = false;   // (what goes up now is what the host holds)
   ctx->bvh.wide8_tri_min = ctx->tri_min_lanes;
   ctx->wide8_host.clear();
   if (!built.wide8_nodes.empty()) {
@@ -1537,10 +1553,18 @@ int sthip_trace_rays(sthip_ctx* ctx, const sthip_ray* rays, uint32_t ray_count, 
 
 // A new top level over bottom levels that stay where they are (a transforms-only update; a refit, whose bottom levels have new
 // boxes): entries and top-level nodes into HBM, the scene bounds, and the forms derived from the binary tree made again.
+static int finish_top_level(sthip_ctx* ctx, const BvhNode* tlas_nodes, size_t tlas_count, uint32_t root_ref, uint32_t top_is_world, uint32_t stack_depth, const float center[3], float radius);
 static int install_top_level(sthip_ctx* ctx, sthip::TopLevelState& next, const std::vector<BvhNode>& tlas, uint32_t root_ref, uint32_t top_is_world, uint32_t stack_depth, const float center[3],
                              float radius) {
   if (!next.entries.empty()) HIP_TRY(ctx, hipMemcpy(ctx->entries.p, next.entries.data(), next.entries.size() * sizeof(TlasEntry), hipMemcpyHostToDevice));
   if (!tlas.empty()) HIP_TRY(ctx, upload_nodes(ctx, next.blas_nodes, tlas.data(), tlas.size()));
+  ctx->top = std::move(next);
+  return finish_top_level(ctx, tlas.data(), tlas.size(), root_ref, top_is_world, stack_depth, center, radius);
+}
+// ... once the entries and the packed top-level nodes are resident and ctx->top describes them (the device builder of
+// sthip_scene_set_transforms comes here directly; `tlas_nodes` may then be NULL unless a host-made layout needs them)
+static int finish_top_level(sthip_ctx* ctx, const BvhNode* tlas_nodes, size_t tlas_count, uint32_t root_ref, uint32_t top_is_world, uint32_t stack_depth, const float center[3], float radius) {
+  const uint32_t blas_nodes = ctx->top.blas_nodes;
   ctx->bvh.root_ref = root_ref;
   ctx->bvh.top_is_world_blas = top_is_world;
   ctx->bvh.stack_depth = stack_depth;
@@ -1548,12 +1572,11 @@ static int install_top_level(sthip_ctx* ctx, sthip::TopLevelState& next, const s
   ctx->bvh.scene_cy = center[1];
   ctx->bvh.scene_cz = center[2];
   ctx->bvh.scene_radius = radius;
-  ctx->bvh_nodes = next.blas_nodes + tlas.size();
-  if (ctx->nodes_host.n && ctx->nodes_host.cap >= (size_t)next.blas_nodes + tlas.size()) {
-    if (!tlas.empty()) memcpy(ctx->nodes_host.p + next.blas_nodes, tlas.data(), tlas.size() * sizeof(BvhNode));
-    ctx->nodes_host.n = std::max(ctx->nodes_host.n, (size_t)next.blas_nodes + tlas.size());
+  ctx->bvh_nodes = blas_nodes + tlas_count;
+  if (ctx->nodes_host.n && ctx->nodes_host.cap >= (size_t)blas_nodes + tlas_count) {
+    if (tlas_count) memcpy(ctx->nodes_host.p + blas_nodes, tlas_nodes, tlas_count * sizeof(BvhNode));
+    ctx->nodes_host.n = std::max(ctx->nodes_host.n, (size_t)blas_nodes + tlas_count);
   }
-  ctx->top = std::move(next);
   // the wide form was made from the old top level: made again from the nodes in HBM (the bottom levels come out as before,
   // the top level new), so a moved scene keeps the walk it was uploaded with
   clear_wide(ctx);
@@ -1561,7 +1584,7 @@ static int install_top_level(sthip_ctx* ctx, sthip::TopLevelState& next, const s
     std::vector<TlasEntry> entries8;
     uint32_t root8 = BVH_INVALID_REF, depth8 = 0;
     clear_wide8(ctx);
-    if (sthip::build_wide8_top(ctx->top, tlas.data(), ctx->top.blas_nodes, root_ref, top_is_world != 0, ctx->wide8_host, entries8, root8, depth8) && ctx->wide8_host.size() <= ctx->wide8_nodes.n &&
+    if (sthip::build_wide8_top(ctx->top, tlas_nodes, ctx->top.blas_nodes, root_ref, top_is_world != 0, ctx->wide8_host, entries8, root8, depth8) && ctx->wide8_host.size() <= ctx->wide8_nodes.n &&
         entries8.size() <= ctx->wide8_entries.n) {
       const int rc = install_wide8(ctx, ctx->top.wide8_blas_nodes, entries8, root8, depth8);
       if (rc != STHIP_OK) return rc;
@@ -1581,12 +1604,29 @@ static int install_top_level(sthip_ctx* ctx, sthip::TopLevelState& next, const s
   return configure_stack(ctx);
 }
 
-int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf, const sthip_TransformData* inv, const sthip_TransformData* motion, uint32_t instance_count) {
-  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
-  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_NO_SCENE, "sthip_scene_update_transforms before sthip_scene_upload");
-  if (!xf || !inv) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_transforms: transforms and inverse transforms are required");
-  if (instance_count != ctx->instance_count) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the instance count changed: upload the scene again");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+// The host's copies of the instance matrices are current again: after a device-pointer call of sthip_scene_set_transforms, or
+// one that derived an array, the kept scene's three arrays and the inverses in ctx->top.entries come back from the device.
+// Called immediately before their next reader, as sync_kept_vertices is.
+static int sync_kept_transforms(sthip_ctx* ctx) {
+  if (!ctx->host_transforms_stale) return STHIP_OK;
+  const uint32_t n = ctx->instance_count;
+  if (ctx->has_scene && n && ctx->xf.p && ctx->inv_xf.p && ctx->motion_xf.p) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<sthip_TransformData> xf(n), inv(n), motion(n);
+    HIP_TRY(ctx, hipMemcpy(xf.data(), ctx->xf.p, (size_t)n * 48, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(inv.data(), ctx->inv_xf.p, (size_t)n * 48, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(motion.data(), ctx->motion_xf.p, (size_t)n * 48, hipMemcpyDeviceToHost));
+    if (ctx->kept.valid && ctx->kept.instances.size() == n) ctx->kept.set_transforms(xf.data(), inv.data(), motion.data(), n);
+    for (TlasEntry& e : ctx->top.entries)
+      if (e.identity != TLAS_ENTRY_IDENTITY && e.id_bits < n) memcpy(e.inv, &inv[e.id_bits], 48);
+  }
+  ctx->host_transforms_stale = false;
+  return STHIP_OK;
+}
+
+// sthip_scene_update_transforms, and the host builder of sthip_scene_set_transforms once its matrices are host arrays
+static int update_transforms_host(sthip_ctx* ctx, const std::string& call, const sthip_TransformData* xf, const sthip_TransformData* inv, const sthip_TransformData* motion, uint32_t instance_count,
+                                  sthip_transforms_info* info) {
   ctx->scene_serial++;  // (first_hits.h; a refused call costs one trace of the first bounce)
   sthip::TopLevelState next = ctx->top;  // nothing changes unless everything succeeds
   std::vector<BvhNode> tlas;
@@ -1603,13 +1643,15 @@ int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf,
         if (rc != STHIP_OK) return rc;
       }
       ctx->kept.set_transforms(xf, inv, motion, instance_count);
+      ctx->host_transforms_stale = false;  // (all three arrays of the kept scene are the call's now; the upload makes the entries)
       ctx->stats.full_rebuilds++;
+      if (info) info->rebuilt = 1;
       return upload_kept_scene(ctx);
     }
-    return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: " + err);
+    return fail(ctx, STHIP_ERR_UNSUPPORTED, call + err);
   }
-  if (stack_depth > STHIP_MAX_STACK_DEPTH) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the new top level is too deep for the traversal stack");
-  if ((size_t)next.blas_nodes + tlas.size() > ctx->nodes.n) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the new top level does not fit: upload the scene again");
+  if (stack_depth > STHIP_MAX_STACK_DEPTH) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "the new top level is too deep for the traversal stack");
+  if ((size_t)next.blas_nodes + tlas.size() > ctx->nodes.n) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "the new top level does not fit: upload the scene again");
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old top level
   HIP_TRY(ctx, drain_in_flight(ctx));               // (sthip_render_async: their copies too, so that their tickets are complete)
   const uint32_t n = instance_count;
@@ -1622,7 +1664,305 @@ int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf,
   // the kept scene follows: a later rebuild from it (sthip_scene_update_vertices on a layout it does not refit) must find the
   // instances where they are now, and the refit takes the transforms of its top level from here instead of from the device
   if (ctx->kept.valid && ctx->kept.instances.size() == n) ctx->kept.set_transforms(xf, inv, motion, n);
+  ctx->host_transforms_stale = false;  // (the kept arrays and every entry's inverse are the call's)
+  if (info) {
+    info->top_level_nodes = (uint32_t)tlas.size();
+    info->top_level_depth = stack_depth - next.blas_depth - 3;
+  }
   return install_top_level(ctx, next, tlas, root_ref, top_is_world, stack_depth, center, radius);
+}
+
+int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf, const sthip_TransformData* inv, const sthip_TransformData* motion, uint32_t instance_count) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_NO_SCENE, "sthip_scene_update_transforms before sthip_scene_upload");
+  if (!xf || !inv) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_transforms: transforms and inverse transforms are required");
+  if (instance_count != ctx->instance_count) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the instance count changed: upload the scene again");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return update_transforms_host(ctx, "sthip_scene_update_transforms: ", xf, inv, motion, instance_count, nullptr);
+}
+
+// The device builder of sthip_scene_set_transforms (top_level.hip). `xf` / `inv` / `motion` are device memory here.
+static int set_transforms_device(sthip_ctx* ctx, const std::string& call, const sthip_TransformData* xf, const sthip_TransformData* inv, const sthip_TransformData* motion, bool derive_motion,
+                                 bool host_mirrors_follow, const sthip_TransformData* host_xf, const sthip_TransformData* host_inv, const sthip_TransformData* host_motion, sthip_transforms_info* info) {
+  const uint32_t n = ctx->instance_count, m = (uint32_t)ctx->top.entries.size();
+  std::string err;
+  // ---- reserve ----
+  if (!ctx->top_level) ctx->top_level = sthip::device_top_level_create();
+  if (!ctx->top_level_static_valid) {
+    if (!sthip::top_level_set_static(ctx->top_level, ctx->top.merged.data(), n, ctx->top.obj_box.data(), m, ctx->stream, err)) return fail(ctx, STHIP_ERR_HIP, call + err);
+    ctx->top_level_static_valid = true;
+  }
+  // ---- frames in flight still read the resident arrays; the work below reads them too (entries, the previous transforms) ----
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, drain_in_flight(ctx));
+  sthip::TopLevelInputs in;
+  in.xf = xf;
+  in.inv = inv;
+  in.motion = motion;
+  in.derive_motion = derive_motion;
+  in.instance_count = n;
+  in.resident_xf = ctx->xf.p;
+  in.entries = ctx->entries.p;
+  in.entry_count = m;
+  in.volumes = ctx->volumes.p;
+  in.volume_count = (uint32_t)std::min<size_t>(ctx->volumes.n, ctx->top.volumes.size());
+  memcpy(in.merged_box, ctx->top.merged_box, sizeof(in.merged_box));
+  in.blas_nodes = ctx->top.blas_nodes;
+  const bool lone_identity = m == 1 && ctx->top.entries[0].identity == TLAS_ENTRY_IDENTITY;
+  in.build_tree = m >= 1 && !lone_identity;
+  sthip::TopLevelResult res{};
+  float gpu_ms = 0;
+  if (!sthip::top_level_build(ctx->top_level, in, ctx->stream, res, gpu_ms, err)) return fail(ctx, STHIP_ERR_HIP, call + err);
+  // ---- everything that can be refused is decided here, from the one read-back; nothing resident has been written ----
+  if (res.flags & TL_FLAG_SINGULAR)
+    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "the transform of instance " + std::to_string(res.first_bad) + " (or a later one) has no inverse: its determinant is 0 or not finite");
+  if (res.flags & TL_FLAG_MERGED_MOVED) {
+    if (ctx->kept.valid && ctx->kept.instances.size() == n) {  // the matrices come to the host and the scene is built again, as the host path does
+      std::vector<sthip_TransformData> hx(n), hi(n), hm(n);
+      DevBuf<sthip_TransformData> tmp;  // (the staging holds the call's three arrays, derived ones included)
+      HIP_TRY(ctx, tmp.ensure((size_t)3 * n));
+      if (!sthip::top_level_install(ctx->top_level, tmp.p, tmp.p + n, tmp.p + 2 * (size_t)n, nullptr, nullptr, ctx->stream, err)) return fail(ctx, STHIP_ERR_HIP, call + err);
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      HIP_TRY(ctx, hipMemcpy(hx.data(), tmp.p, (size_t)n * 48, hipMemcpyDeviceToHost));
+      HIP_TRY(ctx, hipMemcpy(hi.data(), tmp.p + n, (size_t)n * 48, hipMemcpyDeviceToHost));
+      HIP_TRY(ctx, hipMemcpy(hm.data(), tmp.p + 2 * (size_t)n, (size_t)n * 48, hipMemcpyDeviceToHost));
+      {
+        const int rc = sync_kept_vertices(ctx);
+        if (rc != STHIP_OK) return rc;
+      }
+      ctx->kept.set_transforms(hx.data(), hi.data(), hm.data(), n);
+      ctx->host_transforms_stale = false;
+      ctx->stats.full_rebuilds++;
+      if (info) info->rebuilt = 1;
+      return upload_kept_scene(ctx);
+    }
+    return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "an instance of the merged world-space mesh (identity transform at upload) moved: upload the scene again");
+  }
+  if (res.flags & TL_FLAG_BOX) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "the world box of top-level entry " + std::to_string(res.first_bad) + " (or a later one) is not finite");
+  const uint32_t tlas_count = in.build_tree ? (m >= 2 ? m - 1 : 1) : 0;
+  const uint32_t tlas_depth = tlas_count ? res.height + 1 : 0;
+  const uint32_t stack_depth = tlas_depth + ctx->top.blas_depth + 3;
+  if (stack_depth > STHIP_MAX_STACK_DEPTH) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "the new top level is too deep for the traversal stack");
+  if ((size_t)ctx->top.blas_nodes + tlas_count > ctx->nodes.n) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "the new top level does not fit: upload the scene again");
+  // ---- install ----
+  if (!sthip::top_level_install(ctx->top_level, ctx->xf.p, ctx->inv_xf.p, ctx->motion_xf.p, ctx->entries.p, ctx->nodes.p + ctx->top.blas_nodes, ctx->stream, err)) return fail(ctx, STHIP_ERR_HIP, call + err);
+  float center[3] = {ctx->bvh.scene_cx, ctx->bvh.scene_cy, ctx->bvh.scene_cz}, radius = ctx->bvh.scene_radius;
+  {
+    float lo[3], hi[3];
+    for (int a = 0; a < 3; a++) {
+      lo[a] = sthip::top_level_ord2f(res.box[a]);
+      hi[a] = sthip::top_level_ord2f(res.box[3 + a]);
+    }
+    if (m && lo[0] <= hi[0]) {  // (rebuild_top_level's formulas)
+      for (int a = 0; a < 3; a++) center[a] = 0.5f * (lo[a] + hi[a]);
+      radius = 0.5f * sqrtf((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
+    }
+  }
+  uint32_t root_ref = BVH_INVALID_REF, top_is_world = 1;
+  if (lone_identity) {
+    root_ref = ctx->top.entries[0].root;
+  } else if (m) {
+    root_ref = ctx->top.blas_nodes;  // (node 0 of a radix tree is its root; the wrapped leaf is the only node)
+    top_is_world = 0;
+  }
+  // the host's mirrors: they follow at once where the call's arrays are host memory and nothing was derived, else lazily
+  if (host_mirrors_follow) {
+    if (ctx->kept.valid && ctx->kept.instances.size() == n) ctx->kept.set_transforms(host_xf, host_inv, host_motion, n);
+    for (TlasEntry& e : ctx->top.entries)
+      if (e.identity != TLAS_ENTRY_IDENTITY && e.id_bits < n) memcpy(e.inv, &host_inv[e.id_bits], 48);
+    ctx->host_transforms_stale = false;
+  } else {
+    ctx->host_transforms_stale = true;
+  }
+  // layouts whose top level the host makes from host nodes: the new binary nodes come back once, and the entries' inverses
+  std::vector<BvhNode> tlas;
+  if (ctx->bvh.wide8_nodes || !ctx->wide8_host.empty() || ctx->use_treetop || ctx->nodes_host.n) {
+    tlas.resize(tlas_count);
+    if (!sthip::top_level_read_nodes(ctx->top_level, tlas.data(), tlas_count, ctx->stream, err)) return fail(ctx, STHIP_ERR_HIP, call + err);
+    const int rc = sync_kept_transforms(ctx);
+    if (rc != STHIP_OK) return rc;
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the collapse and the copies of the layouts go through other queues)
+  const float wide_before = ctx->stats.bvh_build_gpu_ms;
+  const int rc = finish_top_level(ctx, tlas.empty() ? nullptr : tlas.data(), tlas_count, root_ref, top_is_world, stack_depth, center, radius);
+  if (info) {
+    info->device_ms = gpu_ms + (ctx->stats.bvh_build_gpu_ms - wide_before);
+    info->top_level_nodes = tlas_count;
+    info->top_level_depth = tlas_depth;
+    info->builder_used = 1;
+  }
+  return rc;
+}
+
+int sthip_scene_set_transforms(sthip_ctx* ctx, const sthip_transforms_desc* d, uint32_t struct_size, sthip_transforms_info* info) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  const auto t0 = std::chrono::steady_clock::now();
+  const std::string call = "sthip_scene_set_transforms: ";
+  if (info) memset(info, 0, sizeof(*info));
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_NO_SCENE, "sthip_scene_set_transforms before sthip_scene_upload");
+  if (!d) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "desc is NULL");
+  if (struct_size != sizeof(sthip_transforms_desc)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "struct_size is not sizeof(sthip_transforms_desc)");
+  if (!d->transforms) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "transforms is NULL");
+  if (d->derive_motion && d->motion_transforms) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "derive_motion and motion_transforms exclude each other");
+  if (d->top_level > 1 || d->device_ptr > 1 || d->derive_motion > 1) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "top_level, device_ptr and derive_motion are 0 or 1");
+  if (d->instance_count != ctx->instance_count) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "the instance count changed: upload the scene again");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint32_t n = d->instance_count;
+  int rc = STHIP_OK;
+  auto finish = [&](int code) {
+    if (info) info->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return code;
+  };
+  if (d->top_level == 1 && ctx->top.entries.size() > 0xFFFFu)  // (an upload takes fewer: the keys of top_level.hip hold a 16-bit entry index)
+    return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "more top-level entries than the device builder's keys can index");
+  if (d->top_level == 1) {
+    ctx->scene_serial++;
+    const sthip_TransformData *xf = d->transforms, *inv = d->inverse_transforms, *motion = d->motion_transforms;
+    DevBuf<sthip_TransformData> up;  // host arrays: they go up once, into a staging of the call
+    if (!d->device_ptr) {
+      HIP_TRY(ctx, up.ensure(std::max<size_t>(1, (size_t)3 * n)));
+      HIP_TRY(ctx, hipMemcpyAsync(up.p, xf, (size_t)n * 48, hipMemcpyHostToDevice, ctx->stream));
+      xf = up.p;
+      if (inv) {
+        HIP_TRY(ctx, hipMemcpyAsync(up.p + n, inv, (size_t)n * 48, hipMemcpyHostToDevice, ctx->stream));
+        inv = up.p + n;
+      }
+      if (motion) {
+        HIP_TRY(ctx, hipMemcpyAsync(up.p + 2 * (size_t)n, motion, (size_t)n * 48, hipMemcpyHostToDevice, ctx->stream));
+        motion = up.p + 2 * (size_t)n;
+      }
+    }
+    const bool follow = !d->device_ptr && d->inverse_transforms && !d->derive_motion;
+    rc = set_transforms_device(ctx, call, xf, inv, motion, d->derive_motion != 0, follow, d->transforms, d->inverse_transforms, d->motion_transforms, info);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);  // (`up` goes out of scope)
+    if (rc == STHIP_OK && e != hipSuccess) rc = fail(ctx, STHIP_ERR_HIP, call + hipGetErrorString(e));
+    return finish(rc);
+  }
+  // ---- the host builder: the matrices as host arrays (copied back once; derived with the same arithmetic), then today's path ----
+  std::vector<sthip_TransformData> hx, hi, hm;
+  const sthip_TransformData *xf = d->transforms, *inv = d->inverse_transforms, *motion = d->motion_transforms;
+  if (d->device_ptr) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    hx.resize(n);
+    HIP_TRY(ctx, hipMemcpy(hx.data(), xf, (size_t)n * 48, hipMemcpyDeviceToHost));
+    xf = hx.data();
+    if (inv) {
+      hi.resize(n);
+      HIP_TRY(ctx, hipMemcpy(hi.data(), inv, (size_t)n * 48, hipMemcpyDeviceToHost));
+      inv = hi.data();
+    }
+    if (motion) {
+      hm.resize(n);
+      HIP_TRY(ctx, hipMemcpy(hm.data(), motion, (size_t)n * 48, hipMemcpyDeviceToHost));
+      motion = hm.data();
+    }
+  }
+  if (!inv) {
+    hi.resize(n);
+    for (uint32_t i = 0; i < n; i++)
+      if (!sthip::derive_inverse(&xf[i].m[0][0], &hi[i].m[0][0]))
+        return finish(fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "the transform of instance " + std::to_string(i) + " has no inverse: its determinant is 0 or not finite"));
+    inv = hi.data();
+  }
+  if (d->derive_motion) {
+    std::vector<sthip_TransformData> prev(n);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n) HIP_TRY(ctx, hipMemcpy(prev.data(), ctx->xf.p, (size_t)n * 48, hipMemcpyDeviceToHost));
+    hm.resize(n);
+    for (uint32_t i = 0; i < n; i++) sthip::derive_motion(&prev[i].m[0][0], &inv[i].m[0][0], &hm[i].m[0][0]);
+    motion = hm.data();
+  }
+  rc = update_transforms_host(ctx, call, xf, inv, motion, n, info);
+  return finish(rc);
+}
+
+int sthip_scene_read_transforms(sthip_ctx* ctx, uint32_t first, uint32_t count, sthip_TransformData* xf, sthip_TransformData* inv, sthip_TransformData* motion) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_NO_SCENE, "sthip_scene_read_transforms before sthip_scene_upload");
+  if ((uint64_t)first + count > ctx->instance_count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_transforms: the range ends past the instance count of the resident scene");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (!count) return STHIP_OK;
+  if (xf) HIP_TRY(ctx, hipMemcpy(xf, ctx->xf.p + first, (size_t)count * 48, hipMemcpyDeviceToHost));
+  if (inv) HIP_TRY(ctx, hipMemcpy(inv, ctx->inv_xf.p + first, (size_t)count * 48, hipMemcpyDeviceToHost));
+  if (motion) HIP_TRY(ctx, hipMemcpy(motion, ctx->motion_xf.p + first, (size_t)count * 48, hipMemcpyDeviceToHost));
+  return STHIP_OK;
+}
+
+int sthip_scene_read_top_level(sthip_ctx* ctx, float* entry_boxes, sthip_top_node* nodes, uint32_t node_capacity, uint32_t* entry_count, uint32_t* node_count, uint32_t* root, float center_radius[4]) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  const std::string call = "sthip_scene_read_top_level: ";
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_NO_SCENE, "sthip_scene_read_top_level before sthip_scene_upload");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint32_t n = ctx->instance_count, m = (uint32_t)ctx->top.entries.size(), blas_nodes = ctx->top.blas_nodes;
+  const uint32_t count = ctx->bvh.top_is_world_blas ? 0u : (uint32_t)(ctx->bvh_nodes - blas_nodes);
+  if (entry_count) *entry_count = m;
+  if (node_count) *node_count = count;
+  if (root) *root = ctx->bvh.top_is_world_blas ? 0xFFFFFFFFu : ctx->bvh.root_ref - blas_nodes;
+  if (center_radius) {
+    center_radius[0] = ctx->bvh.scene_cx;
+    center_radius[1] = ctx->bvh.scene_cy;
+    center_radius[2] = ctx->bvh.scene_cz;
+    center_radius[3] = ctx->bvh.scene_radius;
+  }
+  if (nodes && node_capacity < count) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "node_capacity is smaller than the node count");
+  std::string err;
+  if (entry_boxes && m) {  // the boxes of the resident matrices, by the kernel every device build uses
+    if (!ctx->top_level) ctx->top_level = sthip::device_top_level_create();
+    if (!ctx->top_level_static_valid) {
+      if (!sthip::top_level_set_static(ctx->top_level, ctx->top.merged.data(), n, ctx->top.obj_box.data(), m, ctx->stream, err)) return fail(ctx, STHIP_ERR_HIP, call + err);
+      ctx->top_level_static_valid = true;
+    }
+    sthip::TopLevelInputs in;
+    in.xf = ctx->xf.p;
+    in.inv = ctx->inv_xf.p;
+    in.motion = ctx->motion_xf.p;
+    in.instance_count = n;
+    in.resident_xf = ctx->xf.p;
+    in.entries = ctx->entries.p;
+    in.entry_count = m;
+    in.volumes = ctx->volumes.p;
+    in.volume_count = (uint32_t)std::min<size_t>(ctx->volumes.n, ctx->top.volumes.size());
+    memcpy(in.merged_box, ctx->top.merged_box, sizeof(in.merged_box));
+    in.blas_nodes = blas_nodes;
+    in.build_tree = false;
+    sthip::TopLevelResult res{};
+    float ms = 0;
+    if (!sthip::top_level_build(ctx->top_level, in, ctx->stream, res, ms, err)) return fail(ctx, STHIP_ERR_HIP, call + err);
+    if (!sthip::top_level_read_boxes(ctx->top_level, entry_boxes, m, ctx->stream, err)) return fail(ctx, STHIP_ERR_HIP, call + err);
+  }
+  if (nodes && count) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<BvhNodeSlot> slots(count);
+    HIP_TRY(ctx, hipMemcpy(slots.data(), ctx->nodes.p + blas_nodes, (size_t)count * sizeof(BvhNodeSlot), hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < count; k++) {
+      // a plane with the reference byte in its low mantissa byte: whatever that byte holds the plane lies outside the box, so
+      // the byte is pushed outward here (a lower plane to its least value, an upper plane to its greatest)
+      uint32_t w[8], ref[2] = {0, 0};
+      memcpy(w, slots[k].n.n0xy, 16);
+      memcpy(w + 4, slots[k].n.n1xy, 16);
+      float plane[2][6];
+      for (int c = 0; c < 2; c++) {
+        for (int j = 0; j < 4; j++) {
+          const uint32_t u = w[4 * c + j];
+          ref[c] |= (u & 0xFFu) << (8 * j);
+          const bool upper = (j & 1) != 0, negative = (u >> 31) != 0;
+          const uint32_t out = (upper != negative) ? (u | 0xFFu) : (u & ~0xFFu);
+          memcpy(&plane[c][j], &out, 4);
+        }
+        plane[c][4] = slots[k].n.nz[2 * c];
+        plane[c][5] = slots[k].n.nz[2 * c + 1];
+      }
+      sthip_top_node& o = nodes[k];
+      for (int a = 0; a < 3; a++) {
+        o.lo[a] = std::min(plane[0][2 * a], plane[1][2 * a]);
+        o.hi[a] = std::max(plane[0][2 * a + 1], plane[1][2 * a + 1]);
+      }
+      uint32_t* child[2] = {&o.child0, &o.child1};
+      for (int c = 0; c < 2; c++) *child[c] = (ref[c] & BVH_LEAF_BIT) ? (0x80000000u | (ref[c] & 0xFFFFu)) : ref[c] - blas_nodes;
+    }
+  }
+  return STHIP_OK;
 }
 
 // Where the new vertex records of a refit come from: a range of host records that goes up (sthip_scene_update_vertices), or
@@ -1666,6 +2006,7 @@ static int refit_resident_scene(sthip_ctx* ctx, const VertexSource& src, bool ke
                           ctx->stream, res, err))
     return fail(ctx, STHIP_ERR_HIP, call + err);
   // what an upload derives from the meshes' bounds (bvh_build.cpp), with its arithmetic, from the roots' exact boxes
+  ctx->top_level_static_valid = false;  // (top_level.hip keeps the object boxes on the device: they change here)
   sthip::TopLevelState next = ctx->top;
   for (size_t k = 0; k < next.entries.size(); k++) {
     if (root_of_entry[k] == BVH_INVALID_REF) continue;
@@ -1770,6 +2111,10 @@ static int update_resident_vertices(sthip_ctx* ctx, const VertexSource& src, sth
   // the instances' transforms, for the top level: the kept scene has them (sthip_scene_update_transforms keeps it current);
   // without one they are read back from the device
   const uint32_t n = ctx->instance_count;
+  {  // (a device-pointer call of sthip_scene_set_transforms left the kept matrices behind the device's)
+    const int rc = sync_kept_transforms(ctx);
+    if (rc != STHIP_OK) return rc;
+  }
   std::vector<sthip_TransformData> xf_read, inv_read;
   const sthip_TransformData *xf = nullptr, *inv = nullptr;
   if (ctx->kept.valid && ctx->kept.xf.size() == n && ctx->kept.inv.size() == n) {

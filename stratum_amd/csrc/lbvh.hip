@@ -12,6 +12,7 @@
 #include <mutex>
 
 #include "bvh_build.h"
+#include "radix_tree.h"
 
 namespace sthip {
 namespace {
@@ -77,47 +78,10 @@ __global__ void k_lbvh_morton(const LBox* boxes, uint32_t n, const uint32_t* cbo
   vals[i] = i;
 }
 
-// common-prefix length of the keys at sorted positions i and j; equal keys are told apart by position
-__device__ __forceinline__ int delta(const unsigned long long* keys, int n, int i, int j) {
-  if (j < 0 || j >= n) return -1;
-  const unsigned long long a = keys[i], b = keys[j];
-  if (a == b) return 64 + __clz((uint32_t)i ^ (uint32_t)j);
-  return __clzll(a ^ b);
-}
-
-// Karras 2012, Algorithm: one thread per internal node; children >= n - 1 + ... are encoded as leaf | 0x80000000
+// one thread per internal node (radix_tree.h)
 __global__ void k_lbvh_hierarchy(const unsigned long long* keys, int n, uint32_t* left, uint32_t* right, uint32_t* parent_of_internal, uint32_t* parent_of_leaf) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n - 1) return;
-  const int d = (delta(keys, n, i, i + 1) - delta(keys, n, i, i - 1)) >= 0 ? 1 : -1;
-  const int dmin = delta(keys, n, i, i - d);
-  int lmax = 2;
-  while (delta(keys, n, i, i + lmax * d) > dmin) lmax *= 2;
-  int l = 0;
-  for (int t = lmax / 2; t >= 1; t /= 2)
-    if (delta(keys, n, i, i + (l + t) * d) > dmin) l += t;
-  const int j = i + l * d;
-  const int dnode = delta(keys, n, i, j);
-  int s = 0;
-  int t = l;
-  do {
-    t = (t + 1) >> 1;
-    if (delta(keys, n, i, i + (s + t) * d) > dnode) s += t;
-  } while (t > 1);
-  const int gamma = i + s * d + min(d, 0);
-  const int lo = min(i, j), hi = max(i, j);
-  const uint32_t L = (lo == gamma) ? (0x80000000u | (uint32_t)gamma) : (uint32_t)gamma;
-  const uint32_t R = (hi == gamma + 1) ? (0x80000000u | (uint32_t)(gamma + 1)) : (uint32_t)(gamma + 1);
-  left[i] = L;
-  right[i] = R;
-  if (L & 0x80000000u)
-    parent_of_leaf[gamma] = (uint32_t)i;
-  else
-    parent_of_internal[gamma] = (uint32_t)i;
-  if (R & 0x80000000u)
-    parent_of_leaf[gamma + 1] = (uint32_t)i;
-  else
-    parent_of_internal[gamma + 1] = (uint32_t)i;
+  if (i < n - 1) radix_tree_node(keys, n, i, left, right, parent_of_internal, parent_of_leaf);
 }
 
 // One bottom-up pass: an internal node whose children were finished in an EARLIER launch (done < pass) takes

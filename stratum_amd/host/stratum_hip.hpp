@@ -57,6 +57,10 @@
 #pragma weak sthip_scene_set_images
 #pragma weak sthip_scene_set_material_data
 #pragma weak sthip_scene_read_image_range
+// ... and one that cannot take instance matrices from device memory or build the top level there lacks these
+#pragma weak sthip_scene_set_transforms
+#pragma weak sthip_scene_read_transforms
+#pragma weak sthip_scene_read_top_level
 #pragma weak sthip_accumulate
 #pragma weak sthip_denoise_filter
 #include "../../include/sthip_detmath.h"  // det_f16tof32: export_hdr of a half frame
@@ -885,6 +889,11 @@ class Scene {
     if (on != mEnvironmentOnDevice) mDirty = true;
     mEnvironmentOnDevice = on;
   }
+  // true: the transforms-only branch of BDPT::update has the device build the new top level (sthip_scene_set_transforms with
+  // top_level = 1: a radix tree instead of the host's binned SAH — a cheaper call, a tree of somewhat lower quality, the same
+  // frames). Off by default, and off for good with a library that lacks the call.
+  bool top_level_on_device() const { return mTopLevelOnDevice; }
+  void set_top_level_on_device(bool on) { mTopLevelOnDevice = on && sthip_scene_set_transforms; }
 
   // ---- the material conversions, Scene.cpp:123-256 -> kernels/material_convert.hlsl (sthip_convert_material) ----
   // The scalar part in binary32 as upstream writes it; with an image present the kernels run on cb.ctx (host form), and the
@@ -1193,6 +1202,7 @@ class Scene {
   bool mDirty = true;
   bool mPoseOnDevice = sthip_scene_set_rigs && sthip_scene_animate;
   bool mEnvironmentOnDevice = sthip_scene_set_environment != nullptr;
+  bool mTopLevelOnDevice = false;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1394,6 +1404,25 @@ class BDPT {
   BDPTPushConstants& push_constants() { return mPushConstants; }
   const Frame& prev_result() const { return mPrevFrame; }  // BDPT.hpp:18
   bool last_update_was_transforms_only() const { return mLastUpdateWasTransformsOnly; }
+  // Instance matrices that lie in device memory (rigid bodies, particles, a crowd simulated there) go to the resident scene
+  // without a copy to the host (sthip_scene_set_transforms with device_ptr = 1 and the device-built top level): `xf` =
+  // instance_count sthip_TransformData records readable in the order of the context's stream; `inv` NULL: derived by the
+  // library with transform_inverse's arithmetic; `motion` NULL: the identity, or with derive_motion previous x inverse.
+  // The bound Scene's own matrices do not follow (sthip_scene_read_transforms says what is resident); its next change is
+  // compared against what it held before. Throws on a refusal, a moved instance of the merged mesh without a kept scene included.
+  void set_instance_transforms_device(const void* xf, const void* inv, const void* motion, bool derive_motion) {
+    if (!sthip_scene_set_transforms) throw std::runtime_error("set_instance_transforms_device: the library lacks sthip_scene_set_transforms");
+    if (!mBoundData) throw std::runtime_error("set_instance_transforms_device: no scene is bound");
+    sthip_transforms_desc t{};
+    t.transforms = static_cast<const sthip_TransformData*>(xf);
+    t.inverse_transforms = static_cast<const sthip_TransformData*>(inv);
+    t.motion_transforms = static_cast<const sthip_TransformData*>(motion);
+    t.instance_count = (uint32_t)mBoundData->mInstanceTransforms.size();
+    t.device_ptr = 1;
+    t.top_level = 1;
+    t.derive_motion = derive_motion ? 1u : 0u;
+    if (sthip_scene_set_transforms(mCtx, &t, sizeof(t), nullptr) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_set_transforms: ") + sthip_last_error(mCtx));
+  }
   bool last_update_was_vertices_only() const { return mLastUpdateWasVerticesOnly; }  // (no transform changed with them)
   bool last_update_was_environment_only() const { return mLastUpdateWasEnvironmentOnly; }
   bool last_update_was_materials_only() const { return mLastUpdateWasMaterialsOnly; }
@@ -1491,7 +1520,18 @@ class BDPT {
         return;
       }
     } else if (mBoundData && same_geometry(*mBoundData, *scene->data()) && (!rigs || (mRigsResident && same_poses(*mBoundData, sd)))) {
-      const int rc = sthip_scene_update_transforms(mCtx, d.gInstanceTransforms, d.gInstanceInverseTransforms, d.gInstanceMotionTransforms, d.instance_count);
+      int rc;
+      if (scene->top_level_on_device() && sthip_scene_set_transforms) {  // Scene::set_top_level_on_device: the same matrices, the top level built on the device
+        sthip_transforms_desc t{};
+        t.transforms = d.gInstanceTransforms;
+        t.inverse_transforms = d.gInstanceInverseTransforms;
+        t.motion_transforms = d.gInstanceMotionTransforms;
+        t.instance_count = d.instance_count;
+        t.top_level = 1;
+        rc = sthip_scene_set_transforms(mCtx, &t, sizeof(t), nullptr);
+      } else {
+        rc = sthip_scene_update_transforms(mCtx, d.gInstanceTransforms, d.gInstanceInverseTransforms, d.gInstanceMotionTransforms, d.instance_count);
+      }
       if (rc == STHIP_OK)
         updated = true;
       else if (rc != STHIP_ERR_UNSUPPORTED)

@@ -465,6 +465,36 @@ IMAGE_UPDATE_BYTES = 32  # sizeof(sthip_image_update), include/sthip.h
 assert C.sizeof(ImageUpdate) == IMAGE_UPDATE_BYTES and C.sizeof(ImagesInfo) == 24
 
 
+class TransformsDesc(C.Structure):  # sthip_transforms_desc
+    _fields_ = [
+        ("transforms", C.c_void_p),
+        ("inverse_transforms", C.c_void_p),
+        ("motion_transforms", C.c_void_p),
+        ("instance_count", C.c_uint32),
+        ("device_ptr", C.c_uint32),
+        ("top_level", C.c_uint32),
+        ("derive_motion", C.c_uint32),
+    ]
+
+
+class TransformsInfo(C.Structure):  # sthip_transforms_info
+    _fields_ = [
+        ("device_ms", C.c_float),
+        ("total_ms", C.c_float),
+        ("top_level_nodes", C.c_uint32),
+        ("top_level_depth", C.c_uint32),
+        ("rebuilt", C.c_uint32),
+        ("builder_used", C.c_uint32),
+    ]
+
+
+TRANSFORMS_DESC_BYTES = 40  # sizeof(sthip_transforms_desc), include/sthip.h
+assert C.sizeof(TransformsDesc) == TRANSFORMS_DESC_BYTES and C.sizeof(TransformsInfo) == 24
+# sthip_top_node: the union of a top-level node's two child boxes and its children (a node index, or 0x80000000 | entry)
+TopNode = np.dtype([("lo", np.float32, 3), ("child0", np.uint32), ("hi", np.float32, 3), ("child1", np.uint32)])
+assert TopNode.itemsize == 32
+
+
 class ConvertMaterialDesc(C.Structure):
     _fields_ = [
         ("kind", C.c_uint32),
