@@ -1,4 +1,6 @@
-// api.hip — the C ABI of include/sthip.h: context, scene upload, the per-frame launch sequence.
+// api.hip — the C ABI of include/sthip.h: context, scene upload, the edits of a resident scene, the per-frame launch sequence
+// (the calls after the path and the ceilings: post.hip; the context struct both units share: context.h). The one unit that
+// compiles and launches the kernels of kernels.h.
 //
 // sthip_render is the replacement of the dispatch sequence BDPT::render records
 // (src/Node/BDPT.cpp:607-720: fill gShadowRays, dispatch sample_visibility, barrier, dispatch
@@ -21,18 +23,15 @@
 
 #include "../../include/sthip.h"
 #include "animate.h"
-#include "denoise.h"
 #include "environment.h"
 #include "bvh_build.h"
 #include "first_hits.h"
 #include "image_range.h"
-#include "material_convert.h"
 #include "kernel_instances.h"  // kernels.h + the instantiations that live in shade_*.hip / trace_kernels.hip
 #include "mips.h"
-#include "post.h"
 #include "scene_prepare.h"
 #include "top_level.h"
-#include "ceilings.h"
+#include "context.h"
 
 STHIP_DECLARE_KERNEL_INSTANCES
 
@@ -44,429 +43,7 @@ hipError_t hashgrid_build_device(const uint2* keys, const uint32_t* count, uint3
                                  size_t& tmp_bytes, hipStream_t stream, bool force_serial = false);  // hashgrid.hip
 }
 
-namespace {
-thread_local std::string g_create_error;
-
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }  // an early return (HIP_TRY) must not leak a local staging buffer
-  hipError_t ensure(size_t count) {
-    if (count <= n && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    if (count == 0) return hipSuccess;
-    hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-    if (e == hipSuccess) n = count;
-    // tests: STHIP_POISON_ALLOC=<byte> fills every new device buffer with that byte, so that a read of something nothing has
-    // written shows in a fresh process too (where new device memory is zero pages) and not only once the heap is recycled
-    static const int poison = [] {
-      const char* v = getenv("STHIP_POISON_ALLOC");
-      return v && *v ? (int)(strtoul(v, nullptr, 0) & 0xFFu) : -1;
-    }();
-    if (e == hipSuccess && poison >= 0) e = hipMemset(p, poison, count * sizeof(T));
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
-// The unpacked nodes the host keeps (treetop selection, top-level rebuilds): page-locked, so that the device-resident
-// builder's one node copy runs at PCIe speed, and never zero-filled
-struct PinnedNodes {
-  BvhNode* p = nullptr;
-  size_t n = 0, cap = 0;
-  PinnedNodes() = default;
-  PinnedNodes(const PinnedNodes&) = delete;
-  PinnedNodes& operator=(const PinnedNodes&) = delete;
-  ~PinnedNodes() {
-    if (p) (void)hipHostFree(p);
-  }
-  hipError_t ensure(size_t count) {  // capacity only; contents are lost when it grows
-    if (count <= cap && p) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = n = 0;
-    hipError_t e = hipHostMalloc((void**)&p, std::max<size_t>(1, count) * sizeof(BvhNode), hipHostMallocDefault);
-    if (e == hipSuccess) cap = std::max<size_t>(1, count);
-    return e;
-  }
-  bool empty() const { return n == 0; }
-  size_t size() const { return n; }
-  BvhNode* data() { return p; }
-};
-}  // namespace
-
-// The scene as it was uploaded, kept on the host ("keep_scene" = 1, the default): what a change that the resident tree cannot
-// follow — an instance of the merged world-space mesh that moves — is rebuilt from, inside sthip_scene_update_transforms
-// (the reference rebuilds whatever is dirty, Scene.cpp:345,435-459,614-629: it has the scene graph to rebuild from).
-struct KeptScene {
-  std::vector<sthip_PackedVertexData> vertices;
-  std::vector<uint8_t> indices, materials;
-  std::vector<sthip_InstanceData> instances;
-  std::vector<sthip_TransformData> xf, inv, motion;
-  std::vector<uint32_t> lights;
-  std::vector<std::vector<float>> image_pixels, image1_pixels;
-  std::vector<std::vector<uint8_t>> image_bytes, image1_bytes;  // the 8-bit images, as they came: bytes (the float vector of such an image stays empty)
-  std::vector<uint8_t> image_formats, image1_formats;           // sthip_image_format per image (sthip_scene_upload_formats)
-  std::vector<sthip_image_desc> images, images1;
-  std::vector<float> distributions;
-  std::vector<std::vector<uint8_t>> volume_bytes;
-  std::vector<sthip_volume_desc> volumes;
-  bool valid = false;
-  void keep(const sthip_scene_desc& s, const uint8_t* formats, const uint8_t* formats1) {
-    vertices.assign(s.gVertices, s.gVertices + (s.gVertices ? s.vertex_count : 0));
-    indices.assign((const uint8_t*)s.gIndices, (const uint8_t*)s.gIndices + (s.gIndices ? s.indices_bytes : 0));
-    materials.assign((const uint8_t*)s.gMaterialData, (const uint8_t*)s.gMaterialData + (s.gMaterialData ? s.material_bytes : 0));
-    instances.assign(s.gInstances, s.gInstances + s.instance_count);
-    xf.assign(s.gInstanceTransforms, s.gInstanceTransforms + s.instance_count);
-    inv.assign(s.gInstanceInverseTransforms, s.gInstanceInverseTransforms + s.instance_count);
-    motion.clear();
-    if (s.gInstanceMotionTransforms) motion.assign(s.gInstanceMotionTransforms, s.gInstanceMotionTransforms + s.instance_count);
-    lights.assign(s.gLightInstances, s.gLightInstances + (s.gLightInstances ? s.light_count : 0));
-    auto take = [](const sthip_image_desc* in, uint32_t n, size_t channels, const uint8_t* formats, std::vector<std::vector<float>>& px, std::vector<std::vector<uint8_t>>& bytes, std::vector<uint8_t>& fmt,
-                   std::vector<sthip_image_desc>& d) {
-      px.assign(n, {});
-      bytes.assign(n, {});
-      fmt.assign(n, 0);
-      d.assign(n, sthip_image_desc{});
-      for (uint32_t i = 0; i < n; i++) {
-        const size_t count = (size_t)in[i].width * in[i].height * channels;
-        fmt[i] = formats ? formats[i] : 0;
-        if (fmt[i]) {  // 8-bit: `pixels` points at bytes
-          const uint8_t* b = reinterpret_cast<const uint8_t*>(in[i].pixels);
-          bytes[i].assign(b, b + count);
-          d[i] = sthip_image_desc{reinterpret_cast<const float*>(bytes[i].data()), in[i].width, in[i].height};
-        } else {
-          px[i].assign(in[i].pixels, in[i].pixels + count);
-          d[i] = sthip_image_desc{px[i].data(), in[i].width, in[i].height};
-        }
-      }
-    };
-    take(s.gImages, s.gImages ? s.image_count : 0, 4, formats, image_pixels, image_bytes, image_formats, images);
-    take(s.gImage1s, s.gImage1s ? s.image1_count : 0, 1, formats1, image1_pixels, image1_bytes, image1_formats, images1);
-    distributions.assign(s.gDistributions, s.gDistributions + (s.gDistributions ? s.distribution_count : 0));
-    volume_bytes.assign(s.gVolumes ? s.volume_count : 0, {});
-    volumes.assign(volume_bytes.size(), sthip_volume_desc{});
-    for (size_t i = 0; i < volume_bytes.size(); i++) {
-      volume_bytes[i].assign((const uint8_t*)s.gVolumes[i].data, (const uint8_t*)s.gVolumes[i].data + s.gVolumes[i].bytes);
-      volumes[i] = sthip_volume_desc{volume_bytes[i].data(), s.gVolumes[i].bytes};
-    }
-    valid = true;
-  }
-  void set_transforms(const sthip_TransformData* new_xf, const sthip_TransformData* new_inv, const sthip_TransformData* new_motion, uint32_t n) {  // (motion NULL: identity)
-    xf.assign(new_xf, new_xf + n);
-    inv.assign(new_inv, new_inv + n);
-    motion.clear();
-    if (new_motion) motion.assign(new_motion, new_motion + n);
-  }
-  sthip_scene_desc desc() const {
-    sthip_scene_desc d{};
-    d.gVertices = vertices.data();
-    d.vertex_count = (uint32_t)vertices.size();
-    d.gIndices = indices.data();
-    d.indices_bytes = (uint32_t)indices.size();
-    d.gInstances = instances.data();
-    d.instance_count = (uint32_t)instances.size();
-    d.gInstanceTransforms = xf.data();
-    d.gInstanceInverseTransforms = inv.data();
-    d.gInstanceMotionTransforms = motion.empty() ? nullptr : motion.data();
-    d.gMaterialData = materials.data();
-    d.material_bytes = (uint32_t)materials.size();
-    d.gLightInstances = lights.data();
-    d.light_count = (uint32_t)lights.size();
-    d.gImages = images.empty() ? nullptr : images.data();
-    d.image_count = (uint32_t)images.size();
-    d.gDistributions = distributions.empty() ? nullptr : distributions.data();
-    d.distribution_count = (uint32_t)distributions.size();
-    d.gImage1s = images1.empty() ? nullptr : images1.data();
-    d.image1_count = (uint32_t)images1.size();
-    d.gVolumes = volumes.empty() ? nullptr : volumes.data();
-    d.volume_count = (uint32_t)volumes.size();
-    return d;
-  }
-};
-
-// One frame in flight of sthip_render_async: a device staging set of the five images, the copy of the call's view arrays in
-// pinned memory (the arguments are borrowed for the call only), the frame's counters on the device and in a pinned record,
-// and the two events that order it: `rendered` on the render stream, `copied` on the copy stream.
-struct AsyncSlot {
-  DevBuf<float4> radiance, albedo;
-  DevBuf<sthip_VisibilityInfo> visibility;
-  DevBuf<sthip_DepthInfo> depth;
-  DevBuf<float2> prev_uv;
-  DevBuf<unsigned long long> counters;
-  size_t key[3] = {0, 0, 0};  // (pixels, radiance entries, bytes per colour entry) the set was allocated for
-  uint8_t* params = nullptr;  // pinned: gViews | gViewTransforms | gPrevViews | gPrevInverseViewTransforms | gInverseViewTransforms | gViewMediumInstances
-  size_t params_cap = 0;
-  unsigned long long* record = nullptr;  // pinned: CNT_TOTAL counters of the frame
-  hipEvent_t rendered = nullptr, copied = nullptr;
-  uint64_t ticket = 0;            // the ticket in flight in this slot, 0 = free
-  uint64_t* ray_count = nullptr;  // the caller's gRayCount: written from `record` when the ticket is retired
-  AsyncSlot() = default;
-  AsyncSlot(const AsyncSlot&) = delete;
-  AsyncSlot& operator=(const AsyncSlot&) = delete;
-  ~AsyncSlot() {
-    if (params) (void)hipHostFree(params);
-    if (record) (void)hipHostFree(record);
-    if (rendered) (void)hipEventDestroy(rendered);
-    if (copied) (void)hipEventDestroy(copied);
-  }
-  void release_images() {
-    radiance.release();
-    albedo.release();
-    visibility.release();
-    depth.release();
-    prev_uv.release();
-    key[0] = key[1] = key[2] = 0;
-  }
-};
-
-struct sthip_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string error;
-  int cu_count = 256;
-  // scene
-  bool has_scene = false;
-  bool textured = false;      // some material binds an image: k_shade<true> (ray cones, image values, normal maps)
-  bool has_alpha = false;     // some triangle material has an alpha mask (gImage1s)
-  bool has_spheres = false;   // some instance is a sphere: k_shade<., true>
-  bool has_volumes = false;   // some instance is a volume (a Medium): the media instantiations
-  uint32_t volume_count = 0, volume_instances = 0;
-  std::vector<uint8_t> instance_is_volume;
-  sthip::TopLevelState top;  // what sthip_scene_update_transforms rebuilds the top level from
-  KeptScene kept;            // ... and what it rebuilds everything from when the top level alone cannot follow the change
-  bool keep_scene = true;    // "keep_scene"
-  size_t nodes_capacity = 0;
-  DevBuf<uint32_t> volume_words;
-  DevBuf<DeviceVolume> volumes;
-  std::vector<uint8_t> materials_host;                    // gMaterialData as uploaded (validation of the environment record)
-  std::vector<std::pair<uint32_t, uint32_t>> image_dims;  // (width, height) of gImages
-  uint32_t distribution_count = 0;
-  bool has_specular = false;  // some material satisfies DisneyMaterial::is_specular (disney_material.hlsli:125)
-  DevBuf<sthip_PackedVertexData> vertices;
-  DevBuf<uint8_t> indices;
-  DevBuf<sthip_InstanceData> instances;
-  DevBuf<sthip_TransformData> xf, inv_xf, motion_xf;
-  DevBuf<uint8_t> materials;
-  DevBuf<uint32_t> lights;
-  DevBuf<DeviceImage> images;
-  DevBuf<float4> image_texels;
-  DevBuf<uint32_t> image_texels8;        // the RGBA8 images' texels (a word per texel), every level; DeviceImage::offset indexes it for them
-  std::vector<DeviceImage> images_host;  // the table as uploaded (sthip_scene_read_image; the environment's format at render)
-  uint32_t image_count = 0;
-  DevBuf<float2> cone;
-  uint32_t instance_count = 0, light_count = 0;
-  DevBuf<BvhNodeSlot> nodes;
-  DevBuf<BvhTri> tris;
-  DevBuf<TlasEntry> entries;
-  DevBuf<WideNode> wide_nodes;
-  DevBuf<TlasEntry> wide_entries;
-  DevBuf<Wide8Node> wide8_nodes;
-  DevBuf<TlasEntry> wide8_entries;
-  std::vector<Wide8Node> wide8_host;  // the 8-wide nodes as uploaded: a transforms-only update makes the top level's again behind the bottom levels'
-  size_t wide8_node_count = 0;
-  uint32_t tri_min_lanes = 1;  // "tri_min_lanes" (DeviceBvh::wide8_tri_min)
-  DeviceBvh bvh{};
-  uint64_t bvh_nodes = 0, bvh_tris = 0;
-  // treetop (bvh_build.h): rebuilt whenever the top level changes; needs the nodes on the host
-  PinnedNodes nodes_host;
-  DevBuf<BvhNode> raw_nodes;  // device-resident build only: the unpacked nodes before their one copy to nodes_host
-  DevBuf<BvhNodePacked> top_nodes;
-  DevBuf<TlasEntry> top_entries;
-  bool use_treetop = false;  // "treetop": measured +1.5 % before k_trace's loop lost its other exec-mask regions, -0.5 % after
-  // host builds: leaf triangles in the node array behind their parent (bvh_build.h: BuiltBvh::embedded). Measured on the
-  // bench scene: k_trace 2.30 ms either way (the leaf fetch is not what a step waits for), so off: two arrays are simpler
-  bool embed_leaves = false;
-  // "wide_bvh": k_trace walks the 4-wide form of the tree (takes effect at the next sthip_scene_upload). 1 (default) = always:
-  // host-built trees are collapsed on the host, GPU-built ones and the trees of a transforms-only update on the device
-  // (wide.hip). 0 = never (the binary walk every other kernel uses), 2 = only when the binary nodes do not fit one XCD's L2
-  // (4 MiB). Bench scene: k_trace -20 % against the binary walk; instanced forest (a 2.6 MB tree): equal.
-  // 3 = the 8-wide compressed form (bvh.h: Wide8Node) for host-built trees (collapsed on the host, at upload and at every
-  // transforms-only update); trees it cannot take (GPU-built ones, embedded leaves) get the 4-wide form as with 1.
-  int use_wide = 1;
-  size_t wide_node_count = 0;
-  sthip::DeviceWideScratch* wide_scratch = nullptr;  // buffers of the device-side collapse (wide.hip), kept between calls
-  // sthip_scene_set_transforms (top_level.hip): the staging and scratch of the device path; whether its per-entry tables are
-  // those of the resident tree; whether the host's copies of the matrices (the kept scene, top.entries[k].inv) are older
-  // than the device's — a device-pointer call or a derived array left them behind (sync_kept_transforms)
-  sthip::DeviceTopLevel* top_level = nullptr;
-  bool top_level_static_valid = false;
-  bool host_transforms_stale = false;
-  // sthip_scene_update_vertices (refit.hip): the schedule of the resident bottom levels and the refit's scratch; what the
-  // call needs to know of the uploaded arrays; whether the resident layout is one the refit serves
-  sthip::DeviceRefit* refit = nullptr;
-  // the distinct bottom-level roots of the resident entries and each entry's place among them (BVH_INVALID_REF: an entry
-  // without a bottom level): they belong to the resident tree, as the schedule does, and are made with it
-  std::vector<uint32_t> refit_roots, refit_root_of_entry;
-  bool refit_roots_valid = false;
-  uint32_t vertex_count = 0;
-  uint64_t indices_bytes = 0;
-  // sthip_scene_set_rigs / sthip_scene_animate (animate.hip): the rigs as they are resident — per rig its range of gVertices
-  // and where its records start in the arrays below (rest poses and weights: one record per rigged vertex, in rig order;
-  // targets: target_count x vertex_count records per rig; bones: bone_count per rig, staged on the host by every animate call)
-  struct ResidentRig {
-    uint32_t first = 0, count = 0, target_count = 0, bone_count = 0;
-    size_t at = 0, targets_at = 0, bones_at = 0;
-  };
-  std::vector<ResidentRig> rigs;
-  DevBuf<sthip_PackedVertexData> rig_rest, rig_targets;
-  DevBuf<sthip_VertexWeight> rig_weights;
-  DevBuf<sthip_TransformData> rig_bones;
-  std::vector<sthip_TransformData> rig_bones_host;
-  std::vector<std::array<float, 4>> rig_factors;  // of the animate call in progress
-  hipEvent_t rig_ev[2] = {nullptr, nullptr};      // around the k_animate launches of a call (sthip_refit_info::device_ms); around the work of sthip_scene_set_environment
-  // ranges [first, end) of the kept scene's vertices that an animate call left behind the device's: read back before anything
-  // is built from the kept scene (sync_kept_vertices)
-  std::vector<std::pair<uint32_t, uint32_t>> kept_stale;
-  // sthip_scene_set_environment (environment.hip): which images of gImages a material record names (their texels decided the
-  // kernels: the call does not replace them), the s[y] of the rows and the rows' integrals between the passes, and what of the
-  // kept scene the call left behind the device's (fetched before anything is built from the kept scene: sync_kept_environment)
-  std::vector<uint8_t> image_in_material;
-  DevBuf<double> env_sines;
-  DevBuf<float> env_integrals;
-  uint32_t env_rows_per_wave = sthip::ENV_ROWS_PER_WAVE_DEFAULT;  // "env_rows_per_wave": 16 or 64 (environment.h)
-  bool kept_env_tables_stale = false;
-  // the images of the kept scene (gImages / gImage1s, in either format) whose texels came from a device pointer and are
-  // newer on the device than in the kept copy (sthip_scene_set_environment, sthip_scene_set_images)
-  std::set<uint32_t> kept_images_stale, kept_images1_stale;
-  // sthip_scene_set_images / sthip_scene_set_material_data (image_range.hip): what the material analysis needs to run again
-  // without the scene's arrays — per instance its material address and type (whatever "keep_scene" says), per image of gImages
-  // the range of its level 0 as far as somebody scanned it — the alpha masks' table as uploaded, and the scan's buffers
-  std::vector<sthip::MaterialInstance> material_instances;
-  std::vector<sthip::ImageRange> image_ranges;
-  std::vector<DeviceImage1> images1_host;
-  DevBuf<uint32_t> range_partials, range_results;
-  uint32_t image_range_blocks = 0;  // "image_range_blocks": 0 = from cu_count
-  bool embedded_resident = false;  // the leaf triangles lie in the node array (BuiltBvh::embedded)
-  bool want_wide = false;                            // the current scene is walked in its 4-wide form (decided at upload)
-  bool lds_materials = true;  // k_shade stages gMaterialData in LDS when it fits 32 KB
-  // frame
-  DevBuf<uint8_t> views;  // gViews | gViewTransforms | gPrevViews | gPrevInverseViewTransforms
-  DevBuf<float4> ray_o, ray_d, hit, beta, radiance, shadow_sum, accum, shadow_rays, light_vertices, conn, media_state, shadow_hit, shadow_ext, shadow_result;
-  DevBuf<uint32_t> view_medium;
-  DevBuf<uint32_t> meta, queue0, queue1, queue_kept;
-  // "cull_terminal": 1 (default) = in a round where paths can reach their last vertex, k_cull_terminal hands k_shade only the
-  // paths that still have something to do (kernels.h); 0 = k_shade sees the whole queue. Same frames either way.
-  int cull_terminal = 1;
-  DevBuf<unsigned long long> counters;
-  DevBuf<float> distributions;  // gDistributions
-  DevBuf<float4> presampled;    // gPresampledLights
-  DevBuf<float4> bdpt;          // BDPT quantities per path (eConnectToViews)
-  DevBuf<float4> rr;  // eCoherentRR: probes / group verdicts of the round in flight (FrameParams::rr)
-  DevBuf<uint2> cs_nee, cs_lvc;  // eCoherentSampling: probes / group values of the round in flight (FrameParams::cs_nee, cs_lvc)
-  DevBuf<float4> lvc_staging, path_contrib;  // eLVC: staged light vertices, the light paths' path_contrib (eLVCReservoirs)
-  DevBuf<uint32_t> lvc_count, lvc_flags, lvc_offsets;
-  DevBuf<uint8_t> lvc_tmp;
-  // eNEEReservoirReuse: the append stage and its compaction, the keys / destinations of the host-side probing, the grid
-  DevBuf<float4> hg_appends, hg_compact, hg_data;
-  DevBuf<uint32_t> hg_count, hg_flags, hg_offsets, hg_dest, hg_checksums, hg_counters, hg_indices;
-  DevBuf<uint32_t> hg_owner, hg_bucket_of, hg_append, hg_sorted_bucket, hg_sorted_append;  // scratch of the device-side grid build (hashgrid.hip)
-  DevBuf<unsigned long long> hg_key64, hg_sorted_key64;
-  DevBuf<uint2> hg_keys;
-  DevBuf<uint8_t> hg_tmp;
-  DevBuf<float4> lg_appends, lg_compact, lg_data;  // eLVCReservoirReuse: the same for gLVCHashGrid (keys / flags / tmp are shared)
-  DevBuf<uint32_t> lg_checksums, lg_counters, lg_indices;
-  DevBuf<uint32_t> light_trace; // gLightTraceSamples
-  DevBuf<DeviceImage1> images1;  // gImage1s (alpha masks)
-  DevBuf<float> image1_texels;
-  DevBuf<uint8_t> image1_texels8;  // the R8 masks' texels
-  DevBuf<BvhTriUv> tri_uvs;
-  DevBuf<BvhTriShade> tri_shade;  // beside the leaf triangles: their vertices' normals and uvs (k_fill_tri_shade)
-  DevBuf<uint32_t> hit_leaf;      // per path: the leaf triangle of its hit
-  DevBuf<uint32_t> shade_stack;   // media without eDeferShadowRays: a traversal stack column per k_shade thread (visibility_walk_media)
-  DevBuf<float4> debug, out_debug, shadow_debug;  // BDPTDebugMode: per-path pixel of gDebugImage, the image's staging (host pointers), the debug halves of inline shadow rays
-  DevBuf<uint32_t> inst_alpha;
-  DevBuf<uint8_t> inst_flags;  // per instance: INST_FLAG_* of its (untextured) material, for k_cull_terminal
-  std::vector<uint8_t> inst_flags_host;
-  // "answer_last_rays": 1 (default) = the last ray of a path is only queued if it can reach the bounds of an emissive instance
-  // (kernels.h: aims_at_emitter); 0 = every ray is queued and traced. Same frames and ray counts either way.
-  int answer_last_rays = 1;
-  DevBuf<EmitterBounds> emitters;
-  std::vector<EmitterBounds> emitters_host;  // the table as uploaded (sthip_scene_update_vertices makes its boxes again)
-  uint32_t emitter_count = 0;  // 0: not applicable to this scene (no or too many emissive triangle instances)
-  DevBuf<unsigned long long> qctl;  // queue control lines (queue_ctl)
-  DevBuf<uint32_t> post_scratch;  // maxima / metric accumulator of post.h
-  DevBuf<float4> denoise_guide;   // sthip_denoise_filter: {n.x, n.y, n.z, z} per pixel, grows with the largest extent seen
-  uint32_t denoise_block = 0;     // "denoise_block": 0 = 32x8 lanes per block, 1 = 16x16
-  DevBuf<sthip_ray> ray_staging;  // sthip_trace_rays with host pointers
-  DevBuf<sthip_hit> hit_staging;
-  DevBuf<float4> out_radiance, out_albedo;  // staging of the colour images (out_debug too): color_bytes() per entry, so 16 B entries hold 1 or 2
-  DevBuf<float4> albedo_stage;  // half colour precision: k_shade's binary32 albedo, which k_resolve rounds into the RGBA16F image
-  // "half_color_precision": the colour images of sthip_render and of the post calls are RGBA16F (8 B per pixel) instead of RGBA32F
-  bool half_color = false;
-  size_t color_bytes() const { return half_color ? 8 : 16; }
-  DevBuf<sthip_VisibilityInfo> out_visibility;
-  DevBuf<sthip_DepthInfo> out_depth;
-  DevBuf<float2> out_prev_uv;
-  uint32_t shard_rank = 0, shard_count = 1, tile_w = 64, tile_h = 32;
-  // options / stats
-  bool count_traversal = false, time_kernels = false;
-  bool hashgrid_serial = false;  // "hashgrid_serial": build the reuse grids with the one-thread probe sequence (hashgrid.hip's rare-case path; tests)
-  // "reuse_grids_persist": the grids the LAST seed of a call leaves are what the FIRST seed of the next call looks into — upstream's
-  // previous frame for a host that renders one frame per call (BDPT.cpp:482-483,621-627). The key says what they were built for.
-  bool reuse_persist = false, reuse_grids_valid = false;
-  uint64_t reuse_key[3] = {0, 0, 0};
-  uint32_t refill_idle = 16, inner_min_lanes = 24, trace_blocks_per_cu = 0;
-  uint64_t max_paths_in_flight = 1ull << 22;  // (sthip_create sizes it to the device: 2^26 on a 288 GB MI355X — launches large enough that their
-                                              // tails stop mattering: atrium x 8 seeds +7 %, forest at 4K x 16 +38 % over 2^22; tools/in_flight_sweep.py)
-  bool packet_primary = true;  // the first bounce is traced as wave packets (k_trace_primary)
-  // "reuse_first_hits" (first_hits.h): the hits of the first bounce do not depend on the seed, so the packet kernel's output
-  // for ONE seed's paths is kept here (20 B per path, allocated at first use; a call renders without them if that fails) and
-  // the kernel runs again only when the key of a call differs from the key they were traced for. `scene_serial` counts the
-  // calls that can move a triangle, an instance or an alpha mask. The pair (valid, key) changes only where the launch that
-  // fills the buffers is enqueued (run_batches: past the point where a render is tried again), or where the hits are dropped.
-  bool reuse_first_hits = true, first_hits_valid = false;
-  uint64_t scene_serial = 0;
-  sthip::FirstHitKey first_hit_key{};
-  DevBuf<float4> first_hit;
-  DevBuf<uint32_t> first_hit_leaf;
-  bool fuse_trace = true;  // closest-hit rays of a bounce and the shadow rays of the previous one in one launch
-  int bvh_builder = 0;  // sthip::BvhBuilderKind
-  uint32_t sah_top_size = 64;  // "sah_top" (measured 32 .. 16384: 64 traces fastest): the GPU builder's subtrees of at most this many triangles get a host-built SAH top (0: off)
-  int lbvh_algorithm = 1, ploc_radius = 4;  // of the GPU builder (bvh_build.h: DeviceBuildTarget); radius measured: 4 traces fastest (2 .. 32 tried)
-  // levels of the per-lane LDS traversal stack at most; a higher tree runs the BOUNDED instantiations (traverse.h) with the
-  // full stack of an overflowing ray in global memory (spill)
-  // measured (atrium, PLOC tree 40 high): the bounded instantiation costs ~2.5 % per step, a fourth resident block is worth
-  // ~13 %, a treetop ~3 %: so the whole stack stays in LDS as long as four blocks of it fit (40 levels = 160 KB per CU)
-  uint32_t lds_stack_threshold = 40, lds_stack_cap = 32;
-  DevBuf<uint32_t> spill;
-  DevBuf<float4> deep_rays;  // rays that overflowed a bounded LDS stack (k_trace_deep), and their count
-  DevBuf<uint32_t> deep_count;
-  sthip_stats stats{};
-  hipError_t last_hip_error = hipSuccess;  // of the last failed HIP_TRY (sthip_render halves its batch after an out-of-memory)
-  bool render_launched = false;            // the render call in progress has enqueued work (no second attempt from here on)
-  bool stats_pending = false;  // ray / traversal counters of the last render still live on the device
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  // sthip_render_async: "output_ring" staging sets (made at the first submit), the copy stream, tickets issued / retired
-  uint32_t output_ring = 2;
-  std::vector<AsyncSlot*> ring;
-  hipStream_t copy_stream = nullptr;
-  uint64_t next_ticket = 1, retired = 0;
-  // a finished frame whose slot a later submit took over before its ticket was waited for: its counters and the caller's gRayCount
-  struct FinishedFrame {
-    std::vector<unsigned long long> counters;
-    uint64_t* ray_count = nullptr;
-  };
-  std::map<uint64_t, FinishedFrame> finished;
-  std::vector<void*> host_allocs;  // sthip_host_alloc
-};
-
-// The traversal stack is stack_depth x 1 KB of dynamic LDS per 256-thread block. Up to 64 KB needs nothing; beyond it
-// (deep LBVH trees of clustered scenes) the kernels must be told (hipFuncAttributeMaxDynamicSharedMemorySize), and the
-// CU holds fewer blocks. 152 KB leaves room for the runtime's own LDS use.
-#define STHIP_MAX_STACK_LDS ((size_t)152 * 1024)
-// Trees higher than the LDS cap (lds_stack_levels) keep only that many levels in LDS; the rare ray that needs more is traced
-// again with a global-memory stack of the tree's full height — bounded here so that the spill buffer stays small
-#define STHIP_MAX_STACK_DEPTH 512u
+static thread_local std::string g_create_error;
 
 // The instantiations that exist, by key (kernel_variants.h): made from the lists the definitions are compiled from, so that a
 // variant outside them has no entry here — a lookup that finds none is the caller's error, not an instantiation in this file
@@ -503,15 +80,6 @@ static void launch_kernel(const void* fn, uint32_t grid, size_t lds, hipStream_t
   (void)hipLaunchKernel(fn, dim3(grid), dim3(STHIP_BLOCK), ptrs, lds, st);
 }
 
-#define HIP_TRY(ctx, expr)                                                                            \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess) {                                                                           \
-      (ctx)->error = std::string(#expr) + ": " + hipGetErrorString(_e);                               \
-      (ctx)->last_hip_error = _e;                                                                     \
-      return STHIP_ERR_HIP;                                                                           \
-    }                                                                                                 \
-  } while (0)
 
 static void fill_counter_stats(sthip_ctx* ctx, const unsigned long long* c) {
   ctx->stats.rays_total = c[CNT_RAYS_CLOSEST] + c[CNT_RAYS_SHADOW];
@@ -535,10 +103,6 @@ static void fill_counter_stats(sthip_ctx* ctx, const unsigned long long* c) {
 
 static uint32_t grid_for(const sthip_ctx* ctx, size_t n);
 
-static int fail(sthip_ctx* ctx, int code, const std::string& msg) {
-  ctx->error = msg;
-  return code;
-}
 
 // ---- frames in flight of sthip_render_async ----
 static AsyncSlot* slot_of(sthip_ctx* ctx, uint64_t ticket) { return ctx->ring[ticket % ctx->ring.size()]; }
@@ -596,6 +160,133 @@ static void release_ring(sthip_ctx* ctx) {
   for (AsyncSlot* s : ctx->ring) delete s;
   ctx->ring.clear();
 }
+
+// Nothing is in flight any more: the caller's stream has been waited for, and the frames of sthip_render_async are complete.
+// What a call does before it writes what frames in flight still read.
+static int quiesce(sthip_ctx* ctx) {
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, drain_in_flight(ctx));
+  return STHIP_OK;
+}
+
+// ---- the steps the edit calls share ----
+// The two events around the device work of an edit, made at first use
+static int make_edit_events(sthip_ctx* ctx) {
+  for (int k = 0; k < 2; k++)
+    if (!ctx->edit_ev[k]) HIP_TRY(ctx, hipEventCreate(&ctx->edit_ev[k]));
+  return STHIP_OK;
+}
+// device_ms between the two events (the stream has been waited for) and total_ms since the call began
+template <typename Info>
+static void fill_edit_times(sthip_ctx* ctx, Info* info, std::chrono::steady_clock::time_point t0) {
+  info->device_ms = 0;
+  (void)hipEventElapsedTime(&info->device_ms, ctx->edit_ev[0], ctx->edit_ev[1]);
+  info->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// `bytes` of gMaterialData from `offset` on: the host mirror, the device array (in stream order) and the kept scene
+static int write_material_bytes(sthip_ctx* ctx, size_t offset, const void* data, size_t bytes, hipStream_t st) {
+  memcpy(ctx->materials_host.data() + offset, data, bytes);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->materials.p + offset, ctx->materials_host.data() + offset, bytes, hipMemcpyHostToDevice, st));
+  if (ctx->kept.valid && ctx->kept.materials.size() == ctx->materials_host.size()) memcpy(ctx->kept.materials.data() + offset, data, bytes);
+  return STHIP_OK;
+}
+
+// Level 0 of gImages[index] (`mask`: of gImage1s[index]) from `pixels`, host or device memory, in the format the image is resident in
+static int copy_image_level0(sthip_ctx* ctx, bool mask, uint32_t index, const void* pixels, bool device_ptr, hipStream_t st) {
+  const hipMemcpyKind kind = device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (mask) {
+    const DeviceImage1& im = ctx->images1_host[index];
+    const size_t texels = (size_t)im.w * im.h;
+    if (im.format == STHIP_IMAGE_FORMAT_R8_UNORM)
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->image1_texels8.p + im.offset, pixels, texels, kind, st));
+    else
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->image1_texels.p + im.offset, pixels, texels * 4, kind, st));
+    return STHIP_OK;
+  }
+  const DeviceImage& im = ctx->images_host[index];
+  const size_t texels = (size_t)im.w[0] * im.h[0];
+  if (im.format == STHIP_IMAGE_FORMAT_RGBA8_UNORM)
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->image_texels8.p + im.offset[0], pixels, texels * 4, kind, st));
+  else
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->image_texels.p + im.offset[0], pixels, texels * 16, kind, st));
+  return STHIP_OK;
+}
+// ... and the levels above it, each one launch over the level before it (mips.hip)
+static int rebuild_image_mips(sthip_ctx* ctx, uint32_t index, hipStream_t st, const char* call) {
+  const DeviceImage& im = ctx->images_host[index];
+  const bool rgba8 = im.format == STHIP_IMAGE_FORMAT_RGBA8_UNORM;
+  std::string err;
+  for (uint32_t level = 0; level + 1 < im.levels; level++) {
+    const bool ok = rgba8 ? sthip::mip_rgba8_launch(ctx->image_texels8.p + im.offset[level], im.w[level], im.h[level], ctx->image_texels8.p + im.offset[level + 1], ctx->cu_count, st, err)
+                          : sthip::mip_rgba32f_launch(ctx->image_texels.p + im.offset[level], im.w[level], im.h[level], ctx->image_texels.p + im.offset[level + 1], ctx->cu_count, st, err);
+    if (!ok) return fail(ctx, STHIP_ERR_HIP, std::string(call) + ": " + err);
+  }
+  return STHIP_OK;
+}
+// The kept copy of that image follows: host pixels are copied and the copy is current; device pixels leave it stale
+// (sync_kept_environment fetches them before anything is built from the kept scene)
+static void kept_image_follows(sthip_ctx* ctx, bool mask, uint32_t index, const void* pixels, bool device_ptr) {
+  if (!ctx->kept.valid) return;
+  std::vector<std::vector<float>>& floats = mask ? ctx->kept.image1_pixels : ctx->kept.image_pixels;
+  std::vector<std::vector<uint8_t>>& bytes = mask ? ctx->kept.image1_bytes : ctx->kept.image_bytes;
+  std::set<uint32_t>& stale = mask ? ctx->kept.stale_images1 : ctx->kept.stale_images;
+  if (index >= floats.size() || index >= bytes.size()) return;
+  if (device_ptr) {
+    stale.insert(index);
+    return;
+  }
+  const size_t values = mask ? (size_t)ctx->images1_host[index].w * ctx->images1_host[index].h : (size_t)ctx->images_host[index].w[0] * ctx->images_host[index].h[0] * 4;
+  if (bytes[index].size() == values) memcpy(bytes[index].data(), pixels, values);
+  if (floats[index].size() == values) memcpy(floats[index].data(), pixels, values * 4);
+  stale.erase(index);
+}
+
+// Measurement only (sthip.h; tools/environment_times.py, tools/material_update_times.py): HIP events at the borders of a call's
+// stages, and one JSON line per call appended to the file an environment variable names. The variable is read once per
+// process (each variable has its accessor, all of one shape); without it no event is made and no file touched.
+static const char* times_file(const char* variable) {
+  const char* v = getenv(variable);
+  return v && *v ? v : nullptr;
+}
+static const char* environment_times_file() {  // STHIP_ENVIRONMENT_TIMES=<file>: one line per table-building call with the HIP-event time of each stage
+  static const char* const path = times_file("STHIP_ENVIRONMENT_TIMES");
+  return path;
+}
+struct StageTimer {
+  enum { MAX_EVENTS = 8 };
+  hipEvent_t ev[MAX_EVENTS] = {};  // ev[k]: recorded when stage k is enqueued (a stage the call skips is recorded where it would stand: 0 ms)
+  const char* path;
+  int events;
+  bool on = false;
+  StageTimer(const char* path, bool wanted, int events) : path(path), events(events) {
+    if (!path || !wanted || events > MAX_EVENTS) return;
+    on = true;  // (a failure to make an event only loses the measurement)
+    for (int k = 0; k < events; k++) on = on && hipEventCreate(&ev[k]) == hipSuccess;
+  }
+  StageTimer(const StageTimer&) = delete;
+  ~StageTimer() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  void mark(int k, hipStream_t st) {
+    if (on) (void)hipEventRecord(ev[k], st);
+  }
+  // after the stream has been waited for: {<head>, "<names[k]>": <ms from event k to event k + 1>, ...}
+  void write(const std::string& head, const char* const* names) {
+    if (!on) return;
+    if (FILE* f = fopen(path, "a")) {
+      fprintf(f, "{%s", head.c_str());
+      for (int k = 0; k + 1 < events; k++) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+        fprintf(f, ", \"%s\": %.5f", names[k], ms);
+      }
+      fprintf(f, "}\n");
+      fclose(f);
+    }
+  }
+};
 
 extern "C" {
 
@@ -666,7 +357,7 @@ void sthip_destroy(sthip_ctx* ctx) {
   sthip::device_refit_destroy(ctx->refit);
   ctx->refit = nullptr;
   for (int k = 0; k < 2; k++)
-    if (ctx->rig_ev[k]) (void)hipEventDestroy(ctx->rig_ev[k]);
+    if (ctx->edit_ev[k]) (void)hipEventDestroy(ctx->edit_ev[k]);
   ctx->vertices.release();
   ctx->volume_words.release();
   ctx->volumes.release();
@@ -936,30 +627,15 @@ static void drop_rigs(sthip_ctx* ctx) {
 // The kept scene's vertices are current again: the ranges an animate call wrote on the device come back to the host. Called
 // immediately before anything is built from the kept scene.
 static int sync_kept_vertices(sthip_ctx* ctx) {
-  if (ctx->kept_stale.empty()) return STHIP_OK;
+  if (ctx->kept.stale_vertices.empty()) return STHIP_OK;
   if (ctx->kept.valid && ctx->kept.vertices.size() == ctx->vertex_count && ctx->vertices.p) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (k_animate runs on the stream; the copy below does not wait for a non-blocking one)
-    for (const auto& r : ctx->kept_stale)
+    for (const auto& r : ctx->kept.stale_vertices)
       if (r.first < r.second && r.second <= ctx->vertex_count)
         HIP_TRY(ctx, hipMemcpy(ctx->kept.vertices.data() + r.first, ctx->vertices.p + r.first, (size_t)(r.second - r.first) * sizeof(sthip_PackedVertexData), hipMemcpyDeviceToHost));
   }
-  ctx->kept_stale.clear();
+  ctx->kept.stale_vertices.clear();
   return STHIP_OK;
-}
-// The host wrote the kept records [first, first + count): they are not stale any more
-static void kept_vertices_written(sthip_ctx* ctx, uint32_t first, uint32_t count) {
-  if (ctx->kept_stale.empty() || !count) return;
-  const uint32_t end = first + count;
-  std::vector<std::pair<uint32_t, uint32_t>> left;
-  for (const auto& r : ctx->kept_stale) {
-    if (end <= r.first || r.second <= first) {
-      left.push_back(r);
-      continue;
-    }
-    if (r.first < first) left.emplace_back(r.first, first);
-    if (end < r.second) left.emplace_back(end, r.second);
-  }
-  ctx->kept_stale.swap(left);
 }
 
 // The k_animate launches of an animate call: the bones staged in rig_bones_host go up, then one launch per rig. From the
@@ -970,10 +646,10 @@ static int pose_rigs(sthip_ctx* ctx, const char* call) {
   if (ctx->kept.valid)
     for (const auto& r : ctx->rigs) {
       if (!r.count) continue;
-      kept_vertices_written(ctx, r.first, r.count);  // (what is left of the range from earlier calls: one entry per range, however often it is posed)
-      ctx->kept_stale.emplace_back(r.first, r.first + r.count);
+      ctx->kept.vertices_written(r.first, r.count);  // (what is left of the range from earlier calls: one entry per range, however often it is posed)
+      ctx->kept.stale_vertices.emplace_back(r.first, r.first + r.count);
     }
-  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[0], ctx->stream));
+  HIP_TRY(ctx, hipEventRecord(ctx->edit_ev[0], ctx->stream));
   for (size_t k = 0; k < ctx->rigs.size(); k++) {
     const sthip_ctx::ResidentRig& r = ctx->rigs[k];
     sthip::AnimateRig a;
@@ -991,7 +667,7 @@ static int pose_rigs(sthip_ctx* ctx, const char* call) {
     std::string err;
     if (!sthip::animate_launch(a, ctx->cu_count, ctx->stream, err)) return fail(ctx, STHIP_ERR_HIP, std::string(call) + ": " + err);
   }
-  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[1], ctx->stream));
+  HIP_TRY(ctx, hipEventRecord(ctx->edit_ev[1], ctx->stream));
   return STHIP_OK;
 }
 
@@ -999,10 +675,10 @@ static int pose_rigs(sthip_ctx* ctx, const char* call) {
 // sthip_scene_set_images) and tables that were built on the device come back to the host. Called immediately before anything is
 // built from the kept scene.
 static int sync_kept_environment(sthip_ctx* ctx) {
-  if (ctx->kept_images_stale.empty() && ctx->kept_images1_stale.empty() && !ctx->kept_env_tables_stale) return STHIP_OK;
+  if (ctx->kept.stale_images.empty() && ctx->kept.stale_images1.empty() && !ctx->kept.stale_env_tables) return STHIP_OK;
   if (ctx->kept.valid && ctx->has_scene) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (const uint32_t i : ctx->kept_images_stale) {  // level 0, in the format the image is resident and kept in
+    for (const uint32_t i : ctx->kept.stale_images) {  // level 0, in the format the image is resident and kept in
       if (i >= ctx->images_host.size() || i >= ctx->kept.image_pixels.size()) continue;
       const DeviceImage& im = ctx->images_host[i];
       const size_t texels = (size_t)im.w[0] * im.h[0];
@@ -1012,7 +688,7 @@ static int sync_kept_environment(sthip_ctx* ctx) {
         HIP_TRY(ctx, hipMemcpy(ctx->kept.image_pixels[i].data(), ctx->image_texels.p + im.offset[0], texels * 16, hipMemcpyDeviceToHost));
       }
     }
-    for (const uint32_t i : ctx->kept_images1_stale) {
+    for (const uint32_t i : ctx->kept.stale_images1) {
       if (i >= ctx->images1_host.size() || i >= ctx->kept.image1_pixels.size()) continue;
       const DeviceImage1& im = ctx->images1_host[i];
       const size_t texels = (size_t)im.w * im.h;
@@ -1022,18 +698,23 @@ static int sync_kept_environment(sthip_ctx* ctx) {
         HIP_TRY(ctx, hipMemcpy(ctx->kept.image1_pixels[i].data(), ctx->image1_texels.p + im.offset, texels * 4, hipMemcpyDeviceToHost));
       }
     }
-    if (ctx->kept_env_tables_stale && ctx->kept.distributions.size() == ctx->distribution_count && ctx->distribution_count)
+    if (ctx->kept.stale_env_tables && ctx->kept.distributions.size() == ctx->distribution_count && ctx->distribution_count)
       HIP_TRY(ctx, hipMemcpy(ctx->kept.distributions.data(), ctx->distributions.p, (size_t)ctx->distribution_count * sizeof(float), hipMemcpyDeviceToHost));
   }
-  ctx->kept_images_stale.clear();
-  ctx->kept_images1_stale.clear();
-  ctx->kept_env_tables_stale = false;
+  ctx->kept.stale_images.clear();
+  ctx->kept.stale_images1.clear();
+  ctx->kept.stale_env_tables = false;
   return STHIP_OK;
 }
 
-// What the kept copy is built again from: the kept arrays with the formats their images were uploaded in.
+// What the kept copy is built again from: the kept arrays with the formats their images were uploaded in. The one place that
+// brings the kept scene up to date with the device first: vertices, transforms, environment.
 static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t* image_formats, const uint8_t* image1_formats);
 static int upload_kept_scene(sthip_ctx* ctx) {
+  {  // (ranges an animate call posed on the device: the rebuild must see them)
+    const int rc = sync_kept_vertices(ctx);
+    if (rc != STHIP_OK) return rc;
+  }
   {  // (matrices a device-pointer call of sthip_scene_set_transforms left newer than the kept copy)
     const int rc = sync_kept_transforms(ctx);
     if (rc != STHIP_OK) return rc;
@@ -1073,8 +754,8 @@ static int retire_scene(sthip_ctx* ctx, const sthip_scene_desc* s) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // frames of the previous scene may still be in flight on the caller's stream (device output pointers: sthip_render only
   // enqueues), and the copies of the upload go through the null stream, which a non-blocking stream does not wait for
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, drain_in_flight(ctx));  // ... and the copy stream of sthip_render_async still reads the staging sets of its frames
+  // ... and the copy stream of sthip_render_async still reads the staging sets of its frames
+  if (const int rc = quiesce(ctx); rc != STHIP_OK) return rc;
   ctx->has_scene = false;
   ctx->scene_serial++;  // (first_hits.h: from here on the resident triangles are not the ones kept hits were traced against)
   sthip::device_refit_invalidate(ctx->refit);  // (the schedule of a refit belongs to the tree that goes away now)
@@ -1082,7 +763,7 @@ static int retire_scene(sthip_ctx* ctx, const sthip_scene_desc* s) {
   // the rigs name vertex ranges of the scene that goes away; a rebuild from the kept copy is the same scene and keeps them
   if (!(ctx->kept.valid && s->gVertices && s->gVertices == ctx->kept.vertices.data())) {
     drop_rigs(ctx);
-    ctx->kept_stale.clear();
+    ctx->kept.stale_vertices.clear();
   }
   return STHIP_OK;
 }
@@ -1413,13 +1094,12 @@ static int scene_upload(sthip_ctx* ctx, const sthip_scene_desc* s, const uint8_t
   ctx->has_scene = true;
   ctx->reuse_grids_valid = false;  // (stored samples name materials and lights of the scene they were taken in)
   if (ctx->keep_scene) {
-    if (s->gVertices != ctx->kept.vertices.data() || !ctx->kept.valid) ctx->kept.keep(*s, image_formats, image1_formats);  // (a rebuild from the kept copy itself keeps nothing anew)
+    // (a rebuild from the kept copy itself keeps nothing anew; its stale marks are clear already: upload_kept_scene, the only
+    // caller that passes the kept arrays, has run the three syncs, and each clears its marks)
+    if (s->gVertices != ctx->kept.vertices.data() || !ctx->kept.valid) ctx->kept.keep(*s, image_formats, image1_formats);
   } else {
     ctx->kept = KeptScene();
   }
-  ctx->kept_images_stale.clear();  // (what is kept now is what is resident)
-  ctx->kept_images1_stale.clear();
-  ctx->kept_env_tables_stale = false;
   if (getenv("STHIP_VERBOSE"))
     fprintf(stderr, "[sthip] bvh (%s): %zu nodes, %zu tris, %zu top-level entries, stack depth %u (%zu B LDS / block%s, treetop %u nodes), %d trace blocks / CU, build %.1f ms (GPU kernels %.2f ms)\n",
             ctx->bvh_builder ? "lbvh/gpu" : "sah/host", (size_t)ctx->bvh_nodes, (size_t)ctx->bvh_tris, built.entries.size(), built.stack_depth, stack_bytes(ctx), ctx->bvh.spill ? ", bounded" : "", ctx->bvh.top_count,
@@ -1638,10 +1318,6 @@ static int update_transforms_host(sthip_ctx* ctx, const std::string& call, const
     // the scene is built again from the copy kept at upload, with the new transforms — the configured builder ("bvh_builder" = 1:
     // ~10 ms per million triangles on the device), everything else as uploaded. Without the copy ("keep_scene" = 0) it is refused.
     if (ctx->kept.valid && ctx->kept.instances.size() == instance_count) {
-      {  // (ranges an animate call posed on the device: the rebuild must see them)
-        const int rc = sync_kept_vertices(ctx);
-        if (rc != STHIP_OK) return rc;
-      }
       ctx->kept.set_transforms(xf, inv, motion, instance_count);
       ctx->host_transforms_stale = false;  // (all three arrays of the kept scene are the call's now; the upload makes the entries)
       ctx->stats.full_rebuilds++;
@@ -1652,8 +1328,8 @@ static int update_transforms_host(sthip_ctx* ctx, const std::string& call, const
   }
   if (stack_depth > STHIP_MAX_STACK_DEPTH) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "the new top level is too deep for the traversal stack");
   if ((size_t)next.blas_nodes + tlas.size() > ctx->nodes.n) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "the new top level does not fit: upload the scene again");
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old top level
-  HIP_TRY(ctx, drain_in_flight(ctx));               // (sthip_render_async: their copies too, so that their tickets are complete)
+  // frames in flight still read the old top level (sthip_render_async: their copies too, so that their tickets are complete)
+  if (const int rc = quiesce(ctx); rc != STHIP_OK) return rc;
   const uint32_t n = instance_count;
   HIP_TRY(ctx, hipMemcpy(ctx->xf.p, xf, (size_t)n * 48, hipMemcpyHostToDevice));
   HIP_TRY(ctx, hipMemcpy(ctx->inv_xf.p, inv, (size_t)n * 48, hipMemcpyHostToDevice));
@@ -1693,8 +1369,7 @@ static int set_transforms_device(sthip_ctx* ctx, const std::string& call, const 
     ctx->top_level_static_valid = true;
   }
   // ---- frames in flight still read the resident arrays; the work below reads them too (entries, the previous transforms) ----
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, drain_in_flight(ctx));
+  if (const int rc = quiesce(ctx); rc != STHIP_OK) return rc;
   sthip::TopLevelInputs in;
   in.xf = xf;
   in.inv = inv;
@@ -1726,10 +1401,6 @@ static int set_transforms_device(sthip_ctx* ctx, const std::string& call, const 
       HIP_TRY(ctx, hipMemcpy(hx.data(), tmp.p, (size_t)n * 48, hipMemcpyDeviceToHost));
       HIP_TRY(ctx, hipMemcpy(hi.data(), tmp.p + n, (size_t)n * 48, hipMemcpyDeviceToHost));
       HIP_TRY(ctx, hipMemcpy(hm.data(), tmp.p + 2 * (size_t)n, (size_t)n * 48, hipMemcpyDeviceToHost));
-      {
-        const int rc = sync_kept_vertices(ctx);
-        if (rc != STHIP_OK) return rc;
-      }
       ctx->kept.set_transforms(hx.data(), hi.data(), hm.data(), n);
       ctx->host_transforms_stale = false;
       ctx->stats.full_rebuilds++;
@@ -1990,7 +1661,7 @@ static int refit_resident_scene(sthip_ctx* ctx, const VertexSource& src, bool ke
     const uint32_t first_vertex = src.first_vertex, vertex_count = src.vertex_count;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->vertices.p + first_vertex, vertices, (size_t)vertex_count * sizeof(sthip_PackedVertexData), hipMemcpyHostToDevice, ctx->stream));
     if (kept && vertices != ctx->kept.vertices.data() + first_vertex) memcpy(ctx->kept.vertices.data() + first_vertex, vertices, (size_t)vertex_count * sizeof(sthip_PackedVertexData));
-    if (kept) kept_vertices_written(ctx, first_vertex, vertex_count);
+    if (kept) ctx->kept.vertices_written(first_vertex, vertex_count);
   }
   ctx->reuse_grids_valid = false;
   ctx->nodes_host.n = 0;  // (no layout that reads the host copy of the nodes comes this way; it must not outlive the boxes it holds)
@@ -2059,11 +1730,9 @@ static int update_resident_vertices(sthip_ctx* ctx, const VertexSource& src, sth
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->scene_serial++;  // (first_hits.h: sthip_scene_update_vertices and sthip_scene_animate both come this way)
   const bool kept = ctx->kept.valid && ctx->kept.vertices.size() == ctx->vertex_count;
-  auto rebuild_from_kept = [&]() {  // (the kept vertices hold the new range already, or get the posed ranges back from the device here)
-    int rc = sync_kept_vertices(ctx);
-    if (rc != STHIP_OK) return rc;
+  auto rebuild_from_kept = [&]() {  // (the kept vertices hold the new range already, or get the posed ranges back from the device there)
     ctx->stats.full_rebuilds++;
-    rc = upload_kept_scene(ctx);
+    const int rc = upload_kept_scene(ctx);
     if (info) {
       info->rebuilt = 1;
       info->device_ms = ctx->stats.bvh_build_gpu_ms;
@@ -2072,13 +1741,11 @@ static int update_resident_vertices(sthip_ctx* ctx, const VertexSource& src, sth
     return rc;
   };
   if (src.posed())
-    for (int k = 0; k < 2; k++)
-      if (!ctx->rig_ev[k]) HIP_TRY(ctx, hipEventCreate(&ctx->rig_ev[k]));
+    if (const int rc = make_edit_events(ctx); rc != STHIP_OK) return rc;
   if (ctx->embedded_resident || ctx->use_treetop || ctx->bvh.top_count || ctx->bvh.wide8_nodes || !ctx->wide8_host.empty()) {
     if (!kept) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "this layout (embed_leaves, treetop, wide_bvh = 3) is not refitted and no scene was kept (keep_scene = 0): upload the scene again");
     if (src.posed()) {  // the kernel, then the rebuild reads its ranges back
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      HIP_TRY(ctx, drain_in_flight(ctx));
+      if (const int rc = quiesce(ctx); rc != STHIP_OK) return rc;
       const int rc = pose_rigs(ctx, src.call);
       if (rc != STHIP_OK) return rc;
     } else if (src.vertex_count) {
@@ -2103,8 +1770,8 @@ static int update_resident_vertices(sthip_ctx* ctx, const VertexSource& src, sth
     ctx->refit_roots_valid = true;
   }
   if (!ctx->refit) ctx->refit = sthip::device_refit_create();
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old triangles and boxes
-  HIP_TRY(ctx, drain_in_flight(ctx));               // (sthip_render_async: their copies too, so that their tickets are complete)
+  // frames in flight still read the old triangles and boxes (sthip_render_async: their copies too, so that their tickets are complete)
+  if (const int rc = quiesce(ctx); rc != STHIP_OK) return rc;
   std::string err;
   if (!sthip::refit_prepare(ctx->refit, ctx->nodes.p, ctx->top.blas_nodes, ctx->refit_roots, ctx->top.blas_depth, ctx->tris.p, (uint32_t)ctx->bvh_tris, STHIP_MAX_EMITTER_BOUNDS, ctx->stream, err))
     return fail(ctx, STHIP_ERR_HIP, call + err);
@@ -2145,7 +1812,7 @@ static int update_resident_vertices(sthip_ctx* ctx, const VertexSource& src, sth
   }
   if (info) {
     float pose_ms = 0;  // (refit_boxes has waited for the stream: the events around k_animate have been reached)
-    if (src.posed()) (void)hipEventElapsedTime(&pose_ms, ctx->rig_ev[0], ctx->rig_ev[1]);
+    if (src.posed()) (void)hipEventElapsedTime(&pose_ms, ctx->edit_ev[0], ctx->edit_ev[1]);
     info->device_ms = pose_ms + res.gpu_ms + wide_ms;
     info->sah_cost = (float)res.sah_cost;
     info->sah_cost_at_build = (float)res.sah_cost_at_build;
@@ -2318,63 +1985,27 @@ int sthip_scene_set_environment(sthip_ctx* ctx, const sthip_environment_desc* d,
     HIP_TRY(ctx, ctx->env_sines.ensure(plan.height));
     HIP_TRY(ctx, ctx->env_integrals.ensure(plan.height));
   }
-  for (int k = 0; k < 2; k++)
-    if (!ctx->rig_ev[k]) HIP_TRY(ctx, hipEventCreate(&ctx->rig_ev[k]));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old environment
-  HIP_TRY(ctx, drain_in_flight(ctx));               // (sthip_render_async: their copies too, so that their tickets are complete)
-  ctx->reuse_grids_valid = false;                   // (stored samples carry radiance of the environment they were taken in)
+  if ((rc = make_edit_events(ctx)) != STHIP_OK) return rc;
+  // frames in flight still read the old environment (sthip_render_async: their copies too, so that their tickets are complete)
+  if ((rc = quiesce(ctx)) != STHIP_OK) return rc;
+  ctx->reuse_grids_valid = false;  // (stored samples carry radiance of the environment they were taken in)
   hipStream_t st = ctx->stream;
-  const size_t addr = d->material_address;
-  // measurement (sthip.h, tools/environment_times.py): STHIP_ENVIRONMENT_TIMES=<file> gets one line per table-building call
-  // with the HIP-event time of each stage. The variable is read once per process; without it no event is made here.
-  static const char* const times_path = [] {
-    const char* v = getenv("STHIP_ENVIRONMENT_TIMES");
-    return v && *v ? v : nullptr;
-  }();
   enum Stage { STAGE_BEGIN, STAGE_COPY, STAGE_MIPS, STAGE_SINES, STAGE_ROWS, STAGE_MARGINAL, STAGE_NORMALISE, STAGE_COUNT };
-  struct StageEvents {  // ev[k]: recorded when stage k is enqueued (a stage the call skips is recorded where it would stand: 0 ms)
-    hipEvent_t ev[STAGE_COUNT] = {};
-    bool on = false;
-    ~StageEvents() {
-      for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    }
-  } stages;
-  if (times_path && plan.build_tables) {  // (a failure to make one only loses the measurement)
-    stages.on = true;
-    for (hipEvent_t& e : stages.ev) stages.on = stages.on && hipEventCreate(&e) == hipSuccess;
-  }
-  auto stage_done = [&](Stage k) {
-    if (stages.on) (void)hipEventRecord(stages.ev[k], st);
-  };
-  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[0], st));
-  stage_done(STAGE_BEGIN);
-  if (plan.set_value) {
-    memcpy(ctx->materials_host.data() + addr, d->value, 12);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->materials.p + addr, ctx->materials_host.data() + addr, 12, hipMemcpyHostToDevice, st));
-    if (ctx->kept.valid && ctx->kept.materials.size() == ctx->materials_host.size()) memcpy(ctx->kept.materials.data() + addr, d->value, 12);
-  }
+  StageTimer stages(environment_times_file(), plan.build_tables, STAGE_COUNT);
+  HIP_TRY(ctx, hipEventRecord(ctx->edit_ev[0], st));
+  stages.mark(STAGE_BEGIN, st);
+  if (plan.set_value && (rc = write_material_bytes(ctx, d->material_address, d->value, 12, st)) != STHIP_OK) return rc;
   std::string err;
   if (plan.replace_pixels) {
-    const DeviceImage& im = ctx->images_host[plan.image_index];
-    const size_t bytes = (size_t)plan.width * plan.height * 16;
     // (no record names the image now, but one may have and may again: a range kept from the old texels is forgotten, so that
     // sthip_scene_set_material_data scans the new ones when a record binds the image)
     if (plan.image_index < ctx->image_ranges.size()) ctx->image_ranges[plan.image_index] = sthip::ImageRange();
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->image_texels.p + im.offset[0], d->pixels, bytes, d->device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    stage_done(STAGE_COPY);
-    for (uint32_t level = 0; level + 1 < im.levels; level++)
-      if (!sthip::mip_rgba32f_launch(ctx->image_texels.p + im.offset[level], im.w[level], im.h[level], ctx->image_texels.p + im.offset[level + 1], ctx->cu_count, st, err))
-        return fail(ctx, STHIP_ERR_HIP, "sthip_scene_set_environment: " + err);
-    stage_done(STAGE_MIPS);
-    if (ctx->kept.valid && plan.image_index < ctx->kept.image_pixels.size() && ctx->kept.image_pixels[plan.image_index].size() == bytes / 4) {
-      if (d->device_ptr) {
-        ctx->kept_images_stale.insert(plan.image_index);
-      } else {
-        memcpy(ctx->kept.image_pixels[plan.image_index].data(), d->pixels, bytes);
-        ctx->kept_images_stale.erase(plan.image_index);
-      }
-    }
+    // (the general path of sthip_scene_set_images: the format is the resident image's, which check_environment found to be RGBA32F)
+    if ((rc = copy_image_level0(ctx, false, plan.image_index, d->pixels, d->device_ptr != 0, st)) != STHIP_OK) return rc;
+    stages.mark(STAGE_COPY, st);
+    if ((rc = rebuild_image_mips(ctx, plan.image_index, st, "sthip_scene_set_environment")) != STHIP_OK) return rc;
+    stages.mark(STAGE_MIPS, st);
+    kept_image_follows(ctx, false, plan.image_index, d->pixels, d->device_ptr != 0);
   }
   if (plan.build_tables) {
     const DeviceImage& im = ctx->images_host[plan.image_index];
@@ -2390,39 +2021,24 @@ int sthip_scene_set_environment(sthip_ctx* ctx, const sthip_environment_desc* d,
     t.marginal_cdf = ctx->distributions.p + plan.table[2];
     t.row_cdf = ctx->distributions.p + plan.table[3];
     if (!plan.replace_pixels) {
-      stage_done(STAGE_COPY);
-      stage_done(STAGE_MIPS);
+      stages.mark(STAGE_COPY, st);
+      stages.mark(STAGE_MIPS, st);
     }
-    stage_done(STAGE_SINES);
+    stages.mark(STAGE_SINES, st);
     bool ok = sthip::env_rows_launch(t, ctx->env_rows_per_wave, st, err);
-    stage_done(STAGE_ROWS);
+    stages.mark(STAGE_ROWS, st);
     ok = ok && sthip::env_marginal_launch(t, st, err);
-    stage_done(STAGE_MARGINAL);
+    stages.mark(STAGE_MARGINAL, st);
     ok = ok && sthip::env_normalise_launch(t, st, err);
-    stage_done(STAGE_NORMALISE);
+    stages.mark(STAGE_NORMALISE, st);
     if (!ok) return fail(ctx, STHIP_ERR_HIP, "sthip_scene_set_environment: " + err);
-    if (ctx->kept.valid && ctx->kept.distributions.size() == ctx->distribution_count) ctx->kept_env_tables_stale = true;
+    if (ctx->kept.valid && ctx->kept.distributions.size() == ctx->distribution_count) ctx->kept.stale_env_tables = true;
   }
-  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[1], st));
+  HIP_TRY(ctx, hipEventRecord(ctx->edit_ev[1], st));
   HIP_TRY(ctx, hipStreamSynchronize(st));  // (`sines` and a pageable `pixels` array are the caller's again from here on)
-  if (stages.on) {
-    static const char* names[STAGE_COUNT - 1] = {"copy_ms", "mips_ms", "sines_ms", "k_env_rows_ms", "k_env_marginal_ms", "k_env_normalise_ms"};
-    if (FILE* f = fopen(times_path, "a")) {
-      fprintf(f, "{\"rows_per_wave\": %u", ctx->env_rows_per_wave);
-      for (int k = 0; k + 1 < STAGE_COUNT; k++) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, stages.ev[k], stages.ev[k + 1]);
-        fprintf(f, ", \"%s\": %.5f", names[k], ms);
-      }
-      fprintf(f, "}\n");
-      fclose(f);
-    }
-  }
-  if (info) {
-    info->device_ms = 0;
-    (void)hipEventElapsedTime(&info->device_ms, ctx->rig_ev[0], ctx->rig_ev[1]);
-    info->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
+  static const char* const stage_names[STAGE_COUNT - 1] = {"copy_ms", "mips_ms", "sines_ms", "k_env_rows_ms", "k_env_marginal_ms", "k_env_normalise_ms"};
+  stages.write("\"rows_per_wave\": " + std::to_string(ctx->env_rows_per_wave), stage_names);
+  if (info) fill_edit_times(ctx, info, t0);
   return STHIP_OK;
 }
 
@@ -2465,48 +2081,22 @@ static int fetch_image_ranges(sthip_ctx* ctx, const std::vector<uint32_t>& scan,
   }
   return STHIP_OK;
 }
-// Measurement only (sthip.h, tools/material_update_times.py): with STHIP_MATERIAL_TIMES=<file> (read once per process) every call
-// that scans appends one JSON line with the HIP-event time of its k_image_range launches alone. Without the variable no event
-// is made here and no file touched.
-struct RangeTimes {
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool on = false;
-  static const char* path() {
-    static const char* const p = [] {
-      const char* v = getenv("STHIP_MATERIAL_TIMES");
-      return v && *v ? v : nullptr;
-    }();
-    return p;
-  }
-  explicit RangeTimes(bool scans) {
-    if (!scans || !path()) return;
-    on = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;  // (a failure to make one only loses the measurement)
-  }
-  ~RangeTimes() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  void mark(int k, hipStream_t st) {
-    if (on) (void)hipEventRecord(ev[k], st);
-  }
-  void write(const char* call, size_t images, uint32_t blocks) {  // after the stream has been waited for
-    if (!on) return;
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-    if (FILE* f = fopen(path(), "a")) {
-      fprintf(f, "{\"call\": \"%s\", \"images\": %zu, \"blocks\": %u, \"k_image_range_ms\": %.5f}\n", call, images, blocks, ms);
-      fclose(f);
-    }
-  }
-};
+// STHIP_MATERIAL_TIMES=<file> (StageTimer): every call that scans appends one line with the HIP-event time of its
+// k_image_range launches alone
+static const char* material_times_file() {
+  static const char* const path = times_file("STHIP_MATERIAL_TIMES");
+  return path;
+}
+static void write_range_times(StageTimer& times, const char* call, size_t images, uint32_t blocks) {
+  static const char* const names[1] = {"k_image_range_ms"};
+  times.write("\"call\": \"" + std::string(call) + "\", \"images\": " + std::to_string(images) + ", \"blocks\": " + std::to_string(blocks), names);
+}
 static sthip::MaterialAnalysis analyse_resident_materials(const sthip_ctx* ctx) {
   return sthip::analyse_materials(ctx->material_instances.data(), (uint32_t)ctx->material_instances.size(), ctx->materials_host.data(), (uint32_t)ctx->image_ranges.size(), ctx->image_ranges.data());
 }
 static void fill_images_info(sthip_ctx* ctx, sthip_images_info* info, bool before, size_t scanned, std::chrono::steady_clock::time_point t0) {
   if (!info) return;
-  info->device_ms = 0;
-  (void)hipEventElapsedTime(&info->device_ms, ctx->rig_ev[0], ctx->rig_ev[1]);
-  info->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  fill_edit_times(ctx, info, t0);
   info->has_specular_before = before ? 1u : 0u;
   info->has_specular_after = ctx->has_specular ? 1u : 0u;
   info->images_scanned = (uint32_t)scanned;
@@ -2541,10 +2131,8 @@ int sthip_scene_set_images(sthip_ctx* ctx, const sthip_image_update* entries, ui
     }
   }
   if ((rc = reserve_image_ranges(ctx, scan.size(), blocks)) != STHIP_OK) return rc;
-  for (int k = 0; k < 2; k++)
-    if (!ctx->rig_ev[k]) HIP_TRY(ctx, hipEventCreate(&ctx->rig_ev[k]));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old texels
-  HIP_TRY(ctx, drain_in_flight(ctx));
+  if ((rc = make_edit_events(ctx)) != STHIP_OK) return rc;
+  if ((rc = quiesce(ctx)) != STHIP_OK) return rc;  // frames in flight still read the old texels
   ctx->reuse_grids_valid = false;         // (stored samples carry the old materials' radiance)
   if (mask_changed) ctx->scene_serial++;  // (first_hits.h: the alpha test decides first hits; images of gImages alone move none)
   // the range the context holds for a replaced image is the old texels': forgotten here, and made again below for the images
@@ -2552,59 +2140,22 @@ int sthip_scene_set_images(sthip_ctx* ctx, const sthip_image_update* entries, ui
   for (uint32_t k = 0; k < n; k++)
     if (!entries[k].which && entries[k].index < ctx->image_ranges.size()) ctx->image_ranges[entries[k].index] = sthip::ImageRange();
   hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[0], st));
-  std::string err;
+  HIP_TRY(ctx, hipEventRecord(ctx->edit_ev[0], st));
   for (uint32_t k = 0; k < n; k++) {
     const sthip_image_update& e = entries[k];
-    const hipMemcpyKind kind = e.device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (e.which) {
-      const DeviceImage1& im = ctx->images1_host[e.index];
-      const size_t texels = (size_t)im.w * im.h;
-      if (im.format == STHIP_IMAGE_FORMAT_R8_UNORM)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->image1_texels8.p + im.offset, e.pixels, texels, kind, st));
-      else
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->image1_texels.p + im.offset, e.pixels, texels * 4, kind, st));
-      continue;
-    }
-    const DeviceImage& im = ctx->images_host[e.index];
-    const size_t texels = (size_t)im.w[0] * im.h[0];
-    const bool rgba8 = im.format == STHIP_IMAGE_FORMAT_RGBA8_UNORM;
-    if (rgba8)
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->image_texels8.p + im.offset[0], e.pixels, texels * 4, kind, st));
-    else
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->image_texels.p + im.offset[0], e.pixels, texels * 16, kind, st));
-    for (uint32_t level = 0; level + 1 < im.levels; level++) {
-      const bool ok = rgba8 ? sthip::mip_rgba8_launch(ctx->image_texels8.p + im.offset[level], im.w[level], im.h[level], ctx->image_texels8.p + im.offset[level + 1], ctx->cu_count, st, err)
-                            : sthip::mip_rgba32f_launch(ctx->image_texels.p + im.offset[level], im.w[level], im.h[level], ctx->image_texels.p + im.offset[level + 1], ctx->cu_count, st, err);
-      if (!ok) return fail(ctx, STHIP_ERR_HIP, "sthip_scene_set_images: " + err);
-    }
+    if ((rc = copy_image_level0(ctx, e.which != 0, e.index, e.pixels, e.device_ptr != 0, st)) != STHIP_OK) return rc;
+    if (!e.which && (rc = rebuild_image_mips(ctx, e.index, st, "sthip_scene_set_images")) != STHIP_OK) return rc;
   }
-  RangeTimes times(!scan.empty());
+  StageTimer times(material_times_file(), !scan.empty(), 2);
   times.mark(0, st);
   if ((rc = enqueue_image_ranges(ctx, scan, st, "sthip_scene_set_images")) != STHIP_OK) return rc;
   times.mark(1, st);
-  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[1], st));
+  HIP_TRY(ctx, hipEventRecord(ctx->edit_ev[1], st));
   if ((rc = fetch_image_ranges(ctx, scan, st)) != STHIP_OK) return rc;  // (a pageable `pixels` array is the caller's again from here on)
-  times.write("sthip_scene_set_images", scan.size(), blocks);
+  write_range_times(times, "sthip_scene_set_images", scan.size(), blocks);
   const bool before = ctx->has_specular;
   if (!scan.empty()) ctx->has_specular = analyse_resident_materials(ctx).has_specular;  // (nothing else of the analysis depends on texels)
-  if (ctx->kept.valid) {
-    for (uint32_t k = 0; k < n; k++) {
-      const sthip_image_update& e = entries[k];
-      std::vector<std::vector<float>>& floats = e.which ? ctx->kept.image1_pixels : ctx->kept.image_pixels;
-      std::vector<std::vector<uint8_t>>& bytes = e.which ? ctx->kept.image1_bytes : ctx->kept.image_bytes;
-      std::set<uint32_t>& stale = e.which ? ctx->kept_images1_stale : ctx->kept_images_stale;
-      if (e.index >= floats.size() || e.index >= bytes.size()) continue;
-      if (e.device_ptr) {
-        stale.insert(e.index);
-        continue;
-      }
-      const size_t channels = e.which ? 1 : 4, values = (size_t)e.width * e.height * channels;
-      if (bytes[e.index].size() == values) memcpy(bytes[e.index].data(), e.pixels, values);
-      if (floats[e.index].size() == values) memcpy(floats[e.index].data(), e.pixels, values * 4);
-      stale.erase(e.index);
-    }
-  }
+  for (uint32_t k = 0; k < n; k++) kept_image_follows(ctx, entries[k].which != 0, entries[k].index, entries[k].pixels, entries[k].device_ptr != 0);
   fill_images_info(ctx, info, before, scan.size(), t0);
   return STHIP_OK;
 }
@@ -2639,25 +2190,19 @@ int sthip_scene_set_material_data(sthip_ctx* ctx, uint32_t offset, const void* d
       blocks = std::max(blocks, image_range_blocks_for(ctx, ctx->images_host[i]));
     }
   if ((rc = reserve_image_ranges(ctx, scan.size(), blocks)) != STHIP_OK) return rc;
-  for (int k = 0; k < 2; k++)
-    if (!ctx->rig_ev[k]) HIP_TRY(ctx, hipEventCreate(&ctx->rig_ev[k]));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // frames in flight still read the old records
-  HIP_TRY(ctx, drain_in_flight(ctx));
+  if ((rc = make_edit_events(ctx)) != STHIP_OK) return rc;
+  if ((rc = quiesce(ctx)) != STHIP_OK) return rc;  // frames in flight still read the old records
   ctx->reuse_grids_valid = false;  // (stored samples carry the old materials' radiance)
   hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[0], st));
-  if (bytes) {
-    memcpy(ctx->materials_host.data() + offset, data, bytes);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->materials.p + offset, ctx->materials_host.data() + offset, bytes, hipMemcpyHostToDevice, st));
-    if (ctx->kept.valid && ctx->kept.materials.size() == ctx->materials_host.size()) memcpy(ctx->kept.materials.data() + offset, data, bytes);
-  }
-  RangeTimes times(!scan.empty());
+  HIP_TRY(ctx, hipEventRecord(ctx->edit_ev[0], st));
+  if (bytes && (rc = write_material_bytes(ctx, offset, data, bytes, st)) != STHIP_OK) return rc;
+  StageTimer times(material_times_file(), !scan.empty(), 2);
   times.mark(0, st);
   if ((rc = enqueue_image_ranges(ctx, scan, st, "sthip_scene_set_material_data")) != STHIP_OK) return rc;
   times.mark(1, st);
-  HIP_TRY(ctx, hipEventRecord(ctx->rig_ev[1], st));
+  HIP_TRY(ctx, hipEventRecord(ctx->edit_ev[1], st));
   if ((rc = fetch_image_ranges(ctx, scan, st)) != STHIP_OK) return rc;
-  times.write("sthip_scene_set_material_data", scan.size(), blocks);
+  write_range_times(times, "sthip_scene_set_material_data", scan.size(), blocks);
   const bool before = ctx->has_specular;
   sthip::MaterialAnalysis m = analyse_resident_materials(ctx);
   if (m.inst_flags.size() == ctx->inst_flags_host.size() && m.inst_flags != ctx->inst_flags_host)
@@ -3904,471 +3449,6 @@ int sthip_pack_tiles(sthip_ctx* ctx, const void* image, uint32_t width, uint32_t
   hipLaunchKernelGGL(k_pack_tiles, dim3((unsigned)((slots + STHIP_BLOCK - 1) / STHIP_BLOCK)), dim3(STHIP_BLOCK), 0, ctx->stream, reinterpret_cast<const uint32_t*>(image), ctx->shard_rank, ctx->shard_count,
                      slots, ctx->tile_w, ctx->tile_h, width, height, entry_bytes / 4, reinterpret_cast<uint32_t*>(packed));
   HIP_TRY(ctx, hipGetLastError());
-  return STHIP_OK;
-}
-
-// ---- after the path: temporal accumulation, tonemap and image metric (post.h) ----
-
-int sthip_accumulate(sthip_ctx* ctx, const sthip_accumulate_desc* d) {
-  if (!ctx || !d) return STHIP_ERR_INVALID_ARGUMENT;
-  if (!d->gViews || !d->view_count || !d->gRadiance || !d->gPrevAccumColor || !d->gPrevAccumMoments || !d->gAccumColor || !d->gAccumMoments || !d->width || !d->height)
-    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_accumulate: gViews, gRadiance, gPrevAccum*, gAccum* and a non-empty extent are required");
-  if (d->demodulate_albedo && !d->gAlbedo) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_accumulate: gDemodulateAlbedo needs gAlbedo");
-  if (d->reprojection && (!d->gVisibility || !d->gDepth || !d->gPrevUVs || !d->gPrevVisibility || !d->gPrevDepth))
-    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_accumulate: gReprojection needs gVisibility, gDepth, gPrevUVs, gPrevVisibility, gPrevDepth");
-  if ((uint64_t)d->width * d->height > 0x7FFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_accumulate: extent too large");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const size_t n = (size_t)d->width * d->height;
-  std::vector<void*> staged;  // device copies of host inputs, freed on return
-  auto release = [&]() {
-    for (void* q : staged) (void)hipFree(q);
-  };
-  bool bad = false;
-  auto in = [&](const void* host, size_t bytes) -> const void* {
-    if (!host || d->device_ptrs) return host;
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess || hipMemcpyAsync(q, host, bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
-      bad = true;
-      return nullptr;
-    }
-    staged.push_back(q);
-    return q;
-  };
-  AccumulateParams p{};
-  p.width = d->width;
-  p.height = d->height;
-  p.view_count = d->view_count;
-  p.reprojection = d->reprojection;
-  p.demodulate_albedo = d->demodulate_albedo;
-  p.history_limit = d->history_limit;
-  p.instance_count = d->instance_count;
-  if (d->view_count <= ACCUMULATE_INLINE_VIEWS) {  // gViews is a host array in either mode: a few views ride in the kernel's arguments
-    p.views = nullptr;
-    memcpy(p.inline_views, d->gViews, (size_t)d->view_count * sizeof(sthip_ViewData));
-  } else {
-    void* q = nullptr;
-    if (hipMalloc(&q, (size_t)d->view_count * sizeof(sthip_ViewData)) != hipSuccess ||
-        hipMemcpyAsync(q, d->gViews, (size_t)d->view_count * sizeof(sthip_ViewData), hipMemcpyHostToDevice, st) != hipSuccess)
-      bad = true;
-    else
-      staged.push_back(q);
-    p.views = (const sthip_ViewData*)q;
-  }
-  const size_t cb = ctx->color_bytes();  // gRadiance, gAlbedo, gPrevAccumColor, gAccumColor
-  p.radiance = in(d->gRadiance, n * cb);
-  p.albedo = in(d->gAlbedo, n * cb);
-  p.visibility = (const sthip_VisibilityInfo*)in(d->gVisibility, n * 8);
-  p.depth = (const sthip_DepthInfo*)in(d->gDepth, n * 16);
-  p.prev_uvs = (const float2*)in(d->gPrevUVs, n * 8);
-  p.prev_visibility = (const sthip_VisibilityInfo*)in(d->gPrevVisibility, n * 8);
-  p.prev_depth = (const sthip_DepthInfo*)in(d->gPrevDepth, n * 16);
-  p.prev_accum_color = in(d->gPrevAccumColor, n * cb);
-  p.prev_accum_moments = (const float2*)in(d->gPrevAccumMoments, n * 8);
-  p.instance_index_map = (const uint32_t*)in(d->gInstanceIndexMap, (size_t)d->instance_count * 4);
-  void* out_c = d->gAccumColor;
-  float2* out_m = reinterpret_cast<float2*>(d->gAccumMoments);
-  if (!d->device_ptrs) {
-    void *qc = nullptr, *qm = nullptr;
-    if (hipMalloc(&qc, n * cb) != hipSuccess || hipMalloc(&qm, n * 8) != hipSuccess) bad = true;
-    if (qc) staged.push_back(qc);
-    if (qm) staged.push_back(qm);
-    out_c = qc;
-    out_m = (float2*)qm;
-    // pixels outside every view keep what the caller's buffers hold
-    if (!bad && (hipMemcpyAsync(qc, d->gAccumColor, n * cb, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(qm, d->gAccumMoments, n * 8, hipMemcpyHostToDevice, st) != hipSuccess)) bad = true;
-  }
-  if (bad) {
-    (void)hipStreamSynchronize(st);
-    release();
-    return fail(ctx, STHIP_ERR_HIP, "sthip_accumulate: staging the host images on the device failed");
-  }
-  p.accum_color = out_c;
-  p.accum_moments = out_m;
-  if (ctx->half_color)
-    hipLaunchKernelGGL(k_accumulate<Half4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
-  else
-    hipLaunchKernelGGL(k_accumulate<float4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && !d->device_ptrs) {
-    e = hipMemcpyAsync(d->gAccumColor, out_c, n * cb, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d->gAccumMoments, out_m, n * 8, hipMemcpyDeviceToHost, st);
-  }
-  // staged copies must outlive the kernel; with device pointers and inline views nothing is staged: the call is only enqueued
-  const hipError_t es = staged.empty() ? hipSuccess : hipStreamSynchronize(st);
-  release();
-  if (e != hipSuccess || es != hipSuccess) return fail(ctx, STHIP_ERR_HIP, std::string("sthip_accumulate: ") + hipGetErrorString(e != hipSuccess ? e : es));
-  return STHIP_OK;
-}
-
-// The filter of the denoiser (denoise.hip): estimate_variance, the a-trous passes and the history tap, enqueued in order.
-int sthip_denoise_filter(sthip_ctx* ctx, const sthip_denoise_desc* d) {
-  if (!ctx || !d) return STHIP_ERR_INVALID_ARGUMENT;
-  auto refuse = [&](const char* field, const char* why) { return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, std::string("sthip_denoise_filter: ") + field + " " + why); };
-  if (!d->width) return refuse("width", "is 0");
-  if (!d->height) return refuse("height", "is 0");
-  if ((uint64_t)d->width * d->height > 0x7FFFFFFFull) return refuse("width x height", "is too large (more than 2^31 - 1 pixels)");
-  if (!d->view_count) return refuse("view_count", "is 0");
-  if (d->iterations < 1 || d->iterations > sthip::DENOISE_MAX_ITERATIONS) return refuse("iterations", "must be 1 .. 8");
-  if (d->filter_type >= STHIP_FILTER_TYPE_COUNT) return refuse("filter_type", "must be below 6 (STHIP_FILTER_*)");
-  if (!d->gViews) return refuse("gViews", "is NULL");
-  if (!d->gVisibility) return refuse("gVisibility", "is NULL");
-  if (!d->gDepth) return refuse("gDepth", "is NULL");
-  if (!d->gAccumColor) return refuse("gAccumColor", "is NULL");
-  if (!d->gAccumMoments) return refuse("gAccumMoments", "is NULL");
-  if (!d->gFilterImages[0]) return refuse("gFilterImages[0]", "is NULL");
-  if (!d->gFilterImages[1]) return refuse("gFilterImages[1]", "is NULL");
-  if (d->gInstanceIndexMap && !d->instance_count) return refuse("instance_count", "is 0 with a gInstanceIndexMap");
-  for (uint32_t v = 0; v < d->view_count; v++) {  // the taps are bounded by their view: a view must lie inside the images
-    const sthip_ViewData& vw = d->gViews[v];
-    if (vw.image_min[0] < 0 || vw.image_min[1] < 0 || vw.image_max[0] > (int64_t)d->width || vw.image_max[1] > (int64_t)d->height)
-      return refuse("gViews", ("holds a view that leaves the extent (view " + std::to_string(v) + ")").c_str());
-  }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const size_t n = (size_t)d->width * d->height, cb = ctx->color_bytes();
-  const bool tapped = d->history_tap >= 1 && d->history_tap <= d->iterations;
-  HIP_TRY(ctx, ctx->denoise_guide.ensure(n));  // (no allocation unless the extent exceeds every earlier call's)
-  std::vector<void*> staged;  // device copies of host arrays, freed on return
-  auto release = [&]() {
-    for (void* q : staged) (void)hipFree(q);
-  };
-  bool bad = false;
-  // a host array on the device: its contents when `copy` (inputs; outputs too — pixels outside every view keep the caller's)
-  auto stage = [&](const void* host, size_t bytes) -> void* {
-    if (!host || d->device_ptrs) return const_cast<void*>(host);
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess) {
-      bad = true;
-      return nullptr;
-    }
-    staged.push_back(q);
-    if (hipMemcpyAsync(q, host, bytes, hipMemcpyHostToDevice, st) != hipSuccess) bad = true;
-    return q;
-  };
-  sthip::DenoiseParams p{};
-  p.width = d->width;
-  p.height = d->height;
-  p.view_count = d->view_count;
-  p.instance_count = d->instance_count;
-  p.history_limit = d->history_limit;
-  p.variance_boost_length = d->variance_boost_length;
-  p.sigma_luminance_boost = d->sigma_luminance_boost;
-  if (d->view_count <= sthip::DENOISE_INLINE_VIEWS) {  // gViews is a host array in either form
-    p.views = nullptr;
-    memcpy(p.inline_views, d->gViews, (size_t)d->view_count * sizeof(sthip_ViewData));
-  } else {
-    void* q = nullptr;
-    if (hipMalloc(&q, (size_t)d->view_count * sizeof(sthip_ViewData)) != hipSuccess)
-      bad = true;
-    else {
-      staged.push_back(q);
-      if (hipMemcpyAsync(q, d->gViews, (size_t)d->view_count * sizeof(sthip_ViewData), hipMemcpyHostToDevice, st) != hipSuccess) bad = true;
-    }
-    p.views = (const sthip_ViewData*)q;
-  }
-  p.visibility = (const sthip_VisibilityInfo*)stage(d->gVisibility, n * sizeof(sthip_VisibilityInfo));
-  p.depth = (const sthip_DepthInfo*)stage(d->gDepth, n * sizeof(sthip_DepthInfo));
-  p.instance_index_map = (const uint32_t*)stage(d->gInstanceIndexMap, (size_t)d->instance_count * 4);
-  p.accum_color = stage(d->gAccumColor, n * cb);
-  p.accum_moments = stage(d->gAccumMoments, n * 8);
-  p.filter[0] = stage(d->gFilterImages[0], n * cb);
-  p.filter[1] = stage(d->gFilterImages[1], n * cb);
-  p.guide = ctx->denoise_guide.p;
-  if (bad) {
-    (void)hipStreamSynchronize(st);
-    release();
-    return fail(ctx, STHIP_ERR_HIP, "sthip_denoise_filter: staging the host images on the device failed");
-  }
-  hipEvent_t ev[20] = {};
-  bool ran[10] = {};
-  hipError_t e = hipSuccess;
-  if (d->pass_ms)
-    for (int k = 0; k < 20 && e == hipSuccess; k++) e = hipEventCreate(&ev[k]);
-  std::string err;
-  const bool ok = e == hipSuccess && sthip::denoise_launch(p, d->iterations, d->filter_type, d->history_tap, ctx->half_color, ctx->denoise_block, st,
-                                                           d->pass_ms ? reinterpret_cast<void* const*>(ev) : nullptr, ran, err);
-  if (ok && !d->device_ptrs) {
-    e = hipMemcpyAsync(d->gFilterImages[0], p.filter[0], n * cb, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d->gFilterImages[1], p.filter[1], n * cb, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && tapped) e = hipMemcpyAsync(d->gAccumColor, p.accum_color, n * cb, hipMemcpyDeviceToHost, st);
-  }
-  // staged copies must outlive the kernels, and the timings need them finished; the device form with inline views only enqueues
-  const hipError_t es = (staged.empty() && !d->pass_ms) ? hipSuccess : hipStreamSynchronize(st);
-  if (d->pass_ms) {
-    for (int k = 0; k < 10; k++) {
-      d->pass_ms[k] = 0;
-      if (ok && e == hipSuccess && es == hipSuccess && ran[k]) (void)hipEventElapsedTime(&d->pass_ms[k], ev[2 * k], ev[2 * k + 1]);
-    }
-    for (int k = 0; k < 20; k++)
-      if (ev[k]) (void)hipEventDestroy(ev[k]);
-  }
-  release();
-  if (!ok && e == hipSuccess) return fail(ctx, STHIP_ERR_HIP, "sthip_denoise_filter: " + err);
-  if (e != hipSuccess || es != hipSuccess) return fail(ctx, STHIP_ERR_HIP, std::string("sthip_denoise_filter: ") + hipGetErrorString(e != hipSuccess ? e : es));
-  return STHIP_OK;
-}
-
-int sthip_convert_material(sthip_ctx* ctx, const sthip_convert_material_desc* d) {
-  if (!ctx || !d) return STHIP_ERR_INVALID_ARGUMENT;
-  auto refuse = [&](const char* field, const char* why) { return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, std::string("sthip_convert_material: ") + field + " " + why); };
-  if (d->kind >= STHIP_CONVERT_KIND_COUNT) return refuse("kind", "must be below 4 (STHIP_CONVERT_*)");
-  if (!d->width) return refuse("width", "is 0");
-  if (!d->height) return refuse("height", "is 0");
-  if ((uint64_t)d->width * d->height > (1ull << 30)) return refuse("width x height", "is too large (more than 2^30 texels)");
-  if (d->output_format > 1) return refuse("output_format", "is no sthip_image_format");
-  const bool material = d->kind == STHIP_CONVERT_GLTF_PBR || d->kind == STHIP_CONVERT_DIFFUSE_SPECULAR;
-  const bool with_roughness = d->kind == STHIP_CONVERT_DIFFUSE_SPECULAR;
-  const size_t n = (size_t)d->width * d->height, out4 = d->output_format ? 4 : 16, out1 = d->output_format ? 1 : 4;
-  struct Image {  // one image of the descriptor: the bytes of a texel and what a device pointer must be aligned to
-    const char* name;
-    const void* p;
-    size_t texel, align;
-    bool source;
-  };
-  std::vector<Image> images;
-  int i_diffuse = -1, i_specular = -1, i_transmittance = -1, i_roughness = -1, i_input = -1, i_out[3] = {-1, -1, -1}, i_mask = -1, i_min = -1, i_rw = -1;
-  auto add = [&](const char* name, const void* p, size_t texel, size_t align, bool source) {
-    images.push_back({name, p, texel, align, source});
-    return (int)images.size() - 1;
-  };
-  if (material) {
-    if (!d->gDiffuse && !d->gSpecular && !d->gTransmittance && !(with_roughness && d->gRoughness))
-      return refuse(with_roughness ? "gDiffuse / gSpecular / gTransmittance / gRoughness" : "gDiffuse / gSpecular / gTransmittance", "are all NULL: no source");
-    if (d->gDiffuse && d->diffuse_format > 1) return refuse("diffuse_format", "is no sthip_image_format");
-    if (d->gSpecular && d->specular_format > 1) return refuse("specular_format", "is no sthip_image_format");
-    if (d->gTransmittance && d->transmittance_format > 1) return refuse("transmittance_format", "is no sthip_image_format");
-    if (with_roughness && d->gRoughness && d->roughness_format > 1) return refuse("roughness_format", "is no sthip_image_format");
-    if (!d->gOutput[0]) return refuse("gOutput[0]", "is NULL");
-    if (!d->gOutput[1]) return refuse("gOutput[1]", "is NULL");
-    if (!d->gOutput[2]) return refuse("gOutput[2]", "is NULL");
-    if (!d->gOutputMinAlpha) return refuse("gOutputMinAlpha", "is NULL");
-    if (d->gDiffuse && !d->gOutputAlphaMask) return refuse("gOutputAlphaMask", "is NULL although gDiffuse is given");
-    if (d->gDiffuse) i_diffuse = add("gDiffuse", d->gDiffuse, d->diffuse_format ? 4 : 16, d->diffuse_format ? 4 : 16, true);
-    if (d->gSpecular) i_specular = add("gSpecular", d->gSpecular, d->specular_format ? 4 : 16, d->specular_format ? 4 : 16, true);
-    if (d->gTransmittance) i_transmittance = add("gTransmittance", d->gTransmittance, d->transmittance_format ? 4 : 16, d->transmittance_format ? 4 : 16, true);
-    if (with_roughness && d->gRoughness) i_roughness = add("gRoughness", d->gRoughness, d->roughness_format ? 1 : 4, d->roughness_format ? 1 : 4, true);
-    i_out[0] = add("gOutput[0]", d->gOutput[0], out4, out4, false);
-    i_out[1] = add("gOutput[1]", d->gOutput[1], out4, out4, false);
-    i_out[2] = add("gOutput[2]", d->gOutput[2], out4, out4, false);
-    if (d->gDiffuse) i_mask = add("gOutputAlphaMask", d->gOutputAlphaMask, out1, out1, false);
-    i_min = add("gOutputMinAlpha", d->gOutputMinAlpha, 0, 4, false);  // (one word, whatever the extent)
-  } else {
-    if (!d->gInput) return refuse("gInput", "is NULL");
-    if (!d->gRoughnessRW) return refuse("gRoughnessRW", "is NULL");
-    if (d->input_format > 1) return refuse("input_format", "is no sthip_image_format");
-    i_input = add("gInput", d->gInput, d->input_format ? 1 : 4, d->input_format ? 1 : 4, true);
-    i_rw = add("gRoughnessRW", d->gRoughnessRW, out1, out1, false);
-  }
-  if (d->device_ptrs)
-    for (const Image& im : images)
-      if ((uintptr_t)im.p & (im.align - 1)) return refuse(im.name, "is not naturally aligned");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  // host form: one device buffer per image (DevBuf: freed on return; poisoned under STHIP_POISON_ALLOC), sources copied up
-  std::vector<DevBuf<uint8_t>> staged(d->device_ptrs ? 0 : images.size());
-  std::vector<void*> dev(images.size());
-  for (size_t k = 0; k < images.size(); k++) {
-    const size_t bytes = images[k].texel ? n * images[k].texel : 4;
-    if (d->device_ptrs) {
-      dev[k] = const_cast<void*>(images[k].p);
-      continue;
-    }
-    HIP_TRY(ctx, staged[k].ensure(bytes));
-    dev[k] = staged[k].p;
-    if (images[k].source) HIP_TRY(ctx, hipMemcpyAsync(dev[k], images[k].p, bytes, hipMemcpyHostToDevice, st));
-  }
-  auto device_of = [&](int k) -> void* { return k < 0 ? nullptr : dev[k]; };
-  sthip::MaterialConvertParams p{};
-  p.kind = d->kind;
-  p.texels = n;
-  p.output_format = d->output_format;
-  p.diffuse = device_of(i_diffuse);
-  p.specular = device_of(i_specular);
-  p.transmittance = device_of(i_transmittance);
-  p.roughness = device_of(i_roughness);
-  p.input = device_of(i_input);
-  p.diffuse_format = d->diffuse_format, p.specular_format = d->specular_format, p.transmittance_format = d->transmittance_format, p.roughness_format = d->roughness_format;
-  p.input_format = d->input_format;
-  for (int k = 0; k < 3; k++) p.out[k] = device_of(i_out[k]);
-  p.alpha_mask = device_of(i_mask);
-  p.min_alpha = (uint32_t*)device_of(i_min);
-  p.roughness_rw = device_of(i_rw);
-  std::string err;
-  const bool ok = sthip::material_convert_launch(p, st, err);
-  hipError_t e = hipSuccess;
-  if (!d->device_ptrs) {  // the staged buffers must outlive the kernel: always synchronise
-    for (size_t k = 0; ok && e == hipSuccess && k < images.size(); k++)
-      if (!images[k].source) e = hipMemcpyAsync(const_cast<void*>(images[k].p), dev[k], images[k].texel ? n * images[k].texel : 4, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-  }
-  if (!ok) return fail(ctx, STHIP_ERR_HIP, "sthip_convert_material: " + err);
-  if (e != hipSuccess) return fail(ctx, STHIP_ERR_HIP, std::string("sthip_convert_material: ") + hipGetErrorString(e));
-  return STHIP_OK;
-}
-
-// C: the colour images' element, float4 (RGBA32F) or Half4 ("half_color_precision")
-extern "C++" {
-template <typename C>
-static int tonemap_images(sthip_ctx* ctx, const sthip_tonemap_desc* d);
-template <typename C>
-static int compare_images(sthip_ctx* ctx, const float* image1, const float* image2, uint32_t width, uint32_t height, uint32_t metric, uint32_t quantization, uint32_t device_ptrs,
-                          uint32_t* sum_out, uint32_t* overflow_out);
-}
-int sthip_tonemap(sthip_ctx* ctx, const sthip_tonemap_desc* d) {
-  if (!ctx || !d) return STHIP_ERR_INVALID_ARGUMENT;
-  if (!d->gInput || !d->gOutput || d->width == 0 || d->height == 0) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_tonemap: gInput, gOutput and a non-empty extent are required");
-  if (d->mode >= eTonemapModeCount) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_tonemap: unknown mode " + std::to_string(d->mode));
-  if (d->modulate_albedo && !d->gAlbedo) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_tonemap: gModulateAlbedo needs gAlbedo");
-  if ((uint64_t)d->width * d->height > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_tonemap: extent too large");
-  return ctx->half_color ? tonemap_images<Half4>(ctx, d) : tonemap_images<float4>(ctx, d);
-}
-extern "C++" {
-template <typename C>
-static int tonemap_images(sthip_ctx* ctx, const sthip_tonemap_desc* d) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const uint32_t n = d->width * d->height;
-  const C *in = reinterpret_cast<const C*>(d->gInput), *alb = reinterpret_cast<const C*>(d->gAlbedo);
-  C* out = reinterpret_cast<C*>(d->gOutput);
-  DevBuf<C> bin, balb, bout;
-  if (!d->device_ptrs) {
-    HIP_TRY(ctx, bin.ensure(n));
-    HIP_TRY(ctx, bout.ensure(n));
-    HIP_TRY(ctx, hipMemcpyAsync(bin.p, d->gInput, (size_t)n * sizeof(C), hipMemcpyHostToDevice, st));
-    in = bin.p;
-    out = bout.p;
-    if (d->modulate_albedo) {
-      HIP_TRY(ctx, balb.ensure(n));
-      HIP_TRY(ctx, hipMemcpyAsync(balb.p, d->gAlbedo, (size_t)n * sizeof(C), hipMemcpyHostToDevice, st));
-      alb = balb.p;
-    }
-  }
-  HIP_TRY(ctx, ctx->post_scratch.ensure(16));  // 4 quantised maxima, then the 6 floats of the exposure state
-  HIP_TRY(ctx, hipMemsetAsync(ctx->post_scratch.p, 0, 16, st));
-  TonemapState prev;
-  for (int k = 0; k < 6; k++) prev.v[k] = d->exposure_state ? d->exposure_state[k] : 0.0f;
-  float* state_out = d->exposure_state ? reinterpret_cast<float*>(ctx->post_scratch.p + 4) : nullptr;
-  const uint32_t grid = (uint32_t)std::min<size_t>(((size_t)n + 255) / 256, (size_t)ctx->cu_count * 16);
-  hipLaunchKernelGGL(k_tonemap_reduce_max<C>, dim3(grid), dim3(256), 0, st, in, alb, n, d->modulate_albedo, ctx->post_scratch.p);
-  hipLaunchKernelGGL(k_tonemap<C>, dim3(grid), dim3(256), 0, st, in, alb, out, n, d->mode, d->modulate_albedo, d->gamma_correction, d->exposure, ctx->post_scratch.p,
-                     d->exposure_state ? d->exposure_alpha : 0.0f, prev, state_out);
-  HIP_TRY(ctx, hipGetLastError());
-  if (!d->device_ptrs) HIP_TRY(ctx, hipMemcpyAsync(d->gOutput, bout.p, (size_t)n * sizeof(C), hipMemcpyDeviceToHost, st));
-  if (d->out_max) {
-    uint32_t m[4];
-    HIP_TRY(ctx, hipMemcpyAsync(m, ctx->post_scratch.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    for (int k = 0; k < 4; k++) d->out_max[k] = (float)m[k] / TONEMAP_MAX_QUANTIZATION;
-  } else if (!d->device_ptrs) {
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-  }
-  if (d->exposure_state) {  // the state goes back to the caller: this form of the call synchronises
-    HIP_TRY(ctx, hipMemcpyAsync(d->exposure_state, state_out, 24, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-  }
-  return STHIP_OK;
-}
-}  // extern "C++"
-
-int sthip_image_compare(sthip_ctx* ctx, const float* image1, const float* image2, uint32_t width, uint32_t height, uint32_t metric, uint32_t quantization, uint32_t device_ptrs,
-                        uint32_t* sum_out, uint32_t* overflow_out) {
-  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
-  if (!image1 || !image2 || !sum_out || width == 0 || height == 0) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_image_compare: two images, sum_out and a non-empty extent are required");
-  if (metric > 2) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_image_compare: unknown metric " + std::to_string(metric));
-  if ((uint64_t)width * height * 3 > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_image_compare: extent too large");
-  return ctx->half_color ? compare_images<Half4>(ctx, image1, image2, width, height, metric, quantization, device_ptrs, sum_out, overflow_out)
-                         : compare_images<float4>(ctx, image1, image2, width, height, metric, quantization, device_ptrs, sum_out, overflow_out);
-}
-extern "C++" {
-template <typename C>
-static int compare_images(sthip_ctx* ctx, const float* image1, const float* image2, uint32_t width, uint32_t height, uint32_t metric, uint32_t quantization, uint32_t device_ptrs,
-                          uint32_t* sum_out, uint32_t* overflow_out) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const uint32_t n = width * height;
-  const C *a = reinterpret_cast<const C*>(image1), *b = reinterpret_cast<const C*>(image2);
-  DevBuf<C> ba, bb;
-  if (!device_ptrs) {
-    HIP_TRY(ctx, ba.ensure(n));
-    HIP_TRY(ctx, bb.ensure(n));
-    HIP_TRY(ctx, hipMemcpyAsync(ba.p, image1, (size_t)n * sizeof(C), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(bb.p, image2, (size_t)n * sizeof(C), hipMemcpyHostToDevice, st));
-    a = ba.p;
-    b = bb.p;
-  }
-  HIP_TRY(ctx, ctx->post_scratch.ensure(4));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->post_scratch.p, 0, 16, st));
-  hipLaunchKernelGGL(k_image_compare<C>, dim3((n + 63) / 64), dim3(64), 0, st, a, b, n, metric, quantization, ctx->post_scratch.p);
-  HIP_TRY(ctx, hipGetLastError());
-  uint32_t r[2];
-  HIP_TRY(ctx, hipMemcpyAsync(r, ctx->post_scratch.p, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  *sum_out = r[0];
-  if (overflow_out) *overflow_out = r[1];
-  return STHIP_OK;
-}
-}  // extern "C++"
-
-// ---- measured ceilings for the roofline (ceilings.h) ----
-int sthip_measure_ceiling(sthip_ctx* ctx, uint32_t kind, double* gbytes_per_s) {
-  if (!ctx || !gbytes_per_s) return STHIP_ERR_INVALID_ARGUMENT;
-  *gbytes_per_s = 0.0;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const uint32_t blocks = (uint32_t)ctx->cu_count * 8u;  // 2048 threads per CU: every wave slot
-  float best_ms = 0.0f;
-  double bytes = 0.0;
-  if (kind == STHIP_CEILING_TRIAD) {
-    const size_t n = (size_t)32 << 20;  // 3 arrays of 512 MiB: far beyond the 256 MiB Infinity Cache
-    DevBuf<float4> a, b, c;
-    HIP_TRY(ctx, a.ensure(n));
-    HIP_TRY(ctx, b.ensure(n));
-    HIP_TRY(ctx, c.ensure(n));
-    HIP_TRY(ctx, hipMemsetAsync(a.p, 0, n * 16, st));
-    HIP_TRY(ctx, hipMemsetAsync(b.p, 0, n * 16, st));
-    bytes = 3.0 * 16.0 * (double)n;
-    for (int rep = 0; rep < 4; rep++) {
-      HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
-      hipLaunchKernelGGL(k_ceiling_triad, dim3(blocks), dim3(256), 0, st, a.p, b.p, c.p, 0.5f, n);
-      HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-      HIP_TRY(ctx, hipEventSynchronize(ctx->ev[1]));
-      float ms = 0;
-      HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      if (rep > 0 && (best_ms == 0.0f || ms < best_ms)) best_ms = ms;
-    }
-  } else if (kind == STHIP_CEILING_NODE_GATHER_TABLE || kind == STHIP_CEILING_NODE_GATHER_L2 || kind == STHIP_CEILING_NODE_GATHER_L1) {
-    if (!ctx->has_scene || !ctx->bvh_nodes) return fail(ctx, STHIP_ERR_NO_SCENE, "sthip_measure_ceiling: the node-gather ceilings read the resident acceleration structure: upload a scene first");
-    // the nodes k_trace walks: the 48-byte binary ones (3 loads), the 64-byte 4-wide ones (4 loads) or the 80-byte 8-wide ones (5 loads)
-    const bool wide8 = ctx->bvh.wide8_nodes != nullptr, wide = !wide8 && ctx->bvh.wide_nodes != nullptr;
-    const uint32_t nb = wide8 ? (uint32_t)sizeof(Wide8Node) : wide ? (uint32_t)sizeof(WideNode) : BVH_NODE_BYTES;
-    uint32_t count = (uint32_t)std::min<uint64_t>(wide8 ? ctx->wide8_node_count : wide ? ctx->wide_node_count : ctx->bvh_nodes, 0xFFFFFFFFull);
-    if (kind == STHIP_CEILING_NODE_GATHER_L2) count = std::min<uint32_t>(count, (2u << 20) / nb);
-    if (kind == STHIP_CEILING_NODE_GATHER_L1) count = std::min<uint32_t>(count, (16u << 10) / nb);
-    const uint32_t iterations = 64;
-    DevBuf<float> sink;
-    HIP_TRY(ctx, sink.ensure((size_t)blocks * 256));
-    bytes = (double)(wide8 ? sizeof(Wide8Node) : wide ? sizeof(WideNode) : sizeof(BvhNodePacked)) * (double)blocks * 256.0 * iterations * CEIL_UNROLL;
-    for (int rep = 0; rep < 4; rep++) {
-      HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
-      if (wide8)
-        hipLaunchKernelGGL(k_ceiling_node_gather<5>, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const float4*>(ctx->wide8_nodes.p), count, nb, iterations, sink.p);
-      else if (wide)
-        hipLaunchKernelGGL(k_ceiling_node_gather<4>, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const float4*>(ctx->wide_nodes.p), count, nb, iterations, sink.p);
-      else
-        hipLaunchKernelGGL(k_ceiling_node_gather<3>, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const float4*>(ctx->nodes.p), count, nb, iterations, sink.p);
-      HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-      HIP_TRY(ctx, hipEventSynchronize(ctx->ev[1]));
-      float ms = 0;
-      HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-      if (rep > 0 && (best_ms == 0.0f || ms < best_ms)) best_ms = ms;
-    }
-  } else {
-    return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_measure_ceiling: unknown kind");
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  if (best_ms > 0.0f) *gbytes_per_s = bytes / ((double)best_ms * 1e-3) / 1e9;
   return STHIP_OK;
 }
 

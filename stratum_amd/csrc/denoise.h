@@ -1,4 +1,4 @@
-// denoise.h — the filter of the denoiser (denoise.hip): what api.hip hands the passes of sthip_denoise_filter.
+// denoise.h — the filter of the denoiser (denoise.hip): what post.hip hands the passes of sthip_denoise_filter.
 #pragma once
 
 #include <stdint.h>

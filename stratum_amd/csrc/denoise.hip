@@ -1,4 +1,4 @@
-// denoise.hip — the filter of the denoiser on the device (sthip_denoise_filter, api.hip): SVGF's variance estimate and
+// denoise.hip — the filter of the denoiser on the device (sthip_denoise_filter, post.hip): SVGF's variance estimate and
 // the edge-stopping a-trous passes the reference dispatches after its temporal accumulation (src/Node/Denoiser.cpp:215-265):
 //   k_estimate_variance  kernels/estimate_variance.hlsl:51-103
 //   k_atrous             kernels/atrous.hlsl:66-262 (TapData::tap, compute_sigma_luminance, the four tap patterns, main)

@@ -1,4 +1,4 @@
-// material_convert.h — the four conversions of sthip_convert_material (material_convert.hip): what api.hip hands the launch.
+// material_convert.h — the four conversions of sthip_convert_material (material_convert.hip): what post.hip hands the launch.
 #pragma once
 
 #include <math.h>
@@ -43,7 +43,7 @@ struct MaterialConvertParams {
   void* roughness_rw;   // one channel, the roughness kinds only
 };
 
-// Enqueues the clear of min_alpha (material kinds) and one kernel on `stream`. Alignment is the caller's (api.hip checks it):
+// Enqueues the clear of min_alpha (material kinds) and one kernel on `stream`. Alignment is the caller's (post.hip checks it):
 // 4 bytes for an RGBA8 image, 16 for RGBA32F, 4 for R32F. Images that are all 8-bit and 16-byte aligned (one-channel ones 4)
 // go four texels per lane.
 bool material_convert_launch(const MaterialConvertParams& p, void* stream, std::string& err);

@@ -75,7 +75,7 @@ namespace {
 
 constexpr unsigned REFIT_BLOCK = 256;
 
-// tests: STHIP_POISON_ALLOC=<byte> (api.hip, DevBuf::ensure) fills every new buffer of the refit too, the pinned read-back
+// tests: STHIP_POISON_ALLOC=<byte> (context.h, DevBuf::ensure) fills every new buffer of the refit too, the pinned read-back
 // staging included, so that a read of a record no launch has written shows in a fresh process, where new memory is zero pages
 int poison_byte() {
   static const int poison = [] {

@@ -25,7 +25,7 @@ new='''    float4 a[CEIL_UNROLL][LOADS];
 s=s.replace(old,new)
 s=s.replace("#define CEIL_UNROLL 8","#define CEIL_UNROLL 4")
 open(p,'w').write(s)
-p='api.hip'
+p='post.hip'
 s=open(p).read()
 old="    if (kind == STHIP_CEILING_NODE_GATHER_L2) count = std::min<uint32_t>(count, (2u << 20) / BVH_NODE_BYTES);\n    if (kind == STHIP_CEILING_NODE_GATHER_L1) count = std::min<uint32_t>(count, (16u << 10) / BVH_NODE_BYTES);\n"
 new='''    uint32_t nb = BVH_NODE_BYTES, loads = 3;
