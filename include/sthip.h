@@ -498,6 +498,99 @@ typedef struct sthip_convert_material_desc {
 } sthip_convert_material_desc;
 int sthip_convert_material(sthip_ctx* ctx, const sthip_convert_material_desc* desc);
 
+/* ---- density grids from dense voxel arrays (load_volumes.cpp:87-91: GridBuilder<float>(0, FogVolume) over a dense box) ----
+ * gVolumes[] takes finished NanoVDB 32.3 buffers. sthip_build_volume makes one ON THE DEVICE (volume_build.hip) from a dense
+ * box of binary32 values, so that a host whose simulation leaves a dense array in device memory needs neither NanoVDB nor the
+ * CPU. It stands alone, like sthip_convert_material: no scene is needed or touched, and the output is valid as
+ * sthip_volume_desc::data of an upload. stratum_amd/nvdb.py (dense_to_nanovdb) states the same contract in numpy; the two
+ * agree byte for byte.
+ *
+ * INPUT. dense[(x * dims[1] + y) * dims[2] + z], z fastest (a contiguous [nx, ny, nz] array, and NanoVDB's leaf order); dims
+ * each >= 1; origin = the integer index coordinate of dense[0], may be negative and need not be a multiple of 8; voxel_size
+ * and translation in binary64; an optional NUL-terminated name of at most 255 bytes. `dense` is a host pointer or, with
+ * dense_is_device, a device pointer (4-byte aligned; rows that are 16-byte aligned take the wide loads).
+ *
+ * OUTPUT. One NanoVDB 32.3.3 float grid, class FogVolume, background 0, laid out as NanoVDB lays it out: GridData (672 B),
+ * TreeData (64 B), the root (64 B) with its tiles (32 B each), then all upper nodes (270 400 B each), all lower nodes
+ * (33 856 B), all leaves (2 144 B), breadth first. Every byte of the grid is written.
+ *
+ * RULES, each chosen so that every answer the readers use is GridBuilder's.
+ *   - A voxel is active iff its value != 0 (GridBuilder::operator() skips v == background, so -0.0f is inactive and reads
+ *     back as +0). Inactive voxels of an existing leaf hold 0; inactive tiles hold 0.
+ *   - A leaf exists iff it has an active voxel; the same holds for a lower node, an upper node and a root tile. Root tiles are
+ *     ordered ascending by signed tile coordinate (x, then y, then z: NanoVDB's std::map<Coord>). The nodes of a level follow
+ *     their parents' order and then the child index.
+ *   - Minimum, maximum and the index bounding box of the active voxels are exact at every level: leaf bbox_min / bbox_dif,
+ *     node boxes, root box. The root maximum is the majorant of delta tracking, so it is the true maximum.
+ *   - Average and standard deviation are written as 0. The grid flags claim bounding boxes, min/max and breadth-first order
+ *     only (0x26). The checksum is all ones ("none"), the version word 0x04000c03.
+ *   - STATED DIFFERENCE: GridBuilder turns a fully active constant leaf or lower node into a tile; this builder does not
+ *     prune. Every lookup returns the same value either way.
+ *   - Map: matf[i][i] = (float)voxel_size, invmatf[i][i] = (float)(1.0 / voxel_size), vecf = (float)translation; the binary64
+ *     copies hold the unrounded values; both tapers are 1. World box: the binary64 map (index * voxel_size + translation,
+ *     unfused) of the index box [min, max + 1]. Voxel size is written three times.
+ * Refused with STHIP_ERR_INVALID_ARGUMENT before anything the caller owns is written: a NULL desc / dense / info, a struct_size
+ * that is not sizeof(sthip_dense_volume_desc), a zero extent, a NaN or infinite value, no active voxel at all, a zero, negative
+ * or non-finite voxel size, a non-finite translation, a name of more than 255 bytes, a box whose coordinates leave int32, a
+ * box that touches more than 2^24 bricks of 8^3 voxels (2 048^3 voxels fit; the build's scratch is 20 B per brick), a grid of more than 0xFFFFFFF0 bytes, more than 65 536 root tiles, a device `out`
+ * that is not 32-byte aligned.
+ * TWO-CALL IDIOM: `info` is filled whenever the description passes; a capacity below info->bytes (or a NULL `out`) writes
+ * nothing and returns STHIP_ERR_INVALID_ARGUMENT, so a first call with capacity 0 gives the size. With out_is_device the
+ * grid is built in place in `out`; otherwise in a staging area of the context's and copied to the host. The call returns
+ * synchronised. A library without the feature lacks the symbol. */
+typedef struct sthip_dense_volume_desc {
+  uint32_t struct_size; /* sizeof(sthip_dense_volume_desc) */
+  uint32_t dense_is_device;
+  const float* dense;
+  uint32_t dims[3];
+  int32_t origin[3];
+  double voxel_size;
+  double translation[3];
+  const char* name; /* may be NULL */
+} sthip_dense_volume_desc;
+typedef struct sthip_volume_info {
+  uint64_t bytes;                     /* of the grid */
+  int32_t bbox_min[3], bbox_max[3];   /* index box of the active voxels (inclusive) */
+  double world_bbox[6];               /* min xyz, max xyz: what a host needs for gViewMediumInstances */
+  float min, max;                     /* over the active voxels */
+  uint64_t active_voxels;
+  uint32_t leaf_count, lower_count, upper_count, root_tiles;
+  float device_ms; /* stream time of the kernels of the call (HIP events) */
+  float call_ms;   /* wall time of the call */
+} sthip_volume_info;
+int sthip_build_volume(sthip_ctx* ctx, const sthip_dense_volume_desc* desc, void* out, uint64_t capacity, int out_is_device, sthip_volume_info* info);
+
+/* ---- the grids of a resident scene ----
+ * sthip_scene_set_volume replaces resident grid `volume_index` of gVolumes[] without an upload. The source is EITHER a finished
+ * NanoVDB buffer (`data`, `bytes`; host memory, or device memory with data_is_device; checked exactly as the upload checks
+ * it: magic, grid type, size, root and tile table inside the buffer) OR a dense description (`dense`, built on the device
+ * into a staging area by the rules of sthip_build_volume). Every check and the build's read-back come first; a refusal
+ * (STHIP_ERR_INVALID_ARGUMENT: no scene — STHIP_ERR_NO_SCENE —, an index out of range, a wrong struct_size, both or neither
+ * source, anything the upload or sthip_build_volume refuses, grids beyond 16 GiB together) leaves the resident scene as it
+ * was. Then, with no frame in flight, the install: the grids' words are laid out again back to back (so first_word may
+ * change and a larger grid fits), the parsed header replaces the old one on the device and on the host, the entry boxes of
+ * the volume instances that name the grid and the top level are made again by the path sthip_scene_update_transforms uses
+ * (with the resident matrices), and with them the scene bounds. Kept reservoir grids ("reuse_grids_persist") are dropped, as
+ * at an upload. With "keep_scene" the kept copy of the grid follows at once when the source is host bytes; otherwise it is
+ * marked stale and fetched from the device immediately before anything is built again from the kept scene, by the rule
+ * the environment and the images follow. If the top level cannot be made after the words were installed (STHIP_ERR_HIP,
+ * STHIP_ERR_UNSUPPORTED), no scene is resident any more and the kept copy is dropped. The top level is the HOST-built one
+ * afterwards, also where sthip_scene_set_transforms had built the resident one on the device. device_ms covers the build's
+ * kernels and the copies of the install (HIP events); the top-level rebuild on the host, its copies and the read-back of the
+ * resident matrices are part of call_ms only. `info` (may be NULL) is filled as by sthip_build_volume; for a
+ * finished buffer only bytes, the index box, max and the times are known (the other fields are 0).
+ * sthip_scene_read_volume copies what is resident: `*bytes` receives the grid's size (may be NULL); a `dst` of less capacity,
+ * or NULL, is not written and gives STHIP_ERR_INVALID_ARGUMENT (two-call idiom). A library without the feature lacks the symbols. */
+typedef struct sthip_volume_source {
+  uint32_t struct_size; /* sizeof(sthip_volume_source) */
+  uint32_t data_is_device;
+  const void* data; /* a finished grid, or NULL */
+  uint64_t bytes;
+  const sthip_dense_volume_desc* dense; /* a dense box, or NULL */
+} sthip_volume_source;
+int sthip_scene_set_volume(sthip_ctx* ctx, uint32_t volume_index, const sthip_volume_source* source, sthip_volume_info* info);
+int sthip_scene_read_volume(sthip_ctx* ctx, uint32_t volume_index, void* dst, uint64_t capacity, uint64_t* bytes);
+
 /* ---- the environment of a resident scene (environment.h:8-25,96-150; dist2.h:80-154) ----
  * An image environment is three things in HBM: the RGBA32F image of gImages with its mip chain (Environment::sample_texel
  * descends it under eSampleEnvironmentMapDirectly), the four dist2d tables in gDistributions — marginal_pdf[H], row_pdf[H*W],

@@ -33,6 +33,9 @@ EXPORTS = [
     "sthip_scene_animate",
     "sthip_scene_read_vertices",
     "sthip_convert_material",
+    "sthip_build_volume",
+    "sthip_scene_set_volume",
+    "sthip_scene_read_volume",
     "sthip_scene_set_environment",
     "sthip_scene_read_distributions",
     "sthip_scene_set_images",
@@ -129,6 +132,14 @@ def lib():
     if hasattr(L, "sthip_convert_material"):  # (an older build named by STHIP_LIB lacks it: calling it raises)
         L.sthip_convert_material.restype = C.c_int
         L.sthip_convert_material.argtypes = [C.c_void_p, C.POINTER(wire.ConvertMaterialDesc)]
+    if hasattr(L, "sthip_build_volume"):  # (an older build named by STHIP_LIB lacks it: calling it raises)
+        L.sthip_build_volume.restype = C.c_int
+        L.sthip_build_volume.argtypes = [C.c_void_p, C.POINTER(wire.DenseVolumeDesc), C.c_void_p, C.c_uint64, C.c_int, C.POINTER(wire.VolumeInfo)]
+    if hasattr(L, "sthip_scene_set_volume"):  # (an older build named by STHIP_LIB lacks the two: calling them raises)
+        L.sthip_scene_set_volume.restype = C.c_int
+        L.sthip_scene_set_volume.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(wire.VolumeSource), C.POINTER(wire.VolumeInfo)]
+        L.sthip_scene_read_volume.restype = C.c_int
+        L.sthip_scene_read_volume.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     if hasattr(L, "sthip_scene_set_environment"):  # (an older build named by STHIP_LIB lacks the two: calling them raises)
         L.sthip_scene_set_environment.restype = C.c_int
         L.sthip_scene_set_environment.argtypes = [C.c_void_p, C.POINTER(wire.EnvironmentDesc), C.POINTER(wire.EnvironmentInfo)]

@@ -68,6 +68,8 @@ class BDPT:
         self._h = h
         self.device = device
         self._scene = None
+        self._stale_volumes = set()  # indices of gVolumes that set_volume replaced: the scene object's grids are older
+        self.volume_world_bbox = {}  # volume index -> world box (6 doubles) of the grid set_volume installed
         self._device_images = set()  # indices of gImages whose texels set_images took from a device pointer: the scene object's are older
         self._prev_result = None
         self.half_color_precision = False  # BDPT.hpp mHalfColorPrecision: colour images RGBA16F (set_half_color_precision)
@@ -142,6 +144,10 @@ class BDPT:
             for index in sorted(self._device_images):
                 scene.images[index] = self.read_image(index, 0)
         self._device_images = set()
+        if scene is self._scene and self._stale_volumes:  # ... and the grids set_volume left newer on the device
+            for index in sorted(self._stale_volumes):
+                scene.volumes[index] = self.read_volume(index)
+        self._stale_volumes = set()
         d = scene.desc()
         formats, formats1 = scene.formats()
         if formats.any() or formats1.any():  # some image is a uint8 array: it goes up, and stays resident, as 8-bit texels
@@ -458,6 +464,81 @@ class BDPT:
         d.gRoughnessRW = rough.ctypes.data
         self._check(self._lib.sthip_convert_material(self._h, C.byref(d)), "sthip_convert_material")
         return {"roughness": rough}
+
+    def build_volume(self, dense, origin=(0, 0, 0), voxel_size=1.0, translation=(0.0, 0.0, 0.0), name="", dims=None, out=None, capacity=None):
+        """sthip_build_volume: a NanoVDB float grid (FogVolume) from a dense box, built on the device; the bytes are those of
+        nvdb.dense_to_nanovdb. `dense`: a C-contiguous float32 [nx, ny, nz] array, or an int — a device pointer, with `dims`.
+        `out` None: the grid comes back as a uint8 array (two calls: the size, then the grid); `out` an int: a device pointer
+        of `capacity` bytes the grid is built into. Returns (grid or None, info dict)."""
+        d, _keep = self._dense_desc(dense, origin, voxel_size, translation, name, dims)
+        info = wire.VolumeInfo()
+        as_dict = lambda: {f: (list(getattr(info, f)) if hasattr(getattr(info, f), "__len__") else getattr(info, f)) for f, _ in wire.VolumeInfo._fields_}
+        if out is not None:
+            self._check(self._lib.sthip_build_volume(self._h, C.byref(d), C.c_void_p(int(out)), int(capacity), 1, C.byref(info)), "sthip_build_volume")
+            return None, as_dict()
+        rc = self._lib.sthip_build_volume(self._h, C.byref(d), None, 0, 0, C.byref(info))  # the size (refused: capacity 0)
+        if info.bytes == 0:
+            self._check(rc, "sthip_build_volume")
+        grid = np.empty(int(info.bytes), np.uint8)
+        self._check(self._lib.sthip_build_volume(self._h, C.byref(d), wire.ptr(grid), grid.size, 0, C.byref(info)), "sthip_build_volume")
+        return grid, as_dict()
+
+    def _dense_desc(self, dense, origin, voxel_size, translation, name, dims):
+        """(sthip_dense_volume_desc, what must stay alive) for a numpy array or a device pointer with `dims`."""
+        d = wire.DenseVolumeDesc()
+        d.struct_size = C.sizeof(wire.DenseVolumeDesc)
+        if isinstance(dense, np.ndarray):
+            if dense.dtype != np.float32 or dense.ndim != 3 or not dense.flags["C_CONTIGUOUS"]:
+                raise ValueError("dense must be a C-contiguous float32 [nx, ny, nz] array")
+            d.dense, d.dense_is_device, dims = dense.ctypes.data, 0, dense.shape
+        else:
+            d.dense, d.dense_is_device = int(dense.data_ptr() if hasattr(dense, "data_ptr") else dense), 1
+        for k in range(3):
+            d.dims[k], d.origin[k], d.translation[k] = int(dims[k]), int(origin[k]), float(translation[k])
+        d.voxel_size = float(voxel_size)
+        d.name = name.encode() if isinstance(name, str) else name
+        return d, dense
+
+    def set_volume(self, index, grid=None, dense=None, origin=(0, 0, 0), voxel_size=1.0, translation=(0.0, 0.0, 0.0), name="", dims=None, grid_bytes=None):
+        """sthip_scene_set_volume: resident grid `index` is replaced without an upload, by a finished NanoVDB buffer (`grid`: a
+        uint8 array, or a device pointer with `grid_bytes`) or by a dense box built on the device (`dense`: as build_volume
+        takes it). The scene object's copy of the grid is marked stale and fetched (read_volume) before the scene is packed
+        again by update(). Returns the info dict; its world_bbox is kept in self.volume_world_bbox[index] for
+        view_medium_instances."""
+        if (grid is None) == (dense is None):
+            raise ValueError("set_volume: exactly one of grid and dense")
+        s = wire.VolumeSource()
+        s.struct_size = C.sizeof(wire.VolumeSource)
+        if dense is not None:
+            d, keep = self._dense_desc(dense, origin, voxel_size, translation, name, dims)
+            s.dense = C.pointer(d)
+        elif isinstance(grid, np.ndarray):
+            keep = np.ascontiguousarray(grid, dtype=np.uint8)
+            s.data, s.bytes, s.data_is_device = keep.ctypes.data, keep.size, 0
+        else:
+            keep = grid
+            s.data, s.bytes, s.data_is_device = int(grid.data_ptr() if hasattr(grid, "data_ptr") else grid), int(grid_bytes), 1
+        info = wire.VolumeInfo()
+        self._check(self._lib.sthip_scene_set_volume(self._h, int(index), C.byref(s), C.byref(info)), "sthip_scene_set_volume")
+        self._stale_volumes.add(int(index))
+        out = {f: (list(getattr(info, f)) if hasattr(getattr(info, f), "__len__") else getattr(info, f)) for f, _ in wire.VolumeInfo._fields_}
+        if dense is None and isinstance(grid, np.ndarray) and keep.size >= 608:
+            out["world_bbox"] = [float(x) for x in keep[560:608].view("<f8")]  # GridData::mWorldBBox of the finished buffer
+        if dense is not None or isinstance(grid, np.ndarray):
+            self.volume_world_bbox[int(index)] = out["world_bbox"]
+        else:
+            self.volume_world_bbox.pop(int(index), None)  # (a finished device buffer: its header is the caller's to read)
+        return out
+
+    def read_volume(self, index):
+        """The bytes of resident grid `index` (sthip_scene_read_volume)."""
+        n = C.c_uint64(0)
+        self._lib.sthip_scene_read_volume(self._h, int(index), None, 0, C.byref(n))
+        if n.value == 0:
+            self._check(self._lib.sthip_scene_read_volume(self._h, int(index), None, 0, C.byref(n)), "sthip_scene_read_volume")
+        grid = np.empty(int(n.value), np.uint8)
+        self._check(self._lib.sthip_scene_read_volume(self._h, int(index), wire.ptr(grid), grid.size, C.byref(n)), "sthip_scene_read_volume")
+        return grid
 
     def set_stream(self, stream_handle):
         self._check(self._lib.sthip_set_stream(self._h, C.c_void_p(stream_handle)), "sthip_set_stream")

@@ -354,6 +354,8 @@ void sthip_destroy(sthip_ctx* ctx) {
   ctx->wide_scratch = nullptr;
   sthip::device_top_level_destroy(ctx->top_level);
   ctx->top_level = nullptr;
+  sthip::device_volume_build_destroy(ctx->volume_build);
+  ctx->volume_build = nullptr;
   sthip::device_refit_destroy(ctx->refit);
   ctx->refit = nullptr;
   for (int k = 0; k < 2; k++)
@@ -562,6 +564,7 @@ static int trace_occupancy(const sthip_ctx* ctx, size_t lds_bytes);
 static int configure_stack(sthip_ctx* ctx);
 static int refresh_treetop(sthip_ctx* ctx);
 static int sync_kept_transforms(sthip_ctx* ctx);
+static int sync_kept_volumes(sthip_ctx* ctx);
 // packs `count` nodes and writes them into the node array from slot `first` on
 static hipError_t upload_nodes(sthip_ctx* ctx, size_t first, const BvhNode* nodes, size_t count) {
   std::vector<BvhNodePacked> packed;
@@ -723,6 +726,10 @@ static int upload_kept_scene(sthip_ctx* ctx) {
     const int rc = sync_kept_environment(ctx);
     if (rc != STHIP_OK) return rc;
   }
+  {  // (grids sthip_scene_set_volume built on the device or took from a device pointer)
+    const int rc = sync_kept_volumes(ctx);
+    if (rc != STHIP_OK) return rc;
+  }
   const sthip_scene_desc d = ctx->kept.desc();
   return scene_upload(ctx, &d, ctx->kept.image_formats.empty() ? nullptr : ctx->kept.image_formats.data(), ctx->kept.image1_formats.empty() ? nullptr : ctx->kept.image1_formats.data());
 }
@@ -880,7 +887,10 @@ static int install_alpha_masks(sthip_ctx* ctx, const sthip::MaskLayout& masks, b
 
 // gVolumes: the grids back to back as 32-bit words, and their parsed headers
 static int install_volumes(sthip_ctx* ctx, const sthip_scene_desc* s, const std::vector<uint32_t>& first_words, size_t words, sthip::BuiltBvh& built) {
-  for (uint32_t i = 0; i < s->volume_count; i++) built.volumes[i].first_word = first_words[i];
+  for (uint32_t i = 0; i < s->volume_count; i++) {
+    built.volumes[i].first_word = first_words[i];
+    if (i < built.top.volumes.size()) built.top.volumes[i].first_word = first_words[i];  // (the host's copy: read_volume, set_volume)
+  }
   HIP_TRY(ctx, ctx->volume_words.ensure(std::max<size_t>(1, words)));
   HIP_TRY(ctx, ctx->volumes.ensure(std::max<size_t>(1, built.volumes.size())));
   for (uint32_t i = 0; i < s->volume_count; i++)
@@ -1355,6 +1365,159 @@ int sthip_scene_update_transforms(sthip_ctx* ctx, const sthip_TransformData* xf,
   if (instance_count != ctx->instance_count) return fail(ctx, STHIP_ERR_UNSUPPORTED, "sthip_scene_update_transforms: the instance count changed: upload the scene again");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return update_transforms_host(ctx, "sthip_scene_update_transforms: ", xf, inv, motion, instance_count, nullptr);
+}
+
+// ---- the grids of a resident scene: sthip_scene_set_volume / sthip_scene_read_volume ----
+// The kept scene's grids are current again: those a set_volume call left newer on the device come back. Called immediately
+// before anything is built from the kept scene (upload_kept_scene), as sync_kept_environment is.
+static int sync_kept_volumes(sthip_ctx* ctx) {
+  if (ctx->kept.stale_volumes.empty()) return STHIP_OK;
+  // (no scene, or a kept copy of another one: nothing to fetch from; the marks stay until the next upload keeps a scene,
+  // so that nothing is ever built from a grid known to be old)
+  if (!ctx->has_scene || !ctx->kept.valid || ctx->kept.volume_bytes.size() != ctx->top.volumes.size()) return STHIP_OK;
+  {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (const uint32_t i : ctx->kept.stale_volumes) {
+      if (i >= ctx->top.volumes.size()) continue;
+      const DeviceVolume& v = ctx->top.volumes[i];
+      ctx->kept.volume_bytes[i].resize(v.bytes);
+      HIP_TRY(ctx, hipMemcpy(ctx->kept.volume_bytes[i].data(), ctx->volume_words.p + v.first_word, v.bytes, hipMemcpyDeviceToHost));
+      ctx->kept.volumes[i] = sthip_volume_desc{ctx->kept.volume_bytes[i].data(), v.bytes};
+    }
+  }
+  ctx->kept.stale_volumes.clear();
+  return STHIP_OK;
+}
+
+int sthip_scene_read_volume(sthip_ctx* ctx, uint32_t volume_index, void* dst, uint64_t capacity, uint64_t* bytes) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_NO_SCENE, "sthip_scene_read_volume before sthip_scene_upload");
+  if (volume_index >= ctx->top.volumes.size()) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_volume: volume_index is out of range");
+  const DeviceVolume& v = ctx->top.volumes[volume_index];
+  if (bytes) *bytes = v.bytes;
+  if (!dst || capacity < v.bytes) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_read_volume: the grid has " + std::to_string(v.bytes) + " bytes, capacity is " + std::to_string(capacity));
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(dst, ctx->volume_words.p + v.first_word, v.bytes, hipMemcpyDeviceToHost));
+  return STHIP_OK;
+}
+
+int sthip_scene_set_volume(sthip_ctx* ctx, uint32_t volume_index, const sthip_volume_source* src, sthip_volume_info* info) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  const auto t0 = std::chrono::steady_clock::now();
+  const std::string call = "sthip_scene_set_volume: ";
+  if (!ctx->has_scene) return fail(ctx, STHIP_ERR_NO_SCENE, "sthip_scene_set_volume before sthip_scene_upload");
+  if (!src || src->struct_size != sizeof(sthip_volume_source)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "struct_size is not sizeof(sthip_volume_source)");
+  if (volume_index >= ctx->top.volumes.size()) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "volume_index is out of range");
+  if ((src->data != nullptr) == (src->dense != nullptr)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "exactly one of data and dense must be given");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = make_edit_events(ctx)) != STHIP_OK) return rc;
+  // ---- every check, the build and its read-back: nothing resident is touched ----
+  sthip_volume_info local{};
+  DeviceVolume parsed;
+  const void* grid = nullptr;  // where the new grid's bytes lie
+  hipMemcpyKind kind = hipMemcpyHostToDevice;
+  uint64_t grid_bytes = 0;
+  float build_ms = 0;
+  DevBuf<float> staged;
+  std::string err;
+  if (src->dense) {
+    sthip::VolumeBuildInput in{};
+    sthip::VolumeBuildCounts c{};
+    sthip::VolumeHeader header;
+    float scan_ms = 0, emit_ms = 0;
+    if ((rc = dense_volume_scan(ctx, "sthip_scene_set_volume", src->dense, staged, in, c, header, &local, scan_ms)) != STHIP_OK) return rc;
+    void* target = sthip::volume_build_staging(ctx->volume_build, local.bytes, err);
+    if (!target) return fail(ctx, STHIP_ERR_HIP, call + err);
+    if (!sthip::volume_build_emit(ctx->volume_build, in, c, header, target, ctx->stream, emit_ms, err)) return fail(ctx, STHIP_ERR_HIP, call + err);
+    if (!sthip::parse_volume_header((const uint8_t*)header.w, sizeof(header), local.bytes, parsed, err)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + err);
+    grid = target, kind = hipMemcpyDeviceToDevice, grid_bytes = local.bytes, build_ms = scan_ms + emit_ms;
+  } else {
+    const uint64_t n = src->bytes;
+    std::vector<uint8_t> head;  // a device pointer: the header, the tree and the root come to the host for the checks
+    const uint8_t* b = (const uint8_t*)src->data;
+    uint64_t have = n;
+    if (src->data_is_device) {
+      if ((uintptr_t)src->data & 3u) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "data is a device pointer that is not 4-byte aligned");
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      have = std::min<uint64_t>(n, 672 + 64);
+      head.resize(have);
+      if (have) HIP_TRY(ctx, hipMemcpy(head.data(), src->data, have, hipMemcpyDeviceToHost));
+      uint64_t root = 0;
+      if (have >= 672 + 32) memcpy(&root, head.data() + 672 + 24, 8);
+      const uint64_t want = root <= n ? std::min<uint64_t>(n, 672 + root + 64) : have;
+      if (want > have) {
+        head.resize(want);
+        HIP_TRY(ctx, hipMemcpy(head.data() + have, (const uint8_t*)src->data + have, want - have, hipMemcpyDeviceToHost));
+        have = want;
+      }
+      b = head.data();
+      kind = hipMemcpyDeviceToDevice;
+    }
+    if (!sthip::parse_volume_header(b, have, n, parsed, err)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + err);
+    grid = src->data, grid_bytes = n;
+    local.bytes = n;
+    for (int a = 0; a < 3; a++) local.bbox_min[a] = parsed.bbox_min[a], local.bbox_max[a] = parsed.bbox_max[a];
+    local.max = parsed.root_max;
+  }
+  // the new layout: the grids back to back, as the upload lays them out
+  std::vector<DeviceVolume> next = ctx->top.volumes;
+  parsed.first_word = 0;
+  next[volume_index] = parsed;
+  uint64_t words = 0;
+  for (DeviceVolume& v : next) {
+    v.first_word = (uint32_t)words;
+    words += v.bytes / 4;
+  }
+  if (words > 0xFFFFFFFFull) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, call + "gVolumes exceed 16 GiB");
+  DevBuf<uint32_t> fresh;
+  HIP_TRY(ctx, fresh.ensure(std::max<uint64_t>(1, words)));
+  // ---- the install: frames in flight still read the old words ----
+  if ((rc = quiesce(ctx)) != STHIP_OK) return rc;
+  HIP_TRY(ctx, hipEventRecord(ctx->edit_ev[0], ctx->stream));
+  auto lost = [&](int code) {  // (a failure from here on: the resident scene is neither the old nor the new one)
+    ctx->has_scene = false;
+    ctx->kept = KeptScene();  // (its copy of this grid may be the old one: nothing may be built from it any more)
+    return code;
+  };
+  for (size_t i = 0; i < next.size(); i++) {
+    const hipError_t e = i == volume_index ? hipMemcpyAsync(fresh.p + next[i].first_word, grid, grid_bytes, kind, ctx->stream)
+                                           : hipMemcpyAsync(fresh.p + next[i].first_word, ctx->volume_words.p + ctx->top.volumes[i].first_word, next[i].bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e != hipSuccess) return lost(fail(ctx, STHIP_ERR_HIP, call + hipGetErrorString(e)));
+  }
+  if (hipMemcpyAsync(ctx->volumes.p, next.data(), next.size() * sizeof(DeviceVolume), hipMemcpyHostToDevice, ctx->stream) != hipSuccess || hipEventRecord(ctx->edit_ev[1], ctx->stream) != hipSuccess ||
+      hipStreamSynchronize(ctx->stream) != hipSuccess)
+    return lost(fail(ctx, STHIP_ERR_HIP, call + "installing the grids failed"));
+  std::swap(ctx->volume_words.p, fresh.p);  // (the old words are freed with `fresh`)
+  std::swap(ctx->volume_words.n, fresh.n);
+  ctx->top.volumes = next;
+  ctx->reuse_grids_valid = false;  // (stored samples were taken in the old medium)
+  if (ctx->kept.valid && ctx->kept.volume_bytes.size() == next.size()) {
+    if (!src->dense && !src->data_is_device) {
+      ctx->kept.volume_bytes[volume_index].assign((const uint8_t*)src->data, (const uint8_t*)src->data + grid_bytes);
+      ctx->kept.volumes[volume_index] = sthip_volume_desc{ctx->kept.volume_bytes[volume_index].data(), grid_bytes};
+      ctx->kept.stale_volumes.erase(volume_index);
+    } else {
+      ctx->kept.stale_volumes.insert(volume_index);
+    }
+  }
+  // the entry boxes of the volume instances, the top level and the scene bounds: the path sthip_scene_update_transforms
+  // takes, with the matrices that are resident
+  const uint32_t n = ctx->instance_count;
+  if (n) {
+    std::vector<sthip_TransformData> xf(n), inv(n), motion(n);
+    if (hipMemcpy(xf.data(), ctx->xf.p, (size_t)n * 48, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(inv.data(), ctx->inv_xf.p, (size_t)n * 48, hipMemcpyDeviceToHost) != hipSuccess ||
+        (ctx->motion_xf.p && hipMemcpy(motion.data(), ctx->motion_xf.p, (size_t)n * 48, hipMemcpyDeviceToHost) != hipSuccess))
+      return lost(fail(ctx, STHIP_ERR_HIP, call + "reading the resident matrices failed"));
+    if ((rc = update_transforms_host(ctx, call, xf.data(), inv.data(), ctx->motion_xf.p ? motion.data() : nullptr, n, nullptr)) != STHIP_OK) return lost(rc);
+  }
+  local.device_ms = 0;
+  (void)hipEventElapsedTime(&local.device_ms, ctx->edit_ev[0], ctx->edit_ev[1]);
+  local.device_ms += build_ms;
+  local.call_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (info) *info = local;
+  return STHIP_OK;
 }
 
 // The device builder of sthip_scene_set_transforms (top_level.hip). `xf` / `inv` / `motion` are device memory here.

@@ -326,6 +326,41 @@ inline void load_tri(const sthip_scene_desc& s, const InstView& in, uint32_t pri
 
 }  // namespace
 
+bool parse_volume_header(const uint8_t* b, uint64_t have, uint64_t n, DeviceVolume& v, std::string& err) {
+  if (have > n) have = n;
+  auto rd32 = [&](uint64_t off) { uint32_t x = 0; if (off + 4 <= have) memcpy(&x, b + off, 4); return x; };
+  auto rd64 = [&](uint64_t off) { uint64_t x = 0; if (off + 8 <= have) memcpy(&x, b + off, 8); return x; };
+  auto rdf = [&](uint64_t off) { float x = 0; if (off + 4 <= have) memcpy(&x, b + off, 4); return x; };
+  if (!b || n < 672 + 64 + 64 || n > 0xFFFFFFF0ull || (n & 3) || rd64(0) != 0x304244566f6e614eull || rd32(636) != 1u) {
+    err = "gVolumes entry is not a NanoVDB float grid (magic / grid type / size)";
+    return false;
+  }
+  memset(&v, 0, sizeof(v));
+  v.bytes = (uint32_t)n;
+  const uint64_t root = 672 + rd64(672 + 24);
+  if (root + 64 > n) {
+    err = "gVolumes entry: the root node lies outside the buffer";
+    return false;
+  }
+  v.root = (uint32_t)root;
+  const uint64_t tiles = rd32(root + 24);  // the device reader walks the root's tile table linearly
+  if (tiles > 65536 || root + 64 + 32 * tiles > n) {
+    err = "gVolumes entry: the root tile table lies outside the buffer";
+    return false;
+  }
+  for (int k = 0; k < 3; k++) {
+    v.bbox_min[k] = (int32_t)rd32(root + 4 * k);
+    v.bbox_max[k] = (int32_t)rd32(root + 12 + 4 * k);
+    v.vecf[k] = rdf(296 + 72 + 4 * k);
+  }
+  v.root_max = rdf(root + 36);
+  for (int k = 0; k < 9; k++) {
+    v.matf[k] = rdf(296 + 4 * k);
+    v.invmatf[k] = rdf(296 + 36 + 4 * k);
+  }
+  return true;
+}
+
 bool build_scene_bvh(const sthip_scene_desc& s, BuiltBvh& out, std::string& err, int builder, DeviceBuildTarget* device, bool embed_leaves) {
   out = BuiltBvh();
   // device mode: bottom levels of >= DEVICE_MIN_PRIMS triangles are built in place on the GPU from the uploaded scene arrays
@@ -343,39 +378,8 @@ bool build_scene_bvh(const sthip_scene_desc& s, BuiltBvh& out, std::string& err,
   std::vector<uint32_t> merged, separate, spheres, volumes;
   // gVolumes: NanoVDB float grids, format 32.x (PNanoVDB.h:761-777,904-916,964-968, FLOAT row of the type constants)
   for (uint32_t i = 0; i < s.volume_count; i++) {
-    const uint8_t* b = (const uint8_t*)s.gVolumes[i].data;
-    const uint64_t n = s.gVolumes[i].bytes;
-    auto rd32 = [&](uint64_t off) { uint32_t v = 0; if (off + 4 <= n) memcpy(&v, b + off, 4); return v; };
-    auto rd64 = [&](uint64_t off) { uint64_t v = 0; if (off + 8 <= n) memcpy(&v, b + off, 8); return v; };
-    auto rdf = [&](uint64_t off) { float v = 0; if (off + 4 <= n) memcpy(&v, b + off, 4); return v; };
-    if (!b || n < 672 + 64 + 64 || n > 0xFFFFFFF0ull || (n & 3) || rd64(0) != 0x304244566f6e614eull || rd32(636) != 1u) {
-      err = "gVolumes entry is not a NanoVDB float grid (magic / grid type / size)";
-      return false;
-    }
     DeviceVolume v;
-    memset(&v, 0, sizeof(v));
-    v.bytes = (uint32_t)n;
-    const uint64_t root = 672 + rd64(672 + 24);
-    if (root + 64 > n) {
-      err = "gVolumes entry: the root node lies outside the buffer";
-      return false;
-    }
-    v.root = (uint32_t)root;
-    const uint64_t tiles = rd32(root + 24);  // the device reader walks the root's tile table linearly
-    if (tiles > 65536 || root + 64 + 32 * tiles > n) {
-      err = "gVolumes entry: the root tile table lies outside the buffer";
-      return false;
-    }
-    for (int k = 0; k < 3; k++) {
-      v.bbox_min[k] = (int32_t)rd32(root + 4 * k);
-      v.bbox_max[k] = (int32_t)rd32(root + 12 + 4 * k);
-      v.vecf[k] = rdf(296 + 72 + 4 * k);
-    }
-    v.root_max = rdf(root + 36);
-    for (int k = 0; k < 9; k++) {
-      v.matf[k] = rdf(296 + 4 * k);
-      v.invmatf[k] = rdf(296 + 36 + 4 * k);
-    }
+    if (!parse_volume_header((const uint8_t*)s.gVolumes[i].data, s.gVolumes[i].bytes, s.gVolumes[i].bytes, v, err)) return false;
     out.volumes.push_back(v);
   }
   for (uint32_t i = 0; i < s.instance_count; i++) {

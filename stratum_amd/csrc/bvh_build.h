@@ -129,6 +129,9 @@ enum BvhBuilderKind { BVH_BUILDER_SAH_HOST = 0, BVH_BUILDER_LBVH_GPU = 1 };
 // Validates the scene arrays and builds. Returns false and sets `err` on malformed input.
 // `builder`: binned SAH on the host (default; best traversal) or LBVH on the GPU (fastest build; lbvh.hip).
 // With a DeviceBuildTarget (and the LBVH builder) bottom levels of >= 64 triangles are built in place on the device.
+// The header of one gVolumes entry, checked and parsed: `b` holds the first `have` bytes of a grid of `n` bytes (the checks
+// read nothing beyond the root's 64 bytes). The upload and sthip_scene_set_volume share it: the same refusals, the same words.
+bool parse_volume_header(const uint8_t* b, uint64_t have, uint64_t n, DeviceVolume& v, std::string& err);
 bool build_scene_bvh(const sthip_scene_desc& scene, BuiltBvh& out, std::string& err, int builder = BVH_BUILDER_SAH_HOST, DeviceBuildTarget* device = nullptr, bool embed_leaves = false);
 // Collapses the finished binary tree of a host build (out.dev_nodes == 0) into 4-wide nodes with quantised child boxes
 // (bvh.h: WideNode): out.wide_*. Every leaf reference, and with it every triangle and entry, stays what it is, and every

@@ -24,6 +24,7 @@
 #include "scene_prepare.h"
 #include "top_level.h"
 #include "traverse.h"
+#include "volume_build.h"
 
 // (nothing in here is part of the library's interface: the types and the functions stay out of its dynamic symbol table)
 #pragma GCC visibility push(hidden)
@@ -109,6 +110,8 @@ struct KeptScene {
   // (sync_kept_environment)
   std::set<uint32_t> stale_images, stale_images1;
   bool stale_env_tables = false;
+  // the grids of gVolumes that sthip_scene_set_volume built on the device or took from a device pointer (sync_kept_volumes)
+  std::set<uint32_t> stale_volumes;
   // The host wrote the kept records [first, first + count): they are not stale any more
   void vertices_written(uint32_t first, uint32_t count) {
     if (stale_vertices.empty() || !count) return;
@@ -167,6 +170,7 @@ struct KeptScene {
     stale_images.clear();
     stale_images1.clear();
     stale_env_tables = false;
+    stale_volumes.clear();
   }
   void set_transforms(const sthip_TransformData* new_xf, const sthip_TransformData* new_inv, const sthip_TransformData* new_motion, uint32_t n) {  // (motion NULL: identity)
     xf.assign(new_xf, new_xf + n);
@@ -306,6 +310,7 @@ struct sthip_ctx {
   // those of the resident tree; whether the host's copies of the matrices (the kept scene, top.entries[k].inv) are older
   // than the device's — a device-pointer call or a derived array left them behind (sync_kept_transforms)
   sthip::DeviceTopLevel* top_level = nullptr;
+  sthip::DeviceVolumeBuild* volume_build = nullptr;  // sthip_build_volume (volume_build.hip): the build's scratch, made at first use
   bool top_level_static_valid = false;
   bool host_transforms_stale = false;
   // sthip_scene_update_vertices (refit.hip): the schedule of the resident bottom levels and the refit's scratch; what the
@@ -483,5 +488,9 @@ inline int fail(sthip_ctx* ctx, int code, const std::string& msg) {
   ctx->error = msg;
   return code;
 }
+
+// post.hip: the dense half of sthip_build_volume, shared with sthip_scene_set_volume (api.hip)
+int dense_volume_scan(sthip_ctx* ctx, const char* call, const sthip_dense_volume_desc* d, DevBuf<float>& staged, sthip::VolumeBuildInput& in, sthip::VolumeBuildCounts& c, sthip::VolumeHeader& header,
+                      sthip_volume_info* info, float& scan_ms);
 
 #pragma GCC visibility pop

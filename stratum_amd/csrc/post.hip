@@ -1,5 +1,6 @@
 // post.hip — the calls of the C ABI (include/sthip.h) after the path and beside it: temporal accumulation, the denoiser's
-// filter, material conversion, tonemap and image metric, and the measured ceilings of the roofline.
+// filter, material conversion, the density grid of a dense box, tonemap and image metric, and the measured ceilings of the
+// roofline.
 #include "ceilings.h"
 #include "context.h"
 #include "denoise.h"
@@ -304,6 +305,93 @@ int sthip_convert_material(sthip_ctx* ctx, const sthip_convert_material_desc* d)
   }
   if (!ok) return fail(ctx, STHIP_ERR_HIP, "sthip_convert_material: " + err);
   if (e != hipSuccess) return fail(ctx, STHIP_ERR_HIP, std::string("sthip_convert_material: ") + hipGetErrorString(e));
+  return STHIP_OK;
+}
+
+// ---- beside the path: a NanoVDB density grid from a dense box (volume_build.hip) ----
+// The checks of a dense description, the scan with its read-back and every refusal the values decide; then the header and
+// `info`. Nothing of the caller's is written before the last refusal. Shared with sthip_scene_set_volume (api.hip).
+int dense_volume_scan(sthip_ctx* ctx, const char* call, const sthip_dense_volume_desc* d, DevBuf<float>& staged, sthip::VolumeBuildInput& in, sthip::VolumeBuildCounts& c, sthip::VolumeHeader& header,
+                      sthip_volume_info* info, float& scan_ms) {
+  auto refuse = [&](const char* field, const char* why) { return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, std::string(call) + ": " + field + " " + why); };
+  if (!d) return refuse("desc", "is NULL");
+  if (d->struct_size != sizeof(sthip_dense_volume_desc)) return refuse("struct_size", "is not sizeof(sthip_dense_volume_desc)");
+  if (!d->dense) return refuse("dense", "is NULL");
+  if (d->dense_is_device && ((uintptr_t)d->dense & 3u)) return refuse("dense", "is not 4-byte aligned");
+  for (int a = 0; a < 3; a++) {
+    if (!d->dims[a]) return refuse("dims", "has a zero extent");
+    if ((int64_t)d->origin[a] + (int64_t)d->dims[a] - 1 > (int64_t)INT32_MAX) return refuse("origin + dims", "leaves int32");
+    if (!std::isfinite(d->translation[a])) return refuse("translation", "is not finite");
+  }
+  if (!(d->voxel_size > 0.0) || !std::isfinite(d->voxel_size)) return refuse("voxel_size", "must be finite and positive");
+  if (d->name && strlen(d->name) > 255) return refuse("name", "has more than 255 bytes");
+  in = sthip::VolumeBuildInput{};
+  in.dense = d->dense;
+  for (int a = 0; a < 3; a++) in.dims[a] = d->dims[a], in.origin[a] = d->origin[a];
+  {
+    sthip::VbLattice lattice;
+    if (!sthip::vb_lattice(in, lattice)) return refuse("dims", "touch more than 2^24 bricks of 8^3 voxels");
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (!ctx->volume_build) ctx->volume_build = sthip::device_volume_build_create();
+  const uint64_t voxels = (uint64_t)d->dims[0] * d->dims[1] * d->dims[2];  // (at most 2^33: the brick limit above)
+  if (!d->dense_is_device) {  // the host form: the dense box copied up (the caller's buffer, freed when it returns)
+    HIP_TRY(ctx, staged.ensure(voxels));
+    HIP_TRY(ctx, hipMemcpyAsync(staged.p, d->dense, voxels * sizeof(float), hipMemcpyHostToDevice, st));
+    in.dense = staged.p;
+  }
+  std::string err;
+  if (!sthip::volume_build_scan(ctx->volume_build, in, st, c, scan_ms, err)) {
+    (void)hipStreamSynchronize(st);  // (the staged copy must not outlive its buffer)
+    return fail(ctx, STHIP_ERR_HIP, std::string(call) + ": " + err);
+  }
+  // ---- every refusal the values decide ----
+  if (c.nonfinite) return refuse("dense", "holds a NaN or an infinite value");
+  if (!c.active) return refuse("dense", "has no active voxel (every value is 0)");
+  if (c.uppers > sthip::NVDB_MAX_TILES) return refuse("dense", "needs more than 65536 root tiles");
+  const sthip::VolumeLayout lay = sthip::volume_layout(c);
+  if (lay.total > sthip::NVDB_MAX_BYTES) return refuse("dense", "gives a grid of more than 0xFFFFFFF0 bytes");
+  memset(info, 0, sizeof(*info));
+  sthip::volume_header(c, d->voxel_size, d->translation, d->name, header, info->world_bbox);
+  info->bytes = lay.total;
+  for (int a = 0; a < 3; a++) info->bbox_min[a] = c.bbox_min[a], info->bbox_max[a] = c.bbox_max[a];
+  info->min = c.min, info->max = c.max;
+  info->active_voxels = c.active;
+  info->leaf_count = c.leaves, info->lower_count = c.lowers, info->upper_count = c.uppers, info->root_tiles = c.uppers;
+  info->device_ms = scan_ms;
+  return STHIP_OK;
+}
+
+int sthip_build_volume(sthip_ctx* ctx, const sthip_dense_volume_desc* d, void* out, uint64_t capacity, int out_is_device, sthip_volume_info* info) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  const auto t0 = std::chrono::steady_clock::now();
+  auto wall = [&]() { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+  if (!info) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_build_volume: info is NULL");
+  if (out && out_is_device && ((uintptr_t)out & 31u)) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_build_volume: out is a device pointer that is not 32-byte aligned");
+  DevBuf<float> staged;
+  sthip::VolumeBuildInput in{};
+  sthip::VolumeBuildCounts c{};
+  sthip::VolumeHeader header;
+  float scan_ms = 0, emit_ms = 0;
+  if (const int rc = dense_volume_scan(ctx, "sthip_build_volume", d, staged, in, c, header, info, scan_ms); rc != STHIP_OK) return rc;
+  const uint64_t total = info->bytes;
+  info->call_ms = wall();
+  if (!out || capacity < total) return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_build_volume: the grid has " + std::to_string(total) + " bytes, capacity is " + std::to_string(capacity));
+  // ---- emit ----
+  std::string err;
+  void* target = out;
+  if (!out_is_device) {
+    target = sthip::volume_build_staging(ctx->volume_build, total, err);
+    if (!target) return fail(ctx, STHIP_ERR_HIP, "sthip_build_volume: " + err);
+  }
+  if (!sthip::volume_build_emit(ctx->volume_build, in, c, header, target, ctx->stream, emit_ms, err)) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return fail(ctx, STHIP_ERR_HIP, "sthip_build_volume: " + err);
+  }
+  if (!out_is_device) HIP_TRY(ctx, hipMemcpy(out, target, total, hipMemcpyDeviceToHost));
+  info->device_ms = scan_ms + emit_ms;
+  info->call_ms = wall();
   return STHIP_OK;
 }
 

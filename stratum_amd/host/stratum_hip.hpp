@@ -58,6 +58,11 @@
 #pragma weak sthip_scene_set_material_data
 #pragma weak sthip_scene_read_image_range
 // ... and one that cannot take instance matrices from device memory or build the top level there lacks these
+// ... and one that cannot build a density grid on the device or replace a resident one lacks these: a Medium's dense source
+// then needs a finished grid from the host, and a changed grid is an upload
+#pragma weak sthip_build_volume
+#pragma weak sthip_scene_set_volume
+#pragma weak sthip_scene_read_volume
 #pragma weak sthip_scene_set_transforms
 #pragma weak sthip_scene_read_transforms
 #pragma weak sthip_scene_read_top_level
@@ -616,6 +621,69 @@ struct Medium {
   float albedo_scale[3] = {1, 1, 1};
   float attenuation_unit = 1;
   std::shared_ptr<std::vector<uint8_t>> density_buffer, albedo_buffer;
+  // A dense box of densities in DEVICE memory as the source of the density grid (include/sthip.h: sthip_dense_volume_desc):
+  // what a simulation leaves behind every frame. set_density_device() names it; the scene is then marked dirty as for any
+  // change (Scene::mark_dirty()). Where nothing else changed, BDPT::update builds the grid on the device into the resident
+  // scene (sthip_scene_set_volume); density_buffer, the host's copy, is then older than the device's and is fetched
+  // (sthip_scene_read_volume) or built (sthip_build_volume) before it is uploaded anywhere. The memory must stay valid until
+  // the BDPT::update that follows has returned. mark_density_dirty(): the bytes of density_buffer were rewritten in place.
+  struct DenseSource {
+    const float* dense = nullptr;
+    uint32_t dims[3] = {0, 0, 0};
+    int32_t origin[3] = {0, 0, 0};
+    double voxel_size = 1;
+    double translation[3] = {0, 0, 0};
+    std::string name;
+  };
+  DenseSource dense_source;
+  uint32_t density_serial = 0;               // counts set_density_device() / mark_density_dirty(): tells the grids of one buffer object apart
+  mutable bool dense_pending = false;        // dense_source is newer than density_buffer AND than the resident grid
+  mutable bool device_grid_newer = false;    // the resident grid (made from dense_source) is newer than density_buffer
+  mutable bool has_device_world_bbox = false;
+  mutable double device_world_bbox[6] = {0, 0, 0, 0, 0, 0};  // sthip_volume_info::world_bbox of that grid
+  void set_density_device(const float* dense, const uint32_t dims[3], const int32_t origin[3], double voxel_size, const double translation[3], const char* name = "density") {
+    dense_source.dense = dense;
+    for (int a = 0; a < 3; a++) dense_source.dims[a] = dims[a], dense_source.origin[a] = origin[a], dense_source.translation[a] = translation[a];
+    dense_source.voxel_size = voxel_size;
+    dense_source.name = name ? name : "";
+    if (!density_buffer) density_buffer = std::make_shared<std::vector<uint8_t>>();  // (the object the scene pools grids by)
+    density_serial++;
+    dense_pending = true;
+    device_grid_newer = false;
+  }
+  void mark_density_dirty() {
+    density_serial++;
+    dense_pending = device_grid_newer = has_device_world_bbox = false;
+  }
+  sthip_dense_volume_desc dense_desc() const {
+    sthip_dense_volume_desc d{};
+    d.struct_size = sizeof(d);
+    d.dense_is_device = 1;
+    d.dense = dense_source.dense;
+    for (int a = 0; a < 3; a++) d.dims[a] = dense_source.dims[a], d.origin[a] = dense_source.origin[a], d.translation[a] = dense_source.translation[a];
+    d.voxel_size = dense_source.voxel_size;
+    d.name = dense_source.name.c_str();
+    return d;
+  }
+  // density_buffer is the current grid again: built from the pending dense source, or fetched from resident grid `index` of
+  // `ctx` where BDPT::update installed it. Called before the buffer is uploaded (BDPT::update, every rank of MultiDeviceBDPT).
+  void materialise(sthip_ctx* ctx, uint32_t index) const {
+    if (dense_pending) {
+      if (!sthip_build_volume) throw std::runtime_error("Medium: a dense device source needs a library with sthip_build_volume");
+      const sthip_dense_volume_desc d = dense_desc();
+      sthip_volume_info info{};
+      (void)sthip_build_volume(ctx, &d, nullptr, 0, 0, &info);  // the size (refused: capacity 0)
+      if (!info.bytes) throw std::runtime_error(std::string("sthip_build_volume: ") + sthip_last_error(ctx));
+      density_buffer->resize((size_t)info.bytes);
+      if (sthip_build_volume(ctx, &d, density_buffer->data(), info.bytes, 0, &info) != STHIP_OK) throw std::runtime_error(std::string("sthip_build_volume: ") + sthip_last_error(ctx));
+    } else if (device_grid_newer) {
+      uint64_t bytes = 0;
+      (void)sthip_scene_read_volume(ctx, index, nullptr, 0, &bytes);
+      density_buffer->resize((size_t)bytes);
+      if (!bytes || sthip_scene_read_volume(ctx, index, density_buffer->data(), bytes, &bytes) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_read_volume: ") + sthip_last_error(ctx));
+    }
+    dense_pending = device_grid_newer = has_device_world_bbox = false;
+  }
   void store(std::vector<uint32_t>& bytes, MaterialResources& pool) const {
     auto f = [&](float v) { uint32_t u; std::memcpy(&u, &v, 4); bytes.push_back(u); };
     for (float v : density_scale) f(v);
@@ -627,6 +695,10 @@ struct Medium {
   }
   // GridData::mWorldBBox (6 doubles at byte 560 of the grid): what worldBBox() returns
   bool world_bbox(double box[6]) const {
+    if (has_device_world_bbox) {
+      std::memcpy(box, device_world_bbox, 48);
+      return true;
+    }
     if (!density_buffer || density_buffer->size() < 608) return false;
     std::memcpy(box, density_buffer->data() + 560, 48);
     return true;
@@ -811,7 +883,9 @@ class Scene {
       if (!any(mImageFormats) && !any(mImage1Formats)) return sthip_scene_upload(ctx, &d);
       return sthip_scene_upload_formats(ctx, &d, mImageFormats.empty() ? nullptr : mImageFormats.data(), mImage1Formats.empty() ? nullptr : mImage1Formats.data());
     }
-    std::vector<sthip_volume_desc> mVolumeDescs;                          // gVolumes
+    mutable std::vector<sthip_volume_desc> mVolumeDescs;                  // gVolumes (made again by desc(): a grid may have been materialised since)
+    std::vector<uint32_t> mVolumeSerials;                                 // Medium::density_serial of the grids as they were packed, in gVolumes order
+    std::vector<const Medium*> mVolumeMedia;                              // the Medium whose density grid gVolumes[i] is (nullptr: an albedo grid)
     std::vector<std::pair<const Medium*, uint32_t>> mMediumInstances;     // Medium component -> its volume instance (mInstanceTransformMap)
     std::vector<float> mDistributionData;  // gDistributions, Scene.cpp:670-683
     uint32_t mEnvironmentMaterialAddress = ~0u;
@@ -858,6 +932,8 @@ class Scene {
       d.image1_count = (uint32_t)mImage1Descs.size();
       d.gDistributions = mDistributionData.empty() ? nullptr : mDistributionData.data();
       d.distribution_count = (uint32_t)mDistributionData.size();
+      mVolumeDescs.clear();
+      for (const auto* v : mResources.volumes) mVolumeDescs.push_back(sthip_volume_desc{v->data(), (uint64_t)v->size()});
       d.gVolumes = mVolumeDescs.empty() ? nullptr : mVolumeDescs.data();
       d.volume_count = (uint32_t)mVolumeDescs.size();
       return d;
@@ -1073,6 +1149,9 @@ class Scene {
       inst.packed[0] = STHIP_INSTANCE_TYPE_VOLUME | (material_address << 4);
       inst.packed[1] = 0xFFFu;
       inst.packed[2] = sd->mResources.get_index(vol->density_buffer);
+      sd->mVolumeSerials.resize(sd->mResources.volumes.size(), 0u);
+      sd->mVolumeMedia.resize(sd->mResources.volumes.size(), nullptr);
+      if (!sd->mVolumeMedia[inst.packed[2]]) sd->mVolumeSerials[inst.packed[2]] = vol->density_serial, sd->mVolumeMedia[inst.packed[2]] = vol.get();
       const TransformData transform = node_to_world(vol.node());
       sd->mMediumInstances.emplace_back(vol.get(), (uint32_t)sd->mInstances.size());
       sd->mInstances.push_back(inst);
@@ -1082,7 +1161,8 @@ class Scene {
       sd->mInstanceInverseTransforms.push_back(inv);
       sd->mInstanceMotionTransforms.push_back(tmul(prev_of(vol.node(), transform), inv));
     });
-    for (const auto* v : sd->mResources.volumes) sd->mVolumeDescs.push_back(sthip_volume_desc{v->data(), (uint64_t)v->size()});
+    sd->mVolumeSerials.resize(sd->mResources.volumes.size(), 0u);
+    sd->mVolumeMedia.resize(sd->mResources.volumes.size(), nullptr);
     // environment material, Scene.cpp:631-640: the first Environment whose value is not zero
     mNode.root().for_each_descendant<Environment>([&](const component_ptr<Environment>& environment) {
       if (environment && !environment->is_zero() && sd->mEnvironmentMaterialAddress == ~0u) {
@@ -1426,6 +1506,11 @@ class BDPT {
   bool last_update_was_vertices_only() const { return mLastUpdateWasVerticesOnly; }  // (no transform changed with them)
   bool last_update_was_environment_only() const { return mLastUpdateWasEnvironmentOnly; }
   bool last_update_was_materials_only() const { return mLastUpdateWasMaterialsOnly; }
+  bool last_update_was_volumes_only() const { return mLastUpdateWasVolumesOnly; }
+  // sthip_scene_set_volume for a grid that is the only change (default: on where the library has the call); off: such a
+  // change is an upload, as with a library without the symbol
+  void set_volumes_on_device(bool on) { mVolumesOnDevice = on; }
+  uint32_t volume_calls() const { return mVolumeCalls; }                    // sthip_scene_set_volume calls of update() so far
   uint32_t material_data_calls() const { return mMaterialDataCalls; }       // sthip_scene_set_material_data calls of update() so far
   uint32_t image_calls() const { return mImageCalls; }                      // sthip_scene_set_images calls of update() so far
   uint32_t upload_calls() const { return mUploadCalls; }                    // sthip_scene_upload(_formats) calls of update() so far
@@ -1474,6 +1559,21 @@ class BDPT {
     mLastUpdateWasMaterialsOnly = false;
     const Scene::SceneData& sd = *scene->data();
     const bool rigs = !sd.mRigs.empty();  // (packed only with a library that has the calls: Scene::pose_on_device())
+    mLastUpdateWasVolumesOnly = false;
+    if (mBoundData && !same_volume_serials(*mBoundData, sd)) {
+      // A density grid changed (Medium::set_density_device / mark_density_dirty). Where it is the only change, the grid is
+      // replaced in the resident scene: built there from the dense device source, or copied from the host's bytes. Otherwise,
+      // with a library without the call, under MultiDeviceBDPT (mVolumesOnDevice = false) or where the library refuses:
+      // the grids are made current on the host and the scene is uploaded; no partial update may pass over a changed grid.
+      if (mVolumesOnDevice && sthip_scene_set_volume && volumes_only_changed(*mBoundData, sd) && set_volumes(*mBoundData, sd) == STHIP_OK) {
+        mLastUpdateWasVolumesOnly = true;
+        mLastUpdateWasTransformsOnly = false;
+        mBound = scene->data().get();
+        mBoundData = scene->data();
+        return;
+      }
+      mBoundData = nullptr;  // (every partial path below needs it)
+    }
     if (scene->environment_on_device() && mBoundData && environment_only_changed(*mBoundData, sd)) {
       // Only the environment's value and / or the texels of its image changed: the value, the texels, the mip chain and the
       // tables are replaced in the resident scene. A call the library refuses as unsupported (an image a material shares): upload.
@@ -1565,6 +1665,9 @@ class BDPT {
       }
     }
     mLastUpdateWasTransformsOnly = updated;
+    if (!updated)  // the host's grids must be the current ones: a dense source not built yet, a grid only the device has
+      for (size_t i = 0; i < sd.mVolumeMedia.size(); i++)
+        if (sd.mVolumeMedia[i] && (sd.mVolumeMedia[i]->dense_pending || sd.mVolumeMedia[i]->device_grid_newer)) sd.mVolumeMedia[i]->materialise(mCtx, (uint32_t)i);
     if (!updated && sd.upload(mCtx) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_upload: ") + sthip_last_error(mCtx));
     if (!updated) mUploadCalls++;
     if (!updated && sd.mEnvironmentTablesOnDevice) {  // zeroed tables went up: the device builds them from the resident texels
@@ -1884,6 +1987,9 @@ class BDPT {
   bool mLastUpdateWasTransformsOnly = false, mLastUpdateWasVerticesOnly = false, mLastUpdateWasEnvironmentOnly = false, mLastUpdateWasMaterialsOnly = false;
   // false: a changed material is uploaded like any other change. The multi-device driver clears it, as mRefitDeformedMeshes.
   bool mMaterialsOnDevice = true;
+  bool mVolumesOnDevice = true;  // MultiDeviceBDPT: false (a changed grid is a full upload on every rank)
+  bool mLastUpdateWasVolumesOnly = false;
+  uint32_t mVolumeCalls = 0;
   // false: a deformed mesh is uploaded like any other change. The multi-device driver clears it: its ranks must all walk the
   // same tree form, and it sends them uploads or transforms-only updates, nothing else (stratum_hip_multi.hpp).
   bool mRefitDeformedMeshes = true;
@@ -2014,6 +2120,42 @@ class BDPT {
         if (!same_bytes(x.targets[k], y.targets[k])) return false;
     }
     return true;
+  }
+  static bool same_volume_serials(const Scene::SceneData& a, const Scene::SceneData& b) { return a.mVolumeSerials == b.mVolumeSerials; }
+  // everything of `b` is what `a` is except the grids behind some of the same volume objects
+  static bool volumes_only_changed(const Scene::SceneData& a, const Scene::SceneData& b) {
+    return same_geometry(a, b) && same_poses(a, b) && a.mVolumeMedia == b.mVolumeMedia && same_bytes(a.mInstanceTransforms, b.mInstanceTransforms) &&
+           same_bytes(a.mInstanceInverseTransforms, b.mInstanceInverseTransforms) && same_bytes(a.mInstanceMotionTransforms, b.mInstanceMotionTransforms);
+  }
+  // the changed grids into the resident scene; a refusal the library words as unsupported or invalid leaves the upload to the caller
+  int set_volumes(const Scene::SceneData& a, const Scene::SceneData& b) {
+    for (size_t i = 0; i < b.mVolumeSerials.size(); i++) {
+      if (a.mVolumeSerials[i] == b.mVolumeSerials[i]) continue;
+      const Medium* m = b.mVolumeMedia[i];
+      if (!m) return STHIP_ERR_UNSUPPORTED;
+      sthip_volume_source s{};
+      s.struct_size = sizeof(s);
+      sthip_dense_volume_desc d{};
+      if (m->dense_pending) {
+        d = m->dense_desc();
+        s.dense = &d;
+      } else {
+        s.data = m->density_buffer->data();
+        s.bytes = m->density_buffer->size();
+      }
+      sthip_volume_info info{};
+      mVolumeCalls++;
+      const int rc = sthip_scene_set_volume(mCtx, (uint32_t)i, &s, &info);
+      if (rc == STHIP_ERR_HIP || rc == STHIP_ERR_NO_SCENE) throw std::runtime_error(std::string("sthip_scene_set_volume: ") + sthip_last_error(mCtx));
+      if (rc != STHIP_OK) return rc;
+      if (m->dense_pending) {
+        m->dense_pending = false;
+        m->device_grid_newer = true;
+        m->has_device_world_bbox = true;
+        std::memcpy(m->device_world_bbox, info.world_bbox, 48);
+      }
+    }
+    return STHIP_OK;
   }
   static bool same_geometry(const Scene::SceneData& a, const Scene::SceneData& b) { return same_bytes(a.mVertices, b.mVertices) && same_topology(a, b); }
   // everything equal except the CONTENTS of the vertex array (and the transforms, which have update calls of their own)

@@ -151,6 +151,7 @@ class MultiDeviceBDPT : public BDPT {
       : BDPT(node, devices.empty() ? 0 : devices[0]), mDevices(devices), mTileW(tile_w), mTileH(tile_h) {
     if (devices.empty()) throw std::invalid_argument("MultiDeviceBDPT: no devices");
     mRefitDeformedMeshes = false;  // (update() below: a deformed mesh is a full upload on every rank, rank 0 included)
+    mVolumesOnDevice = false;      // (... and a changed density grid: sthip_scene_set_volume is not driven here; rank 0 makes the grid current on the host)
     mMaterialsOnDevice = false;    // (... and so is a changed material: sthip_scene_set_images / _set_material_data are not driven here)
     mDenoise = false;  // this driver has no denoiser: a Denoiser in the graph is not used
     mRanks.resize(devices.size());

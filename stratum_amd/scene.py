@@ -447,6 +447,13 @@ class SceneBuilder:
         self._volumes.append(np.ascontiguousarray(np.frombuffer(bytes(grid_bytes), dtype=np.uint8) if not isinstance(grid_bytes, np.ndarray) else grid_bytes.astype(np.uint8)))
         return len(self._volumes) - 1
 
+    def add_dense_volume(self, dense, origin=(0, 0, 0), voxel_size=1.0, translation=(0.0, 0.0, 0.0), name="density"):
+        """A dense [nx, ny, nz] box of float32 densities as a NanoVDB fog volume (nvdb.dense_to_nanovdb: the contract of
+        sthip_build_volume, on the host): what load_volumes.cpp:87-91 does with GridBuilder. Returns the volume's index."""
+        from . import nvdb
+
+        return self.add_volume(nvdb.dense_to_nanovdb(dense, origin, voxel_size, translation, name))
+
     def add_medium(self, density_volume, density_scale=(1, 1, 1), albedo_scale=(1, 1, 1), anisotropy=0.0, attenuation_unit=1.0, albedo_volume=None, transform=None):
         """A Medium component (Material.hpp:72-87) on a node: one volume instance of the scene (Scene.cpp:556-590)."""
         m = np.eye(4) if transform is None else np.asarray(transform, dtype=np.float64)

@@ -417,6 +417,45 @@ CONVERT_KINDS = ["GltfPbr", "DiffuseSpecular", "AlphaToRoughness", "ShininessToR
 CONVERT = {n: i for i, n in enumerate(CONVERT_KINDS)}
 
 
+class DenseVolumeDesc(C.Structure):  # sthip_dense_volume_desc
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dense_is_device", C.c_uint32),
+        ("dense", C.c_void_p),
+        ("dims", C.c_uint32 * 3),
+        ("origin", C.c_int32 * 3),
+        ("voxel_size", C.c_double),
+        ("translation", C.c_double * 3),
+        ("name", C.c_char_p),
+    ]
+
+
+class VolumeInfo(C.Structure):  # sthip_volume_info
+    _fields_ = [
+        ("bytes", C.c_uint64),
+        ("bbox_min", C.c_int32 * 3),
+        ("bbox_max", C.c_int32 * 3),
+        ("world_bbox", C.c_double * 6),
+        ("min", C.c_float),
+        ("max", C.c_float),
+        ("active_voxels", C.c_uint64),
+        ("leaf_count", C.c_uint32),
+        ("lower_count", C.c_uint32),
+        ("upper_count", C.c_uint32),
+        ("root_tiles", C.c_uint32),
+        ("device_ms", C.c_float),
+        ("call_ms", C.c_float),
+    ]
+
+
+class VolumeSource(C.Structure):  # sthip_volume_source
+    _fields_ = [("struct_size", C.c_uint32), ("data_is_device", C.c_uint32), ("data", C.c_void_p), ("bytes", C.c_uint64), ("dense", C.POINTER(DenseVolumeDesc))]
+
+
+DENSE_VOLUME_DESC_BYTES, VOLUME_INFO_BYTES = 80, 120  # sizeof(sthip_dense_volume_desc), sizeof(sthip_volume_info), include/sthip.h
+assert C.sizeof(DenseVolumeDesc) == DENSE_VOLUME_DESC_BYTES and C.sizeof(VolumeInfo) == VOLUME_INFO_BYTES and C.sizeof(VolumeSource) == 32
+
+
 class EnvironmentDesc(C.Structure):  # sthip_environment_desc
     _fields_ = [
         ("struct_size", C.c_uint32),
