@@ -974,6 +974,8 @@ typedef struct sthip_stats {
   uint64_t max_paths_in_flight;
   uint32_t batch_halvings;
   uint32_t full_rebuilds; /* sthip_scene_update_transforms calls that had to build the scene again (an instance of the merged mesh moved) */
+  uint32_t leaf_records;  /* 1: the persistent trace kernel of the last render tested leaves from their 64-byte records ("leaf_pairs") */
+  uint32_t reserved0;
 } sthip_stats;
 int sthip_get_stats(sthip_ctx* ctx, sthip_stats* out);
 
@@ -1001,7 +1003,13 @@ int sthip_measure_ceiling(sthip_ctx* ctx, uint32_t kind, double* gbytes_per_s);
  * transforms-only update on the device; 0 = never; 2 = only when the binary nodes exceed 4 MiB, one XCD's L2; 3 = the 8-wide
  * compressed form (80-byte nodes whose children are addressed by a base and a mask, 64-bit group stack) for host-built
  * trees, the 4-wide form for the others; not with "treetop" or "embed_leaves"), "tri_min_lanes" (1..64, default 1: the
- * 8-wide walk's leaf phase goes on while at least this many lanes hold a triangle), "hashgrid_serial" (0/1: build the reservoir-reuse hash grids with the one-thread serial probe
+ * 8-wide walk's leaf phase goes on while at least this many lanes hold a triangle), "leaf_pairs" (default 1: the persistent trace kernel tests a
+ * leaf of a host-built 4-wide tree from one 64-byte record that holds the four vertices of its two edge-sharing triangles,
+ * one memory round trip per leaf instead of one per triangle; 0 = from the per-triangle array, on the same tree. Takes effect
+ * at the next render. The records take 64 bytes of device memory per leaf triangle, whatever the option says; a device that
+ * cannot hold them renders without. Scenes with alpha masks or volumes and GPU-built trees have none and ignore the option;
+ * a vertex update or a pose drops them until the next upload, a transforms-only update keeps them; sthip_stats::leaf_records
+ * says whether the last render used them), "hashgrid_serial" (0/1: build the reservoir-reuse hash grids with the one-thread serial probe
  * sequence instead of the parallel device build: the same grids, for tests), "reuse_grids_persist" (default 0: every call starts a
  * new chain, its first seed finds no grid — upstream's first frame, gReservoirSpatialM = 0, BDPT.cpp:482-483. 1: the grids the
  * last seed of a call leaves are what the first seed of the NEXT call looks into, as long as that call asks for the same reuse

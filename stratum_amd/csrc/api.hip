@@ -65,9 +65,10 @@ static const void* find_kernel(const KernelEntry (&table)[N], uint32_t key) {
   return nullptr;
 }
 // k_trace by (count_traversal, alpha masks / volumes, bounded stack) for the tree the scene is walked in: the 8-wide or 4-wide
-// form ("wide_bvh"; never with the treetop) or the binary one
+// form ("wide_bvh"; never with the treetop) or the binary one; the 4-wide form over its leaf records where the tree has them
+// ("leaf_pairs") and the instantiation exists
 static const void* trace_kernel(const DeviceBvh& bvh, bool count, bool alpha, bool top) {
-  const int wide = bvh.wide8_nodes ? 2 : bvh.wide_nodes ? 1 : 0;
+  const int wide = bvh.wide8_nodes ? 2 : bvh.wide_nodes ? (bvh.pairs && !alpha ? 3 : 1) : 0;
   return find_kernel(g_trace_kernels, sthip::trace_key(count, alpha, bvh.spill != nullptr, top && wide == 0, wide));
 }
 // The kernels with two bool template arguments, all four instantiations of each compiled here
@@ -102,6 +103,7 @@ static void fill_counter_stats(sthip_ctx* ctx, const unsigned long long* c) {
 }
 
 static uint32_t grid_for(const sthip_ctx* ctx, size_t n);
+static void bind_leaf_pairs(sthip_ctx* ctx);
 
 
 // ---- frames in flight of sthip_render_async ----
@@ -491,6 +493,9 @@ int sthip_set_option(sthip_ctx* ctx, const char* name, int64_t value) {
       (void)hipStreamSynchronize(ctx->stream);
       if (hipMemcpy(ctx->deep_count.p, junk, 8, hipMemcpyHostToDevice) != hipSuccess) return fail(ctx, STHIP_ERR_HIP, "poison_deep_queue: copy failed");
     }
+  } else if (!strcmp(name, "leaf_pairs")) {  // takes effect at the next render: the same tree, its leaves from the records or from BvhTri
+    ctx->leaf_pairs = value != 0;
+    bind_leaf_pairs(ctx);
   } else if (!strcmp(name, "tri_min_lanes"))  // the 8-wide walk's leaf phase goes on while at least this many lanes hold a triangle
     ctx->tri_min_lanes = ctx->bvh.wide8_tri_min = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 64);
   else if (!strcmp(name, "lbvh_algorithm"))  // 0: Karras radix tree, 1: PLOC (default)
@@ -575,6 +580,15 @@ static hipError_t upload_nodes(sthip_ctx* ctx, size_t first, const BvhNode* node
   return hipMemcpy(ctx->nodes.p + first, slots.data(), count * sizeof(BvhNodeSlot), hipMemcpyHostToDevice);
 }
 
+// the leaf records k_trace reads: the resident ones while "leaf_pairs" is on
+static void bind_leaf_pairs(sthip_ctx* ctx) { ctx->bvh.pairs = ctx->leaf_pairs && ctx->leaf_pairs_resident ? reinterpret_cast<const uint4*>(ctx->pairs.p) : nullptr; }
+// The resident leaf records no longer describe the leaf triangles: k_trace tests leaves from BvhTri. Before anything writes
+// leaf triangles on the device or replaces them (bvh.h: LeafPair lists the writers). A transforms-only update keeps them: the
+// leaf triangles stay, and the wide form collapsed again on the device has the binary tree's leaves, which all have a record.
+static void drop_leaf_pairs(sthip_ctx* ctx) {
+  ctx->leaf_pairs_resident = false;
+  ctx->bvh.pairs = nullptr;
+}
 static void clear_wide(sthip_ctx* ctx) {  // no 4-wide form: k_trace walks the binary tree (or the 8-wide form)
   ctx->bvh.wide_nodes = nullptr;
   ctx->bvh.wide_entries = nullptr;
@@ -992,11 +1006,11 @@ static int install_tree(sthip_ctx* ctx, sthip::BuiltBvh& built) {
     if (!packed.empty()) HIP_TRY(ctx, hipMemcpy(ctx->nodes.p, packed.data(), packed.size() * sizeof(BvhNodePacked), hipMemcpyHostToDevice));
   } else {
     if (!built.nodes.empty()) HIP_TRY(ctx, upload_nodes(ctx, built.dev_nodes, built.nodes.data(), built.nodes.size()));
-    if (!built.tris.empty()) HIP_TRY(ctx, hipMemcpy(ctx->tris.p + built.dev_tris, built.tris.data(), built.tris.size() * sizeof(BvhTri), hipMemcpyHostToDevice));
-  }
+  }  // (the leaf triangles: below, once build_leaf_pairs has had its say about their order)
   if (!built.entries.empty()) HIP_TRY(ctx, hipMemcpy(ctx->entries.p, built.entries.data(), built.entries.size() * sizeof(TlasEntry), hipMemcpyHostToDevice));
   clear_wide(ctx);
   clear_wide8(ctx);
+  drop_leaf_pairs(ctx);  // (they describe the tree that goes away)
   ctx->top_level_static_valid = false;  // (top_level.hip: the per-entry tables belong to the tree that goes away)
   ctx->host_transforms_stale = false;   // (what goes up now is what the host holds)
   ctx->bvh.wide8_tri_min = ctx->tri_min_lanes;
@@ -1013,6 +1027,20 @@ static int install_tree(sthip_ctx* ctx, sthip::BuiltBvh& built) {
   if (ctx->want_wide && built.dev_nodes == 0) {  // a host-built tree: collapsed on the host from its exact boxes (a device build: below, from the nodes in HBM)
     sthip::build_wide_bvh(built);
     if (!built.wide_nodes.empty() && built.wide_nodes.size() * sizeof(WideNode) <= 0xFFFFFFFFull) {
+      sthip::build_leaf_pairs(built);  // (the records are made whatever "leaf_pairs" says: the option picks the kernel, not the tree)
+      // (64 bytes per leaf triangle; a device that cannot hold them walks the tree without: the triangles' order stays swapped, which no result depends on)
+      if (!built.leaf_pairs.empty() && ctx->pairs.ensure(built.leaf_pairs.size()) != hipSuccess) {
+        (void)hipGetLastError();
+        built.leaf_pairs.clear();
+      }
+      if (!built.leaf_pairs.empty()) {
+        HIP_TRY(ctx, hipMemcpy(ctx->pairs.p, built.leaf_pairs.data(), built.leaf_pairs.size() * sizeof(LeafPair), hipMemcpyHostToDevice));
+        ctx->leaf_pairs_resident = true;
+        bind_leaf_pairs(ctx);
+        if (getenv("STHIP_VERBOSE"))
+          fprintf(stderr, "[sthip] leaf records: %zu single, %zu fan, %zu strip (%zu swapped), %zu two-triangle leaves fit no pattern\n", built.pair_single, built.pair_fan, built.pair_strip, built.pair_swapped,
+                  built.pair_unfit);
+      }
       HIP_TRY(ctx, ctx->wide_nodes.ensure(built.wide_nodes.size()));
       HIP_TRY(ctx, ctx->wide_entries.ensure(std::max<size_t>(1, built.wide_entries.size())));
       HIP_TRY(ctx, hipMemcpy(ctx->wide_nodes.p, built.wide_nodes.data(), built.wide_nodes.size() * sizeof(WideNode), hipMemcpyHostToDevice));
@@ -1024,6 +1052,7 @@ static int install_tree(sthip_ctx* ctx, sthip::BuiltBvh& built) {
       ctx->wide_node_count = built.wide_nodes.size();
     }
   }
+  if (!built.embedded && !built.tris.empty()) HIP_TRY(ctx, hipMemcpy(ctx->tris.p + built.dev_tris, built.tris.data(), built.tris.size() * sizeof(BvhTri), hipMemcpyHostToDevice));
   ctx->bvh.nodes = reinterpret_cast<const float4*>(ctx->nodes.p);
   ctx->bvh.tris = built.embedded ? reinterpret_cast<const float4*>(ctx->nodes.p) : reinterpret_cast<const float4*>(ctx->tris.p);
   ctx->bvh.entries = ctx->entries.p;
@@ -1828,6 +1857,7 @@ static int refit_resident_scene(sthip_ctx* ctx, const VertexSource& src, bool ke
   }
   ctx->reuse_grids_valid = false;
   ctx->nodes_host.n = 0;  // (no layout that reads the host copy of the nodes comes this way; it must not outlive the boxes it holds)
+  drop_leaf_pairs(ctx);   // (new positions go into BvhTri only; the wide form is collapsed again below)
   if (!sthip::refit_gather(ctx->refit, ctx->tris.p, (uint32_t)ctx->bvh_tris, ctx->vertices.p, ctx->vertex_count, ctx->indices.p, ctx->indices_bytes, ctx->stream, err))
     return fail(ctx, STHIP_ERR_HIP, call + err);
   if (ctx->bvh_tris && ctx->vertex_count) {
@@ -2749,6 +2779,7 @@ static int plan_render(sthip_ctx* ctx, const sthip_BDPTPushConstants* pc_in, uin
                       debug_mode != STHIP_DEBUG_ENVIRONMENT_SAMPLE_TEST && debug_mode != STHIP_DEBUG_ENVIRONMENT_SAMPLE_PDF &&
                       sthip::first_hit_key_make(r.first_hit_key, ctx->scene_serial, pc->gOutputExtent, r.view_count, pc->gMaxPathVertices, ctx->shard_rank, ctx->shard_count, ctx->tile_w, ctx->tile_h,
                                                 r.paths_per_seed, ctx->has_alpha && flag(STHIP_eAlphaTest), flag(STHIP_eFlipTriangleUVs), frame->gViews, frame->gViewTransforms);
+  ctx->stats.leaf_records = (!ctx->bvh.wide8_nodes && ctx->bvh.wide_nodes && ctx->bvh.pairs && !alpha) ? 1u : 0u;  // (trace_kernel's rule)
   ctx->stats.paths_per_seed = r.paths_per_seed;
   ctx->stats.seeds_in_flight = batch;
   return STHIP_OK;

@@ -86,6 +86,42 @@ struct WideNode {
   uint32_t pad[2];
   uint32_t ref[4];
 };
+// The triangles of one leaf of the 4-wide tree as ONE record ("leaf_pairs"; bvh_build.h: build_leaf_pairs): 64 aligned bytes =
+// four 16-byte loads in one round trip, where BvhTri takes three loads per triangle and a round trip each. A leaf's two
+// triangles that share an edge have four vertices between them: A = (p0, p1, p2) is the leaf's first triangle in its own
+// vertex order, B its second, also in its own order, as one of two fixed patterns over the four vertices (the triangle test's
+// t, b1, b2 and edge signs depend on the order; shared vertices are bit-equal positions):
+//   LEAF_PAIR_SINGLE  a one-triangle leaf: p3 = p0, id_b = 0xFFFFFFFF, B is never tested
+//   LEAF_PAIR_FAN     B = (p0, p2, p3): the other half of a quad cut along p0 - p2
+//   LEAF_PAIR_STRIP   B = (p1, p3, p2): the next triangle of a strip over the edge p1 - p2
+//   LEAF_PAIR_SPLIT   a two-triangle leaf that fits neither pattern in either order: a one-triangle record of A here, and a
+//                     LEAF_PAIR_SINGLE record of B in the next slot, which the lane visits in its next leaf phase
+// The builder may swap the two triangles of a leaf (in BvhTri too: hits do not depend on their order) to reach a pattern.
+// The record of the leaf whose first triangle is BvhTri f lies at index f, so a leaf reference — unchanged, the binary tree's —
+// needs no second index; the slot behind the record of a two-triangle leaf is unused unless the leaf is split. When a tree
+// has records every triangle leaf its wide nodes refer to has one. hit.leaf stays the BvhTri index (first for A, first + 1
+// for B). The array costs 64 bytes per leaf triangle of device memory (51 MB on the 801 256 leaf triangles of the atrium).
+// WRITERS of leaf-triangle positions, and what each does about the records:
+//   api.hip install_tree        host build: writes BvhTri and the records together (build_leaf_pairs)
+//   refit.hip k_refit_gather    new positions into BvhTri only — vertices that were bit-equal need not stay so; the records are
+//   animate.hip k_animate         dropped before it runs (api.hip refit_resident_scene) and the wide form is collapsed again
+//                                 from the binary tree
+//   lbvh.hip / wide.hip         device build and device collapse: no records (api.hip clear_wide)
+// READERS: k_trace<COUNT, false, BOUNDED, false, 3> (traverse.h: Traversal::pair_step) and nothing else.
+#define LEAF_PAIR_SINGLE 0u
+#define LEAF_PAIR_FAN 1u
+#define LEAF_PAIR_STRIP 2u
+#define LEAF_PAIR_SPLIT 3u
+struct LeafPair {
+  float p0[3];
+  uint32_t id_a;   // BvhTri::id of A
+  float p1[3];
+  uint32_t id_b;   // ... of B; 0xFFFFFFFF (an id that never wins a tie and is never exposed) for LEAF_PAIR_SINGLE
+  float p2[3];
+  uint32_t first;  // the leaf's first BvhTri (= this record's index)
+  float p3[3];
+  uint32_t form;   // LEAF_PAIR_*
+};
 // The 8-wide compressed node ("wide_bvh" = 3; bvh_build.h: build_wide8_bvh): 80 bytes = five 16-byte loads per lane, after
 // Ylitie, Karras, Laine, "Efficient Incoherent Ray Traversal on GPUs Through Compressed Wide BVHs" (HPG 2017). The boxes of
 // up to eight children as 8-bit planes on the node's grid (as WideNode). No child references: the INNER children of a node
@@ -186,5 +222,7 @@ static_assert(sizeof(BvhTri) == 48, "BvhTri");
 static_assert(sizeof(BvhTriShade) == 64, "BvhTriShade");
 static_assert(sizeof(WideNode) == 64, "WideNode");
 static_assert(sizeof(Wide8Node) == 80, "Wide8Node");
+static_assert(sizeof(LeafPair) == 64, "LeafPair");
+static_assert(BVH_MAX_LEAF_TRIS <= 2, "a LeafPair record holds at most two triangles");
 static_assert(sizeof(TlasEntry) == 80, "TlasEntry");
 #endif

@@ -1100,6 +1100,87 @@ void build_wide_bvh(BuiltBvh& out) {
   }
 }
 
+// ---- the leaf records of the 4-wide form (bvh.h: LeafPair) ----
+bool leaf_pair_form(const BvhTri& a, const BvhTri& b, uint32_t& form, const float*& p3) {
+  if (!memcmp(b.v0, a.v0, 12) && !memcmp(b.v1, a.v2, 12)) {  // B = (p0, p2, p3)
+    form = LEAF_PAIR_FAN;
+    p3 = b.v2;
+    return true;
+  }
+  if (!memcmp(b.v0, a.v1, 12) && !memcmp(b.v2, a.v2, 12)) {  // B = (p1, p3, p2)
+    form = LEAF_PAIR_STRIP;
+    p3 = b.v1;
+    return true;
+  }
+  return false;
+}
+
+void build_leaf_pairs(BuiltBvh& out) {
+  out.leaf_pairs.clear();
+  out.pair_single = out.pair_fan = out.pair_strip = out.pair_swapped = out.pair_unfit = 0;
+  if (out.wide_nodes.empty() || out.embedded || out.dev_nodes || out.tris.empty() || out.tris.size() * sizeof(LeafPair) > 0xFFFFFFFFull) return;
+  const auto is_tri_leaf = [](uint32_t r) { return (r & (BVH_LEAF_BIT | BVH_INST_BIT)) == BVH_LEAF_BIT; };
+  for (const WideNode& w : out.wide_nodes)
+    for (int k = 0; k < 4; k++)
+      if (is_tri_leaf(w.ref[k]) && ((w.ref[k] & 3u) > 1u || ((w.ref[k] & 0x3FFFFFFFu) >> 2) + (w.ref[k] & 3u) >= out.tris.size())) return;
+  out.leaf_pairs.resize(out.tris.size());
+  memset(out.leaf_pairs.data(), 0, out.leaf_pairs.size() * sizeof(LeafPair));
+  std::vector<uint8_t> state(out.tris.size(), 0);  // of the leaf that starts here: 0 = not seen yet, 1 = has one record, 2 = fits no pattern (split)
+  for (const WideNode& w : out.wide_nodes)
+    for (int k = 0; k < 4; k++) {
+      const uint32_t r = w.ref[k];
+      if (!is_tri_leaf(r)) continue;
+      const uint32_t first = (r & 0x3FFFFFFFu) >> 2;
+      if (state[first] == 0) {
+        LeafPair& p = out.leaf_pairs[first];
+        state[first] = 1;
+        const float* p3 = nullptr;
+        if ((r & 1u) == 0) {
+          p.form = LEAF_PAIR_SINGLE;
+          p.id_b = 0xFFFFFFFFu;
+          p3 = out.tris[first].v0;
+          out.pair_single++;
+        } else {
+          BvhTri &a = out.tris[first], &b = out.tris[first + 1];
+          if (!leaf_pair_form(a, b, p.form, p3)) {
+            if (leaf_pair_form(b, a, p.form, p3)) {
+              std::swap(a, b);
+              p3 = p.form == LEAF_PAIR_FAN ? b.v2 : b.v1;  // (the swap moved what it pointed at)
+              out.pair_swapped++;
+            } else {
+              // neither order fits: two one-triangle records, in this slot and in the next
+              state[first] = 2;
+              out.pair_unfit++;
+              LeafPair& q = out.leaf_pairs[first + 1];
+              memcpy(q.p0, b.v0, 12);
+              memcpy(q.p1, b.v1, 12);
+              memcpy(q.p2, b.v2, 12);
+              memcpy(q.p3, b.v0, 12);
+              q.id_a = b.id;
+              q.id_b = 0xFFFFFFFFu;
+              q.first = first + 1;
+              q.form = LEAF_PAIR_SINGLE;
+              p.form = LEAF_PAIR_SPLIT;
+              p.id_b = 0xFFFFFFFFu;
+              p3 = a.v0;
+            }
+          }
+          if (p.form != LEAF_PAIR_SPLIT) {
+            (p.form == LEAF_PAIR_FAN ? out.pair_fan : out.pair_strip)++;
+            p.id_b = b.id;
+          }
+        }
+        const BvhTri& a = out.tris[first];
+        memcpy(p.p0, a.v0, 12);
+        memcpy(p.p1, a.v1, 12);
+        memcpy(p.p2, a.v2, 12);
+        memcpy(p.p3, p3, 12);
+        p.id_a = a.id;
+        p.first = first;
+      }
+    }
+}
+
 // ---- the 8-wide compressed form (bvh.h: Wide8Node) ----
 namespace {
 struct Wide8Child {

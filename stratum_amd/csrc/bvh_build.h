@@ -72,6 +72,10 @@ struct BuiltBvh {
   std::vector<TlasEntry> wide_entries;
   uint32_t wide_root_ref = BVH_INVALID_REF;
   uint32_t wide_stack_depth = 0;
+  // The leaf records of the 4-wide form (build_leaf_pairs; bvh.h: LeafPair): one slot per leaf triangle, filled at the index
+  // of each leaf's first triangle. Empty: no records. The counts say how the leaves fared.
+  std::vector<LeafPair> leaf_pairs;
+  size_t pair_single = 0, pair_fan = 0, pair_strip = 0, pair_swapped = 0, pair_unfit = 0;
   // The 8-wide compressed form (build_wide8_bvh; bvh.h: Wide8Node): nodes, the entry table in the order the top level's
   // nodes refer to it (roots index wide8_nodes), the node the walk starts at, the number of 64-bit stack entries it needs.
   std::vector<Wide8Node> wide8_nodes;
@@ -137,6 +141,14 @@ bool build_scene_bvh(const sthip_scene_desc& scene, BuiltBvh& out, std::string& 
 // (bvh.h: WideNode): out.wide_*. Every leaf reference, and with it every triangle and entry, stays what it is, and every
 // decoded box contains the box it stands for: a traversal of the wide tree finds the hits the binary one finds.
 void build_wide_bvh(BuiltBvh& out);
+// The leaf records of a finished 4-wide form (bvh.h: LeafPair): out.leaf_pairs, one or (split) two per triangle leaf;
+// no change to out.wide_nodes. May SWAP the two triangles of a leaf in out.tris (never a triangle's vertices): call it
+// before the triangles are uploaded. Leaves nothing where records cannot stand in for the triangles: embedded leaves, a leaf
+// of more than two triangles (STHIP_LEAF_TRIS), an array of records beyond 32-bit byte offsets.
+void build_leaf_pairs(BuiltBvh& out);
+// Which pattern (bvh.h: LEAF_PAIR_FAN / LEAF_PAIR_STRIP) B takes beside A = (p0, p1, p2), and B's vertex that becomes p3;
+// false: none. Positions compare as bits.
+bool leaf_pair_form(const BvhTri& a, const BvhTri& b, uint32_t& form, const float*& p3);
 
 // Collapses the finished binary tree of a host build (out.dev_nodes == 0, no embedded leaves) into 8-wide compressed nodes
 // (bvh.h: Wide8Node): out.wide8_*. The items of a node's leaf children must be consecutive, so this PERMUTES out.tris

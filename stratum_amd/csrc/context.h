@@ -281,6 +281,11 @@ struct sthip_ctx {
   DevBuf<TlasEntry> entries;
   DevBuf<WideNode> wide_nodes;
   DevBuf<TlasEntry> wide_entries;
+  // "leaf_pairs": the leaf records of a host-built 4-wide tree (bvh.h: LeafPair), made at upload. 1 (default): k_trace tests
+  // leaves from them while they are resident; 0: from BvhTri, on the same tree. Anything that moves leaf triangles on the
+  // device drops them (api.hip: drop_leaf_pairs).
+  DevBuf<LeafPair> pairs;
+  bool leaf_pairs = true, leaf_pairs_resident = false;
   DevBuf<Wide8Node> wide8_nodes;
   DevBuf<TlasEntry> wide8_entries;
   std::vector<Wide8Node> wide8_host;  // the 8-wide nodes as uploaded: a transforms-only update makes the top level's again behind the bottom levels'

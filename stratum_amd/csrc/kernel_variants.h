@@ -21,7 +21,9 @@
 #define STHIP_TRACE_ROWS(Y, TOP, WIDE) \
   Y(false, false, false, TOP, WIDE) Y(true, false, false, TOP, WIDE) Y(false, true, false, TOP, WIDE) Y(true, true, false, TOP, WIDE) Y(false, false, true, TOP, WIDE) Y(true, false, true, TOP, WIDE) \
   Y(false, true, true, TOP, WIDE) Y(true, true, true, TOP, WIDE)
-#define STHIP_TRACE_ALL(Y) STHIP_TRACE_ROWS(Y, false, 0) STHIP_TRACE_ROWS(Y, true, 0) STHIP_TRACE_ROWS(Y, false, 1) STHIP_TRACE_ROWS(Y, false, 2)
+// (WIDE = 3, the 4-wide walk over leaf records, exists without ALPHA only: the mask lookup reads per-triangle uvs)
+#define STHIP_TRACE_PAIR_ROWS(Y) Y(false, false, false, false, 3) Y(true, false, false, false, 3) Y(false, false, true, false, 3) Y(true, false, true, false, 3)
+#define STHIP_TRACE_ALL(Y) STHIP_TRACE_ROWS(Y, false, 0) STHIP_TRACE_ROWS(Y, true, 0) STHIP_TRACE_ROWS(Y, false, 1) STHIP_TRACE_ROWS(Y, false, 2) STHIP_TRACE_PAIR_ROWS(Y)
 // Z(TEXTURED, EXT, MEDIA)
 #define STHIP_SHADE_LIGHT(Z) Z(false, true, false) Z(true, true, false) Z(false, true, true) Z(true, true, true)
 

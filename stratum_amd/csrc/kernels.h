@@ -377,6 +377,8 @@ DEV void finish_ray(const FrameParams& p, float4* target, uint32_t slot, bool sh
 // steps. Its stack has three levels from the last usable one on: every step writes top, top + 1 and top + 2.
 // WIDE = 2: the walk goes over the 8-wide compressed form (DeviceBvh::wide8_nodes, "wide_bvh" = 3; traverse.h: Traversal8):
 // the stack holds 64-bit groups, one push per step at most.
+// WIDE = 3: the 4-wide form, its leaves tested from their LeafPair records (bvh.h; DeviceBvh::pairs, "leaf_pairs"): one round
+// trip per leaf instead of one per triangle. Never with ALPHA (the mask lookup reads per-triangle uvs beside BvhTri).
 #ifndef STHIP_TRACE_ATTR
 #define STHIP_TRACE_ATTR  // (experiments: e.g. __attribute__((amdgpu_waves_per_eu(5))) — EXPERIMENTS.md, round 4)
 #endif
@@ -404,7 +406,7 @@ __global__ void __launch_bounds__(STHIP_BLOCK) STHIP_TRACE_ATTR k_trace(FramePar
   cnt[0].clear();
   cnt[1].clear();
   uint32_t round_slots[2] = {0, 0}, busy_rounds[2] = {0, 0};
-  if (WIDE == 1) {
+  if (WIDE == 1 || WIDE == 3) {
     bvh.entries = p.bvh.wide_entries;
     bvh.root_ref = p.bvh.wide_root_ref;
   }
@@ -413,7 +415,7 @@ __global__ void __launch_bounds__(STHIP_BLOCK) STHIP_TRACE_ATTR k_trace(FramePar
     bvh.root_ref = p.bvh.wide8_root;
   }
   typename std::conditional<WIDE == 2, Traversal8<COUNT, STHIP_BLOCK, ALPHA, BOUNDED, STHIP_ENTRY_BATCH>,
-                            Traversal<TRAV_MIXED, COUNT, STHIP_BLOCK, ALPHA, TOP, BOUNDED, true, STHIP_ENTRY_BATCH, WIDE == 1>>::type tr;  // SAVE_WORLD: 13 more registers, no occupancy step crossed (118 of 128; the ALPHA instantiations sit between 128 and 168 either way)
+                            Traversal<TRAV_MIXED, COUNT, STHIP_BLOCK, ALPHA, TOP, BOUNDED, true, STHIP_ENTRY_BATCH, WIDE == 1 || WIDE == 3, WIDE == 3>>::type tr;  // SAVE_WORLD: 13 more registers, no occupancy step crossed (118 of 128; the ALPHA instantiations sit between 128 and 168 either way)
   if constexpr (WIDE == 2) {
     tr.tri_min = p.bvh.wide8_tri_min;
     if (BOUNDED) tr.limit = (p.bvh.lds_levels - 1u) * STHIP_BLOCK;

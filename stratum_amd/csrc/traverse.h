@@ -19,6 +19,8 @@
 #include "bvh.h"
 #include "device_math.h"
 #include "media.h"
+#define TRI_FN DEV
+#include "tri_test.h"
 
 struct DeviceBvh {
   const float4* nodes;  // BvhNodePacked = 3 x float4 (48 bytes; the child references ride in the low bytes of the x / y planes)
@@ -62,6 +64,9 @@ struct DeviceBvh {
   uint32_t wide8_root;
   uint32_t wide8_stack_depth;
   uint32_t wide8_tri_min;  // the leaf phase of the 8-wide walk goes on while at least this many lanes of the wave hold a triangle ("tri_min_lanes")
+  // The leaf records of the 4-wide form (bvh.h: LeafPair; "leaf_pairs"), read by k_trace<., false, ., false, 3> only: nullptr
+  // when the tree has none or the option is off.
+  const uint4* pairs;
 };
 // level-0 lookup of a one-channel image: bilinear, repeat addressing (the same arithmetic as DisneyMaterial::bilinear)
 DEV float sample_image1(const DeviceBvh& bvh, uint32_t index, float u, float v) {
@@ -200,32 +205,24 @@ DEV bool sphere_test(f3 o, f3 d, float r, float tmin, float tmax, float& t) {
 // closest-hit ordering key: instance first, then primitive
 DEV uint32_t hit_key(uint32_t ip) { return (ip << 16) | (ip >> 16); }
 
-// Watertight ray/triangle test, arithmetic exactly as the contract states. Edge functions are
-// products rounded separately (no fma) so that a shared edge evaluates antisymmetrically.
-DEV bool tri_test(const RaySpace& s, f3 p0, f3 p1, f3 p2, float tmin, float tmax, float& t, float& b1, float& b2) {
-  const f3 A = p0 - s.o, B = p1 - s.o, C = p2 - s.o;
-  const int kx = s.k & 3, ky = (s.k >> 2) & 3, kz = s.k >> 4;
-  const float Akz = comp3(A, kz), Bkz = comp3(B, kz), Ckz = comp3(C, kz);
-  const float Ax = fmaf(-s.Sx, Akz, comp3(A, kx)), Ay = fmaf(-s.Sy, Akz, comp3(A, ky));
-  const float Bx = fmaf(-s.Sx, Bkz, comp3(B, kx)), By = fmaf(-s.Sy, Bkz, comp3(B, ky));
-  const float Cx = fmaf(-s.Sx, Ckz, comp3(C, kx)), Cy = fmaf(-s.Sy, Ckz, comp3(C, ky));
-  const float U = Cx * By - Cy * Bx;
-  const float V = Ax * Cy - Ay * Cx;
-  const float W = Bx * Ay - By * Ax;
-  // No early exits: in a wave every lane waits for the slowest one anyway, and each `return` would cost an exec-mask
-  // region (the tests are the same, in the same arithmetic; a zero determinant makes rcp infinite and tt fail its range
-  // test, or NaN, which fails it too — det != 0 is tested all the same).
-  const bool edges_disagree = ((U < 0.0f) | (V < 0.0f) | (W < 0.0f)) & ((U > 0.0f) | (V > 0.0f) | (W > 0.0f));
-  const float det = U + V + W;
-  const float Az = s.Sz * Akz, Bz = s.Sz * Bkz, Cz = s.Sz * Ckz;
-  const float T = fmaf(W, Cz, fmaf(V, Bz, U * Az));
-  const float rcp = 1.0f / det;
-  const float tt = T * rcp;
-  t = tt;
-  b1 = V * rcp;
-  b2 = W * rcp;
-  return !edges_disagree & (det != 0.0f) & (tt > tmin) & (tt < tmax);
+// Watertight ray/triangle test: tri_test.h states it (plain C++ that a host check compiles too), whole and in its per-vertex
+// and per-triangle parts; these put the ray space and the vectors of this file into its terms.
+DEV TriRay tri_ray(const RaySpace& s) {
+  const TriRay r = {s.o.x, s.o.y, s.o.z, s.Sx, s.Sy, s.Sz, s.k};
+  return r;
 }
+DEV TriV tri_v(f3 p) {
+  const TriV r = {p.x, p.y, p.z};
+  return r;
+}
+DEV bool tri_test(const RaySpace& s, f3 p0, f3 p1, f3 p2, float tmin, float tmax, float& t, float& b1, float& b2) {
+  return tri_whole(tri_ray(s), tri_v(p0), tri_v(p1), tri_v(p2), tmin, tmax, t, b1, b2);
+}
+DEV f3 shear_vertex(const RaySpace& s, f3 p) {
+  const TriV r = tri_shear(tri_ray(s), tri_v(p));
+  return F3(r.x, r.y, r.z);
+}
+DEV bool tri_test_sheared(f3 a, f3 b, f3 c, float tmin, float tmax, float& t, float& b1, float& b2) { return tri_edges(tri_v(a), tri_v(b), tri_v(c), tmin, tmax, t, b1, b2); }
 
 // stack sentinels (both carry the leaf bits, so the inner-node loop hands them to the leaf handler)
 #define TRAV_DONE 0xFFFFFFFFu           // bottom of the stack: the ray is finished
@@ -251,8 +248,10 @@ DEV bool tri_test(const RaySpace& s, f3 p0, f3 p1, f3 p2, float tmin, float tmax
 #ifndef STHIP_ENTRY_BATCH
 #define STHIP_ENTRY_BATCH 12u
 #endif
-template <int MODE, bool COUNT, uint32_t STRIDE, bool ALPHA = false, bool TOP = false, bool BOUNDED = false, bool SAVE_WORLD = false, uint32_t ENTRY_BATCH = 1, bool WIDE = false>  // ALPHA: gAlphaTest is compiled in (scenes with alpha masks)
+// PAIRS (with WIDE, never with ALPHA): every triangle leaf is tested from its LeafPair record (pair_step); the tree must have them
+template <int MODE, bool COUNT, uint32_t STRIDE, bool ALPHA = false, bool TOP = false, bool BOUNDED = false, bool SAVE_WORLD = false, uint32_t ENTRY_BATCH = 1, bool WIDE = false, bool PAIRS = false>  // ALPHA: gAlphaTest is compiled in (scenes with alpha masks)
 struct Traversal {
+  static_assert(!PAIRS || (WIDE && !ALPHA), "leaf records: the 4-wide walk without alpha masks");
   const LdsFloat4* top_lds;  // TOP only
   uint32_t limit;            // BOUNDED only: (levels - 1) * STRIDE
   DEV bool overflowed(const uint32_t* stack) const { return BOUNDED && stack[limit] != TRAV_CANARY; }
@@ -635,8 +634,70 @@ struct Traversal {
     return candidate & any_lane;
   }
 
+  // A candidate folded into the hit record (as one_triangle, without the alpha test); returns whether an occlusion lane found its hit
+  DEV bool fold_candidate(bool candidate, float t, float b1, float b2, uint32_t ip, uint32_t index) {
+    const bool any_lane = is_any();
+    const bool closer = candidate & !any_lane & ((t < hit.t) | ((t == hit.t) & (hit.ip != 0xFFFFFFFFu) & (hit_key(ip) < hit_key(hit.ip))));
+    hit.t = closer ? t : hit.t;
+    hit.b1 = closer ? b1 : hit.b1;
+    hit.b2 = closer ? b2 : hit.b2;
+    hit.ip = closer ? ip : hit.ip;
+    hit.leaf = closer ? index : hit.leaf;
+    return candidate & any_lane;
+  }
+
+  // ref is a triangle leaf with a record (bvh.h: LeafPair): the whole leaf in ONE round trip — four 16-byte loads, as many
+  // registers in flight as the node step holds (which is never live beside this) — then A and B with the arithmetic and in
+  // the order (first, first + 1) of the loop in triangles_step, then the pop. B's vertices are picked from the four by the
+  // form: one layer of selects, no indexed registers. A one-triangle leaf's B is masked out.
+  DEV void pair_step(const DeviceBvh& bvh, uint32_t* stack, TraverseCounters& cnt) {
+    const uint32_t first = (ref & 0x3FFFFFFFu) >> 2;
+    // 32-bit byte offset, first * 64 (the builder keeps the array below 4 GiB)
+    const uint4* rec = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(bvh.pairs) + ((ref & 0x3FFFFFFCu) << 4));
+    const uint4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
+    uint4 q3 = rec[3];
+    const uint32_t popped = stack[top - STRIDE];
+    asm volatile("" : "+v"(q3.x), "+v"(q3.y), "+v"(q3.z), "+v"(q3.w));  // all four loads in flight before anything is computed
+    const bool two = (q3.w == LEAF_PAIR_FAN) | (q3.w == LEAF_PAIR_STRIP), strip = q3.w == LEAF_PAIR_STRIP;
+    // What the lane holds next, decided before the tests (no mask to keep across them): the popped reference — or, for a split
+    // leaf (two triangles that fit no pattern: two one-triangle records), its second record, the next slot, tested in the
+    // next leaf phase. (`top` of a lane whose ray ends here as occluded is not read again.)
+    const bool split = q3.w == LEAF_PAIR_SPLIT;
+    const uint32_t next = split ? (ref | 3u) + 1u : popped;  // (first + 1, count 1)
+    top = split ? top : top - STRIDE;
+    if (COUNT) {
+      cnt.tris += two ? 2u : 1u;
+      if (first_active_lane()) cnt.tri_slots += 64;
+    }
+    // each of the four vertices goes through tri_test's per-vertex part once (it depends on the vertex and the ray alone, so a
+    // shared vertex gives both triangles the bits tri_test would): twelve values replace the twelve loaded ones
+    const f3 s0 = shear_vertex(sp, F3(__uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z)));
+    const f3 s1 = shear_vertex(sp, F3(__uint_as_float(q1.x), __uint_as_float(q1.y), __uint_as_float(q1.z)));
+    const f3 s2 = shear_vertex(sp, F3(__uint_as_float(q2.x), __uint_as_float(q2.y), __uint_as_float(q2.z)));
+    const f3 s3 = shear_vertex(sp, F3(__uint_as_float(q3.x), __uint_as_float(q3.y), __uint_as_float(q3.z)));
+    const uint32_t ip_a = q0.w | id_bits, ip_b = q1.w | id_bits;
+    float t, b1, b2;
+    const bool hit_a = tri_test_sheared(s0, s1, s2, tmin, tmax, t, b1, b2);
+    const f3 u0 = F3(strip ? s1.x : s0.x, strip ? s1.y : s0.y, strip ? s1.z : s0.z);
+    const f3 u1 = F3(strip ? s3.x : s2.x, strip ? s3.y : s2.y, strip ? s3.z : s2.z);
+    const f3 u2 = F3(strip ? s2.x : s3.x, strip ? s2.y : s3.y, strip ? s2.z : s3.z);
+    // A is folded before B is tested, and B's vertices are picked before A is folded: in this order the bounded instantiation
+    // needs 128 registers, in every other one tried 129 to 132 (four waves per SIMD end at 128: tools/kernel_resources.py)
+    __builtin_amdgcn_sched_barrier(0);
+    bool occluded = fold_candidate(hit_a, t, b1, b2, ip_a, first);
+    __builtin_amdgcn_sched_barrier(0);
+    const bool hit_b = tri_test_sheared(u0, u1, u2, tmin, tmax, t, b1, b2) & two;
+    occluded |= fold_candidate(hit_b, t, b1, b2, ip_b, first + 1u);
+    hit.ip = occluded ? 0u : hit.ip;
+    ref = occluded ? TRAV_DONE : next;
+  }
+
   // ref is a triangle leaf: all its triangles, then the pop
   DEV void triangles_step(const DeviceBvh& bvh, uint32_t* stack, TraverseCounters& cnt) {
+    if (PAIRS) {  // (every triangle leaf of a tree with records has one: bvh.h)
+      pair_step(bvh, stack, cnt);
+      return;
+    }
     const uint32_t first = (ref & 0x3FFFFFFFu) >> 2;
     const uint32_t count = (ref & 3u) + 1u;
     // an occlusion lane's verdict is collected in `occluded` and applied behind the loop

@@ -246,6 +246,8 @@ class Stats(C.Structure):
         ("max_paths_in_flight", C.c_uint64),
         ("batch_halvings", C.c_uint32),
         ("full_rebuilds", C.c_uint32),
+        ("leaf_records", C.c_uint32),
+        ("reserved0", C.c_uint32),
     ]
 
 

@@ -185,6 +185,7 @@ def run(cases=60, seed=1):
             if os.environ.get("STHIP_FUZZ_WIDE") is not None: opts["wide_bvh"] = int(os.environ["STHIP_FUZZ_WIDE"])  # the 4-wide walk forced on / off (without drawing: the cases of a seed stay the same)
             elif (seed0 >> 2) & 1: opts["wide_bvh"] = 3  # the 8-wide compressed walk (host-built trees; the others fall back to the 4-wide one)
             if (seed0 >> 3) & 1: opts["tri_min_lanes"] = 1 + (seed0 >> 5) % 24
+            if (seed0 >> 6) & 1: opts["leaf_pairs"] = 0  # leaves from the per-triangle array instead of their records (without drawing: the cases of a seed stay the same)
             for kv in filter(None, os.environ.get("STHIP_FUZZ_SET", "").split(",")):  # "name=value,name=": options forced / dropped (narrowing a case down)
                 k, _, v = kv.partition("=")
                 if v == "": opts.pop(k, None)
