@@ -423,6 +423,74 @@ int sthip_scene_set_rigs(sthip_ctx* ctx, const sthip_rig_desc* rigs, uint32_t ri
 int sthip_scene_animate(sthip_ctx* ctx, const sthip_rig_pose* poses, uint32_t pose_count, sthip_refit_info* info);
 int sthip_scene_read_vertices(sthip_ctx* ctx, uint32_t first_vertex, uint32_t vertex_count, sthip_PackedVertexData* out);
 
+/* ---- vertices from streams: a deformed mesh whose positions are already on the device (kernels/copy_vertices.hlsl) ----
+ * sthip_scene_update_vertices takes finished records from host memory. A simulation that leaves positions on the device would
+ * have to copy them back, make normals on the host, interleave records and send 32 B per vertex up again. This call takes the
+ * strided position / normal / texcoord streams as they are — device memory (device_ptr = 1: read in the order of the context's
+ * stream) or host memory (device_ptr = 0: the spans of the streams are copied into a staging buffer on the stream, then the same
+ * kernels run) — packs them into the resident gVertices and, on request, makes the shading normals of the range again from
+ * the moved positions. Everything after the write of gVertices is the chain of sthip_scene_update_vertices, unchanged: the
+ * frames in flight are completed first, then gather, shading records, refit, top level, emitter bounds, the wide form; kept
+ * reservoir grids are dropped. sthip_refit_info as for the vertex call; device_ms includes the new kernels.
+ *
+ * PACK CONTRACT (k_pack_vertices, vertex_streams.hip; PackedVertexData::set, copy_vertices.hlsl:29-37, scene.h:81-94):
+ *   record first_vertex + i becomes {positions[i], u, normals[i], v} with (u, v) = texcoords[i], all as bit copies. The fields
+ *   of an absent (NULL) stream keep their resident bits. Records outside the range are not written. Only 4-byte alignment is
+ *   assumed of the streams; element i of a stream lies `stride` bytes behind element i - 1.
+ *
+ * NORMAL CONTRACT (recompute_normals = 1; k_face_vectors, k_vertex_normals). Arithmetic is binary32 and unfused, in the order
+ * written (sthip_detmath.h):
+ *   meshes:  the distinct tuples (indices_byte_offset, first_vertex, index_stride, prim_count) of the scene's triangle
+ *            instances, in ascending order of that tuple; instances that share a tuple count once; spheres and volumes have none.
+ *   face vectors:  for triangle t of mesh m the three indices are read as the refit reads them (zero-extended 16- or 32-bit,
+ *            plus first_vertex); p0, p1, p2 are the resident positions after this call's write; e1 = p1 - p0, e2 = p2 - p0,
+ *            g = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x), every product rounded before the
+ *            subtraction (an area-weighted face normal, not normalised).
+ *   sum and normalise:  for a vertex v of the range, s = +0; for every corner (m, t, c) whose absolute index is v, in
+ *            ascending (m, t, c): s = s + g(m, t); d = (s.x*s.x + s.y*s.y) + s.z*s.z; if d > 0 and d < inf the normal becomes
+ *            s * (1.0f / sqrtf(d)) (normalize3, as k_animate uses it), otherwise the resident normal stays.
+ *   the resident normal therefore stays for a vertex no triangle names, a vertex whose face vectors sum to zero (all of its
+ *            faces degenerate, or faces that cancel) and a NaN (or an overflow) in the sum.
+ *   neighbours outside the range contribute their resident positions and are not rewritten themselves: a caller that moves
+ *            a whole mesh passes the whole mesh.
+ * The sum is made store-then-sum: every face vector goes to a slot of a scratch array, then one lane per vertex adds its
+ * row of an adjacency in the contract's order. No float atomics decide anything, so the same positions give the same bytes.
+ * The adjacency is made once per uploaded topology, at the first call that asks for normals, and dropped at every upload.
+ *
+ * Refused with STHIP_ERR_INVALID_ARGUMENT, a message that names the field, and nothing changed: no scene resident, a
+ * struct_size below sizeof(sthip_vertex_streams), a NULL `positions`, a range past the uploaded vertex_count, a pointer or
+ * stride of a present stream that is not a multiple of 4, a stride below the element size (12 / 12 / 8), `normals` together
+ * with recompute_normals. vertex_count = 0 is a valid no-op (STHIP_OK). Failure rules are the vertex call's: everything that
+ * can be refused or can run out of memory happens before gVertices is touched; afterwards a failure ends in a rebuild from
+ * the kept scene, or with "keep_scene" = 0 in no resident scene. For the layouts the refit does not serve ("embed_leaves",
+ * "treetop", "wide_bvh" = 3) the call runs the kernels, reads the range back into the kept scene and builds the scene again
+ * (rebuilt = 1); with "keep_scene" = 0 it returns STHIP_ERR_UNSUPPORTED and changes nothing. The copy "keep_scene" keeps is
+ * not written per call: the range is marked stale and fetched immediately before anything is built from the kept scene; a
+ * later sthip_scene_update_vertices over part of the range makes that part current. Over a rigged range the call behaves as
+ * sthip_scene_update_vertices does: the resident records change until the next sthip_scene_animate, the rest pose does not.
+ * Measured on the 1M-triangle atrium (profiles/r15/vertices.json, medians of 9 calls, device-built tree, the forms alternating
+ * in one process), all 408 970 vertices: 0.85 ms for the call from device streams with positions, normals and uvs and 0.88 ms
+ * with positions only and recompute_normals, against 1.59 ms for sthip_scene_update_vertices with the same vertices sent up
+ * (0.72 / 0.75 / 0.73 ms of them on the stream); the first call on a topology also makes the adjacency, 7.5 ms; one instance's
+ * mesh (5 440 vertices): 0.83 / 0.85 against 0.84 ms. The kernels alone: k_pack_vertices 0.018 ms, k_face_vectors 0.014 ms,
+ * k_vertex_normals 0.014 ms.
+ * Measurement only: with the environment variable STHIP_VERTEX_TIMES=<file> (read once per process) every call appends one
+ * JSON line to the file with the HIP-event time of each of its kernels (k_pack_vertices_ms, k_face_vectors_ms,
+ * k_vertex_normals_ms; 0 for one that did not run) and waits for the stream behind them. Without the variable the call makes
+ * no extra event and touches no file.
+ * The ABI is additive (STHIP_ABI_VERSION stays 11): a library without the feature lacks the symbol. */
+typedef struct sthip_vertex_streams {
+  uint32_t struct_size;
+  uint32_t first_vertex, vertex_count; /* records of gVertices that are written */
+  uint32_t device_ptr;                 /* 1: the three streams are device memory, readable in the order of the context's stream */
+  uint32_t recompute_normals;          /* 1: normals of the range are made on the device (contract above); `normals` must be NULL */
+  uint32_t position_stride, normal_stride, texcoord_stride; /* bytes between elements */
+  const void* positions;               /* float3 per vertex, required */
+  const void* normals;                 /* float3 per vertex, or NULL: normals stay (or are recomputed) */
+  const void* texcoords;               /* float2 per vertex (u, v), or NULL: u and v of the resident records stay */
+} sthip_vertex_streams;
+int sthip_scene_set_vertices(sthip_ctx* ctx, const sthip_vertex_streams* streams, sthip_refit_info* info);
+
 /* ---- material conversion: where the images of a material come from (Scene.cpp:123-256 -> kernels/material_convert.hlsl) ----
  * The library renders from three R8G8B8A8Unorm images per material (DisneyMaterialData, disney_data.h) and one R8Unorm alpha
  * mask. Upstream makes them on the device from what an asset holds: Scene::make_metallic_roughness_material (glTF: base colour

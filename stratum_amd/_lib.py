@@ -32,6 +32,7 @@ EXPORTS = [
     "sthip_scene_set_rigs",
     "sthip_scene_animate",
     "sthip_scene_read_vertices",
+    "sthip_scene_set_vertices",
     "sthip_convert_material",
     "sthip_build_volume",
     "sthip_scene_set_volume",
@@ -129,6 +130,9 @@ def lib():
     L.sthip_scene_animate.argtypes = [C.c_void_p, C.POINTER(wire.RigPose), C.c_uint32, C.POINTER(wire.RefitInfo)]
     L.sthip_scene_read_vertices.restype = C.c_int
     L.sthip_scene_read_vertices.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    if hasattr(L, "sthip_scene_set_vertices"):  # (an older build named by STHIP_LIB lacks it: calling it raises)
+        L.sthip_scene_set_vertices.restype = C.c_int
+        L.sthip_scene_set_vertices.argtypes = [C.c_void_p, C.POINTER(wire.VertexStreams), C.POINTER(wire.RefitInfo)]
     if hasattr(L, "sthip_convert_material"):  # (an older build named by STHIP_LIB lacks it: calling it raises)
         L.sthip_convert_material.restype = C.c_int
         L.sthip_convert_material.argtypes = [C.c_void_p, C.POINTER(wire.ConvertMaterialDesc)]

@@ -298,6 +298,54 @@ class BDPT:
         self._check(self._lib.sthip_scene_animate(self._h, c_poses, n, C.byref(info)), "sthip_scene_animate")
         return {f: getattr(info, f) for f, _ in wire.RefitInfo._fields_ if f != "pad"}
 
+    def set_vertices(self, first_vertex, positions, normals=None, texcoords=None, recompute_normals=False):
+        """New vertices for the resident scene from strided streams (sthip_scene_set_vertices): records first_vertex ..
+        first_vertex + N - 1 become {positions[i], u, normals[i], v}, bit copies; an absent stream leaves its fields as they
+        are resident. With recompute_normals=True (and normals=None) the shading normals of the range are made again on the
+        device from the moved positions: the normalised sum of the area-weighted face vectors around each vertex, in the order
+        include/sthip.h fixes. Each stream is a float32 numpy array of shape (N, 3) / (N, 2) with any row stride and inner
+        stride 1, or anything with data_ptr(), shape and stride() (a float32 torch tensor or view on this device); all given
+        streams must be of one kind. Strides come from the object. The gather, the refit and the top level follow as for
+        update_vertices. The scene object handed to update() does NOT follow: its `vertices` are behind the device from here
+        on, and read_vertices() says what is resident. Returns sthip_refit_info as a dict."""
+        d = wire.VertexStreams()
+        d.struct_size = C.sizeof(wire.VertexStreams)
+        d.first_vertex = int(first_vertex)
+        d.recompute_normals = 1 if recompute_normals else 0
+        device = hasattr(positions, "data_ptr")
+        keep = []
+
+        def stream(a, name, width):
+            if a is None:
+                return None, 0
+            if hasattr(a, "data_ptr") != device:
+                raise ValueError("set_vertices: host and device streams cannot be mixed")
+            if device:
+                if "float32" not in str(a.dtype) or len(a.shape) != 2 or a.shape[1] != width or (a.shape[0] and a.stride(1) != 1):
+                    raise ValueError("set_vertices: %s must be a float32 tensor of shape (N, %d) with inner stride 1" % (name, width))
+                count, pointer, step = int(a.shape[0]), int(a.data_ptr()), int(a.stride(0)) * 4
+            else:
+                a = np.asarray(a)
+                if a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != width or (a.shape[0] and a.strides[1] != 4):
+                    raise ValueError("set_vertices: %s must be a float32 array of shape (N, %d) with inner stride 1" % (name, width))
+                keep.append(a)
+                count, pointer, step = int(a.shape[0]), int(a.ctypes.data), int(a.strides[0])
+            if name == "positions":
+                d.vertex_count = count
+            elif count != d.vertex_count:
+                raise ValueError("set_vertices: %s has %d elements, positions %d" % (name, count, d.vertex_count))
+            if step < 0:
+                raise ValueError("set_vertices: %s has a negative row stride" % name)
+            return pointer, step
+
+        d.positions, d.position_stride = stream(positions, "positions", 3)
+        d.normals, d.normal_stride = stream(normals, "normals", 3)
+        d.texcoords, d.texcoord_stride = stream(texcoords, "texcoords", 2)
+        d.device_ptr = 1 if device else 0
+        info = wire.RefitInfo()
+        self._check(self._lib.sthip_scene_set_vertices(self._h, C.byref(d), C.byref(info)), "sthip_scene_set_vertices")
+        return {f: getattr(info, f) for f, _ in wire.RefitInfo._fields_ if f != "pad"}
+
     def read_vertices(self, first, count):
         """The resident vertex records [first, first + count) as a wire.PackedVertexData array (sthip_scene_read_vertices)."""
         out = np.zeros(int(count), dtype=wire.PackedVertexData)

@@ -255,6 +255,10 @@ static const char* environment_times_file() {  // STHIP_ENVIRONMENT_TIMES=<file>
   static const char* const path = times_file("STHIP_ENVIRONMENT_TIMES");
   return path;
 }
+static const char* vertex_times_file() {  // STHIP_VERTEX_TIMES=<file>: one line per sthip_scene_set_vertices call with the HIP-event time of each of its kernels
+  static const char* const path = times_file("STHIP_VERTEX_TIMES");
+  return path;
+}
 struct StageTimer {
   enum { MAX_EVENTS = 8 };
   hipEvent_t ev[MAX_EVENTS] = {};  // ev[k]: recorded when stage k is enqueued (a stage the call skips is recorded where it would stand: 0 ms)
@@ -360,6 +364,8 @@ void sthip_destroy(sthip_ctx* ctx) {
   ctx->volume_build = nullptr;
   sthip::device_refit_destroy(ctx->refit);
   ctx->refit = nullptr;
+  sthip::device_vertex_adjacency_destroy(ctx->adjacency);
+  ctx->adjacency = nullptr;
   for (int k = 0; k < 2; k++)
     if (ctx->edit_ev[k]) (void)hipEventDestroy(ctx->edit_ev[k]);
   ctx->vertices.release();
@@ -780,6 +786,7 @@ static int retire_scene(sthip_ctx* ctx, const sthip_scene_desc* s) {
   ctx->has_scene = false;
   ctx->scene_serial++;  // (first_hits.h: from here on the resident triangles are not the ones kept hits were traced against)
   sthip::device_refit_invalidate(ctx->refit);  // (the schedule of a refit belongs to the tree that goes away now)
+  sthip::device_vertex_adjacency_invalidate(ctx->adjacency);  // (... and the corners of sthip_scene_set_vertices to its index buffer)
   ctx->refit_roots_valid = false;
   // the rigs name vertex ranges of the scene that goes away; a rebuild from the kept copy is the same scene and keeps them
   if (!(ctx->kept.valid && s->gVertices && s->gVertices == ctx->kept.vertices.data())) {
@@ -1829,13 +1836,49 @@ int sthip_scene_read_top_level(sthip_ctx* ctx, float* entry_boxes, sthip_top_nod
 }
 
 // Where the new vertex records of a refit come from: a range of host records that goes up (sthip_scene_update_vertices), or
-// the resident rigs in the pose an animate call staged, written on the device (sthip_scene_animate: `vertices` is NULL)
+// the resident rigs in the pose an animate call staged, written on the device (sthip_scene_animate: `vertices` is NULL), or
+// streams on the device that are packed into the range there (sthip_scene_set_vertices: `streams`)
 struct VertexSource {
   const char* call;  // the entry point, for messages
   const sthip_PackedVertexData* vertices;
   uint32_t first_vertex, vertex_count;
-  bool posed() const { return vertices == nullptr; }
+  const sthip::VertexStreams* streams = nullptr;
+  bool recompute_normals = false;
+  bool streamed() const { return streams != nullptr; }
+  bool posed() const { return vertices == nullptr && !streams; }
+  bool on_device() const { return vertices == nullptr; }  // the device writes the records: the kept scene falls behind
 };
+
+// The kernels of sthip_scene_set_vertices: the pack, then the normals of the range. From the first launch on the kept
+// vertices of the range are behind the device's.
+static int write_vertex_streams(sthip_ctx* ctx, const VertexSource& src) {
+  if (ctx->kept.valid && src.vertex_count) {
+    ctx->kept.vertices_written(src.first_vertex, src.vertex_count);  // (one entry per range, however often it is written)
+    ctx->kept.stale_vertices.emplace_back(src.first_vertex, src.first_vertex + src.vertex_count);
+  }
+  std::string err;
+  StageTimer times(vertex_times_file(), true, 4);  // (measurement only: sthip.h)
+  HIP_TRY(ctx, hipEventRecord(ctx->edit_ev[0], ctx->stream));
+  times.mark(0, ctx->stream);
+  if (!sthip::pack_vertices_launch(ctx->vertices.p, *src.streams, ctx->stream, err)) return fail(ctx, STHIP_ERR_HIP, std::string(src.call) + ": " + err);
+  times.mark(1, ctx->stream);
+  if (src.recompute_normals &&
+      !sthip::vertex_normals_launch(ctx->adjacency, ctx->vertices.p, ctx->vertex_count, ctx->indices.p, ctx->indices_bytes, src.first_vertex, src.vertex_count, ctx->stream,
+                                    times.on ? times.ev[2] : nullptr, err))
+    return fail(ctx, STHIP_ERR_HIP, std::string(src.call) + ": " + err);
+  if (!src.recompute_normals) times.mark(2, ctx->stream);
+  times.mark(3, ctx->stream);
+  HIP_TRY(ctx, hipEventRecord(ctx->edit_ev[1], ctx->stream));
+  if (times.on) {
+    static const char* const names[3] = {"k_pack_vertices_ms", "k_face_vectors_ms", "k_vertex_normals_ms"};
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    times.write("\"call\": \"" + std::string(src.call) + "\", \"vertices\": " + std::to_string(src.vertex_count) + ", \"recompute_normals\": " + (src.recompute_normals ? "1" : "0"), names);
+  }
+  return STHIP_OK;
+}
+
+// The layouts a vertex update does not refit: they are built again from the kept scene
+static bool layout_not_refitted(const sthip_ctx* ctx) { return ctx->embedded_resident || ctx->use_treetop || ctx->bvh.top_count || ctx->bvh.wide8_nodes || !ctx->wide8_host.empty(); }
 
 // The part of a vertex update that changes the resident scene: the vertex range goes up or the rigs are posed, the leaf
 // triangles are gathered again, the bottom levels refitted and everything an upload derives from the meshes' bounds made again.
@@ -1847,6 +1890,9 @@ static int refit_resident_scene(sthip_ctx* ctx, const VertexSource& src, bool ke
   const std::vector<uint32_t>& root_of_entry = ctx->refit_root_of_entry;
   if (src.posed()) {
     const int rc = pose_rigs(ctx, src.call);
+    if (rc != STHIP_OK) return rc;
+  } else if (src.streamed()) {
+    const int rc = write_vertex_streams(ctx, src);
     if (rc != STHIP_OK) return rc;
   } else if (src.vertex_count) {
     const sthip_PackedVertexData* vertices = src.vertices;
@@ -1933,13 +1979,13 @@ static int update_resident_vertices(sthip_ctx* ctx, const VertexSource& src, sth
     }
     return rc;
   };
-  if (src.posed())
+  if (src.on_device())
     if (const int rc = make_edit_events(ctx); rc != STHIP_OK) return rc;
-  if (ctx->embedded_resident || ctx->use_treetop || ctx->bvh.top_count || ctx->bvh.wide8_nodes || !ctx->wide8_host.empty()) {
+  if (layout_not_refitted(ctx)) {
     if (!kept) return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "this layout (embed_leaves, treetop, wide_bvh = 3) is not refitted and no scene was kept (keep_scene = 0): upload the scene again");
-    if (src.posed()) {  // the kernel, then the rebuild reads its ranges back
+    if (src.on_device()) {  // the kernels, then the rebuild reads their ranges back
       if (const int rc = quiesce(ctx); rc != STHIP_OK) return rc;
-      const int rc = pose_rigs(ctx, src.call);
+      const int rc = src.posed() ? pose_rigs(ctx, src.call) : write_vertex_streams(ctx, src);
       if (rc != STHIP_OK) return rc;
     } else if (src.vertex_count) {
       const int rc = sync_kept_vertices(ctx);  // (before the host's records go in: they are the newer ones)
@@ -2000,12 +2046,13 @@ static int update_resident_vertices(sthip_ctx* ctx, const VertexSource& src, sth
     const std::string why = ctx->error;
     ctx->has_scene = false;
     sthip::device_refit_invalidate(ctx->refit);
+    sthip::device_vertex_adjacency_invalidate(ctx->adjacency);
     ctx->refit_roots_valid = false;
     return fail(ctx, rc, why + " (the resident scene was dropped half changed: upload the scene again)");
   }
   if (info) {
     float pose_ms = 0;  // (refit_boxes has waited for the stream: the events around k_animate have been reached)
-    if (src.posed()) (void)hipEventElapsedTime(&pose_ms, ctx->edit_ev[0], ctx->edit_ev[1]);
+    if (src.on_device()) (void)hipEventElapsedTime(&pose_ms, ctx->edit_ev[0], ctx->edit_ev[1]);
     info->device_ms = pose_ms + res.gpu_ms + wide_ms;
     info->sah_cost = (float)res.sah_cost;
     info->sah_cost_at_build = (float)res.sah_cost_at_build;
@@ -2024,6 +2071,72 @@ int sthip_scene_update_vertices(sthip_ctx* ctx, const sthip_PackedVertexData* ve
   if ((uint64_t)first_vertex + vertex_count > ctx->vertex_count)
     return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, "sthip_scene_update_vertices: the range ends past the vertex_count of the uploaded scene");
   return update_resident_vertices(ctx, VertexSource{"sthip_scene_update_vertices", vertices, first_vertex, vertex_count}, info, t0);
+}
+
+// sthip.h: refused on the host (scene_prepare.cpp), then everything that needs memory is made — the staging of host streams,
+// the adjacency of the resident topology at the first call that asks for normals — and from there on the call is a vertex
+// update whose records are written by k_pack_vertices (and k_vertex_normals) instead of coming up from the host.
+int sthip_scene_set_vertices(sthip_ctx* ctx, const sthip_vertex_streams* d, sthip_refit_info* info) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (info) memset(info, 0, sizeof(*info));
+  const std::string call = "sthip_scene_set_vertices: ";
+  {
+    int code = STHIP_OK;
+    std::string message;
+    if (!sthip::check_vertex_streams(ctx->has_scene, ctx->vertex_count, d, code, message)) return fail(ctx, code, message);
+  }
+  if (!d->vertex_count) return STHIP_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (layout_not_refitted(ctx) && !(ctx->kept.valid && ctx->kept.vertices.size() == ctx->vertex_count))  // (before anything is made for the call)
+    return fail(ctx, STHIP_ERR_UNSUPPORTED, call + "this layout (embed_leaves, treetop, wide_bvh = 3) is not refitted and no scene was kept (keep_scene = 0): upload the scene again");
+  sthip::VertexStreams s;
+  s.positions = d->positions;
+  s.normals = d->normals;
+  s.texcoords = d->texcoords;
+  s.position_stride = d->position_stride;
+  s.normal_stride = d->normal_stride;
+  s.texcoord_stride = d->texcoord_stride;
+  s.first_vertex = d->first_vertex;
+  s.vertex_count = d->vertex_count;
+  if (!d->device_ptr) {  // the spans of the host streams go up as they are (strides and all): one code path on the device
+    const void** stream_of[3] = {&s.positions, &s.normals, &s.texcoords};
+    const uint32_t strides[3] = {s.position_stride, s.normal_stride, s.texcoord_stride}, elements[3] = {12, 12, 8};
+    size_t at[3] = {0, 0, 0}, span[3] = {0, 0, 0}, total = 0;
+    for (int k = 0; k < 3; k++) {
+      if (!*stream_of[k]) continue;
+      span[k] = (size_t)(d->vertex_count - 1) * strides[k] + elements[k];
+      at[k] = total;
+      total += (span[k] + 15) & ~(size_t)15;
+    }
+    HIP_TRY(ctx, ctx->stream_staging.ensure(total));
+    for (int k = 0; k < 3; k++) {
+      if (!*stream_of[k]) continue;
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->stream_staging.p + at[k], *stream_of[k], span[k], hipMemcpyHostToDevice, ctx->stream));
+      *stream_of[k] = ctx->stream_staging.p + at[k];
+    }
+  }
+  if (d->recompute_normals) {
+    if (!ctx->adjacency) ctx->adjacency = sthip::device_vertex_adjacency_create();
+    if (!sthip::vertex_adjacency_valid(ctx->adjacency)) {
+      // the instances say which meshes there are: the kept scene has them; without one they are read back from the device
+      std::vector<sthip_InstanceData> read;
+      const sthip_InstanceData* instances = ctx->kept.valid && ctx->kept.instances.size() == ctx->instance_count ? ctx->kept.instances.data() : nullptr;
+      if (!instances) {
+        read.resize(ctx->instance_count);
+        if (ctx->instance_count) HIP_TRY(ctx, hipMemcpy(read.data(), ctx->instances.p, (size_t)ctx->instance_count * sizeof(sthip_InstanceData), hipMemcpyDeviceToHost));
+        instances = read.data();
+      }
+      std::string err;
+      bool built = false;
+      if (!sthip::vertex_adjacency_prepare(ctx->adjacency, sthip::list_vertex_meshes(instances, ctx->instance_count), ctx->indices.p, ctx->indices_bytes, ctx->vertex_count, ctx->stream, built, err))
+        return fail(ctx, STHIP_ERR_HIP, call + err);
+    }
+  }
+  VertexSource src{"sthip_scene_set_vertices", nullptr, d->first_vertex, d->vertex_count};
+  src.streams = &s;
+  src.recompute_normals = d->recompute_normals != 0;
+  return update_resident_vertices(ctx, src, info, t0);
 }
 
 // sthip.h: validated on the host, then the rest poses are taken on the device and targets and weights go up once. Everything is

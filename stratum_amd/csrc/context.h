@@ -24,6 +24,7 @@
 #include "scene_prepare.h"
 #include "top_level.h"
 #include "traverse.h"
+#include "vertex_streams.h"
 #include "volume_build.h"
 
 // (nothing in here is part of the library's interface: the types and the functions stay out of its dynamic symbol table)
@@ -346,6 +347,10 @@ struct sthip_ctx {
   DevBuf<double> env_sines;
   DevBuf<float> env_integrals;
   uint32_t env_rows_per_wave = sthip::ENV_ROWS_PER_WAVE_DEFAULT;  // "env_rows_per_wave": 16 or 64 (environment.h)
+  // sthip_scene_set_vertices (vertex_streams.hip): the corners of the resident meshes grouped by vertex, made at the first
+  // call that asks for normals and dropped where the refit's schedule is; the staging of a call with host streams
+  sthip::DeviceVertexAdjacency* adjacency = nullptr;
+  DevBuf<uint8_t> stream_staging;
   // around the device work of a resident edit (device_ms of its info struct): the k_animate launches of sthip_scene_animate,
   // the enqueues of sthip_scene_set_environment, sthip_scene_set_images and sthip_scene_set_material_data
   hipEvent_t edit_ev[2] = {nullptr, nullptr};

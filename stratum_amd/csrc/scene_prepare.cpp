@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 
 namespace sthip {
@@ -321,6 +322,47 @@ void environment_row_sines(uint32_t height, std::vector<double>& out) {
   out.resize(height);
   const float inv_height = 1 / (float)height;
   for (uint32_t y = 0; y < height; y++) out[y] = std::sin(M_PI * (y + 0.5f) * inv_height);
+}
+
+bool check_vertex_streams(bool has_scene, uint32_t scene_vertex_count, const sthip_vertex_streams* d, int& code, std::string& message) {
+  auto bad = [&](const std::string& m) {
+    code = STHIP_ERR_INVALID_ARGUMENT;
+    message = "sthip_scene_set_vertices: " + m;
+    return false;
+  };
+  if (!has_scene) return bad("no scene is resident (before sthip_scene_upload)");
+  if (!d) return bad("the description is NULL");
+  if (d->struct_size < sizeof(sthip_vertex_streams)) return bad("struct_size is " + std::to_string(d->struct_size) + ", below sizeof(sthip_vertex_streams) = " + std::to_string(sizeof(sthip_vertex_streams)));
+  if (!d->positions) return bad("positions is NULL");
+  if ((uint64_t)d->first_vertex + d->vertex_count > scene_vertex_count) return bad("first_vertex + vertex_count ends past the vertex_count of the uploaded scene");
+  struct Stream {
+    const char* name;
+    const void* p;
+    uint32_t stride, element;
+  };
+  const Stream streams[3] = {{"position", d->positions, d->position_stride, 12}, {"normal", d->normals, d->normal_stride, 12}, {"texcoord", d->texcoords, d->texcoord_stride, 8}};
+  for (const Stream& s : streams) {
+    if (!s.p) continue;  // (the stride of an absent stream is not read)
+    const std::string field = std::string(s.name) + "s", stride = std::string(s.name) + "_stride";
+    if ((uintptr_t)s.p & 3) return bad(field + " is not 4-byte aligned");
+    if (s.stride & 3) return bad(stride + " = " + std::to_string(s.stride) + " is not a multiple of 4");
+    if (s.stride < s.element) return bad(stride + " = " + std::to_string(s.stride) + " is below the element size " + std::to_string(s.element));
+  }
+  if (d->normals && d->recompute_normals) return bad("normals together with recompute_normals");
+  return true;
+}
+
+std::vector<VertexMesh> list_vertex_meshes(const sthip_InstanceData* instances, uint32_t instance_count) {
+  std::vector<VertexMesh> out;
+  for (uint32_t i = 0; instances && i < instance_count; i++) {
+    const sthip_InstanceData& in = instances[i];
+    if (instance_type(in) != STHIP_INSTANCE_TYPE_TRIANGLES) continue;
+    out.push_back(VertexMesh{in.packed[3], in.packed[2], in.packed[1] >> 28, (in.packed[1] >> 12) & 0xFFFFu});
+  }
+  auto key = [](const VertexMesh& m) { return std::array<uint32_t, 4>{{m.indices_byte_offset, m.first_vertex, m.index_stride, m.prim_count}}; };
+  std::sort(out.begin(), out.end(), [&](const VertexMesh& a, const VertexMesh& b) { return key(a) < key(b); });
+  out.erase(std::unique(out.begin(), out.end(), [&](const VertexMesh& a, const VertexMesh& b) { return key(a) == key(b); }), out.end());
+  return out;
 }
 
 bool pad_emitter_bounds(EmitterBounds& b) {

@@ -111,6 +111,17 @@ bool check_environment(const ResidentEnvironmentScene& scene, const sthip_enviro
 // s[y] = sin(M_PI * (y + 0.5f) * (1 / (float)H)) for the H rows of a lat-long image, with libm (sthip.h: the device gets them as they are)
 void environment_row_sines(uint32_t height, std::vector<double>& out);
 
+// ---- sthip_scene_set_vertices: what of it needs no device ----
+// Every refusal of the call (sthip.h), from the arguments and the resident vertex count alone. false: `code` and `message`
+// (which names the field) say why and the caller changes nothing.
+bool check_vertex_streams(bool has_scene, uint32_t scene_vertex_count, const sthip_vertex_streams* d, int& code, std::string& message);
+// A mesh of the normal contract: the tuple its triangle instances share
+struct VertexMesh {
+  uint32_t indices_byte_offset, first_vertex, index_stride, prim_count;
+};
+// The meshes of a scene: the distinct tuples of its triangle instances in ascending order (spheres and volumes have none)
+std::vector<VertexMesh> list_vertex_meshes(const sthip_InstanceData* instances, uint32_t instance_count);
+
 // The bounds of the emissive triangle instances (bvh.h: EmitterBounds), from the validated scene arrays: the box of the
 // vertices an instance's triangles refer to, widened by 2^-15 of its coordinates' magnitude as the packed nodes of the
 // tree are, in world space for an instance with identity transforms (that is where its triangles are tested, whether the

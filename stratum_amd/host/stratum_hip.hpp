@@ -66,6 +66,8 @@
 #pragma weak sthip_scene_set_transforms
 #pragma weak sthip_scene_read_transforms
 #pragma weak sthip_scene_read_top_level
+// ... and one that cannot take vertices from device streams lacks this: BDPT::set_vertices_device then throws
+#pragma weak sthip_scene_set_vertices
 #pragma weak sthip_accumulate
 #pragma weak sthip_denoise_filter
 #include "../../include/sthip_detmath.h"  // det_f16tof32: export_hdr of a half frame
@@ -1503,6 +1505,33 @@ class BDPT {
     t.derive_motion = derive_motion ? 1u : 0u;
     if (sthip_scene_set_transforms(mCtx, &t, sizeof(t), nullptr) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_set_transforms: ") + sthip_last_error(mCtx));
   }
+  // Vertices that lie in device memory (a cloth or soft-body step there) go to the resident scene without a copy to the host
+  // (sthip_scene_set_vertices with device_ptr = 1): `positions` (required), `normals` and `texcoords` (NULL: the resident
+  // fields stay) are strided streams of vertex_count elements readable in the order of the context's stream;
+  // recompute_normals: the shading normals of the range are made on the device from the moved positions (normals NULL).
+  // The bound Scene's own vertices do not follow (sthip_scene_read_vertices says what is resident): they are marked as behind
+  // the device, and the next update() that binds new SceneData uploads it instead of comparing against them. Throws on a
+  // refusal and on a layout the library does not refit without a kept scene.
+  void set_vertices_device(uint32_t first_vertex, uint32_t vertex_count, const void* positions, uint32_t position_stride, const void* normals = nullptr, uint32_t normal_stride = 0,
+                           const void* texcoords = nullptr, uint32_t texcoord_stride = 0, bool recompute_normals = false, sthip_refit_info* info = nullptr) {
+    if (!sthip_scene_set_vertices) throw std::runtime_error("set_vertices_device: the library lacks sthip_scene_set_vertices");
+    if (!mBoundData) throw std::runtime_error("set_vertices_device: no scene is bound");
+    sthip_vertex_streams s{};
+    s.struct_size = sizeof(s);
+    s.first_vertex = first_vertex;
+    s.vertex_count = vertex_count;
+    s.device_ptr = 1;
+    s.recompute_normals = recompute_normals ? 1u : 0u;
+    s.position_stride = position_stride;
+    s.normal_stride = normal_stride;
+    s.texcoord_stride = texcoord_stride;
+    s.positions = positions;
+    s.normals = normals;
+    s.texcoords = texcoords;
+    if (sthip_scene_set_vertices(mCtx, &s, info) != STHIP_OK) throw std::runtime_error(std::string("sthip_scene_set_vertices: ") + sthip_last_error(mCtx));
+    if (vertex_count) mVerticesBehindDevice = true;
+  }
+  bool vertices_behind_device() const { return mVerticesBehindDevice; }
   bool last_update_was_vertices_only() const { return mLastUpdateWasVerticesOnly; }  // (no transform changed with them)
   bool last_update_was_environment_only() const { return mLastUpdateWasEnvironmentOnly; }
   bool last_update_was_materials_only() const { return mLastUpdateWasMaterialsOnly; }
@@ -1560,6 +1589,12 @@ class BDPT {
     const Scene::SceneData& sd = *scene->data();
     const bool rigs = !sd.mRigs.empty();  // (packed only with a library that has the calls: Scene::pose_on_device())
     mLastUpdateWasVolumesOnly = false;
+    if (mVerticesBehindDevice) {
+      // set_vertices_device wrote the resident vertices: the bound data's are older than the device's, and a comparison
+      // against them would take a mesh for unchanged that is not. The new data is uploaded whole.
+      mBoundData = nullptr;  // (every partial path below needs it)
+      mVerticesBehindDevice = false;
+    }
     if (mBoundData && !same_volume_serials(*mBoundData, sd)) {
       // A density grid changed (Medium::set_density_device / mark_density_dirty). Where it is the only change, the grid is
       // replaced in the resident scene: built there from the dense device source, or copied from the host's bytes. Otherwise,
@@ -1985,6 +2020,7 @@ class BDPT {
   const void* mBound = nullptr;
   std::shared_ptr<Scene::SceneData> mBoundData;
   bool mLastUpdateWasTransformsOnly = false, mLastUpdateWasVerticesOnly = false, mLastUpdateWasEnvironmentOnly = false, mLastUpdateWasMaterialsOnly = false;
+  bool mVerticesBehindDevice = false;  // set_vertices_device wrote the resident vertices: the bound data's are older
   // false: a changed material is uploaded like any other change. The multi-device driver clears it, as mRefitDeformedMeshes.
   bool mMaterialsOnDevice = true;
   bool mVolumesOnDevice = true;  // MultiDeviceBDPT: false (a changed grid is a full upload on every rank)

@@ -285,6 +285,26 @@ RIG_DESC_BYTES, RIG_POSE_BYTES, VERTEX_WEIGHT_BYTES = 56, 24, 32  # sizeof of th
 assert C.sizeof(RigDesc) == RIG_DESC_BYTES and C.sizeof(RigPose) == RIG_POSE_BYTES
 
 
+class VertexStreams(C.Structure):  # sthip_vertex_streams
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("first_vertex", C.c_uint32),
+        ("vertex_count", C.c_uint32),
+        ("device_ptr", C.c_uint32),
+        ("recompute_normals", C.c_uint32),
+        ("position_stride", C.c_uint32),
+        ("normal_stride", C.c_uint32),
+        ("texcoord_stride", C.c_uint32),
+        ("positions", C.c_void_p),
+        ("normals", C.c_void_p),
+        ("texcoords", C.c_void_p),
+    ]
+
+
+VERTEX_STREAMS_BYTES = 56  # sizeof(sthip_vertex_streams), include/sthip.h
+assert C.sizeof(VertexStreams) == VERTEX_STREAMS_BYTES
+
+
 def ptr(a):
     """void* of a C-contiguous numpy array (None -> NULL)."""
     if a is None:
