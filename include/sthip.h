@@ -57,8 +57,10 @@ typedef struct sthip_image_desc {
  *                      STHIP_IMAGE_FORMAT_RGBA8_UNORM (1): `pixels` points at width * height * 4 BYTES, row 0 first, R G B A.
  * Formats of gImage1s: STHIP_IMAGE_FORMAT_R32F (0): width * height floats.
  *                      STHIP_IMAGE_FORMAT_R8_UNORM (1): width * height BYTES.
- * sRGB formats are out of scope: the images the reference binds after material_convert are all Unorm, and a byte is
- * never passed through a transfer curve here.
+ * Resident formats stay Unorm: the images the reference binds after material_convert are all Unorm, and a resident byte is
+ * never passed through a transfer curve. The two images upstream binds undecoded — the sRGB emission image of an emissive
+ * material and the RGB8 normal map — and every other format an asset holds (sRGB, one to three channels, 16-bit, BC1-BC5)
+ * are decoded on the way in: sthip_texel_format and sthip_decode_texels below.
  *
  * Decode: a byte b is the binary32 quotient (float)b / 255.0f, correctly rounded (IEEE division; the build has no
  * fast-math and no contraction).
@@ -500,8 +502,9 @@ int sthip_scene_set_vertices(sthip_ctx* ctx, const sthip_vertex_streams* streams
  *
  * Images are linear arrays of width * height texels, row 0 first. Sources: gDiffuse, gSpecular, gTransmittance — four
  * channels, STHIP_IMAGE_FORMAT_RGBA32F or _RGBA8_UNORM, a format byte each; gRoughness (DIFFUSE_SPECULAR) and gInput (the two
- * roughness kinds) — one channel, _R32F or _R8_UNORM. A NULL source is upstream's gUseX = false. A byte decodes as
- * (float)b / 255.0f. Outputs: gOutput[3], the three DisneyMaterialData vectors per texel (data[0] = base colour rgb, emission;
+ * roughness kinds) — one channel, _R32F or _R8_UNORM. Every source format byte also takes a sthip_texel_format from 16 up (the
+ * asset's own format, decoded in the kernel: see "source texel formats" below; 2 .. 15 are no format). A NULL source is
+ * upstream's gUseX = false. A byte decodes as (float)b / 255.0f. Outputs: gOutput[3], the three DisneyMaterialData vectors per texel (data[0] = base colour rgb, emission;
  * data[1] = metallic, roughness, anisotropic, subsurface; data[2] = clearcoat, clearcoat gloss, transmission, eta);
  * gOutputAlphaMask, one channel, written only when gDiffuse is given; gOutputMinAlpha, one uint32_t, set to 0xFFFFFFFF by the
  * call itself and then reduced; gRoughnessRW (one channel) for the roughness kinds. output_format 1: bytes (RGBA8 / R8, what
@@ -565,6 +568,130 @@ typedef struct sthip_convert_material_desc {
   void* gRoughnessRW;        /* one channel; the roughness kinds */
 } sthip_convert_material_desc;
 int sthip_convert_material(sthip_ctx* ctx, const sthip_convert_material_desc* desc);
+
+/* ---- source texel formats: what an asset holds, decoded on the way in (load_gltf.cpp:42-56, Image.cpp:22-40,107-121) ----
+ * Upstream's conversion shaders read Texture2D<float4>: the texture unit decodes the loader's format before the shader sees
+ * a texel. A sthip_texel_format names such a format; sthip_decode_texels is that decode as a device stage, and the format
+ * bytes of sthip_convert_material take the same values (the decode then happens in its kernels, no image in between).
+ * Nothing resident changes: the renderer keeps RGBA32F / RGBA8_UNORM / R32F / R8_UNORM images, and a transfer curve is
+ * applied only here, on the way in.
+ *
+ * VALUES. 0 and 1 keep their meaning (sthip_image_format: RGBA32F and RGBA8_UNORM, or R32F and R8_UNORM where the source has
+ * one channel; in sthip_decode_texels they are the four-channel forms). 2 .. 15 stay no format. From 16 up:
+ *   linear formats   16 + 4 * class + (channels - 1), class 0 unorm8, 1 sRGB8, 2 unorm16 (little-endian), 3 binary32
+ *   block formats    32 .. 39
+ *   48 .. 79         formats the loaders' table knows but no material path gives a meaning: named, refused with
+ *                    STHIP_ERR_UNSUPPORTED and a message that names the format: snorm, integer and 64-bit formats, BC4 / BC5
+ *                    snorm, BC6H, BC7.
+ * Any other value is no format (STHIP_ERR_INVALID_ARGUMENT).
+ *
+ * LAYOUT. A linear image is width * height texels, tightly packed, row 0 first, the channels of a texel in the order R G B A.
+ * A block image is ceil(width / 4) * ceil(height / 4) blocks, row-major, 8 bytes each (BC1, BC4) or 16 (BC2, BC3, BC5);
+ * texel (x, y) lies in block (x / 4, y / 4) as its texel t = 4 * (y % 4) + (x % 4). Texels of a block beyond the extent are
+ * never read as texels. Flipping and file parsing are the caller's: the API takes texels, not files.
+ *
+ * DECODE, to four binary32 channels. Absent channels: G = B = 0, A = 1. Every value is a real number rounded once by one
+ * IEEE operation.
+ *   unorm8    (float)b / 255.0f                         unorm16   (float)v / 65535.0f, v = lo | hi << 8
+ *   binary32  the value as it is
+ *   colour block (8 bytes: BC1, and bytes 8 .. 15 of BC2 and BC3)
+ *             c0 = byte0 | byte1 << 8, c1 = byte2 | byte3 << 8, endpoints RGB565: red = c >> 11, green = (c >> 5) & 63,
+ *             blue = c & 31. bits = byte4 | byte5 << 8 | byte6 << 16 | byte7 << 24; the index of texel t is
+ *             (bits >> 2t) & 3. With e0, e1 the INTEGER endpoint values of a channel:
+ *               index 0: (float)e0 / 31.0f  (63.0f for green)        index 1: (float)e1 / 31.0f  (63.0f)
+ *               four-colour rule (BC1 with c0 > c1 as integers; BC2 and BC3 always):
+ *                 index 2: (float)(2 * e0 + e1) / 93.0f (189.0f)     index 3: (float)(e0 + 2 * e1) / 93.0f (189.0f)
+ *               three-colour rule (BC1 with c0 <= c1):
+ *                 index 2: (float)(e0 + e1) / 62.0f (126.0f)         index 3: 0, 0, 0
+ *             BC1_RGB: alpha is 1 for every index (the reference never asks for BC1 alpha).
+ *   BC2 alpha (bytes 0 .. 7): the nibble of texel t is (byte[t / 2] >> 4 * (t % 2)) & 15; alpha = (float)a4 / 15.0f.
+ *   RGTC block (8 bytes: BC4; bytes 0 .. 7 of BC3, its alpha; bytes 0 .. 7 of BC5 for R and bytes 8 .. 15 for G)
+ *             r0 = byte0, r1 = byte1; bits = byte2 | byte3 << 8 | ... | byte7 << 40 (48 bits in bytes 2 .. 7); the index of
+ *             texel t is (bits >> 3t) & 7.
+ *               index 0: (float)r0 / 255.0f     index 1: (float)r1 / 255.0f
+ *               r0 > r1:   index i = 2 .. 7: (float)((8 - i) * r0 + (i - 1) * r1) / 1785.0f
+ *               r0 <= r1:  index i = 2 .. 5: (float)((6 - i) * r0 + (i - 1) * r1) / 1275.0f; index 6: 0; index 7: 1
+ *             BC4: R, with G = B = 0, A = 1. BC5: R and G, B = 0, A = 1. BC3: RGB from its colour block, A from its RGTC block.
+ *   sRGB      on R, G, B only (alpha is linear), applied to the binary32 value c of the rules above:
+ *               c <= 0.04045f ? c / 12.92f : det_powf((c + 0.055f) / 1.055f, 2.4f)
+ *             all binary32, unfused, det_powf of sthip_detmath.h. (A kernel may serve bytes from a 256-entry table made with
+ *             this function; the table is no part of the contract.)
+ * These are the ratios the Khronos Data Format Specification gives for S3TC and RGTC.
+ *
+ * sthip_decode_texels. Source: a format, a pointer, width and height. Destination: one of the library's four forms —
+ * dst_channels 4: RGBA32F (dst_format 0) or RGBA8_UNORM (1); dst_channels 1: R32F (0) or R8_UNORM (1) of the channel
+ * `channel` (0 .. 3) of the decoded texel. An 8-bit destination is quantised as in sthip_convert_material:
+ * byte = (uint32_t)(saturate(v) * 255.0f + 0.5f). Consequence: a unorm8 source of any channel count into an 8-bit destination
+ * gives the source bytes back, for all 256 values.
+ * device_ptrs as in sthip_convert_material: host form — the source is staged, the destination copied back, the call returns
+ * synchronised; device form — one kernel is enqueued on the context's stream, nothing is allocated or waited for. A device
+ * pointer is naturally aligned: a block image to the size of its block (8 or 16 bytes), a linear image to the size of one
+ * component (1, 2 or 4), the destination to its texel (16, 4, 4, 1). Linear 8-bit sources aligned to 4 bytes with a destination
+ * aligned to 16 (R8: 4) go four texels per lane.
+ * Refused with STHIP_ERR_INVALID_ARGUMENT, the message naming the field: an empty extent (width, height) or one of more than
+ * 2^30 texels (width x height); src_format that is none; dst_format above 1; dst_channels other than 1 or 4; channel above 3;
+ * a NULL src or dst; a device pointer that is not naturally aligned. A refused call writes nothing.
+ * In sthip_convert_material every source format byte and input_format take these values; a one-channel source (gRoughness,
+ * gInput) given in a multi-channel format takes channel 0, as a Texture2D<float> read does; the alignment of a device source
+ * is the one above; all given sources still have the extent width x height. What every glTF file gives — gDiffuse
+ * RGBA8_SRGB, the other sources format 1, 8-bit outputs — takes the all-8-bit kernel where gDiffuse is aligned as an RGBA8_UNORM
+ * image is (16 bytes: four texels per lane); every other mix of formats goes one texel per lane. The results do not depend on
+ * the path.
+ * A library without the feature lacks the symbol sthip_decode_texels. */
+enum sthip_texel_format {
+  STHIP_TEXEL_RGBA32F = 0, /* = STHIP_IMAGE_FORMAT_RGBA32F */
+  STHIP_TEXEL_RGBA8_UNORM = 1, /* = STHIP_IMAGE_FORMAT_RGBA8_UNORM */
+  STHIP_TEXEL_FIRST = 16,
+  STHIP_TEXEL_R8_UNORM = 16,
+  STHIP_TEXEL_RG8_UNORM = 17,
+  STHIP_TEXEL_RGB8_UNORM = 18,
+  STHIP_TEXEL_RGBA8_UNORM_ = 19, /* the same texels as 1 */
+  STHIP_TEXEL_R8_SRGB = 20,
+  STHIP_TEXEL_RG8_SRGB = 21,
+  STHIP_TEXEL_RGB8_SRGB = 22,
+  STHIP_TEXEL_RGBA8_SRGB = 23,
+  STHIP_TEXEL_R16_UNORM = 24,
+  STHIP_TEXEL_RG16_UNORM = 25,
+  STHIP_TEXEL_RGB16_UNORM = 26,
+  STHIP_TEXEL_RGBA16_UNORM = 27,
+  STHIP_TEXEL_R32F = 28,
+  STHIP_TEXEL_RG32F = 29,
+  STHIP_TEXEL_RGB32F = 30,
+  STHIP_TEXEL_RGBA32F_ = 31, /* the same texels as 0 */
+  STHIP_TEXEL_BC1_RGB = 32,
+  STHIP_TEXEL_BC2 = 33,
+  STHIP_TEXEL_BC3 = 34,
+  STHIP_TEXEL_BC4_UNORM = 35,
+  STHIP_TEXEL_BC5_UNORM = 36,
+  STHIP_TEXEL_BC1_RGB_SRGB = 37,
+  STHIP_TEXEL_BC2_SRGB = 38,
+  STHIP_TEXEL_BC3_SRGB = 39,
+  STHIP_TEXEL_END = 40, /* one past the last format that is built */
+  /* named and refused (STHIP_ERR_UNSUPPORTED) */
+  STHIP_TEXEL_UNSUPPORTED_FIRST = 48,
+  STHIP_TEXEL_BC4_SNORM = 48,
+  STHIP_TEXEL_BC5_SNORM = 49,
+  STHIP_TEXEL_BC6H_UFLOAT = 50,
+  STHIP_TEXEL_BC6H_SFLOAT = 51,
+  STHIP_TEXEL_BC7_UNORM = 52,
+  STHIP_TEXEL_BC7_SRGB = 53,
+  STHIP_TEXEL_R8_SNORM = 56, /* .. 59: R, RG, RGB, RGBA */
+  STHIP_TEXEL_R16_SNORM = 60, /* .. 63 */
+  STHIP_TEXEL_R8_UINT = 64, /* .. 67; 68 .. 71 SINT; 72 .. 75 16-bit UINT; 76 .. 79 16-bit SINT and wider integers, 64-bit */
+  STHIP_TEXEL_UNSUPPORTED_END = 80
+};
+typedef struct sthip_decode_texels_desc {
+  uint32_t src_format; /* sthip_texel_format */
+  uint32_t width, height;
+  uint32_t device_ptrs;
+  uint32_t dst_format;   /* sthip_image_format: 0 binary32, 1 unorm8 */
+  uint32_t dst_channels; /* 4: RGBA, 1: one channel */
+  uint32_t channel;      /* 0 .. 3, which channel a one-channel destination takes; ignored with dst_channels 4 */
+  uint32_t pad_;
+  const void* src;
+  void* dst;
+} sthip_decode_texels_desc;
+int sthip_decode_texels(sthip_ctx* ctx, const sthip_decode_texels_desc* desc);
 
 /* ---- density grids from dense voxel arrays (load_volumes.cpp:87-91: GridBuilder<float>(0, FogVolume) over a dense box) ----
  * gVolumes[] takes finished NanoVDB 32.3 buffers. sthip_build_volume makes one ON THE DEVICE (volume_build.hip) from a dense

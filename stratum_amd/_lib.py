@@ -34,6 +34,7 @@ EXPORTS = [
     "sthip_scene_read_vertices",
     "sthip_scene_set_vertices",
     "sthip_convert_material",
+    "sthip_decode_texels",
     "sthip_build_volume",
     "sthip_scene_set_volume",
     "sthip_scene_read_volume",
@@ -136,6 +137,9 @@ def lib():
     if hasattr(L, "sthip_convert_material"):  # (an older build named by STHIP_LIB lacks it: calling it raises)
         L.sthip_convert_material.restype = C.c_int
         L.sthip_convert_material.argtypes = [C.c_void_p, C.POINTER(wire.ConvertMaterialDesc)]
+    if hasattr(L, "sthip_decode_texels"):  # (an older build named by STHIP_LIB lacks it: calling it raises)
+        L.sthip_decode_texels.restype = C.c_int
+        L.sthip_decode_texels.argtypes = [C.c_void_p, C.POINTER(wire.DecodeTexelsDesc)]
     if hasattr(L, "sthip_build_volume"):  # (an older build named by STHIP_LIB lacks it: calling it raises)
         L.sthip_build_volume.restype = C.c_int
         L.sthip_build_volume.argtypes = [C.c_void_p, C.POINTER(wire.DenseVolumeDesc), C.c_void_p, C.c_uint64, C.c_int, C.POINTER(wire.VolumeInfo)]

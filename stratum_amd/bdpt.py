@@ -471,10 +471,11 @@ class BDPT:
 
     def convert_material(self, kind, diffuse=None, specular=None, transmittance=None, roughness=None, input=None, output_format=1):
         """sthip_convert_material in its host form (kernels/material_convert.hlsl). `kind`: a name of wire.CONVERT or its
-        number. Sources are C-contiguous uint8 or float32 arrays, (H, W, 4) or, for `roughness` / `input`, (H, W); None =
-        absent. Returns a dict: "output" (three (H, W, 4) arrays), "alpha_mask" ((H, W), or None without `diffuse`) and
-        "min_alpha" (int) for the two material kinds, "roughness" ((H, W)) for the two roughness kinds; uint8 with
-        output_format 1, float32 with 0."""
+        number. Sources are C-contiguous uint8 or float32 arrays, (H, W, 4) or, for `roughness` / `input`, (H, W), or a
+        wire.TexelImage (an asset's image in its own texel format, decoded in the kernel; a one-channel source takes its
+        channel 0); None = absent. Returns a dict: "output" (three (H, W, 4) arrays), "alpha_mask" ((H, W), or None without
+        `diffuse`) and "min_alpha" (int) for the two material kinds, "roughness" ((H, W)) for the two roughness kinds; uint8
+        with output_format 1, float32 with 0."""
         kind = wire.CONVERT[kind] if isinstance(kind, str) else int(kind)
         sources = {"gDiffuse": diffuse, "gSpecular": specular, "gTransmittance": transmittance, "gRoughness": roughness, "gInput": input}
         formats = {"gDiffuse": "diffuse_format", "gSpecular": "specular_format", "gTransmittance": "transmittance_format", "gRoughness": "roughness_format", "gInput": "input_format"}
@@ -485,14 +486,19 @@ class BDPT:
             if a is None:
                 continue
             channels = 1 if name in ("gRoughness", "gInput") else 4
-            if a.dtype not in (np.uint8, np.float32) or not a.flags["C_CONTIGUOUS"] or a.ndim != (2 if channels == 1 else 3) or (channels == 4 and a.shape[2] != 4):
-                raise ValueError("%s must be a C-contiguous uint8 or float32 array of %d channel(s)" % (name, channels))
+            if isinstance(a, wire.TexelImage):
+                shape, address = (a.height, a.width), a.data.ctypes.data
+                fmt = {0: 31, 1: 19}.get(a.format, a.format) if channels == 1 else a.format  # (0 / 1 of a TexelImage are the four-channel forms)
+            else:
+                if a.dtype not in (np.uint8, np.float32) or not a.flags["C_CONTIGUOUS"] or a.ndim != (2 if channels == 1 else 3) or (channels == 4 and a.shape[2] != 4):
+                    raise ValueError("%s must be a C-contiguous uint8 or float32 array of %d channel(s), or a TexelImage" % (name, channels))
+                shape, address, fmt = a.shape[:2], a.ctypes.data, (1 if a.dtype == np.uint8 else 0)
             if extent is None:
-                extent = a.shape[:2]
-            elif a.shape[:2] != extent:
-                raise ValueError("%s has the extent %s, the first image %s: all sources must have one extent" % (name, a.shape[:2], extent))
-            setattr(d, name, a.ctypes.data)
-            setattr(d, formats[name], 1 if a.dtype == np.uint8 else 0)
+                extent = shape
+            elif shape != extent:
+                raise ValueError("%s has the extent %s, the first image %s: all sources must have one extent" % (name, shape, extent))
+            setattr(d, name, address)
+            setattr(d, formats[name], fmt)
         if extent is None:
             raise ValueError("convert_material: no source image")
         H, W = extent
@@ -512,6 +518,20 @@ class BDPT:
         d.gRoughnessRW = rough.ctypes.data
         self._check(self._lib.sthip_convert_material(self._h, C.byref(d)), "sthip_convert_material")
         return {"roughness": rough}
+
+    def decode_texels(self, image, dst_format=0, channel=None):
+        """sthip_decode_texels in its host form: a wire.TexelImage (an asset's image in its own texel format: sRGB, 16-bit,
+        BC1-BC5, ...) to an (H, W, 4) array, or with `channel` 0..3 to the (H, W) array of that channel; float32 with
+        dst_format 0, uint8 with 1."""
+        if not hasattr(self._lib, "sthip_decode_texels"):
+            raise StratumHipError("this libstratum_hip.so has no sthip_decode_texels")
+        d = wire.DecodeTexelsDesc()
+        d.src_format, d.width, d.height, d.device_ptrs, d.dst_format = image.format, image.width, image.height, 0, int(dst_format)
+        d.dst_channels, d.channel = (4, 0) if channel is None else (1, int(channel))
+        out = np.zeros((image.height, image.width, 4) if channel is None else (image.height, image.width), np.uint8 if dst_format else np.float32)
+        d.src, d.dst = image.data.ctypes.data, out.ctypes.data
+        self._check(self._lib.sthip_decode_texels(self._h, C.byref(d)), "sthip_decode_texels")
+        return out
 
     def build_volume(self, dense, origin=(0, 0, 0), voxel_size=1.0, translation=(0.0, 0.0, 0.0), name="", dims=None, out=None, capacity=None):
         """sthip_build_volume: a NanoVDB float grid (FogVolume) from a dense box, built on the device; the bytes are those of

@@ -26,10 +26,12 @@ STHIP_CONVERT_HD inline float decode_unorm8(uint32_t b) {
   return fmaf(fmaf(-q, 255.0f, f), k, q);
 }
 
-// All pointers are device pointers; a null source is upstream's gUseX = false. A format is a sthip_image_format (1 = bytes).
+// All pointers are device pointers; a null source is upstream's gUseX = false. A format is 0 or 1 (sthip_image_format, 1 = bytes)
+// or a sthip_texel_format from 16 up, which the generic kernels decode with texel_decode.h.
 struct MaterialConvertParams {
   uint32_t kind;    // STHIP_CONVERT_*
   uint64_t texels;  // width * height, 1 .. 2^30
+  uint32_t width, height;
   const void* diffuse;
   const void* specular;
   const void* transmittance;

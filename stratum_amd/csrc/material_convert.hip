@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "material_convert.h"
+#include "texel_decode.h"
 
 namespace sthip {
 namespace {
@@ -16,15 +17,21 @@ constexpr uint32_t NO_ALPHA = 0xFFFFFFFFu;  // (the largest reduced value is (1 
 
 struct Switches {  // upstream's specialisation constants gUseX: kernel arguments here, uniform over the launch
   bool diffuse, specular, transmittance, roughness;
+  bool diffuse_srgb;  // k_material_bytes only: gDiffuse is RGBA8_SRGB, its colour bytes go through the tables
+};
+// The sRGB curve of a byte as k_material_bytes serves it: linear[b] = srgb_to_linear(decode_unorm8(b)), the value the generic
+// kernel computes, and byte[b] = texel_quantise(linear[b]), the byte it stores for a base colour that only passes through. Each
+// workgroup fills both itself, one entry per lane (CONVERT_BLOCK = 256).
+struct SrgbTables {
+  float linear[256];
+  uint32_t byte[256];
 };
 
-__device__ __forceinline__ float saturate1(float a) { return a > 0.0f ? (a < 1.0f ? a : 1.0f) : 0.0f; }
 __device__ __forceinline__ float luminance3(float x, float y, float z) { return (x * 0.2126f + y * 0.7152f) + z * 0.0722f; }
 __device__ __forceinline__ float decode1(uint32_t b) { return decode_unorm8(b); }  // = (float)b / 255.0f
-__device__ __forceinline__ uint32_t quantise1(float v) { return (uint32_t)(saturate1(v) * 255.0f + 0.5f); }
 __device__ __forceinline__ float4 decode4(uint32_t w) { return make_float4(decode1(w & 0xFFu), decode1((w >> 8) & 0xFFu), decode1((w >> 16) & 0xFFu), decode1(w >> 24)); }
-__device__ __forceinline__ uint32_t quantise4(float4 v) { return quantise1(v.x) | (quantise1(v.y) << 8) | (quantise1(v.z) << 16) | (quantise1(v.w) << 24); }
-__device__ __forceinline__ uint32_t alpha_word(float a) { return a < 1.0f ? (uint32_t)(saturate1(a) * 4294967296.0f) : NO_ALPHA; }
+__device__ __forceinline__ uint32_t quantise4(float4 v) { return texel_quantise(v.x) | (texel_quantise(v.y) << 8) | (texel_quantise(v.z) << 16) | (texel_quantise(v.w) << 24); }
+__device__ __forceinline__ uint32_t alpha_word(float a) { return a < 1.0f ? (uint32_t)(texel_saturate(a) * 4294967296.0f) : NO_ALPHA; }
 
 // One texel of a material kind: decoded sources in (an absent one is ignored), the three DisneyMaterialData vectors out.
 template <uint32_t KIND>
@@ -33,7 +40,7 @@ __device__ __forceinline__ void convert_texel(const Switches u, float4 d, float4
     if (!u.diffuse) d = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
     if (!u.specular) s = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
     const float l = luminance3(d.x, d.y, d.z);
-    const float transmission = u.transmittance ? saturate1(luminance3(t.x, t.y, t.z) / (l > 0.0f ? l : 1.0f)) : 0.0f;
+    const float transmission = u.transmittance ? texel_saturate(luminance3(t.x, t.y, t.z) / (l > 0.0f ? l : 1.0f)) : 0.0f;
     o0 = make_float4(d.x, d.y, d.z, 1.0f);
     o1 = make_float4(s.z, s.y, 1.0f, 1.0f);
     o2 = make_float4(1.0f, 1.0f, transmission, 1.0f);
@@ -44,8 +51,8 @@ __device__ __forceinline__ void convert_texel(const Switches u, float4 d, float4
     const float ld = luminance3(d.x, d.y, d.z), ls = luminance3(s.x, s.y, s.z), lt = luminance3(t.x, t.y, t.z);
     const float den = (ls + ld) + lt;
     o0 = make_float4(((d.x * ld + s.x * ls) + t.x * lt) / den, ((d.y * ld + s.y * ls) + t.y * lt) / den, ((d.z * ld + s.z * ls) + t.z * lt) / den, 1.0f);
-    o1 = make_float4(u.specular ? saturate1(ls / den) : 1.0f, u.roughness ? r : 1.0f, 1.0f, 1.0f);
-    o2 = make_float4(1.0f, 1.0f, u.transmittance ? saturate1(lt / den) : 1.0f, 1.0f);
+    o1 = make_float4(u.specular ? texel_saturate(ls / den) : 1.0f, u.roughness ? r : 1.0f, 1.0f, 1.0f);
+    o2 = make_float4(1.0f, 1.0f, u.transmittance ? texel_saturate(lt / den) : 1.0f, 1.0f);
   }
 }
 
@@ -62,24 +69,32 @@ __device__ __forceinline__ void reduce_min_alpha(uint32_t v, uint32_t* min_alpha
 
 // Everything 8-bit. Lanes [0, groups) take the texels [4 lane, 4 lane + 4): one 16-byte load per present source (4 bytes of
 // gRoughness), three 16-byte stores and 4 bytes of mask. Lanes [groups, groups + singles) take texel 4 groups + (lane - groups).
-// A byte that only passes through (GLTF base colour, metallic, roughness; gRoughness; the mask) is copied: quantise1(decode1(b))
+// A byte that only passes through (GLTF base colour, metallic, roughness; gRoughness; the mask) is copied: texel_quantise(decode1(b))
 // is b for all 256 bytes, which tests/test_material_convert.py checks on the numpy statement and against the generic kernel.
+// With an sRGB gDiffuse the colour bytes of the base colour become tables.byte[b] and its decoded floats tables.linear[b];
+// the alpha byte is linear and passes through as before.
+__device__ __forceinline__ float4 decode4_diffuse(const Switches u, const SrgbTables& tables, uint32_t w) {
+  if (!u.diffuse_srgb) return decode4(w);
+  return make_float4(tables.linear[w & 0xFFu], tables.linear[(w >> 8) & 0xFFu], tables.linear[(w >> 16) & 0xFFu], decode1(w >> 24));
+}
 template <uint32_t KIND>
-__device__ __forceinline__ void bytes_texel(const Switches u, uint32_t d, uint32_t s, uint32_t t, uint32_t r, uint32_t& w0, uint32_t& w1, uint32_t& w2, uint32_t& lane_min) {
+__device__ __forceinline__ void bytes_texel(const Switches u, const SrgbTables& tables, uint32_t d, uint32_t s, uint32_t t, uint32_t r, uint32_t& w0, uint32_t& w1, uint32_t& w2,
+                                            uint32_t& lane_min) {
   if (u.diffuse && (d >> 24) != 255u) lane_min = min(lane_min, alpha_word(decode1(d >> 24)));
   if (KIND == STHIP_CONVERT_GLTF_PBR) {
-    w0 = u.diffuse ? (d | 0xFF000000u) : 0xFFFFFFFFu;
+    const uint32_t base = u.diffuse_srgb ? (tables.byte[d & 0xFFu] | (tables.byte[(d >> 8) & 0xFFu] << 8) | (tables.byte[(d >> 16) & 0xFFu] << 16)) : d;
+    w0 = u.diffuse ? (base | 0xFF000000u) : 0xFFFFFFFFu;
     w1 = u.specular ? (((s >> 16) & 0xFFu) | (s & 0xFF00u) | 0xFFFF0000u) : 0xFFFFFFFFu;
     uint32_t tr = 0;
     if (u.transmittance) {
-      const float4 df = u.diffuse ? decode4(d) : make_float4(1.0f, 1.0f, 1.0f, 1.0f), tf = decode4(t);
+      const float4 df = u.diffuse ? decode4_diffuse(u, tables, d) : make_float4(1.0f, 1.0f, 1.0f, 1.0f), tf = decode4(t);
       const float l = luminance3(df.x, df.y, df.z);
-      tr = quantise1(saturate1(luminance3(tf.x, tf.y, tf.z) / (l > 0.0f ? l : 1.0f)));
+      tr = texel_quantise(texel_saturate(luminance3(tf.x, tf.y, tf.z) / (l > 0.0f ? l : 1.0f)));
     }
     w2 = 0xFF00FFFFu | (tr << 16);
   } else {
     float4 o0, o1, o2;
-    convert_texel<KIND>(u, decode4(d), decode4(s), decode4(t), 1.0f, o0, o1, o2);
+    convert_texel<KIND>(u, decode4_diffuse(u, tables, d), decode4(s), decode4(t), 1.0f, o0, o1, o2);
     w0 = quantise4(o0);
     w1 = (quantise4(o1) & 0xFFFF00FFu) | ((u.roughness ? r : 255u) << 8);
     w2 = quantise4(o2);
@@ -92,6 +107,13 @@ __global__ void __launch_bounds__(CONVERT_BLOCK) k_material_bytes(Switches u, co
                                                                   uint8_t* __restrict__ mask, uint32_t* __restrict__ min_alpha, uint32_t groups, uint32_t singles) {
   const uint32_t lane = blockIdx.x * CONVERT_BLOCK + threadIdx.x;
   uint32_t lane_min = NO_ALPHA;
+  __shared__ SrgbTables tables;
+  if (u.diffuse_srgb) {  // (uniform over the launch: every lane of the workgroup arrives at the barrier)
+    const float v = srgb_to_linear(decode_unorm8(threadIdx.x));
+    tables.linear[threadIdx.x] = v;
+    tables.byte[threadIdx.x] = texel_quantise(v);
+    __syncthreads();
+  }
   if (lane < groups) {
     const uint4 zero = make_uint4(0, 0, 0, 0);
     const uint4 d = u.diffuse ? reinterpret_cast<const uint4*>(diffuse)[lane] : zero;
@@ -99,10 +121,10 @@ __global__ void __launch_bounds__(CONVERT_BLOCK) k_material_bytes(Switches u, co
     const uint4 t = u.transmittance ? reinterpret_cast<const uint4*>(transmittance)[lane] : zero;
     const uint32_t r = u.roughness ? reinterpret_cast<const uint32_t*>(roughness)[lane] : 0u;
     uint4 w0, w1, w2;
-    bytes_texel<KIND>(u, d.x, s.x, t.x, r & 0xFFu, w0.x, w1.x, w2.x, lane_min);
-    bytes_texel<KIND>(u, d.y, s.y, t.y, (r >> 8) & 0xFFu, w0.y, w1.y, w2.y, lane_min);
-    bytes_texel<KIND>(u, d.z, s.z, t.z, (r >> 16) & 0xFFu, w0.z, w1.z, w2.z, lane_min);
-    bytes_texel<KIND>(u, d.w, s.w, t.w, r >> 24, w0.w, w1.w, w2.w, lane_min);
+    bytes_texel<KIND>(u, tables, d.x, s.x, t.x, r & 0xFFu, w0.x, w1.x, w2.x, lane_min);
+    bytes_texel<KIND>(u, tables, d.y, s.y, t.y, (r >> 8) & 0xFFu, w0.y, w1.y, w2.y, lane_min);
+    bytes_texel<KIND>(u, tables, d.z, s.z, t.z, (r >> 16) & 0xFFu, w0.z, w1.z, w2.z, lane_min);
+    bytes_texel<KIND>(u, tables, d.w, s.w, t.w, r >> 24, w0.w, w1.w, w2.w, lane_min);
     reinterpret_cast<uint4*>(out0)[lane] = w0;
     reinterpret_cast<uint4*>(out1)[lane] = w1;
     reinterpret_cast<uint4*>(out2)[lane] = w2;
@@ -112,7 +134,7 @@ __global__ void __launch_bounds__(CONVERT_BLOCK) k_material_bytes(Switches u, co
     const uint32_t d = u.diffuse ? diffuse[i] : 0u, s = u.specular ? specular[i] : 0u, t = u.transmittance ? transmittance[i] : 0u;
     const uint32_t r = u.roughness ? roughness[i] : 0u;
     uint32_t w0, w1, w2;
-    bytes_texel<KIND>(u, d, s, t, r, w0, w1, w2, lane_min);
+    bytes_texel<KIND>(u, tables, d, s, t, r, w0, w1, w2, lane_min);
     out0[i] = w0;
     out1[i] = w1;
     out2[i] = w2;
@@ -121,24 +143,33 @@ __global__ void __launch_bounds__(CONVERT_BLOCK) k_material_bytes(Switches u, co
   if (u.diffuse) reduce_min_alpha(lane_min, min_alpha);
 }
 
-__device__ __forceinline__ float4 load_texel4(const void* p, bool bytes, uint64_t i) {
-  return bytes ? decode4(static_cast<const uint32_t*>(p)[i]) : static_cast<const float4*>(p)[i];
+// A source format is a launch-uniform byte: 0 and 1 are the library's own forms (aligned to their texel: one load), anything else a
+// sthip_texel_format from 16 up, decoded by texel_decode.h at texel (i % width, i / width). A one-channel source takes channel 0.
+__device__ __forceinline__ float4 load_texel4(const void* p, uint32_t format, uint32_t i, uint32_t width, uint32_t height) {
+  if (format == 0) return static_cast<const float4*>(p)[i];
+  if (format == 1) return decode4(static_cast<const uint32_t*>(p)[i]);
+  const Texel4 v = decode_texel(format, p, width, height, i % width, i / width);
+  return make_float4(v.x, v.y, v.z, v.w);
 }
-__device__ __forceinline__ float load_texel1(const void* p, bool bytes, uint64_t i) { return bytes ? decode1(static_cast<const uint8_t*>(p)[i]) : static_cast<const float*>(p)[i]; }
+__device__ __forceinline__ float load_texel1(const void* p, uint32_t format, uint32_t i, uint32_t width, uint32_t height) {
+  if (format == 0) return static_cast<const float*>(p)[i];
+  if (format == 1) return decode1(static_cast<const uint8_t*>(p)[i]);
+  return decode_texel(format, p, width, height, i % width, i / width).x;
+}
 
-// One texel per lane, any mix of source formats (uniform over the launch); OUT8: RGBA8 / R8 outputs, else RGBA32F / R32F.
+// One texel per lane, any mix of source formats (uniform over the launch: `formats` holds a byte per source, gDiffuse lowest); OUT8: RGBA8 / R8 outputs, else RGBA32F / R32F.
 template <uint32_t KIND, bool OUT8>
 __global__ void __launch_bounds__(CONVERT_BLOCK) k_material_texels(Switches u, const void* __restrict__ diffuse, const void* __restrict__ specular, const void* __restrict__ transmittance,
-                                                                   const void* __restrict__ roughness, uint32_t source_bytes, void* __restrict__ out0, void* __restrict__ out1,
+                                                                   const void* __restrict__ roughness, uint32_t formats, uint32_t width, uint32_t height, void* __restrict__ out0, void* __restrict__ out1,
                                                                    void* __restrict__ out2, void* __restrict__ mask, uint32_t* __restrict__ min_alpha, uint32_t texels) {
   const uint32_t i = blockIdx.x * CONVERT_BLOCK + threadIdx.x;
   uint32_t lane_min = NO_ALPHA;
   if (i < texels) {
     const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    const float4 d = u.diffuse ? load_texel4(diffuse, source_bytes & 1u, i) : none;
-    const float4 s = u.specular ? load_texel4(specular, source_bytes & 2u, i) : none;
-    const float4 t = u.transmittance ? load_texel4(transmittance, source_bytes & 4u, i) : none;
-    const float r = u.roughness ? load_texel1(roughness, source_bytes & 8u, i) : 1.0f;
+    const float4 d = u.diffuse ? load_texel4(diffuse, formats & 0xFFu, i, width, height) : none;
+    const float4 s = u.specular ? load_texel4(specular, (formats >> 8) & 0xFFu, i, width, height) : none;
+    const float4 t = u.transmittance ? load_texel4(transmittance, (formats >> 16) & 0xFFu, i, width, height) : none;
+    const float r = u.roughness ? load_texel1(roughness, formats >> 24, i, width, height) : 1.0f;
     float4 o0, o1, o2;
     convert_texel<KIND>(u, d, s, t, r, o0, o1, o2);
     if (OUT8) {
@@ -152,7 +183,7 @@ __global__ void __launch_bounds__(CONVERT_BLOCK) k_material_texels(Switches u, c
     }
     if (u.diffuse) {
       if (OUT8)
-        static_cast<uint8_t*>(mask)[i] = (uint8_t)quantise1(d.w);
+        static_cast<uint8_t*>(mask)[i] = (uint8_t)texel_quantise(d.w);
       else
         static_cast<float*>(mask)[i] = d.w;
       lane_min = alpha_word(d.w);
@@ -162,23 +193,24 @@ __global__ void __launch_bounds__(CONVERT_BLOCK) k_material_texels(Switches u, c
 }
 
 __device__ __forceinline__ float to_roughness(uint32_t kind, float x) {
-  return kind == STHIP_CONVERT_ALPHA_TO_ROUGHNESS ? saturate1(sqrtf(x)) : saturate1(sqrtf(2.0f / (x + 2.0f)));
+  return kind == STHIP_CONVERT_ALPHA_TO_ROUGHNESS ? texel_saturate(sqrtf(x)) : texel_saturate(sqrtf(2.0f / (x + 2.0f)));
 }
 
 // The two roughness kinds. With 8-bit input and output, lanes [0, groups) take four texels (one 4-byte load, one 4-byte store),
-// the lanes behind them one texel each; otherwise groups = 0.
+// the lanes behind them one texel each; otherwise groups = 0. IN8 is false for every input that is not R8_UNORM (format 1).
 template <bool IN8, bool OUT8>
-__global__ void __launch_bounds__(CONVERT_BLOCK) k_to_roughness(uint32_t kind, const void* __restrict__ input, void* __restrict__ output, uint32_t groups, uint32_t singles) {
+__global__ void __launch_bounds__(CONVERT_BLOCK) k_to_roughness(uint32_t kind, const void* __restrict__ input, uint32_t format, uint32_t width, uint32_t height, void* __restrict__ output,
+                                                                uint32_t groups, uint32_t singles) {
   const uint32_t lane = blockIdx.x * CONVERT_BLOCK + threadIdx.x;
   if (IN8 && OUT8 && lane < groups) {
     const uint32_t w = static_cast<const uint32_t*>(input)[lane];
-    static_cast<uint32_t*>(output)[lane] = quantise1(to_roughness(kind, decode1(w & 0xFFu))) | (quantise1(to_roughness(kind, decode1((w >> 8) & 0xFFu))) << 8) |
-                                           (quantise1(to_roughness(kind, decode1((w >> 16) & 0xFFu))) << 16) | (quantise1(to_roughness(kind, decode1(w >> 24))) << 24);
+    static_cast<uint32_t*>(output)[lane] = texel_quantise(to_roughness(kind, decode1(w & 0xFFu))) | (texel_quantise(to_roughness(kind, decode1((w >> 8) & 0xFFu))) << 8) |
+                                           (texel_quantise(to_roughness(kind, decode1((w >> 16) & 0xFFu))) << 16) | (texel_quantise(to_roughness(kind, decode1(w >> 24))) << 24);
   } else if (lane >= groups && lane - groups < singles) {
     const uint64_t i = (uint64_t)groups * 4u + (lane - groups);
-    const float v = to_roughness(kind, IN8 ? decode1(static_cast<const uint8_t*>(input)[i]) : static_cast<const float*>(input)[i]);
+    const float v = to_roughness(kind, IN8 ? decode1(static_cast<const uint8_t*>(input)[i]) : load_texel1(input, format, (uint32_t)i, width, height));
     if (OUT8)
-      static_cast<uint8_t*>(output)[i] = (uint8_t)quantise1(v);
+      static_cast<uint8_t*>(output)[i] = (uint8_t)texel_quantise(v);
     else
       static_cast<float*>(output)[i] = v;
   }
@@ -199,18 +231,18 @@ bool material_convert_launch(const MaterialConvertParams& p, void* stream_, std:
     return e == hipSuccess;
   };
   if (p.kind == STHIP_CONVERT_ALPHA_TO_ROUGHNESS || p.kind == STHIP_CONVERT_SHININESS_TO_ROUGHNESS) {
-    const bool in8 = p.input_format != 0;
+    const bool in8 = p.input_format == 1;
     const bool four = in8 && out8 && aligned(p.input, 4) && aligned(p.roughness_rw, 4);
     const uint32_t groups = four ? texels / 4 : 0, singles = texels - groups * 4;
     const dim3 grid = blocks((uint64_t)groups + singles);
     if (in8 && out8)
-      hipLaunchKernelGGL((k_to_roughness<true, true>), grid, dim3(CONVERT_BLOCK), 0, stream, p.kind, p.input, p.roughness_rw, groups, singles);
+      hipLaunchKernelGGL((k_to_roughness<true, true>), grid, dim3(CONVERT_BLOCK), 0, stream, p.kind, p.input, (uint32_t)p.input_format, p.width, p.height, p.roughness_rw, groups, singles);
     else if (in8)
-      hipLaunchKernelGGL((k_to_roughness<true, false>), grid, dim3(CONVERT_BLOCK), 0, stream, p.kind, p.input, p.roughness_rw, groups, singles);
+      hipLaunchKernelGGL((k_to_roughness<true, false>), grid, dim3(CONVERT_BLOCK), 0, stream, p.kind, p.input, (uint32_t)p.input_format, p.width, p.height, p.roughness_rw, groups, singles);
     else if (out8)
-      hipLaunchKernelGGL((k_to_roughness<false, true>), grid, dim3(CONVERT_BLOCK), 0, stream, p.kind, p.input, p.roughness_rw, groups, singles);
+      hipLaunchKernelGGL((k_to_roughness<false, true>), grid, dim3(CONVERT_BLOCK), 0, stream, p.kind, p.input, (uint32_t)p.input_format, p.width, p.height, p.roughness_rw, groups, singles);
     else
-      hipLaunchKernelGGL((k_to_roughness<false, false>), grid, dim3(CONVERT_BLOCK), 0, stream, p.kind, p.input, p.roughness_rw, groups, singles);
+      hipLaunchKernelGGL((k_to_roughness<false, false>), grid, dim3(CONVERT_BLOCK), 0, stream, p.kind, p.input, (uint32_t)p.input_format, p.width, p.height, p.roughness_rw, groups, singles);
     return finish("k_to_roughness");
   }
   const bool gltf = p.kind == STHIP_CONVERT_GLTF_PBR;
@@ -224,8 +256,11 @@ bool material_convert_launch(const MaterialConvertParams& p, void* stream_, std:
     err = std::string("clearing gOutputMinAlpha: ") + hipGetErrorString(e);
     return false;
   }
-  const uint32_t source_bytes = (u.diffuse && p.diffuse_format ? 1u : 0u) | (u.specular && p.specular_format ? 2u : 0u) | (u.transmittance && p.transmittance_format ? 4u : 0u) |
-                                (u.roughness && p.roughness_format ? 8u : 0u);
+  // the 8-bit kernel also takes the diffuse image every glTF file has: RGBA8_SRGB, where it is aligned as an RGBA8_UNORM one is
+  u.diffuse_srgb = u.diffuse && p.diffuse_format == STHIP_TEXEL_RGBA8_SRGB && aligned(p.diffuse, 4);
+  const uint32_t source_bytes = (u.diffuse && (p.diffuse_format == 1 || u.diffuse_srgb) ? 1u : 0u) | (u.specular && p.specular_format == 1 ? 2u : 0u) | (u.transmittance && p.transmittance_format == 1 ? 4u : 0u) |
+                                (u.roughness && p.roughness_format == 1 ? 8u : 0u);
+  const uint32_t formats = (uint32_t)p.diffuse_format | ((uint32_t)p.specular_format << 8) | ((uint32_t)p.transmittance_format << 16) | ((uint32_t)p.roughness_format << 24);
   const uint32_t present = (u.diffuse ? 1u : 0u) | (u.specular ? 2u : 0u) | (u.transmittance ? 4u : 0u) | (u.roughness ? 8u : 0u);
   if (out8 && source_bytes == present) {
     const bool four = (!u.diffuse || (aligned(p.diffuse, 16) && aligned(p.alpha_mask, 4))) && (!u.specular || aligned(p.specular, 16)) && (!u.transmittance || aligned(p.transmittance, 16)) &&
@@ -243,7 +278,7 @@ bool material_convert_launch(const MaterialConvertParams& p, void* stream_, std:
     return finish("k_material_bytes");
   }
   const dim3 grid = blocks(texels);
-#define STHIP_TEXELS_ARGS u, p.diffuse, p.specular, p.transmittance, p.roughness, source_bytes, p.out[0], p.out[1], p.out[2], p.alpha_mask, p.min_alpha, texels
+#define STHIP_TEXELS_ARGS u, p.diffuse, p.specular, p.transmittance, p.roughness, formats, p.width, p.height, p.out[0], p.out[1], p.out[2], p.alpha_mask, p.min_alpha, texels
   if (gltf && out8)
     hipLaunchKernelGGL((k_material_texels<STHIP_CONVERT_GLTF_PBR, true>), grid, dim3(CONVERT_BLOCK), 0, stream, STHIP_TEXELS_ARGS);
   else if (gltf)

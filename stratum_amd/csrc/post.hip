@@ -6,6 +6,7 @@
 #include "denoise.h"
 #include "material_convert.h"
 #include "post.h"
+#include "texel_decode.h"
 
 // ---- after the path: temporal accumulation, tonemap and image metric (post.h) ----
 
@@ -220,34 +221,49 @@ int sthip_convert_material(sthip_ctx* ctx, const sthip_convert_material_desc* d)
   const bool material = d->kind == STHIP_CONVERT_GLTF_PBR || d->kind == STHIP_CONVERT_DIFFUSE_SPECULAR;
   const bool with_roughness = d->kind == STHIP_CONVERT_DIFFUSE_SPECULAR;
   const size_t n = (size_t)d->width * d->height, out4 = d->output_format ? 4 : 16, out1 = d->output_format ? 1 : 4;
-  struct Image {  // one image of the descriptor: the bytes of a texel and what a device pointer must be aligned to
+  struct Image {  // one image of the descriptor: its bytes and what a device pointer must be aligned to
     const char* name;
     const void* p;
-    size_t texel, align;
+    size_t bytes, align;
     bool source;
   };
   std::vector<Image> images;
   int i_diffuse = -1, i_specular = -1, i_transmittance = -1, i_roughness = -1, i_input = -1, i_out[3] = {-1, -1, -1}, i_mask = -1, i_min = -1, i_rw = -1;
   auto add = [&](const char* name, const void* p, size_t texel, size_t align, bool source) {
-    images.push_back({name, p, texel, align, source});
+    images.push_back({name, p, texel ? n * texel : 4, align, source});
+    return (int)images.size() - 1;
+  };
+  // a source: format 0 / 1 is the library's own form of `channels` channels, from 16 up a sthip_texel_format (texel_decode.h)
+  int format_status = STHIP_OK;
+  auto format_ok = [&](const char* field, uint32_t format) {
+    if (format <= 1 || (sthip::texel_format_built(format))) return true;
+    if (sthip::texel_format_named_unsupported(format))
+      format_status = fail(ctx, STHIP_ERR_UNSUPPORTED, std::string("sthip_convert_material: ") + field + " " + std::to_string(format) + " (" + sthip::texel_unsupported_name(format) + ") has no meaning on a material path and is not built");
+    else
+      format_status = refuse(field, "is no sthip_image_format");
+    return false;
+  };
+  auto add_source = [&](const char* name, const void* p, uint32_t format, size_t channels) {
+    if (format <= 1) return add(name, p, format ? channels : 4 * channels, format ? channels : 4 * channels, true);
+    images.push_back({name, p, (size_t)sthip::texel_image_bytes(format, d->width, d->height), sthip::texel_alignment(format), true});
     return (int)images.size() - 1;
   };
   if (material) {
     if (!d->gDiffuse && !d->gSpecular && !d->gTransmittance && !(with_roughness && d->gRoughness))
       return refuse(with_roughness ? "gDiffuse / gSpecular / gTransmittance / gRoughness" : "gDiffuse / gSpecular / gTransmittance", "are all NULL: no source");
-    if (d->gDiffuse && d->diffuse_format > 1) return refuse("diffuse_format", "is no sthip_image_format");
-    if (d->gSpecular && d->specular_format > 1) return refuse("specular_format", "is no sthip_image_format");
-    if (d->gTransmittance && d->transmittance_format > 1) return refuse("transmittance_format", "is no sthip_image_format");
-    if (with_roughness && d->gRoughness && d->roughness_format > 1) return refuse("roughness_format", "is no sthip_image_format");
+    if (d->gDiffuse && !format_ok("diffuse_format", d->diffuse_format)) return format_status;
+    if (d->gSpecular && !format_ok("specular_format", d->specular_format)) return format_status;
+    if (d->gTransmittance && !format_ok("transmittance_format", d->transmittance_format)) return format_status;
+    if (with_roughness && d->gRoughness && !format_ok("roughness_format", d->roughness_format)) return format_status;
     if (!d->gOutput[0]) return refuse("gOutput[0]", "is NULL");
     if (!d->gOutput[1]) return refuse("gOutput[1]", "is NULL");
     if (!d->gOutput[2]) return refuse("gOutput[2]", "is NULL");
     if (!d->gOutputMinAlpha) return refuse("gOutputMinAlpha", "is NULL");
     if (d->gDiffuse && !d->gOutputAlphaMask) return refuse("gOutputAlphaMask", "is NULL although gDiffuse is given");
-    if (d->gDiffuse) i_diffuse = add("gDiffuse", d->gDiffuse, d->diffuse_format ? 4 : 16, d->diffuse_format ? 4 : 16, true);
-    if (d->gSpecular) i_specular = add("gSpecular", d->gSpecular, d->specular_format ? 4 : 16, d->specular_format ? 4 : 16, true);
-    if (d->gTransmittance) i_transmittance = add("gTransmittance", d->gTransmittance, d->transmittance_format ? 4 : 16, d->transmittance_format ? 4 : 16, true);
-    if (with_roughness && d->gRoughness) i_roughness = add("gRoughness", d->gRoughness, d->roughness_format ? 1 : 4, d->roughness_format ? 1 : 4, true);
+    if (d->gDiffuse) i_diffuse = add_source("gDiffuse", d->gDiffuse, d->diffuse_format, 4);
+    if (d->gSpecular) i_specular = add_source("gSpecular", d->gSpecular, d->specular_format, 4);
+    if (d->gTransmittance) i_transmittance = add_source("gTransmittance", d->gTransmittance, d->transmittance_format, 4);
+    if (with_roughness && d->gRoughness) i_roughness = add_source("gRoughness", d->gRoughness, d->roughness_format, 1);
     i_out[0] = add("gOutput[0]", d->gOutput[0], out4, out4, false);
     i_out[1] = add("gOutput[1]", d->gOutput[1], out4, out4, false);
     i_out[2] = add("gOutput[2]", d->gOutput[2], out4, out4, false);
@@ -256,8 +272,8 @@ int sthip_convert_material(sthip_ctx* ctx, const sthip_convert_material_desc* d)
   } else {
     if (!d->gInput) return refuse("gInput", "is NULL");
     if (!d->gRoughnessRW) return refuse("gRoughnessRW", "is NULL");
-    if (d->input_format > 1) return refuse("input_format", "is no sthip_image_format");
-    i_input = add("gInput", d->gInput, d->input_format ? 1 : 4, d->input_format ? 1 : 4, true);
+    if (!format_ok("input_format", d->input_format)) return format_status;
+    i_input = add_source("gInput", d->gInput, d->input_format, 1);
     i_rw = add("gRoughnessRW", d->gRoughnessRW, out1, out1, false);
   }
   if (d->device_ptrs)
@@ -269,7 +285,7 @@ int sthip_convert_material(sthip_ctx* ctx, const sthip_convert_material_desc* d)
   std::vector<DevBuf<uint8_t>> staged(d->device_ptrs ? 0 : images.size());
   std::vector<void*> dev(images.size());
   for (size_t k = 0; k < images.size(); k++) {
-    const size_t bytes = images[k].texel ? n * images[k].texel : 4;
+    const size_t bytes = images[k].bytes;
     if (d->device_ptrs) {
       dev[k] = const_cast<void*>(images[k].p);
       continue;
@@ -282,6 +298,7 @@ int sthip_convert_material(sthip_ctx* ctx, const sthip_convert_material_desc* d)
   sthip::MaterialConvertParams p{};
   p.kind = d->kind;
   p.texels = n;
+  p.width = d->width, p.height = d->height;
   p.output_format = d->output_format;
   p.diffuse = device_of(i_diffuse);
   p.specular = device_of(i_specular);
@@ -299,12 +316,61 @@ int sthip_convert_material(sthip_ctx* ctx, const sthip_convert_material_desc* d)
   hipError_t e = hipSuccess;
   if (!d->device_ptrs) {  // the staged buffers must outlive the kernel: always synchronise
     for (size_t k = 0; ok && e == hipSuccess && k < images.size(); k++)
-      if (!images[k].source) e = hipMemcpyAsync(const_cast<void*>(images[k].p), dev[k], images[k].texel ? n * images[k].texel : 4, hipMemcpyDeviceToHost, st);
+      if (!images[k].source) e = hipMemcpyAsync(const_cast<void*>(images[k].p), dev[k], images[k].bytes, hipMemcpyDeviceToHost, st);
     const hipError_t es = hipStreamSynchronize(st);
     if (e == hipSuccess) e = es;
   }
   if (!ok) return fail(ctx, STHIP_ERR_HIP, "sthip_convert_material: " + err);
   if (e != hipSuccess) return fail(ctx, STHIP_ERR_HIP, std::string("sthip_convert_material: ") + hipGetErrorString(e));
+  return STHIP_OK;
+}
+
+// A source image in an asset's own texel format to one of the library's four forms (texel_decode.hip).
+int sthip_decode_texels(sthip_ctx* ctx, const sthip_decode_texels_desc* d) {
+  if (!ctx || !d) return STHIP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const char* field, const char* why) { return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, std::string("sthip_decode_texels: ") + field + " " + why); };
+  if (!d->width) return refuse("width", "is 0");
+  if (!d->height) return refuse("height", "is 0");
+  if ((uint64_t)d->width * d->height > (1ull << 30)) return refuse("width x height", "is too large (more than 2^30 texels)");
+  if (sthip::texel_format_named_unsupported(d->src_format))
+    return fail(ctx, STHIP_ERR_UNSUPPORTED, std::string("sthip_decode_texels: src_format ") + std::to_string(d->src_format) + " (" + sthip::texel_unsupported_name(d->src_format) + ") has no meaning on a material path and is not built");
+  if (!sthip::texel_format_built(d->src_format)) return refuse("src_format", "is no sthip_texel_format");
+  if (d->dst_format > 1) return refuse("dst_format", "is no sthip_image_format");
+  if (d->dst_channels != 1 && d->dst_channels != 4) return refuse("dst_channels", "must be 1 or 4");
+  if (d->dst_channels == 1 && d->channel > 3) return refuse("channel", "is above 3");
+  if (!d->src) return refuse("src", "is NULL");
+  if (!d->dst) return refuse("dst", "is NULL");
+  const uint32_t f = sthip::texel_canonical(d->src_format);
+  const size_t n = (size_t)d->width * d->height, dst_texel = (d->dst_channels == 4 ? 4 : 1) * (d->dst_format ? 1 : 4);
+  const size_t src_bytes = (size_t)sthip::texel_image_bytes(f, d->width, d->height), dst_bytes = n * dst_texel;
+  if (d->device_ptrs) {
+    if ((uintptr_t)d->src & (sthip::texel_alignment(f) - 1)) return refuse("src", "is not naturally aligned");
+    if ((uintptr_t)d->dst & (dst_texel - 1)) return refuse("dst", "is not naturally aligned");
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  DevBuf<uint8_t> staged_src, staged_dst;  // host form only (freed on return; poisoned under STHIP_POISON_ALLOC)
+  sthip::TexelDecodeParams p{};
+  p.format = f;
+  p.width = d->width, p.height = d->height;
+  p.dst8 = d->dst_format, p.dst_one = d->dst_channels == 1, p.channel = d->channel;
+  p.src = d->src, p.dst = d->dst;
+  if (!d->device_ptrs) {
+    HIP_TRY(ctx, staged_src.ensure(src_bytes));
+    HIP_TRY(ctx, staged_dst.ensure(dst_bytes));
+    HIP_TRY(ctx, hipMemcpyAsync(staged_src.p, d->src, src_bytes, hipMemcpyHostToDevice, st));
+    p.src = staged_src.p, p.dst = staged_dst.p;
+  }
+  std::string err;
+  const bool ok = sthip::texel_decode_launch(p, st, err);
+  hipError_t e = hipSuccess;
+  if (!d->device_ptrs) {  // the staged buffers must outlive the kernel: always synchronise
+    if (ok) e = hipMemcpyAsync(d->dst, staged_dst.p, dst_bytes, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+  }
+  if (!ok) return fail(ctx, STHIP_ERR_HIP, "sthip_decode_texels: " + err);
+  if (e != hipSuccess) return fail(ctx, STHIP_ERR_HIP, std::string("sthip_decode_texels: ") + hipGetErrorString(e));
   return STHIP_OK;
 }
 

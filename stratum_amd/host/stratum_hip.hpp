@@ -50,6 +50,7 @@
 // ... and one without the post block lacks these: Denoiser::denoise then throws
 // ... and one without the material conversions lacks this: Scene::make_*_material then throw for a material with images
 #pragma weak sthip_convert_material
+#pragma weak sthip_decode_texels
 // ... and one that cannot replace the environment of a resident scene lacks these: the host builds the tables and uploads
 #pragma weak sthip_scene_set_environment
 #pragma weak sthip_scene_read_distributions
@@ -407,6 +408,12 @@ struct Image {
   uint32_t width = 0, height = 0;
   std::vector<float> pixels;   // width * height * 4, row 0 first
   std::vector<uint8_t> bytes;  // width * height * 4, row 0 first: a byte b is the texel (float)b / 255.0f (sthip.h)
+  // An asset's image as its file holds it (sRGB, one to three channels, 16-bit, BC1-BC5: sthip_texel_format, from 16 up), when
+  // `texels` is filled instead: a source of the material conversions, which decode it on the device. It is never resident:
+  // Scene::decode_image makes the Image to bind (an emission image, a normal map).
+  std::vector<uint8_t> texels;
+  uint32_t texel_format = 0;
+  bool is_raw() const { return !texels.empty(); }
   bool is_8bit() const { return !bytes.empty(); }
   float channel(size_t i) const { return is_8bit() ? (float)bytes[i] / 255.0f : pixels[i]; }
   // counts mark_dirty(): what tells the texels of one Image object apart. A host that repaints the texels in place (same extent,
@@ -420,6 +427,9 @@ struct Image1 {
   uint32_t width = 0, height = 0;
   std::vector<float> pixels;   // width * height, row 0 first
   std::vector<uint8_t> bytes;  // width * height, row 0 first
+  std::vector<uint8_t> texels;  // as Image::texels; a format of several channels gives its channel 0
+  uint32_t texel_format = 0;
+  bool is_raw() const { return !texels.empty(); }
   bool is_8bit() const { return !bytes.empty(); }
   uint32_t serial = 0;  // as Image::serial
   void mark_dirty() { serial++; }
@@ -982,7 +992,7 @@ class Scene {
   Material make_metallic_roughness_material(CommandBuffer& cb, const ImageValue3& base_color, const ImageValue4& metallic_roughness, const ImageValue3& transmission, float eta,
                                             const ImageValue3& emission) {  // Scene.cpp:156-203
     Material dst;
-    if (emissive(emission, dst)) return dst;
+    if (emissive(cb, emission, dst)) return dst;
     for (int k = 0; k < 3; k++) dst.base_color()[k] = base_color.value[k];
     dst.emission() = 0;
     dst.metallic() = metallic_roughness.value[2];
@@ -997,7 +1007,7 @@ class Scene {
   Material make_diffuse_specular_material(CommandBuffer& cb, const ImageValue3& diffuse, const ImageValue3& specular, const ImageValue1& roughness, const ImageValue3& transmission, float eta,
                                           const ImageValue3& emission) {  // Scene.cpp:204-256
     Material dst;
-    if (emissive(emission, dst)) return dst;
+    if (emissive(cb, emission, dst)) return dst;
     const float ld = luminance(diffuse.value), ls = luminance(specular.value), lt = luminance(transmission.value);
     const float den = (ld + ls) + lt;
     for (int k = 0; k < 3; k++) dst.base_color()[k] = ((diffuse.value[k] * ld + specular.value[k] * ls) + transmission.value[k] * lt) / den;
@@ -1199,6 +1209,10 @@ class Scene {
         formats.push_back(0);
       }
     };
+    for (const Image* im : sd->mResources.image4s)
+      if (im->is_raw()) throw std::invalid_argument("an Image of raw texels is a source, not a resident image: bind Scene::decode_image() of it");
+    for (const Image1* im : sd->mResources.image1s)
+      if (im->is_raw()) throw std::invalid_argument("an Image1 of raw texels is a source, not a resident image: bind Scene::decode_image1() of it");
     for (const Image* im : sd->mResources.image4s) describe(im->pixels, im->bytes, im->width, im->height, sd->mImageDescs, sd->mImageFormats);
     for (const Image1* im : sd->mResources.image1s) describe(im->pixels, im->bytes, im->width, im->height, sd->mImage1Descs, sd->mImage1Formats);
     for (const Image* im : sd->mResources.image4s) sd->mImageSerials.push_back(im->serial);
@@ -1211,10 +1225,10 @@ class Scene {
 
  private:
   // the early return of both material functions, Scene.cpp:158-164,206-212
-  static bool emissive(const ImageValue3& emission, Material& dst) {
+  bool emissive(CommandBuffer& cb, const ImageValue3& emission, Material& dst) {
     if (!(emission.value[0] > 0 || emission.value[1] > 0 || emission.value[2] > 0)) return false;
     const float l = luminance(emission.value);
-    dst.values[0].image = emission.image;
+    dst.values[0].image = (emission.image && emission.image->is_raw()) ? decode_image(cb, *emission.image) : emission.image;  // (bound as it is upstream: the sampler decodes)
     for (int k = 0; k < 3; k++) dst.base_color()[k] = emission.value[k] / l;
     dst.emission() = l;
     dst.eta() = 0;
@@ -1230,9 +1244,57 @@ class Scene {
     if (!im) return;
     if (!width) width = im->width, height = im->height;  // (upstream's order: the extent is the first present image's)
     if (im->width != width || im->height != height) throw std::invalid_argument("material conversion: all source images must have the extent of the first one");
+    if (im->is_raw()) {
+      if (im->texel_format < STHIP_TEXEL_FIRST) throw std::invalid_argument("material conversion: raw texels need a sthip_texel_format from 16 up");
+      p = im->texels.data();
+      format = (uint8_t)im->texel_format;
+      return;
+    }
     p = im->is_8bit() ? (const void*)im->bytes.data() : (const void*)im->pixels.data();
     format = im->is_8bit() ? 1 : 0;
   }
+  // dst_channels 4 or 1 (channel 0); `identity`: the decode gives the source bytes back, so the result stays 8-bit
+  template <typename I>
+  static void decode_into(CommandBuffer& cb, const I& raw, uint32_t dst_channels, int resident, I& out) {
+    if (!sthip_decode_texels) throw std::runtime_error("this libstratum_hip.so has no sthip_decode_texels");
+    if (!cb.ctx) throw std::invalid_argument("decoding an image needs CommandBuffer::ctx (BDPT::context()): the kernel runs on the device");
+    if (!raw.is_raw()) throw std::invalid_argument("decode_image: the image holds no raw texels");
+    const bool identity = raw.texel_format >= STHIP_TEXEL_R8_UNORM && raw.texel_format <= STHIP_TEXEL_RGBA8_UNORM_;
+    const bool as_bytes = resident < 0 ? identity : resident == 1;
+    sthip_decode_texels_desc d{};
+    d.src_format = raw.texel_format;
+    d.width = raw.width, d.height = raw.height;
+    d.dst_format = as_bytes ? 1 : 0;
+    d.dst_channels = dst_channels;
+    d.src = raw.texels.data();
+    out.width = raw.width, out.height = raw.height;
+    const size_t n = (size_t)raw.width * raw.height * dst_channels;
+    if (as_bytes) {
+      out.bytes.resize(n);
+      d.dst = out.bytes.data();
+    } else {
+      out.pixels.resize(n);
+      d.dst = out.pixels.data();
+    }
+    if (sthip_decode_texels(cb.ctx, &d) != STHIP_OK) throw std::runtime_error(std::string("sthip_decode_texels: ") + sthip_last_error(cb.ctx));
+  }
+
+ public:
+  // An image of raw texels as the Image to bind where upstream binds the asset's image undecoded and lets the sampler decode it:
+  // the emission image of an emissive material (Scene.cpp:158-164) and the normal map (load_gltf.cpp:104). RGBA8 / R8 where the
+  // decode is the identity on bytes (unorm8 of any channel count), RGBA32F / R32F (exact) otherwise; `resident` 0 or 1 overrides.
+  component_ptr<Image> decode_image(CommandBuffer& cb, const Image& raw, int resident = -1) {
+    auto out = mNode.make_child("decoded image").make_component<Image>();
+    decode_into(cb, raw, 4, resident, *out);
+    return out;
+  }
+  component_ptr<Image1> decode_image1(CommandBuffer& cb, const Image1& raw, int resident = -1) {
+    auto out = mNode.make_child("decoded image").make_component<Image1>();
+    decode_into(cb, raw, 1, resident, *out);
+    return out;
+  }
+
+ private:
   ImageValue1 to_roughness(CommandBuffer& cb, const ImageValue1& x, uint32_t kind) {
     ImageValue1 roughness;
     roughness.value = kind == STHIP_CONVERT_ALPHA_TO_ROUGHNESS ? std::sqrt(x.value) : std::sqrt(2.0f / (x.value + 2.0f));

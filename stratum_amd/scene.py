@@ -213,9 +213,22 @@ class SceneData:
         return d
 
 
+TexelImage = wire.TexelImage  # TexelImage(data, format, width, height): an asset's image in its own texel format (sthip_texel_format)
+
+
+def _extent(image):
+    return (image.height, image.width) if isinstance(image, TexelImage) else image.shape[:2]
+
+
+def _decodes_to_its_bytes(fmt):
+    """unorm8 of any channel count: quantising the decoded texel gives the source byte back (include/sthip.h)."""
+    return fmt == 1 or 16 <= fmt <= 19
+
+
 class ImageValue:
     """ImageValue1 / ImageValue3 / ImageValue4 (image_value.h): a constant `value` (1, 3 or 4 floats) and an optional image, a
-    C-contiguous uint8 or float32 array, (H, W) for one channel and (H, W, 4) otherwise. What the material conversions of
+    C-contiguous uint8 or float32 array, (H, W) for one channel and (H, W, 4) otherwise, or a TexelImage (the asset's own
+    format: sRGB, one to three channels, 16-bit, BC1-BC5; decoded on the device). What the material conversions of
     SceneBuilder take; a plain number or sequence stands for a value without an image."""
 
     def __init__(self, value, image=None):
@@ -277,17 +290,37 @@ class SceneBuilder:
         self._materials.append(rec)
         return len(self._materials) - 1  # a handle; byte addresses are assigned in build() in order of first use
 
-    def add_image(self, rgba):
+    def _decoded(self, image, context, resident, channel):
+        if context is None:
+            raise ValueError("decoding a TexelImage needs a context (a BDPT): the kernel runs on the device")
+        if resident is None:
+            as_bytes = _decodes_to_its_bytes(image.format)
+        elif resident in ("RGBA8", "R8", 1):
+            as_bytes = True
+        elif resident in ("RGBA32F", "R32F", 0):
+            as_bytes = False
+        else:
+            raise ValueError("resident must be None, 'RGBA8' / 'R8' / 1 or 'RGBA32F' / 'R32F' / 0")
+        return context.decode_texels(image, dst_format=int(as_bytes), channel=channel)
+
+    def add_image(self, rgba, context=None, resident=None):
         """Registers a Texture2D<float4> (float32 array H x W x 4, row 0 first); returns its index in gImages.
-        A uint8 array stays uint8: it is uploaded and kept resident as RGBA8_UNORM (a byte b is the texel b / 255)."""
+        A uint8 array stays uint8: it is uploaded and kept resident as RGBA8_UNORM (a byte b is the texel b / 255).
+        A TexelImage is decoded on the device (`context`: a BDPT) and the decoded image registered: RGBA8 where the decode is the
+        identity on bytes (unorm8 of any channel count), RGBA32F (exact) otherwise; `resident` ("RGBA8" / "RGBA32F") overrides."""
+        if isinstance(rgba, TexelImage):
+            rgba = self._decoded(rgba, context, resident, None)
         im = np.ascontiguousarray(rgba, dtype=np.uint8 if np.asarray(rgba).dtype == np.uint8 else np.float32)
         assert im.ndim == 3 and im.shape[2] == 4
         self._images.append(im)
         return len(self._images) - 1
 
-    def add_image1(self, gray):
+    def add_image1(self, gray, context=None, resident=None):
         """Registers a Texture2D<float> (float32 array H x W, row 0 first); returns its handle (gImage1s index by first use).
-        A uint8 array stays uint8: it is uploaded and kept resident as R8_UNORM."""
+        A uint8 array stays uint8: it is uploaded and kept resident as R8_UNORM. A TexelImage: its channel 0, decoded on the
+        device as in add_image (R8 or R32F)."""
+        if isinstance(gray, TexelImage):
+            gray = self._decoded(gray, context, resident, 0)
         im = np.ascontiguousarray(gray, dtype=np.uint8 if np.asarray(gray).dtype == np.uint8 else np.float32)
         assert im.ndim == 2
         self._images1.append(im)
@@ -338,12 +371,13 @@ class SceneBuilder:
         """Scene::shininess_to_roughness (Scene.cpp:139-154): sqrt(2 / (shininess + 2)), value and image."""
         return self._roughness("ShininessToRoughness", shininess, context)
 
-    def _emissive(self, emission):
-        # the early return of both functions, Scene.cpp:158-164,206-212: the emission image becomes the base colour image
+    def _emissive(self, emission, context=None):
+        # the early return of both functions, Scene.cpp:158-164,206-212: the emission image becomes the base colour image, as it
+        # is (upstream's sampler decodes it; a TexelImage is decoded on the way in)
         lum = _luminance(emission.value)
         m = self.add_material(emission.value / lum, emission=float(lum), eta=0.0)
         if emission.image is not None:
-            self.set_material_images(m, base_color_image=self.add_image(emission.image))
+            self.set_material_images(m, base_color_image=self.add_image(emission.image, context=context))
         return m
 
     def _converted(self, material, kind, sources, context):
@@ -353,7 +387,7 @@ class SceneBuilder:
         if context is None:
             raise ValueError("converting images needs a context (a BDPT): the kernels run on the device")
         for a in images:
-            if a.shape[:2] != images[0].shape[:2]:
+            if _extent(a) != _extent(images[0]):
                 raise ValueError("all source images must have the extent of the first one")
         r = context.convert_material(kind, output_format=1, **sources)
         handles = [self.add_image(im) for im in r["output"]]
@@ -373,7 +407,7 @@ class SceneBuilder:
         base_color, metallic_roughness = ImageValue.of(base_color, 3), ImageValue.of(metallic_roughness, 4)
         transmission, emission = ImageValue.of(transmission, 3), ImageValue.of(emission, 3)
         if (emission.value > 0).any():
-            return self._emissive(emission)
+            return self._emissive(emission, context)
         m = self.add_material(base_color.value, emission=0.0, metallic=metallic_roughness.value[2], roughness=metallic_roughness.value[1], anisotropic=0.0, subsurface=0.0, clearcoat=0.0,
                               clearcoat_gloss=1.0, transmission=_luminance(transmission.value), eta=eta)
         return self._converted(m, "GltfPbr", {"diffuse": base_color.image, "specular": metallic_roughness.image, "transmittance": transmission.image}, context)
@@ -385,7 +419,7 @@ class SceneBuilder:
         diffuse, specular, roughness = ImageValue.of(diffuse, 3), ImageValue.of(specular, 3), ImageValue.of(roughness, 1)
         transmission, emission = ImageValue.of(transmission, 3), ImageValue.of(emission, 3)
         if (emission.value > 0).any():
-            return self._emissive(emission)
+            return self._emissive(emission, context)
         ld, ls, lt = _luminance(diffuse.value), _luminance(specular.value), _luminance(transmission.value)
         with np.errstate(invalid="ignore", divide="ignore"):
             den = np.float32(np.float32(ld + ls) + lt)

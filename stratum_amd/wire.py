@@ -439,6 +439,65 @@ CONVERT_KINDS = ["GltfPbr", "DiffuseSpecular", "AlphaToRoughness", "ShininessToR
 CONVERT = {n: i for i, n in enumerate(CONVERT_KINDS)}
 
 
+# sthip_texel_format (include/sthip.h): the formats an asset's images come in, decoded on the way in
+TEXEL_FORMATS = {"RGBA32F": 0, "RGBA8_UNORM": 1}
+for _c, _class in enumerate(("8_UNORM", "8_SRGB", "16_UNORM", "32F")):
+    for _n, _channels in enumerate(("R", "RG", "RGB", "RGBA")):
+        if _channels + _class not in TEXEL_FORMATS:  # (RGBA8_UNORM and RGBA32F keep 1 and 0; 19 and 31 name the same texels)
+            TEXEL_FORMATS[_channels + _class] = 16 + 4 * _c + _n
+TEXEL_FORMATS.update({"BC1_RGB": 32, "BC2": 33, "BC3": 34, "BC4_UNORM": 35, "BC5_UNORM": 36, "BC1_RGB_SRGB": 37, "BC2_SRGB": 38, "BC3_SRGB": 39})
+TEXEL_UNSUPPORTED = {"BC4_SNORM": 48, "BC5_SNORM": 49, "BC6H_UFLOAT": 50, "BC6H_SFLOAT": 51, "BC7_UNORM": 52, "BC7_SRGB": 53, "R8_SNORM": 56, "R16_SNORM": 60, "R8_UINT": 64}  # named, refused
+
+
+def texel_format(f):
+    """The number of a sthip_texel_format given by name or number."""
+    return TEXEL_FORMATS[f] if isinstance(f, str) else int(f)
+
+
+def texel_format_info(f):
+    """(block bytes or 0, channels, component bytes, sRGB) of a built format: the layout rules of include/sthip.h."""
+    f = {0: 31, 1: 19}.get(texel_format(f), texel_format(f))
+    if not 16 <= f < 40:
+        raise ValueError("%d is no built sthip_texel_format" % f)
+    if f >= 32:
+        return (8 if f in (32, 35, 37) else 16), {35: 1, 36: 2, 32: 3, 37: 3}.get(f, 4), 0, f >= 37
+    cls = (f - 16) >> 2
+    return 0, ((f - 16) & 3) + 1, (1, 1, 2, 4)[cls], cls == 1
+
+
+def texel_image_bytes(f, width, height):
+    block, channels, size, _ = texel_format_info(f)
+    return ((width + 3) // 4) * ((height + 3) // 4) * block if block else width * height * channels * size
+
+
+class TexelImage:
+    """An image in an asset's own texel format: `data` (any C-contiguous array or bytes of exactly the image's size), a
+    sthip_texel_format by name or number, and the extent."""
+
+    def __init__(self, data, format, width, height):
+        import numpy as np
+
+        self.format, self.width, self.height = texel_format(format), int(width), int(height)
+        self.data = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data).view(np.uint8).reshape(-1)
+        if self.data.size != texel_image_bytes(self.format, self.width, self.height):
+            raise ValueError("a %d x %d image of format %d has %d bytes, not %d" % (self.width, self.height, self.format, texel_image_bytes(self.format, self.width, self.height), self.data.size))
+
+
+class DecodeTexelsDesc(C.Structure):  # sthip_decode_texels_desc
+    _fields_ = [
+        ("src_format", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("device_ptrs", C.c_uint32),
+        ("dst_format", C.c_uint32),
+        ("dst_channels", C.c_uint32),
+        ("channel", C.c_uint32),
+        ("pad_", C.c_uint32),
+        ("src", C.c_void_p),
+        ("dst", C.c_void_p),
+    ]
+
+
 class DenseVolumeDesc(C.Structure):  # sthip_dense_volume_desc
     _fields_ = [
         ("struct_size", C.c_uint32),
