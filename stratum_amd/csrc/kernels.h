@@ -1240,6 +1240,11 @@ __global__ void __launch_bounds__(STHIP_BLOCK, MEDIA ? 2 : 3) k_shade_light(Fram
         path_pdf *= T_dir_pdf;
       }
       path_length++;
+      // loop condition of bdpt.hlsl:145: next_vertex() is entered only while beta has a positive component and no NaN. What
+      // trace() does with the hit before the test is local to this thread, so the test stands here. (Without it a light path
+      // whose throughput went NaN in one channel went on: rays the reference does not trace, vertices it does not store.
+      // Found by tools/fuzz_scenes.py.)
+      if (!(any_gt0(beta) && !any_nan(beta))) break;
       if (MEDIA && medium_vertex) {
         // ---- a vertex inside a medium: trace()'s tail (path.hlsli:1033-1043) and next_vertex(Medium), light branch (:955-998) ----
         Medium mm;
@@ -2242,7 +2247,10 @@ __global__ void __launch_bounds__(STHIP_BLOCK, (LT || (EXT && !PROBE)) ? 2 : SHA
           }
           if (p.out_prev_uv) p.out_prev_uv[pixel] = make_float2(((float)px + 0.5f - (float)view.image_min[0]) / ex, ((float)py + 0.5f - (float)view.image_min[1]) / ey);
         }
-        if (has_env) {
+        // Past the first vertex the background is evaluated inside next_vertex(), which the loop of bdpt.hlsl:298 enters only
+        // while beta has a positive component and no NaN: a path whose throughput went NaN in one channel (a black base colour
+        // times an infinite weight) ends at its miss without the environment's term. Found by tools/fuzz_scenes.py.
+        if (has_env && (primary || (any_gt0(beta) && !any_nan(beta)))) {
           // bdpt.hlsl:236-240 / path.hlsli:1051-1055 -> eval_emission (path.hlsli:847-894) for the background: cos = 1,
           // G = 1 (trace(), path.hlsli:1015-1019), pdf of the direction from Environment::eval_pdf (light.hlsli:155-162)
           Environment env;
@@ -2276,7 +2284,9 @@ __global__ void __launch_bounds__(STHIP_BLOCK, (LT || (EXT && !PROBE)) ? 2 : SHA
           shape_pdf = 1 / sd.shape_area;
         } else {
           const Xf t = load_xf(p.scene.xf, inst_index);
-          const f3 to_center = F3(t.r0.w, t.r1.w, t.r2.w) - origin;
+          // `origin` of intersection.hlsli:154 is the argument of the trace_ray call that found the sphere: with media the start
+          // of the walk's last segment (a volume boundary), not the path's previous vertex. Found by tools/fuzz_scenes.py.
+          const f3 to_center = F3(t.r0.w, t.r1.w, t.r2.w) - seg_origin;
           const float sin_elevation_max_sq = pow2f(in.radius()) / dot3(to_center, to_center);
           const float cos_elevation_max = sqrtf(fmaxf(0.0f, 1 - sin_elevation_max_sq));
           shape_pdf = 1 / (DET_2PI * (1 - cos_elevation_max));
@@ -2724,8 +2734,10 @@ __global__ void __launch_bounds__(STHIP_BLOCK, (LT || (EXT && !PROBE)) ? 2 : SHA
               if (p.debug_mode == STHIP_DEBUG_RESERVOIR_WEIGHT && reservoirs) dc = F3s(ris_W);
               if (p.debug_mode == STHIP_DEBUG_PATH_LENGTH_CONTRIBUTION && p.pc.gDebugLightPathLength == 1u && path_length == p.pc.gDebugViewPathLength) dc = beta * contrib;
             }
-            // deferred: a zero/negative contribution never adds light and trace_shadows traces no ray for it (bdpt.hlsl:313)
-            if (all_le0(c) && !inline_ray) break;
+            // deferred: a zero/negative contribution never adds light and trace_shadows traces no ray for it (bdpt.hlsl:313).
+            // Not deferred, the reservoir's ray is traced (and counted) for `contrib` alone (path.hlsli:450,476), whatever
+            // beta and the weight make of it: a throughput that is black where `contrib` is not still costs its ray
+            if (all_le0(c) && flag(p, STHIP_eDeferShadowRays)) break;
             // eLVC with eDeferShadowRays: connect_lvc stores its record into the SAME gShadowRays slot right after this one
             // (path.hlsli:775-783 after :355-364), unconditionally, so upstream never traces this record: neither do we
             if (LT && flag(p, STHIP_eLVC) && flag(p, STHIP_eConnectToLightPaths) && flag(p, STHIP_eDeferShadowRays)) break;

@@ -739,6 +739,19 @@ def _prepared_scenes():
     for k in range(17):
         b.add_instance(quad, light, translate((3.0 * k, 0, 0)))
     out.append(("emitters17", b.build(), None))
+    # emissive spheres beside emissive triangle instances: the table counts triangle instances only, so 16 + 2 still has one
+    # (of 16 entries) and 14 + 1 has 14; a scene with a sphere renders through an instantiation that never consults the table,
+    # so only the host side can show this rule
+    for lamps, spheres in ((16, 2), (14, 1)):
+        b = SceneBuilder("emitters%d_spheres%d" % (lamps, spheres))
+        quad = b.add_mesh(*scenes._quad((-1, 0, 1), (1, 0, 1), (1, 0, -1), (-1, 0, -1), (0, 1, 0)))
+        light = b.add_emitter((5.0, 5.0, 5.0))
+        for k in range(lamps):
+            if k == spheres:  # (spheres between the triangle instances, not behind them all)
+                for j in range(spheres):
+                    b.add_sphere(light, 0.3, translate((3.0 * j, 4.0, 0)))
+            b.add_instance(quad, light, translate((3.0 * k, 0, 0)))
+        out.append(("emitters%d_spheres%d" % (lamps, spheres), b.build(), None))
     # two grids back to back
     sc = foggy_cornell()[0]
     sc.volumes = [sc.volumes[0], sc.volumes[0].copy()]
@@ -759,6 +772,8 @@ def test_scene_prepare_matches_its_numpy_restatement(scene_prepare_check, tmp_pa
             assert [int(t["levels"]) for t in results["image_table"][[0, 2, 3]]] == [1, 2, 3]  # 1x1, 2x2, 3x5
         if name == "emitters17":
             assert results["emitter_count"] == 0
+        if name in ("emitters16_spheres2", "emitters14_spheres1"):
+            assert results["emitter_count"] == int(name[8:10]) and sc.light_count == int(name[8:10]) + int(name[-1])
         if name == "cornell_box":
             assert results["emitter_count"] == 1 and results["emitters"]["identity"][0] == 1
         if name == "shared_mesh_scene":
