@@ -1114,6 +1114,61 @@ typedef struct sthip_hit {
 int sthip_trace_rays(sthip_ctx* ctx, const sthip_ray* rays, uint32_t ray_count, sthip_hit* hits, uint32_t any_hit,
                      uint32_t device_ptrs);
 
+/* ---- the reuse hash grid on its own (test entry for the grid's defined order; hashgrid.hlsli:43-88) ----
+ * The grids of eNEEReservoirReuse / eLVCReservoirReuse are built on the device. Their contents are DEFINED by a serial run:
+ * the appends take effect in append order, append k probing the slots home .. home + 31 of a table of bucket_count + 32
+ * slots (probing does not wrap) as the earlier appends left it — the first empty slot is claimed, the first slot that
+ * holds the append's checksum is joined, an append that finds neither is dropped. counters[slot] is the number of appends
+ * of the slot, indices its exclusive prefix sum in slot order, and dest[k] = indices[slot] + the rank of k among the slot's
+ * appends in append order (0xFFFFFFFF for a dropped append). sthip_build_hash_grid runs the build a render runs — the same
+ * kernels in the same order on the context's own buffers, with "hashgrid_serial" applying as it does in a render — and
+ * copies the result to host memory. It needs a context and no scene. All pointers are host pointers. Two forms:
+ *   form 0 (keys): keys[count] are (home bucket, checksum) pairs. The device arrays are sized by `slots` (>= count); the
+ *     build bounds itself by the count in device memory, as in a render. `records`, `compacted_keys` and `data` are ignored.
+ *   form 1 (NEE append records, 4 float4 each; staged when the last word of float4 2 — the cell size — is not zero as bits)
+ *   form 2 (LVC append records, 6 float4 each; staged when the last word of float4 0 — the cell size — is not zero as bits):
+ *     `records` holds `slots` records with holes. They are compacted in order, hashed (position = the first three words of
+ *     float4 0, hashgrid_bucket_index), built, and scattered to `data` (3 resp. 5 float4 per record: NEE float4 0 =
+ *     (r0.w, r1.x, r1.y, r1.z), 1 = (r2.x, r2.y, r2.z, r3.w), 2 = (r3.x, r3.y, r3.z, r1.w); LVC = float4 1..5 of the
+ *     record). `keys` and `count` are ignored; info->count is the compacted count.
+ * Outputs: checksums / counters / indices, bucket_count + 32 words each (checksum 0 = an empty slot); dest, of which the
+ * first info->count words are written (the caller provides `count` words in form 0, `slots` otherwise); records forms only:
+ * compacted_keys, 2 * slots words of which the first 2 * info->count are written, and data, slots * 3 (5) float4 — every
+ * record the build did not place is zero. info: count; special_cells = the (home, checksum) cells that share their checksum
+ * with a cell whose home is fewer than 32 slots away, as the device counted them; serial_rebuild
+ * = 1 when the one-thread probe sequence built the table ("hashgrid_serial", or more than 1024 special cells); dropped =
+ * the appends without a slot.
+ * Refused with STHIP_ERR_INVALID_ARGUMENT before anything is touched (no device work, no output written): a NULL ctx, desc
+ * or info; a struct_size that is not sizeof(sthip_hash_grid_desc); a form above 2; bucket_count outside (0, 2^28]; slots 0
+ * or above 2^31 - 1; count > slots; a NULL pointer among those the form uses (keys may be NULL when count is 0); in form 0 a
+ * home >= bucket_count or a checksum of 0 (0 marks an empty slot; hashgrid_bucket_index never produces it).
+ * The call builds in the buffers a render keeps its grids in, so it DROPS the grids kept for the next render
+ * ("reuse_grids_persist": the next render starts without a previous grid, as after a scene upload); it never hands a render a grid
+ * of its own. It synchronises the context's stream. */
+typedef struct sthip_hash_grid_desc {
+  uint32_t struct_size; /* sizeof(sthip_hash_grid_desc) */
+  uint32_t form;        /* 0 keys, 1 NEE append records, 2 LVC append records */
+  uint32_t slots;
+  uint32_t count;       /* form 0 */
+  uint32_t bucket_count;
+  uint32_t reserved0;
+  const uint32_t* keys;  /* form 0: count x (home bucket, checksum) */
+  const float* records;  /* forms 1, 2: slots x 4 (6) float4 */
+  uint32_t* checksums;
+  uint32_t* counters;
+  uint32_t* indices;
+  uint32_t* dest;
+  uint32_t* compacted_keys; /* forms 1, 2 */
+  float* data;              /* forms 1, 2 */
+} sthip_hash_grid_desc;
+typedef struct sthip_hash_grid_info {
+  uint32_t count;
+  uint32_t special_cells;
+  uint32_t serial_rebuild;
+  uint32_t dropped;
+} sthip_hash_grid_info;
+int sthip_build_hash_grid(sthip_ctx* ctx, const sthip_hash_grid_desc* desc, sthip_hash_grid_info* info);
+
 /* ---- measurement ---- */
 typedef struct sthip_stats {
   uint64_t rays_total;     /* gRayCount[0] semantics, last render */

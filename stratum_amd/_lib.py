@@ -51,6 +51,7 @@ EXPORTS = [
     "sthip_wait_outputs",
     "sthip_set_shard",
     "sthip_trace_rays",
+    "sthip_build_hash_grid",
     "sthip_get_stats",
     "sthip_set_option",
     "sthip_shard_slot_count",
@@ -192,6 +193,9 @@ def lib():
     L.sthip_set_shard.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sthip_trace_rays.restype = C.c_int
     L.sthip_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
+    if hasattr(L, "sthip_build_hash_grid"):  # (an older build named by STHIP_LIB lacks it: calling it raises)
+        L.sthip_build_hash_grid.restype = C.c_int
+        L.sthip_build_hash_grid.argtypes = [C.c_void_p, C.POINTER(wire.HashGridDesc), C.POINTER(wire.HashGridInfo)]
     L.sthip_get_stats.restype = C.c_int
     L.sthip_get_stats.argtypes = [C.c_void_p, C.POINTER(wire.Stats)]
     L.sthip_set_option.restype = C.c_int

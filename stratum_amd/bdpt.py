@@ -843,3 +843,43 @@ class BDPT:
         rc = self._lib.sthip_trace_rays(self._h, wire.ptr(rays), rays.shape[0], wire.ptr(hits), mode, 0)
         self._check(rc, "sthip_trace_rays")
         return hits
+
+    # ---- the reuse hash grid on its own ----
+    def build_hash_grid(self, bucket_count, keys=None, slots=None, records=None, lvc=False):
+        """sthip_build_hash_grid (include/sthip.h): the reuse grid's device build on its own, read back. Keys form: `keys`, a
+        (count, 2) uint32 array of (home bucket, checksum) pairs, with `slots` >= count (default: max(count, 1)). Records form:
+        `records`, a (slots, 4, 4) float32 array of NEE append records or, with `lvc`, (slots, 6, 4) of LVC append records,
+        holes included. Returns a dict: checksums / counters / indices (bucket_count + 32 words), dest (count words), count,
+        special_cells, serial_rebuild, dropped, and for records also keys (count, 2) and data (slots, 3 or 5, 4) float32.
+        Drops the grids kept for the next render."""
+        if not hasattr(self._lib, "sthip_build_hash_grid"):
+            raise StratumHipError("this libstratum_hip.so has no sthip_build_hash_grid")
+        d, info = wire.HashGridDesc(), wire.HashGridInfo()
+        d.struct_size, d.bucket_count = C.sizeof(wire.HashGridDesc), int(bucket_count)
+        buckets = int(bucket_count) + 32
+        table = [np.full(max(buckets, 1), 0xA5A5A5A5, np.uint32) for _ in range(3)]
+        d.checksums, d.counters, d.indices = (t.ctypes.data for t in table)
+        if records is None:
+            keys = np.ascontiguousarray(np.zeros((0, 2), np.uint32) if keys is None else keys, dtype=np.uint32).reshape(-1, 2)
+            d.form, d.count = 0, keys.shape[0]
+            d.slots = max(keys.shape[0], 1) if slots is None else int(slots)
+            d.keys = keys.ctypes.data if keys.shape[0] else None
+            dest = np.full(max(keys.shape[0], 1), 0xA5A5A5A5, np.uint32)
+            out_keys = data = None
+        else:
+            rec, out_rec = (6, 5) if lvc else (4, 3)
+            records = np.ascontiguousarray(records, dtype=np.float32)
+            if records.ndim != 3 or records.shape[1:] != (rec, 4) or not records.shape[0]:
+                raise ValueError("build_hash_grid: records must be a (slots, %d, 4) float32 array" % rec)
+            d.form, d.slots, d.records = (2 if lvc else 1), records.shape[0], records.ctypes.data
+            dest = np.full(records.shape[0], 0xA5A5A5A5, np.uint32)
+            out_keys = np.full((records.shape[0], 2), 0xA5A5A5A5, np.uint32)
+            data = np.full((records.shape[0], out_rec, 4), np.float32(-7.0))
+            d.compacted_keys, d.data = out_keys.ctypes.data, data.ctypes.data
+        d.dest = dest.ctypes.data
+        self._check(self._lib.sthip_build_hash_grid(self._h, C.byref(d), C.byref(info)), "sthip_build_hash_grid")
+        out = {"checksums": table[0][:buckets], "counters": table[1][:buckets], "indices": table[2][:buckets], "dest": dest[: info.count], "count": int(info.count),
+               "special_cells": int(info.special_cells), "serial_rebuild": int(info.serial_rebuild), "dropped": int(info.dropped)}
+        if records is not None:
+            out["keys"], out["data"] = out_keys[: info.count], data
+        return out

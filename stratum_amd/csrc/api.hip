@@ -2550,26 +2550,132 @@ int sthip_scene_read_vertices(sthip_ctx* ctx, uint32_t first_vertex, uint32_t ve
 // One hash grid from one seed's staged appends (hashgrid.h): compact the stage in (path, vertex) order, hash the keys, build
 // the table the serial probe sequence of find_or_insert would build (hashgrid.hlsli:43-58; in parallel: hashgrid.hip), prefix
 // the bucket counters (compute_indices, :72-79) and scatter the records into their bucket ranges (swizzle, :81-88) — all of it
-// enqueued on the stream, nothing visits the host.
+// enqueued on the stream, nothing visits the host. appends == nullptr (sthip_build_hash_grid's keys form): hg_keys / hg_count
+// hold the keys already, and there are no records to compact or scatter.
 static int build_hash_grid(sthip_ctx* ctx, hipStream_t st, const float4* appends, float4* compact, float4* data, size_t slots, uint32_t rec, uint32_t flag_at, bool lvc_records,
                            uint32_t bucket_count, DevBuf<uint32_t>& d_checksums, DevBuf<uint32_t>& d_counters, DevBuf<uint32_t>& d_indices) {
   const uint32_t buckets = bucket_count + 32u;  // probing does not wrap
-  size_t tmp_bytes = ctx->hg_tmp.n;
-  HIP_TRY(ctx, sthip::lvc_compact(appends, (uint32_t)slots, 1, (uint32_t)slots, compact, ctx->hg_count.p, ctx->hg_flags.p, ctx->hg_offsets.p, ctx->hg_tmp.p, tmp_bytes, st, rec, flag_at));
   const unsigned kgrid = (unsigned)((slots + STHIP_BLOCK - 1) / STHIP_BLOCK);
-  if (lvc_records)
-    hipLaunchKernelGGL(k_hg_keys_lvc, dim3(kgrid), dim3(STHIP_BLOCK), 0, st, compact, ctx->hg_count.p, bucket_count, ctx->hg_keys.p);
-  else
-    hipLaunchKernelGGL(k_hg_keys, dim3(kgrid), dim3(STHIP_BLOCK), 0, st, compact, ctx->hg_count.p, bucket_count, ctx->hg_keys.p);
+  if (appends) {
+    size_t tmp_bytes = ctx->hg_tmp.n;
+    HIP_TRY(ctx, sthip::lvc_compact(appends, (uint32_t)slots, 1, (uint32_t)slots, compact, ctx->hg_count.p, ctx->hg_flags.p, ctx->hg_offsets.p, ctx->hg_tmp.p, tmp_bytes, st, rec, flag_at));
+    if (lvc_records)
+      hipLaunchKernelGGL(k_hg_keys_lvc, dim3(kgrid), dim3(STHIP_BLOCK), 0, st, compact, ctx->hg_count.p, bucket_count, ctx->hg_keys.p);
+    else
+      hipLaunchKernelGGL(k_hg_keys, dim3(kgrid), dim3(STHIP_BLOCK), 0, st, compact, ctx->hg_count.p, bucket_count, ctx->hg_keys.p);
+  }
   // the probe sequence, the bucket ranges and every record's place, on the device (hashgrid.hip): no host hop
   size_t build_bytes = ctx->hg_tmp.n;
   HIP_TRY(ctx, sthip::hashgrid_build_device(ctx->hg_keys.p, ctx->hg_count.p, (uint32_t)slots, buckets, d_checksums.p, d_counters.p, d_indices.p, ctx->hg_dest.p, ctx->hg_owner.p, ctx->hg_bucket_of.p,
                                             ctx->hg_append.p, ctx->hg_sorted_bucket.p, ctx->hg_sorted_append.p, ctx->hg_key64.p, ctx->hg_sorted_key64.p, ctx->hg_tmp.p, build_bytes, st, ctx->hashgrid_serial));
-  if (lvc_records)
-    hipLaunchKernelGGL(k_hg_scatter_lvc, dim3(kgrid), dim3(STHIP_BLOCK), 0, st, compact, ctx->hg_count.p, ctx->hg_dest.p, data);
-  else
-    hipLaunchKernelGGL(k_hg_scatter, dim3(kgrid), dim3(STHIP_BLOCK), 0, st, compact, ctx->hg_count.p, ctx->hg_dest.p, data);
+  if (appends) {
+    if (lvc_records)
+      hipLaunchKernelGGL(k_hg_scatter_lvc, dim3(kgrid), dim3(STHIP_BLOCK), 0, st, compact, ctx->hg_count.p, ctx->hg_dest.p, data);
+    else
+      hipLaunchKernelGGL(k_hg_scatter, dim3(kgrid), dim3(STHIP_BLOCK), 0, st, compact, ctx->hg_count.p, ctx->hg_dest.p, data);
+  }
   HIP_TRY(ctx, hipGetLastError());
+  return STHIP_OK;
+}
+
+// The buffers of a reuse grid's build at `hg_slots` append slots and `hg_buckets` table slots (DevBuf::ensure keeps what is large
+// enough): the stage, its compaction and the bucket ranges of the record kinds asked for, the table, hashgrid.hip's scratch, and
+// the two temp-size queries. sthip_render's plan and sthip_build_hash_grid size them here.
+static int reserve_hash_grid_buffers(sthip_ctx* ctx, size_t hg_slots, uint32_t hg_buckets, bool nee, bool lvc) {
+  if (nee) {
+    HIP_TRY(ctx, ctx->hg_appends.ensure(4 * hg_slots));
+    HIP_TRY(ctx, ctx->hg_compact.ensure(4 * hg_slots));
+    HIP_TRY(ctx, ctx->hg_data.ensure(3 * hg_slots));
+  }
+  if (lvc) {
+    HIP_TRY(ctx, ctx->lg_appends.ensure(6 * hg_slots));
+    HIP_TRY(ctx, ctx->lg_compact.ensure(6 * hg_slots));
+    HIP_TRY(ctx, ctx->lg_data.ensure(5 * hg_slots));
+    for (DevBuf<uint32_t>* b : {&ctx->lg_checksums, &ctx->lg_counters, &ctx->lg_indices}) HIP_TRY(ctx, b->ensure(hg_buckets));
+  }
+  for (DevBuf<uint32_t>* b : {&ctx->hg_flags, &ctx->hg_offsets, &ctx->hg_dest, &ctx->hg_bucket_of, &ctx->hg_append, &ctx->hg_sorted_bucket, &ctx->hg_sorted_append}) HIP_TRY(ctx, b->ensure(hg_slots));
+  for (DevBuf<unsigned long long>* b : {&ctx->hg_key64, &ctx->hg_sorted_key64}) HIP_TRY(ctx, b->ensure(hg_slots));
+  for (DevBuf<uint32_t>* b : {&ctx->hg_checksums, &ctx->hg_counters, &ctx->hg_indices}) HIP_TRY(ctx, b->ensure(hg_buckets));
+  HIP_TRY(ctx, ctx->hg_keys.ensure(hg_slots));
+  HIP_TRY(ctx, ctx->hg_count.ensure(1));
+  HIP_TRY(ctx, ctx->hg_owner.ensure(hg_buckets + 2 + 1024));  // (+ hashgrid.hip's control words and special-cell list)
+  size_t tmp_bytes = 0, build_bytes = 0;
+  HIP_TRY(ctx, sthip::lvc_compact(nullptr, (uint32_t)hg_slots, 1, 0, nullptr, nullptr, ctx->hg_flags.p, ctx->hg_offsets.p, nullptr, tmp_bytes, ctx->stream));
+  HIP_TRY(ctx, sthip::hashgrid_build_device(nullptr, nullptr, (uint32_t)hg_slots, hg_buckets, nullptr, ctx->hg_counters.p, ctx->hg_indices.p, nullptr, nullptr, ctx->hg_bucket_of.p, ctx->hg_append.p,
+                                            ctx->hg_sorted_bucket.p, ctx->hg_sorted_append.p, ctx->hg_key64.p, ctx->hg_sorted_key64.p, nullptr, build_bytes, ctx->stream));
+  HIP_TRY(ctx, ctx->hg_tmp.ensure(std::max<size_t>(16, std::max(tmp_bytes, build_bytes))));
+  return STHIP_OK;
+}
+
+// The reuse grid's build on its own (include/sthip.h): the keys, or staged records, of the caller through build_hash_grid on the
+// buffers a render builds in, and everything it left copied back. The grids kept for the next render are dropped.
+int sthip_build_hash_grid(sthip_ctx* ctx, const sthip_hash_grid_desc* d, sthip_hash_grid_info* info) {
+  if (!ctx) return STHIP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const char* field, const std::string& why) { return fail(ctx, STHIP_ERR_INVALID_ARGUMENT, std::string("sthip_build_hash_grid: ") + field + " " + why); };
+  if (!d) return refuse("desc", "is NULL");
+  if (!info) return refuse("info", "is NULL");
+  if (d->struct_size != sizeof(sthip_hash_grid_desc)) return refuse("struct_size", "is not sizeof(sthip_hash_grid_desc)");
+  if (d->form > 2u) return refuse("form", "is not 0 (keys), 1 (NEE records) or 2 (LVC records)");
+  if (d->bucket_count == 0 || d->bucket_count > (1u << 28)) return refuse("bucket_count", "is outside (0, 2^28]");
+  if (d->slots == 0 || d->slots > 0x7FFFFFFFu) return refuse("slots", "is outside [1, 2^31 - 1]");
+  const bool records = d->form != 0, lvc = d->form == 2;
+  if (!records && d->count > d->slots) return refuse("count", "is above slots");
+  if (!d->checksums) return refuse("checksums", "is NULL");
+  if (!d->counters) return refuse("counters", "is NULL");
+  if (!d->indices) return refuse("indices", "is NULL");
+  if (!d->dest) return refuse("dest", "is NULL");
+  if (records) {
+    if (!d->records) return refuse("records", "is NULL");
+    if (!d->compacted_keys) return refuse("compacted_keys", "is NULL");
+    if (!d->data) return refuse("data", "is NULL");
+  } else {
+    if (d->count && !d->keys) return refuse("keys", "is NULL");
+    for (uint32_t k = 0; k < d->count; k++) {
+      if (d->keys[2 * (size_t)k] >= d->bucket_count) return refuse("keys", "[" + std::to_string(k) + "]: the home bucket is not below bucket_count");
+      if (d->keys[2 * (size_t)k + 1] == 0u) return refuse("keys", "[" + std::to_string(k) + "]: a checksum of 0 marks an empty slot");
+    }
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->reuse_grids_valid = false;  // (the table and the records of the last render are overwritten)
+  const size_t slots = d->slots;
+  const uint32_t buckets = d->bucket_count + 32u, rec = lvc ? 6u : 4u, out_rec = lvc ? 5u : 3u;
+  const int rc = reserve_hash_grid_buffers(ctx, slots, buckets, d->form == 1, lvc);
+  if (rc != STHIP_OK) return rc;
+  hipStream_t st = ctx->stream;
+  DevBuf<uint32_t>&d_checksums = lvc ? ctx->lg_checksums : ctx->hg_checksums, &d_counters = lvc ? ctx->lg_counters : ctx->hg_counters, &d_indices = lvc ? ctx->lg_indices : ctx->hg_indices;
+  float4 *appends = nullptr, *compact = nullptr, *data = nullptr;
+  if (records) {
+    appends = lvc ? ctx->lg_appends.p : ctx->hg_appends.p;
+    compact = lvc ? ctx->lg_compact.p : ctx->hg_compact.p;
+    data = lvc ? ctx->lg_data.p : ctx->hg_data.p;
+    HIP_TRY(ctx, hipMemcpyAsync(appends, d->records, slots * rec * sizeof(float4), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(data, 0, slots * out_rec * sizeof(float4), st));  // (a render reads the records the build placed only)
+  } else {
+    if (d->count) HIP_TRY(ctx, hipMemcpyAsync(ctx->hg_keys.p, d->keys, (size_t)d->count * sizeof(uint2), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->hg_count.p, &d->count, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));  // (the sources are the caller's pageable memory)
+  const int rc2 = build_hash_grid(ctx, st, appends, compact, data, slots, rec, lvc ? 0u : 2u, lvc, d->bucket_count, d_checksums, d_counters, d_indices);
+  if (rc2 != STHIP_OK) return rc2;
+  uint32_t count = 0, ctl[2] = {0, 0};
+  HIP_TRY(ctx, hipMemcpyAsync(&count, ctx->hg_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(ctl, ctx->hg_owner.p + buckets, sizeof ctl, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d->checksums, d_checksums.p, buckets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d->counters, d_counters.p, buckets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d->indices, d_indices.p, buckets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (count > slots) return fail(ctx, STHIP_ERR_HIP, "sthip_build_hash_grid: the device counted more appends than slots");
+  if (count) HIP_TRY(ctx, hipMemcpyAsync(d->dest, ctx->hg_dest.p, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (records) {
+    if (count) HIP_TRY(ctx, hipMemcpyAsync(d->compacted_keys, ctx->hg_keys.p, (size_t)count * sizeof(uint2), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d->data, data, slots * out_rec * sizeof(float4), hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  info->count = count;
+  info->special_cells = ctl[1];
+  info->serial_rebuild = ctl[0];
+  info->dropped = 0;
+  for (uint32_t k = 0; k < count; k++) info->dropped += d->dest[k] == 0xFFFFFFFFu ? 1u : 0u;
   return STHIP_OK;
 }
 
@@ -2920,28 +3026,8 @@ static int reserve_render_buffers(sthip_ctx* ctx, RenderPlan& r, const sthip_out
     }
   }
   if (r.nee_reuse || r.lvc_reuse) {
-    if (r.nee_reuse) {
-      HIP_TRY(ctx, ctx->hg_appends.ensure(4 * hg_slots));
-      HIP_TRY(ctx, ctx->hg_compact.ensure(4 * hg_slots));
-      HIP_TRY(ctx, ctx->hg_data.ensure(3 * hg_slots));
-    }
-    if (r.lvc_reuse) {
-      HIP_TRY(ctx, ctx->lg_appends.ensure(6 * hg_slots));
-      HIP_TRY(ctx, ctx->lg_compact.ensure(6 * hg_slots));
-      HIP_TRY(ctx, ctx->lg_data.ensure(5 * hg_slots));
-      for (DevBuf<uint32_t>* b : {&ctx->lg_checksums, &ctx->lg_counters, &ctx->lg_indices}) HIP_TRY(ctx, b->ensure(r.hg_buckets));
-    }
-    for (DevBuf<uint32_t>* b : {&ctx->hg_flags, &ctx->hg_offsets, &ctx->hg_dest, &ctx->hg_bucket_of, &ctx->hg_append, &ctx->hg_sorted_bucket, &ctx->hg_sorted_append}) HIP_TRY(ctx, b->ensure(hg_slots));
-    for (DevBuf<unsigned long long>* b : {&ctx->hg_key64, &ctx->hg_sorted_key64}) HIP_TRY(ctx, b->ensure(hg_slots));
-    for (DevBuf<uint32_t>* b : {&ctx->hg_checksums, &ctx->hg_counters, &ctx->hg_indices}) HIP_TRY(ctx, b->ensure(r.hg_buckets));
-    HIP_TRY(ctx, ctx->hg_keys.ensure(hg_slots));
-    HIP_TRY(ctx, ctx->hg_count.ensure(1));
-    HIP_TRY(ctx, ctx->hg_owner.ensure(r.hg_buckets + 2 + 1024));  // (+ hashgrid.hip's control words and special-cell list)
-    size_t tmp_bytes = 0, build_bytes = 0;
-    HIP_TRY(ctx, sthip::lvc_compact(nullptr, (uint32_t)hg_slots, 1, 0, nullptr, nullptr, ctx->hg_flags.p, ctx->hg_offsets.p, nullptr, tmp_bytes, ctx->stream));
-    HIP_TRY(ctx, sthip::hashgrid_build_device(nullptr, nullptr, (uint32_t)hg_slots, r.hg_buckets, nullptr, ctx->hg_counters.p, ctx->hg_indices.p, nullptr, nullptr, ctx->hg_bucket_of.p, ctx->hg_append.p,
-                                              ctx->hg_sorted_bucket.p, ctx->hg_sorted_append.p, ctx->hg_key64.p, ctx->hg_sorted_key64.p, nullptr, build_bytes, ctx->stream));
-    HIP_TRY(ctx, ctx->hg_tmp.ensure(std::max<size_t>(16, std::max(tmp_bytes, build_bytes))));
+    const int rc = reserve_hash_grid_buffers(ctx, hg_slots, r.hg_buckets, r.nee_reuse, r.lvc_reuse);
+    if (rc != STHIP_OK) return rc;
   }
 
   for (DevBuf<float4>* b : {&ctx->ray_o, &ctx->ray_d, &ctx->hit, &ctx->beta, &ctx->radiance, &ctx->shadow_sum}) HIP_TRY(ctx, b->ensure(P));

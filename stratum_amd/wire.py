@@ -498,6 +498,33 @@ class DecodeTexelsDesc(C.Structure):  # sthip_decode_texels_desc
     ]
 
 
+class HashGridDesc(C.Structure):  # sthip_hash_grid_desc
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("form", C.c_uint32),
+        ("slots", C.c_uint32),
+        ("count", C.c_uint32),
+        ("bucket_count", C.c_uint32),
+        ("reserved0", C.c_uint32),
+        ("keys", C.c_void_p),
+        ("records", C.c_void_p),
+        ("checksums", C.c_void_p),
+        ("counters", C.c_void_p),
+        ("indices", C.c_void_p),
+        ("dest", C.c_void_p),
+        ("compacted_keys", C.c_void_p),
+        ("data", C.c_void_p),
+    ]
+
+
+class HashGridInfo(C.Structure):  # sthip_hash_grid_info
+    _fields_ = [("count", C.c_uint32), ("special_cells", C.c_uint32), ("serial_rebuild", C.c_uint32), ("dropped", C.c_uint32)]
+
+
+HASH_GRID_DESC_BYTES = 88  # sizeof(sthip_hash_grid_desc), include/sthip.h
+assert C.sizeof(HashGridDesc) == HASH_GRID_DESC_BYTES and C.sizeof(HashGridInfo) == 16
+
+
 class DenseVolumeDesc(C.Structure):  # sthip_dense_volume_desc
     _fields_ = [
         ("struct_size", C.c_uint32),
